@@ -13,11 +13,18 @@ One step = one pass of the hot path over one batch of synthetic utterances resid
   without the backward pass.  Utterances are independent: each rank runs its own batch (replicas, no collective
   on the data path); value = all ranks' utterances / max-over-ranks time.
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant contraction kernel, HIP-event timed on the launching stream
-inside the timed region) and `cpu_baseline` (the reference's op sequence on stock torch-CPU operators, oracle/stock_cpu.py,
-N = 1 only).  The headline is measured at the reference's precision (`dtype` "f32": exact fp32 MFMA, one stream); the
-split-bf16 mode is attached as the clearly labelled secondary record `alt` (same workload, `dtype` "bf16x3"), together with
-a two-stream run of it whose output is compared bit for bit with the one-stream output (`two_stream_bit_exact`).
+A plain run sets up, warms up, times --steps steps and prints ONE JSON line (rank 0): `metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` (one timed step) and the run's configuration.  The headline is measured at the
+reference's precision (`dtype` "f32": exact fp32 MFMA, one stream).  --dump-outputs DIR writes what the last timed step
+computed (the step's outputs and loss; a train step's loss and parameters after Adam) as DIR/<name>.npy.  Inputs, weights
+and latent draws are seeded, so two builds run with the same arguments can be compared output for output: the forward
+workloads repeat bit for bit, the train steps within rounding (atomic reductions in the backward).
+
+--full adds what the headline does not need: `roofline` (dominant contraction kernel, HIP-event timed on the launching stream
+inside the timed region), `cpu_baseline` (the reference's op sequence on stock torch-CPU operators, oracle/stock_cpu.py,
+N = 1 only), and for dccrn_cl the split-bf16 mode as the clearly labelled secondary record `alt` (same workload, `dtype`
+"bf16x3"), together with two-stream runs whose output is compared bit for bit with the one-stream output
+(`two_stream`, `alt.two_stream_bit_exact`).
 
 Other workloads (--workload): enhance | enhance_complex_mask (the evaluation script's inference, 10 latent samples per
 utterance), cvae_elbo | nsvae_kl | twophase (BASELINE.json configs 2, 3, 5: forward + loss) and the
@@ -80,7 +87,7 @@ def build_workload(name, B, device, rank):
 
         def step():
             est, est_stft = model(noisy, train=False)
-            return loss.final_ete_loss(est_stft, model.stft(clean), clean, est)[0]
+            return {"loss": loss.final_ete_loss(est_stft, model.stft(clean), clean, est)[0], "est": est, "est_stft": est_stft}
         return step, B, {"workload": "supervised DCCRN-CL forward(train=False) + final_ete_loss (weights 0/0/1)",
                          "batch_per_gpu": B}
     if name == "cvae_elbo":
@@ -92,7 +99,8 @@ def build_workload(name, B, device, rank):
         def step():
             z, miu, ls, dl, skiper, C, F, stft_x = enc(clean, train=False)
             recon, pred = dec(stft_x, z, skiper, C, F, train=False)
-            return loss.cal_loss(clean, recon, stft_x, pred, miu, ls, dl, z, 100)[0]
+            return {"loss": loss.cal_loss(clean, recon, stft_x, pred, miu, ls, dl, z, 100)[0], "recon": recon, "pred": pred,
+                    "miu": miu, "log_sigma": ls}
         return step, B, {"workload": "pretrained CVAE forward (eval BN) + ELBO, num_samples=5", "batch_per_gpu": B}
     if name == "nsvae_kl":
         ns, zdim = 2, 128
@@ -107,8 +115,9 @@ def build_workload(name, B, device, rank):
             # three independent encoders: one HIP stream each (their H = 384 / 768 recurrences are latency-bound)
             c, n, s = ops.concurrent([lambda: ce(clean, train=False), lambda: ne(noise, train=False),
                                       lambda: se(noisy, train=False)], device)
-            return loss.final_nsvae_loss(c[1], n[1], s[1], s[5], c[2], n[2], s[2], s[6], c[3], n[3], s[3], s[7],
-                                         s[0], s[4], c[4], n[4], s[8])[0]
+            return {"loss": loss.final_nsvae_loss(c[1], n[1], s[1], s[5], c[2], n[2], s[2], s[6], c[3], n[3], s[3], s[7],
+                                                  s[0], s[4], c[4], n[4], s[8])[0],
+                    "miu_speech": s[1], "log_sigma_speech": s[2], "miu_noise": s[5], "log_sigma_noise": s[6]}
         return step, B, {"workload": "NSVAE: 2 frozen CVAE/NVAE encoders + noisy encoder (latent_num=2) + nsvae KL loss",
                          "batch_per_gpu": B}
     if name == "twophase":
@@ -120,7 +129,7 @@ def build_workload(name, B, device, rank):
         def step():
             s = se(noisy, train=False)
             recon, pred = dec(s[11], s[0], s[8], s[9], s[10], train=False, pad='sig')
-            return loss.phase_2_loss(pred, s[11], clean, recon, None, None, None, None)[0]
+            return {"loss": loss.phase_2_loss(pred, s[11], clean, recon, None, None, None, None)[0], "recon": recon, "pred": pred}
         return step, B, {"workload": "two-phase decoder fine-tune forward: frozen NSVAE encoder + decoder(mask, pad='sig') + SI-SNR",
                          "batch_per_gpu": B}
     if name in ("enhance", "enhance_complex_mask"):
@@ -133,13 +142,17 @@ def build_workload(name, B, device, rank):
         dec = synth_state(pm.nsvae_pvae_dccrn_decoder_twophase(np_, True, device, ns, zdim, NFFT, HOP, WIN, "mask", True, SKIP, False), 57).to(device)
         if name == "enhance":
             def step():
-                return inf.compute_sisdr(inf.enhance_vae(se, dec, noisy, check=False), clean).mean()
+                enhanced = inf.enhance_vae(se, dec, noisy, check=False)
+                sisdr = inf.compute_sisdr(enhanced, clean)
+                return {"loss": sisdr.mean(), "enhanced": enhanced, "sisdr": sisdr}
             what = "enhancement inference: noisy encoder + fine-tuned decoder on 10 latent samples, mean over samples, SI-SDR"
         else:
             dn = synth_state(pm.nsvae_pvae_dccrn_decoder_twophase(np_, True, device, ns, zdim, NFFT, HOP, WIN, "mask", True, SKIP, False), 58).to(device)
 
             def step():
-                return inf.compute_sisdr(inf.enhance_vae_two_latents(se, dec, dn, noisy, "complex_mask", 2, check=False), clean).mean()
+                enhanced = inf.enhance_vae_two_latents(se, dec, dn, noisy, "complex_mask", 2, check=False)
+                sisdr = inf.compute_sisdr(enhanced, clean)
+                return {"loss": sisdr.mean(), "enhanced": enhanced, "sisdr": sisdr}
             what = ("enhancement inference, latent_to_use 2: noisy encoder + speech and noise decoders on 10 latent samples each, "
                     "complex-mask estimator, ISTFT, SI-SDR")
         return step, B, {"workload": what, "batch_per_gpu": B, "num_samples": ns}
@@ -171,7 +184,7 @@ def build_workload(name, B, device, rank):
                 if red is not None:
                     red.reduce()
                 opt.step()
-            return loss.detach()
+            return {"loss": loss.detach(), "params": params}      # the parameters after Adam: what the trainer goes on with
         return step
 
     if name == "dccrn_cl_train":
@@ -540,9 +553,11 @@ def two_stream_probe(step, steps, ops, utt_per_step, batch):
         ops.STREAM_SPLIT = keep
 
 
-def timed(step, steps, ops, barrier=None):
+def timed(step, steps, ops, barrier=None, log_launches=True):
+    """steps x step() between two device synchronisations -> (seconds, launch log, what the last step returned).  With
+    log_launches the contraction launches record HIP events inside the region (the material of `roofline`, --full)."""
     import torch
-    ops.LAUNCH_LOG = []
+    ops.LAUNCH_LOG = [] if log_launches else None
     if barrier:
         barrier()
     torch.cuda.synchronize()
@@ -559,21 +574,67 @@ def timed(step, steps, ops, barrier=None):
     return el, launches, last
 
 
+DUMP_BUDGET_BYTES = 60_000_000      # --dump-outputs: all .npy files of a run together, headers included (under 64 MB)
+
+
+def host_arrays(outputs):
+    """What one step returned -> {name: numpy array}: float64 tensors stay float64, every other tensor becomes float32, a
+    complex tensor its (real, imag) pairs in a trailing axis of 2, a list of tensors (a train step's parameters) one flat array
+    in parameter order."""
+    import torch
+    out = {}
+    for name, t in outputs.items():
+        if isinstance(t, (list, tuple)):
+            t = torch.cat([p_.detach().reshape(-1).float() for p_ in t])
+        t = t.detach()
+        if t.is_complex():
+            t = torch.view_as_real(t)
+        out[name] = (t.double() if t.dtype == torch.float64 else t.float()).cpu().numpy()
+    return out
+
+
+def write_outputs(directory, arrays, budget=DUMP_BUDGET_BYTES):
+    """DIR/<name>.npy for every output, smallest first, each within an equal share of what the budget has left: an output
+    larger than its share is written as a fixed, seeded sample of its flattened elements (sorted indices, the same in every
+    run with the same arguments)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    names = sorted(arrays, key=lambda k: (arrays[k].nbytes, k))
+    left = budget
+    for i, name in enumerate(names):
+        a = arrays[name]
+        keep = max(1, (left // (len(names) - i) - 128) // a.itemsize)          # 128: the .npy header
+        if a.size > keep:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))
+            log(f"dump {name}: {a.size} elements of shape {a.shape}, writing a seeded sample of {keep}")
+            a = a.reshape(-1)[idx]
+        path = os.path.join(directory, name + ".npy")
+        np.save(path, a)
+        left -= os.path.getsize(path)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=None, help="utterances per GPU per step (default 64; train workloads 32)")
     ap.add_argument("--workload", default="dccrn_cl")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-alt", action="store_true", help="skip the secondary bf16x3 record")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline does not need: `roofline` "
+                    "(launch events inside the timed region), the fp32 two-stream probe, the bf16x3 record `alt` and `cpu_baseline`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed (rank 0) as DIR/<name>.npy, float32 or "
+                         "float64, under 64 MB in all: an output over its share is a fixed, seeded sample of its elements")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip `cpu_baseline`")
+    ap.add_argument("--no-alt", action="store_true", help="--full: skip the secondary bf16x3 record and the two-stream probe")
     ap.add_argument("--stream", action="store_true", help="twophase_train: stream fresh synthetic DNS3-shaped mixtures from the "
                     "host every step (pinned memory + copy stream) instead of re-using one resident batch")
     ap.add_argument("--precision", default=os.environ.get("IDV_PRECISION", "fp32"), choices=["fp32", "bf16x3"],
                     help="conv contraction arithmetic of the HEADLINE: exact fp32 MFMA (the reference's precision, default), "
                          "or split-bf16 (3 bf16 MFMAs, fp32 accumulate)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     train = args.workload in TRAIN_WORKLOADS
     global STREAM
     STREAM = args.stream
@@ -614,6 +675,9 @@ def main():
     ops = importlib.import_module("i-dccrn-vae_amd").ops
     ops.set_precision(args.precision)
     torch.set_grad_enabled(False)                # train workloads enable grad inside their step
+    # the VAE workloads draw their latent samples from torch's default generators: seeded, like the inputs, so that a run
+    # with the same arguments draws the same samples
+    torch.manual_seed(123 + 1000 * rank)
     step, utt_per_step, cfg = build_workload(args.workload, args.batch, device, rank)
 
     log(f"workload {args.workload} B={args.batch} precision={args.precision} built; warmup {args.warmup}")
@@ -626,28 +690,32 @@ def main():
         if dist_on:
             dist.barrier()
 
-    elapsed, launches, last = timed(step, args.steps, ops, barrier)
-    loss_val = float(last)
+    elapsed, launches, last = timed(step, args.steps, ops, barrier, log_launches=args.full)
     log(f"timed {args.steps} steps in {elapsed:.3f} s")
+    loss_val = float(last["loss"])
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, host_arrays(last))
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
+    del last
     n_streams = ops.stream_split(args.batch) if args.workload == "dccrn_cl" else 1
 
     dt = importlib.import_module("i-dccrn-vae_amd.utils.dist_timing")
     red_dev = device if (not dist_on or dist.get_backend() == "nccl") else torch.device("cpu")
     value, elapsed_max = dt.job_throughput(elapsed, float(utt_per_step * args.steps), red_dev, force=dist_on)
-    roofline = roofline_of(launches, args.steps, elapsed / args.steps, args.precision, args.batch, args.workload)
+    roofline = roofline_of(launches, args.steps, elapsed / args.steps, args.precision, args.batch, args.workload) if args.full else None
     if roofline is not None and n_streams > 1:
         roofline["note"] = (f"timed region ran {n_streams} sub-batch streams (IDV_STREAM_SPLIT): event intervals include CU "
                             "time-slicing with the other stream")
 
     # ---- informational: the same fp32 workload with the opt-in two-stream sub-batch split (never `value`), checked bit for bit
     two_f32 = None
-    if (world == 1 and not args.no_alt and args.workload == "dccrn_cl" and args.precision == "fp32" and n_streams == 1):
+    if (args.full and world == 1 and not args.no_alt and args.workload == "dccrn_cl" and args.precision == "fp32" and n_streams == 1):
         two_f32 = two_stream_probe(step, args.steps, ops, utt_per_step, args.batch)
         log(f"fp32 two-stream (opt-in): {two_f32}")
 
     # ---- secondary record: the split-bf16 mode on the same workload (narrower arithmetic than the reference: never `value`)
     alt = None
-    if (world == 1 and not args.no_alt and args.workload == "dccrn_cl" and args.precision == "fp32"):
+    if (args.full and world == 1 and not args.no_alt and args.workload == "dccrn_cl" and args.precision == "fp32"):
         keep_split = ops.STREAM_SPLIT
         try:
             ops.set_precision("bf16x3")
@@ -658,7 +726,7 @@ def main():
             alt = {"dtype": "bf16x3 (split-fp32 operands on the bf16 MFMA: w*x ~ w_hi*x_hi + w_hi*x_lo + w_lo*x_hi, fp32 "
                             "accumulate; ~16-17 significant bits per operand, waveform 5e-6 from the fp32 reference)",
                    "value": round(utt_per_step * args.steps / a_el, 3), "unit": "utterances/sec",
-                   "ms_per_step": round(a_el / args.steps * 1e3, 3), "streams": 1, "loss": float(a_last),
+                   "ms_per_step": round(a_el / args.steps * 1e3, 3), "streams": 1, "loss": float(a_last["loss"]),
                    "roofline": roofline_of(a_launch, args.steps, a_el / args.steps, "bf16x3", args.batch, args.workload)}
             ts = two_stream_probe(step, args.steps, ops, utt_per_step, args.batch)
             alt["two_stream"], alt["two_stream_bit_exact"] = ts["two_stream"], ts["bit_exact"]
@@ -682,17 +750,18 @@ def main():
                            parallelism=(f"data-parallel x{world}: sharded batch, Sync-CBN moment all-reduce, gradient all-reduce (RCCL)"
                                         if train else f"replicas x{world}"),
                            streams=n_streams, loss=loss_val, input=("streamed from the host per step" if args.stream else "resident in HBM")),
-            "roofline": roofline,
         }
+        if args.full:
+            out["roofline"] = roofline
         if two_f32 is not None:
             out["two_stream"] = dict(two_f32["two_stream"], bit_exact=two_f32["bit_exact"],
                                      note="opt-in IDV_STREAM_SPLIT=2 (DESIGN.md 5.1); `value` is the one-stream default")
         if alt is not None:
             out["alt"] = alt
-        if world == 1 and not args.no_cpu_baseline and args.workload in ("dccrn_cl", "dccrn_cl_train"):
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload in ("dccrn_cl", "dccrn_cl_train"):
             log("cpu baseline ...")
             out["cpu_baseline"] = cpu_baseline(train=train)
-        else:
+        elif args.full:
             out["cpu_baseline"] = None
         print(json.dumps(out))
     if dist_on:

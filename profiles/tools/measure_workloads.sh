@@ -1,6 +1,6 @@
 set -o pipefail
 o=gpurun_out/meas; mkdir -p $o
-b() { name=$1; shift; timeout -k 10 250 python bench.py "$@" --no-cpu-baseline > $o/$name.json 2> $o/$name.err || { echo FAIL $name; tail -3 $o/$name.err; exit 1; }; echo $name done; }
+b() { name=$1; shift; timeout -k 10 250 python bench.py --full "$@" --no-cpu-baseline > $o/$name.json 2> $o/$name.err || { echo FAIL $name; tail -3 $o/$name.err; exit 1; }; echo $name done; }
 b nsvae_kl_bf16 --workload nsvae_kl --precision bf16x3 --batch 32 --steps 10 --warmup 3
 IDV_CONCURRENT=1 b nsvae_kl_bf16_conc --workload nsvae_kl --precision bf16x3 --batch 32 --steps 10 --warmup 3
 b nsvae_kl_f32 --workload nsvae_kl --batch 32 --steps 6 --warmup 2

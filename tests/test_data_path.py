@@ -26,15 +26,18 @@ def _write(path, n, seed, fs=16000, dtype="int16"):
     return x.astype(np.float32)
 
 
-def test_segment_indexing_matches_the_reference_formulas(dl, tmp_path):
+def test_segment_indexing_matches_the_reference_formulas(dl, tmp_path, monkeypatch):
     hop, seq = 100, 31                                  # seq_length = 3000 samples
     lens = {"a": 9100, "b": 2999, "c": 3100, "d": 48000, "e": 0}
     noisy_dir, clean_dir, noise_dir = tmp_path / "noisy", tmp_path / "clean", tmp_path / "noise"
     for d_ in (noisy_dir, clean_dir, noise_dir):
         d_.mkdir()
+    # the file id is read from the WHOLE noisy path up to its first '.' (as the reference does): noisy files are named
+    # relative to tmp_path, so a '.' in the directories above it cannot cut the path short
+    monkeypatch.chdir(tmp_path)
     files, sigs = [], {}
     for k, (name, n) in enumerate(lens.items()):
-        f = str(noisy_dir / f"mix_snr5_fileid_{k}.wav")
+        f = os.path.join("noisy", f"mix_snr5_fileid_{k}.wav")
         sigs[k] = (_write(f, n, k), _write(str(clean_dir / f"clean_fileid_{k}.wav"), n, 100 + k, dtype="float32"),
                    _write(str(noise_dir / f"noise_fileid_{k}.wav"), n, 200 + k))
         files.append(f)

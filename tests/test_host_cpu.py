@@ -301,6 +301,33 @@ def test_bench_self_launch_starts_ranks_as_a_child_and_relays_rank0(monkeypatch,
     assert ("torch" in _sys.modules) == had_torch                       # the launcher itself imports no torch
 
 
+def test_bench_dump_outputs_fits_the_budget_and_samples_the_same_elements(tmp_path):
+    """`bench.py --dump-outputs DIR`: every output of the last step as DIR/<name>.npy in float32 (float64 stays float64),
+    complex as (real, imag) pairs, a train step's parameter list flattened; all files together under the budget, an output
+    over its share replaced by a seeded sample that is the same in every run."""
+    import numpy as np
+    bench = importlib.import_module("bench")
+    g = torch.Generator().manual_seed(3)
+    outs = {"loss": torch.tensor(0.25), "est": torch.randn(8, 6400, generator=g),
+            "est_stft": torch.randn(8, 257, 65, 2, generator=g), "d": torch.randn(5, generator=g, dtype=torch.float64),
+            "params": [torch.randn(40, 3, generator=g), torch.randn(7, generator=g).bfloat16()]}
+    outs["est_stft"] = torch.view_as_complex(outs["est_stft"])
+    budget = 500_000                  # est (205 kB) fits its share, est_stft (1.07 MB) does not
+    for d in ("a", "b"):
+        bench.write_outputs(str(tmp_path / d), bench.host_arrays(outs), budget=budget)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["d.npy", "est.npy", "est_stft.npy", "loss.npy", "params.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= budget
+    a = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert a["d"].dtype == np.float64 and all(v.dtype == np.float32 for k, v in a.items() if k != "d")
+    assert float(a["loss"]) == 0.25 and a["params"].shape == (127,)
+    np.testing.assert_array_equal(a["est"], outs["est"].numpy())                                # small enough: whole
+    stft = torch.view_as_real(outs["est_stft"]).numpy().reshape(-1)
+    assert 0 < a["est_stft"].size < stft.size and np.isin(a["est_stft"], stft).all()           # too large: a sample
+    for f in files:
+        np.testing.assert_array_equal(a[f[:-4]], np.load(tmp_path / "b" / f))
+
+
 def test_call_sites_match_header_prototypes(amd):
     """Static ABI check (no GPU): every ``call("idv_x", ...)`` / ``lib().idv_x(...)`` / ``_ll_fn("idv_x")(...)`` site of the package,
     bench.py and the tests passes as many arguments as include/idccrn_hip.h declares, with wrappers (p / i / ll / f / d) of the
