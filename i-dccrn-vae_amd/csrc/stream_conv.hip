@@ -1,0 +1,258 @@
+// Streaming complex conv / transposed conv of the DCCRN blocks (model/complex_progress.py:8-36, 222-279) over the k frames
+// that one push of streaming.StreamingDCCRN completes, with the frame before them taken from a per-stream history column.
+//
+// Time taps: conv y[t] = W0 x[t-1] + W1 x[t], transposed y[t] = W0 x[t] + W1 x[t-1] (causal crop).  x[t-1] of a stream's
+// first frame comes from hist_in ([2][C][F][B]), of the others from the same source; the last output column of every stream
+// goes to hist_out (NULL: no consumer), so the next push finds its x[t-1] there.  The caller double-buffers hist by push parity: a block reads
+// hist[p] and writes hist[1-p], and the consumer of this block's output still finds the previous column in hist[p].
+//
+// Vector-ALU contraction: one lane = one (output bin, column), CO_T complex output channels in registers; the weights of one
+// (ci, kf) are the same for the whole workgroup (scalar loads).  Split-K over the input channels: nsplit parts write
+// partial sums, idv_stream_cconv_combine adds them in the order 0..nsplit-1 and runs the epilogue (bias, folded eval BN,
+// PReLU).  nsplit is a function of the layer shape and B only (idv_stream_cconv_splits), so the arithmetic of every column
+// is the same however a signal is cut into pushes.
+#include "common.hpp"
+#include "../../include/idccrn_hip.h"
+
+namespace {
+
+constexpr int SC_THREADS = 256;
+
+struct SconvArgs {
+    const float* x0; const float* h0; int C0;
+    const float* x1; const float* h1; int C1;
+    const float* w;         // [co tiles][Cin][5][CO_T][4]: (wr, wi) of the x[t-1] tap, (wr, wi) of the x[t] tap
+    const float* bias;      // [Cout][2]: (b_re - b_im, b_re + b_im)
+    const float* fold;      // [Cout][6] or NULL
+    const float* slope;     // PReLU slope or NULL
+    float* out; float* hist_out; float* x0hist_out;
+    float* work;            // [nsplit][2][Cout][Fout][J] partial sums (nsplit > 1)
+    int transposed, Cout, Fin, Fout, B, k, Tp, Jp, nsplit, cps;
+};
+
+__device__ __forceinline__ void epilogue(const SconvArgs& a, int co, int fo, int b, int t, float vr, float vi) {
+    vr += a.bias[2 * co];
+    vi += a.bias[2 * co + 1];
+    if (a.fold) {
+        const float* z = a.fold + (size_t)co * 6;
+        const float r = z[0] * vr + z[1] * vi + z[4];
+        const float i = z[2] * vr + z[3] * vi + z[5];
+        vr = r; vi = i;
+    }
+    if (a.slope) {
+        const float s = *a.slope;
+        vr = vr >= 0.f ? vr : s * vr;
+        vi = vi >= 0.f ? vi : s * vi;
+    }
+    const size_t plane = (size_t)a.Fout * a.Jp;
+    const size_t o = (size_t)co * plane + (size_t)fo * a.Jp + (size_t)b * a.Tp + 1 + t;
+    a.out[o] = vr;
+    a.out[(size_t)a.Cout * plane + o] = vi;
+    if (a.hist_out && t == a.k - 1) {
+        const size_t h = ((size_t)co * a.Fout + fo) * a.B + b;
+        a.hist_out[h] = vr;
+        a.hist_out[(size_t)a.Cout * a.Fout * a.B + h] = vi;
+    }
+}
+
+// grid: x = position blocks, y = co tiles, z = split * (transposed ? 2 : 1) + output-bin parity
+template <int CO_T>
+__global__ __launch_bounds__(SC_THREADS) void stream_cconv_kernel(const SconvArgs a) {
+    const int J = a.B * a.k;
+    const int par = a.transposed ? (int)(blockIdx.z & 1) : 0;
+    const int split = a.transposed ? (int)(blockIdx.z >> 1) : (int)blockIdx.z;
+    const int cot = blockIdx.y;
+    const int Cin = a.C0 + a.C1;
+
+    // last input column of x0 -> x0hist_out (the source's own producer cannot write its history)
+    if (a.x0hist_out && blockIdx.y == 0 && blockIdx.z == 0) {
+        const long long n = 2LL * a.C0 * a.Fin * a.B;
+        for (long long e = blockIdx.x * (long long)SC_THREADS + threadIdx.x; e < n; e += (long long)gridDim.x * SC_THREADS) {
+            const int b = (int)(e % a.B);
+            const long long pf = e / a.B;                     // (ri * C0 + ci) * Fin + fi
+            a.x0hist_out[e] = a.x0[pf * a.Jp + (long long)b * a.Tp + a.k];
+        }
+    }
+
+    const int nfq = a.transposed ? (par == 0 ? a.Fin : a.Fin - 1) : a.Fout;
+    const int q = blockIdx.x * SC_THREADS + threadIdx.x;
+    const bool live = q < nfq * J;
+    const int fq = live ? q / J : 0, j = live ? q - (q / J) * J : 0;
+    const int b = j / a.k, t = j - b * a.k;
+    const int fo = a.transposed ? 2 * fq + par : fq;
+    const int ci0 = split * a.cps, ci1 = min(Cin, ci0 + a.cps);
+
+    float accr[CO_T], acci[CO_T];
+#pragma unroll
+    for (int c = 0; c < CO_T; ++c) accr[c] = acci[c] = 0.f;
+
+    const size_t colc = (size_t)b * a.Tp + 1 + t;
+    for (int ci = ci0; ci < ci1; ++ci) {
+        const bool second = ci >= a.C0;
+        const float* x = second ? a.x1 : a.x0;
+        const float* hs = second ? a.h1 : a.h0;
+        const int C = second ? a.C1 : a.C0;
+        const int cl = second ? ci - a.C0 : ci;
+        const size_t pr = (size_t)cl * a.Fin, pi = (size_t)(C + cl) * a.Fin;
+        const float* wc = a.w + ((size_t)cot * Cin + ci) * 5 * CO_T * 4;
+        for (int kf = a.transposed ? par : 0; kf < 5; kf += a.transposed ? 2 : 1) {
+            const int fi = a.transposed ? (fo + 2 - kf) / 2 : 2 * fo - 2 + kf;
+            const bool ok = live && fi >= 0 && fi < a.Fin;
+            float xcr = 0.f, xci = 0.f, xpr = 0.f, xpi = 0.f;
+            if (ok) {
+                xcr = x[(pr + fi) * a.Jp + colc];
+                xci = x[(pi + fi) * a.Jp + colc];
+                if (t > 0) {
+                    xpr = x[(pr + fi) * a.Jp + colc - 1];
+                    xpi = x[(pi + fi) * a.Jp + colc - 1];
+                } else {
+                    xpr = hs[(pr + fi) * a.B + b];
+                    xpi = hs[(pi + fi) * a.B + b];
+                }
+            }
+            const float* wk = wc + kf * CO_T * 4;
+#pragma unroll
+            for (int c = 0; c < CO_T; ++c) {
+                const float wrp = wk[4 * c], wip = wk[4 * c + 1], wrc = wk[4 * c + 2], wic = wk[4 * c + 3];
+                accr[c] = fmaf(wrp, xpr, accr[c]);
+                accr[c] = fmaf(-wip, xpi, accr[c]);
+                accr[c] = fmaf(wrc, xcr, accr[c]);
+                accr[c] = fmaf(-wic, xci, accr[c]);
+                acci[c] = fmaf(wrp, xpi, acci[c]);
+                acci[c] = fmaf(wip, xpr, acci[c]);
+                acci[c] = fmaf(wrc, xci, acci[c]);
+                acci[c] = fmaf(wic, xcr, acci[c]);
+            }
+        }
+    }
+    if (!live) return;
+#pragma unroll
+    for (int c = 0; c < CO_T; ++c) {
+        const int co = cot * CO_T + c;
+        if (co >= a.Cout) break;
+        if (a.nsplit == 1) {
+            epilogue(a, co, fo, b, t, accr[c], acci[c]);
+        } else {
+            const size_t slab = (size_t)a.Cout * a.Fout * J;
+            const size_t o = (size_t)split * 2 * slab + ((size_t)co * a.Fout + fo) * J + j;
+            a.work[o] = accr[c];
+            a.work[o + slab] = acci[c];
+        }
+    }
+}
+
+__global__ void stream_cconv_combine_kernel(const SconvArgs a) {
+    const int J = a.B * a.k;
+    const long long n = (long long)a.Cout * a.Fout * J;
+    const size_t slab = (size_t)n;
+    for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
+        const int j = (int)(e % J);
+        const int fo = (int)((e / J) % a.Fout);
+        const int co = (int)(e / ((long long)J * a.Fout));
+        float vr = 0.f, vi = 0.f;
+        for (int s = 0; s < a.nsplit; ++s) {             // fixed order
+            vr += a.work[(size_t)s * 2 * slab + e];
+            vi += a.work[(size_t)s * 2 * slab + slab + e];
+        }
+        epilogue(a, co, fo, j / a.k, j % a.k, vr, vi);
+    }
+}
+
+// w_re / w_im: conv [Cout][Cin][5][2], transposed [Cin][Cout][5][2]; taps reordered to (x[t-1], x[t])
+__global__ void stream_pack_cconv_kernel(const float* __restrict__ w_re, const float* __restrict__ w_im,
+                                         const float* __restrict__ b_re, const float* __restrict__ b_im, int Cin, int Cout,
+                                         int transposed, int co_t, float* __restrict__ w, float* __restrict__ bias) {
+    const int ntile = (Cout + co_t - 1) / co_t;
+    const long long n = (long long)ntile * Cin * 5 * co_t * 4;
+    for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
+        const int r = (int)(e & 3);
+        const int c = (int)((e >> 2) % co_t);
+        const int kf = (int)((e / (4LL * co_t)) % 5);
+        const int ci = (int)((e / (20LL * co_t)) % Cin);
+        const int tile = (int)(e / (20LL * co_t * Cin));
+        const int co = tile * co_t + c;
+        float v = 0.f;
+        if (co < Cout) {
+            const int tap_prev = transposed ? 1 : 0;
+            const int kt = (r < 2) ? tap_prev : 1 - tap_prev;
+            const size_t src = transposed ? (((size_t)ci * Cout + co) * 5 + kf) * 2 + kt : (((size_t)co * Cin + ci) * 5 + kf) * 2 + kt;
+            v = (r & 1) ? w_im[src] : w_re[src];
+        }
+        w[e] = v;
+    }
+    for (int co = blockIdx.x * blockDim.x + threadIdx.x; co < Cout; co += gridDim.x * blockDim.x) {
+        bias[2 * co] = b_re[co] - b_im[co];
+        bias[2 * co + 1] = b_re[co] + b_im[co];
+    }
+}
+
+inline int co_tile(int Cout) { return Cout >= 16 ? 16 : 1; }
+
+inline int fout_of(int transposed, int Fin) { return transposed ? 2 * Fin - 1 : (Fin - 1) / 2 + 1; }
+
+}  // namespace
+
+extern "C" long long idv_stream_cconv_wfloats(int Cin, int Cout) {
+    if (Cin <= 0 || Cout <= 0) return -1;
+    const int ct = co_tile(Cout);
+    return (long long)((Cout + ct - 1) / ct) * Cin * 5 * ct * 4;
+}
+
+extern "C" int idv_stream_pack_cconv(const float* w_re, const float* w_im, const float* b_re, const float* b_im, int Cin, int Cout,
+                                     int transposed, float* w, float* bias, void* stream) {
+    if (!w_re || !w_im || !b_re || !b_im || !w || !bias || Cin <= 0 || Cout <= 0) return IDV_EINVAL;
+    const long long n = idv_stream_cconv_wfloats(Cin, Cout);
+    long long g = (n + 255) / 256;
+    g = g > 4096 ? 4096 : (g < 1 ? 1 : g);
+    hipLaunchKernelGGL(stream_pack_cconv_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, w_re, w_im, b_re, b_im, Cin,
+                       Cout, transposed ? 1 : 0, co_tile(Cout), w, bias);
+    return idv_launch_status();
+}
+
+extern "C" int idv_stream_cconv_splits(int transposed, int Cin, int Cout, int Fin, int B) {
+    if (Cin <= 0 || Cout <= 0 || Fin <= 0 || B <= 0) return -1;
+    // about 1024 workgroups at one frame per stream, no part below 8 input channels, at most 32 parts
+    const int ct = co_tile(Cout);
+    const long long pos = (long long)(transposed ? 2 * Fin - 1 : fout_of(0, Fin)) * B;
+    const long long wgs = (pos + SC_THREADS - 1) / SC_THREADS * ((Cout + ct - 1) / ct);
+    long long s = 1024 / (wgs > 0 ? wgs : 1);
+    const long long smax = Cin / 8 > 1 ? Cin / 8 : 1;
+    if (s > smax) s = smax;
+    if (s > 32) s = 32;
+    return s < 1 ? 1 : (int)s;
+}
+
+extern "C" int idv_stream_cconv(const float* x0, const float* h0, int C0, const float* x1, const float* h1, int C1,
+                                const float* w, const float* bias, const float* fold, const float* prelu_slope, float* out,
+                                float* hist_out, float* x0hist_out, float* work, int nsplit, int transposed, int Cout, int Fin,
+                                int B, int k, int Tp, int Jp, void* stream) {
+    if (!x0 || !h0 || C0 <= 0 || C1 < 0 || (C1 > 0 && (!x1 || !h1)) || !w || !bias || !out || Cout <= 0 ||
+        Fin <= 0 || B <= 0 || k <= 0 || Tp < k + 1 || Jp < B * Tp || nsplit <= 0 || (nsplit > 1 && !work))
+        return IDV_EINVAL;
+    SconvArgs a{};
+    a.x0 = x0; a.h0 = h0; a.C0 = C0; a.x1 = x1; a.h1 = h1; a.C1 = C1;
+    a.w = w; a.bias = bias; a.fold = fold; a.slope = prelu_slope;
+    a.out = out; a.hist_out = hist_out; a.x0hist_out = x0hist_out; a.work = work;
+    a.transposed = transposed ? 1 : 0; a.Cout = Cout; a.Fin = Fin; a.Fout = fout_of(a.transposed, Fin);
+    a.B = B; a.k = k; a.Tp = Tp; a.Jp = Jp; a.nsplit = nsplit;
+    const int Cin = C0 + C1;
+    a.cps = (Cin + nsplit - 1) / nsplit;
+    const long long J = (long long)B * k;
+    const int nfq = a.transposed ? Fin : a.Fout;
+    const long long pos = nfq * J;
+    if (pos > 0x7fffffffLL) return IDV_EINVAL;
+    const int ct = co_tile(Cout);
+    dim3 grid((unsigned)((pos + SC_THREADS - 1) / SC_THREADS), (unsigned)((Cout + ct - 1) / ct),
+              (unsigned)(nsplit * (a.transposed ? 2 : 1)));
+    hipStream_t st = (hipStream_t)stream;
+    if (ct == 16)
+        hipLaunchKernelGGL(stream_cconv_kernel<16>, grid, dim3(SC_THREADS), 0, st, a);
+    else
+        hipLaunchKernelGGL(stream_cconv_kernel<1>, grid, dim3(SC_THREADS), 0, st, a);
+    int rc = idv_launch_status();
+    if (rc || nsplit == 1) return rc;
+    long long g = ((long long)Cout * a.Fout * J + 255) / 256;
+    g = g > 4096 ? 4096 : (g < 1 ? 1 : g);
+    hipLaunchKernelGGL(stream_cconv_combine_kernel, dim3((unsigned)g), dim3(256), 0, st, a);
+    return idv_launch_status();
+}

@@ -1,0 +1,143 @@
+// Streaming two-layer complex LSTM (model/complex_progress.py:39-74) over the k steps of one push, with h and c of both layers
+// carried in device state buffers from push to push.  The layer-0 input projection (W_ih0 x + b_ih0 + b_hh0) comes from
+// idv_pw_gemm with the idv_pack_lstm_ih fragments, as in the offline path; this kernel adds W_hh0 h0, runs the cell, then
+// layer 1 (W_ih1 h0 + W_hh1 h1 + b1) for the same step.
+//
+// One workgroup = one run (input part z x weight set s, run = 2z + s) x SB streams; thread r owns gate row r (torch order
+// i, f, g, o).  The three [4H][H] matrices of the weight set are read transposed ([H][4H], coalesced along r) from L2 on
+// every step: 3 x 256 KiB per weight set at H = 128.  No cooperative launch, no spin-wait.
+#include "common.hpp"
+#include "../../include/idccrn_hip.h"
+
+namespace {
+
+constexpr int SL_H = 128;
+constexpr int SL_SB = 8;
+
+__global__ __launch_bounds__(4 * SL_H) void stream_lstm_kernel(const float* __restrict__ G, const float* __restrict__ wt,
+                                                               const float* __restrict__ b1, float* __restrict__ state,
+                                                               float* __restrict__ hout, int B, int k) {
+    constexpr int H = SL_H, SB = SL_SB, G4 = 4 * H;
+    __shared__ float hs0[SB][H], hs1[SB][H], gs[SB][G4];
+    const int r = threadIdx.x;
+    const int run = blockIdx.y, z = run >> 1, s = run & 1;
+    const int b0 = blockIdx.x * SB;
+    const float* w_hh0 = wt + (size_t)(s * 3 + 0) * H * G4;
+    const float* w_ih1 = wt + (size_t)(s * 3 + 1) * H * G4;
+    const float* w_hh1 = wt + (size_t)(s * 3 + 2) * H * G4;
+    const float bias1 = b1[s * G4 + r];
+    // state[run][layer][h | c][B][H]
+    float* st = state + (size_t)run * 4 * B * H;
+    const size_t sz = (size_t)B * H;
+
+    constexpr int PAIRS = SB * H / G4;              // (stream, unit) pairs whose cells this thread updates
+    float c0[PAIRS], c1[PAIRS];
+#pragma unroll
+    for (int q = 0; q < PAIRS; ++q) {
+        const int e = r + q * G4, sb = e / H, u = e % H, b = b0 + sb;
+        const bool ok = b < B;
+        hs0[sb][u] = ok ? st[0 * sz + (size_t)b * H + u] : 0.f;
+        c0[q] = ok ? st[1 * sz + (size_t)b * H + u] : 0.f;
+        hs1[sb][u] = ok ? st[2 * sz + (size_t)b * H + u] : 0.f;
+        c1[q] = ok ? st[3 * sz + (size_t)b * H + u] : 0.f;
+    }
+    // column of gate row r in the idv_pack_lstm_ih order: set s, ((u/16)*4 + g)*16 + u%16
+    const int g_r = r / H, u_r = r % H;
+    const int colp = s * G4 + ((u_r >> 4) * 4 + g_r) * 16 + (u_r & 15);
+    __syncthreads();
+
+    for (int t = 0; t < k; ++t) {
+        float acc[SB];
+#pragma unroll
+        for (int sb = 0; sb < SB; ++sb) {
+            const int b = min(b0 + sb, B - 1);
+            acc[sb] = G[(size_t)z * k * B * 2 * G4 + ((size_t)t * B + b) * 2 * G4 + colp];
+        }
+        for (int kk = 0; kk < H; ++kk) {
+            const float w = w_hh0[(size_t)kk * G4 + r];
+#pragma unroll
+            for (int sb = 0; sb < SB; ++sb) acc[sb] = fmaf(w, hs0[sb][kk], acc[sb]);
+        }
+#pragma unroll
+        for (int sb = 0; sb < SB; ++sb) gs[sb][r] = acc[sb];
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < PAIRS; ++q) {
+            const int e = r + q * G4, sb = e / H, u = e % H;
+            const float ig = sigmoidf_(gs[sb][u]), fg = sigmoidf_(gs[sb][H + u]);
+            const float gg = tanhf_(gs[sb][2 * H + u]), og = sigmoidf_(gs[sb][3 * H + u]);
+            c0[q] = fg * c0[q] + ig * gg;
+            hs0[sb][u] = og * tanhf_(c0[q]);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int sb = 0; sb < SB; ++sb) acc[sb] = bias1;
+        for (int kk = 0; kk < H; ++kk) {
+            const float w = w_ih1[(size_t)kk * G4 + r];
+#pragma unroll
+            for (int sb = 0; sb < SB; ++sb) acc[sb] = fmaf(w, hs0[sb][kk], acc[sb]);
+        }
+        for (int kk = 0; kk < H; ++kk) {
+            const float w = w_hh1[(size_t)kk * G4 + r];
+#pragma unroll
+            for (int sb = 0; sb < SB; ++sb) acc[sb] = fmaf(w, hs1[sb][kk], acc[sb]);
+        }
+#pragma unroll
+        for (int sb = 0; sb < SB; ++sb) gs[sb][r] = acc[sb];
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < PAIRS; ++q) {
+            const int e = r + q * G4, sb = e / H, u = e % H, b = b0 + sb;
+            const float ig = sigmoidf_(gs[sb][u]), fg = sigmoidf_(gs[sb][H + u]);
+            const float gg = tanhf_(gs[sb][2 * H + u]), og = sigmoidf_(gs[sb][3 * H + u]);
+            c1[q] = fg * c1[q] + ig * gg;
+            const float h = og * tanhf_(c1[q]);
+            hs1[sb][u] = h;
+            if (b < B) hout[((size_t)run * k * B + (size_t)t * B + b) * H + u] = h;
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int q = 0; q < PAIRS; ++q) {
+        const int e = r + q * G4, sb = e / H, u = e % H, b = b0 + sb;
+        if (b >= B) continue;
+        st[0 * sz + (size_t)b * H + u] = hs0[sb][u];
+        st[1 * sz + (size_t)b * H + u] = c0[q];
+        st[2 * sz + (size_t)b * H + u] = hs1[sb][u];
+        st[3 * sz + (size_t)b * H + u] = c1[q];
+    }
+}
+
+// real = rr - ii, imag = ir + ri (runs 0, 3, 2, 1) -> planar [2][H][Jp] at column b*Tp + 1 + t
+__global__ void stream_lstm_combine_kernel(const float* __restrict__ h, int H, int B, int k, int Tp, int Jp, float* __restrict__ out) {
+    const long long n = (long long)H * B * k;
+    const size_t run = (size_t)k * B * H;
+    for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
+        const int u = (int)(e % H);
+        const long long tb = e / H;                       // t * B + b
+        const int t = (int)(tb / B), b = (int)(tb % B);
+        const size_t o = (size_t)tb * H + u;
+        const size_t j = (size_t)u * Jp + (size_t)b * Tp + 1 + t;
+        out[j] = h[o] - h[3 * run + o];
+        out[(size_t)H * Jp + j] = h[2 * run + o] + h[run + o];
+    }
+}
+
+}  // namespace
+
+extern "C" int idv_stream_lstm_supported(int H) { return H == SL_H ? 1 : 0; }
+
+extern "C" int idv_stream_clstm(const float* G, const float* wt, const float* b1, float* state, float* hout, float* out, int H, int B,
+                                int k, int Tp, int Jp, void* stream) {
+    if (!G || !wt || !b1 || !state || !hout || !out || B <= 0 || k <= 0 || Tp < k + 1 || Jp < B * Tp) return IDV_EINVAL;
+    if (!idv_stream_lstm_supported(H)) return IDV_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(stream_lstm_kernel, dim3((unsigned)((B + SL_SB - 1) / SL_SB), 4), dim3(4 * SL_H), 0, st, G, wt, b1, state, hout,
+                       B, k);
+    int rc = idv_launch_status();
+    if (rc) return rc;
+    long long g = ((long long)H * B * k + 255) / 256;
+    g = g > 4096 ? 4096 : (g < 1 ? 1 : g);
+    hipLaunchKernelGGL(stream_lstm_combine_kernel, dim3((unsigned)g), dim3(256), 0, st, hout, H, B, k, Tp, Jp, out);
+    return idv_launch_status();
+}

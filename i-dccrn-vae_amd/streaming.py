@@ -1,0 +1,410 @@
+"""Streaming enhancement with a causal DCCRN (DCCRN-CL): chunked ``push`` / ``flush`` on the HIP kernels.
+
+    st = StreamingDCCRN(model, batch=B)     # model: model.pvae_module.DCCRN_ with causal=True, parameters on the GPU
+    y = st.push(x)                          # x: [B, n] float32 on the GPU, n >= 0 -> [B, m]: the samples that became final
+    y = st.flush()                          # end of all B signals -> the remaining samples; the streamer is then reset
+
+Concatenating every ``push`` output and the ``flush`` output gives ``model(x_full, train=False)[0]``.  Every block of the causal
+model reads one frame of history, the LSTM is unidirectional and eval-mode batch norm is a per-channel affine map, so the only
+look-ahead is the STFT window: frame t reads samples [hop*t - win/2, hop*t + win/2).  :class:`StreamPlan` holds the frame and
+emission bookkeeping from which every kernel launch takes its ranges.
+"""
+from __future__ import annotations
+
+from typing import List, NamedTuple, Optional
+
+import torch
+
+from . import _lib as L
+from . import ops
+from ._lib import call, i, ll, p, stream_ptr
+from .ops import Planar
+
+
+class Chunk(NamedTuple):
+    """One launch group of a push: frames t0 .. t0+k-1 (k may be 0 at flush), output samples e0 .. e1-1, padded OLA positions
+    up to p_end, carried overlap lengths in and out, and the history parity it reads (it writes 1 - parity)."""
+    t0: int
+    k: int
+    e0: int
+    e1: int
+    p_end: int
+    carry_in: int
+    carry_out: int
+    parity: int
+
+
+class StreamPlan:
+    """Frame and sample bookkeeping of a lock-step stream (host side only; no tensors).
+
+    With half = n_fft/2 and left = (n_fft - win)/2, frame t reads original samples s = hop*t + lo + i, i in [0, win), lo = left -
+    half, mirrored at the start (x[-s] = x[s]) and, at flush, at the end (x[L-1+j] = x[L-1-j]).  Before the end is known, frame t
+    is computable once every sample it reads has arrived, the mirrored ones included; output sample m is final once every frame
+    t with hop*t + left <= m + half is done."""
+
+    def __init__(self, n_fft: int, hop: int, win: int, cap: int = 64):
+        if not (0 < win <= n_fft and hop > 0 and cap > 0):
+            raise ValueError("StreamPlan: need 0 < win <= n_fft, hop > 0, cap > 0")
+        self.n_fft, self.hop, self.win, self.cap = n_fft, hop, win, cap
+        self.half = n_fft // 2
+        self.left = (n_fft - win) // 2
+        self.lo = self.left - self.half              # first sample of frame 0 (before mirroring)
+        self.hi = self.lo + win                      # one past its last sample
+        self.ring = n_fft                            # input samples kept from push to push
+        self.carry_cap = n_fft + win                 # overlap-add positions kept from push to push
+        self.reset()
+
+    def reset(self):
+        self.n = 0            # samples received
+        self.k = 0            # frames computed
+        self.emitted = 0      # output samples returned
+        self.carry = 0        # overlap-add positions carried
+        self.parity = 0
+
+    # -- formulas
+    def frames_ready(self, n: int) -> int:
+        """k(n): frames computable from the first n samples before the end is known."""
+        need0 = max(self.hi, 1 - self.lo)            # frame 0: its last sample and its deepest start-mirror sample
+        if n < need0:
+            return 0
+        return (n - self.hi) // self.hop + 1
+
+    def final_samples(self, k: int) -> int:
+        """Output samples final once frames 0 .. k-1 are done (before the end is known)."""
+        return max(0, self.hop * k + self.lo)
+
+    def total_frames(self, L: int) -> int:
+        return 1 + L // self.hop
+
+    def total_samples(self, L: int) -> int:
+        return self.hop * (self.total_frames(L) - 1)
+
+    def check_flush(self, L: int):
+        if L <= self.half:
+            raise ValueError(f"flush: {L} samples in total, but torch.stft's reflect padding needs more than n_fft/2 = {self.half}")
+
+    # -- schedules (advance the state)
+    def _chunks(self, k_to: int, L_end: Optional[int]) -> List[Chunk]:
+        out = []
+        while self.k < k_to or (L_end is not None and not out):
+            kc = min(self.cap, k_to - self.k)
+            t0 = self.k
+            e1 = self.final_samples(t0 + kc)
+            if L_end is not None:
+                e1 = self.total_samples(L_end) if t0 + kc == k_to else min(e1, self.total_samples(L_end))
+            p_start = self.half + self.emitted
+            p_end = p_start + self.carry
+            if kc > 0:
+                p_end = max(p_end, self.hop * (t0 + kc - 1) + self.left + self.win)
+            p_end = max(p_end, self.half + e1)
+            carry_out = p_end - (self.half + e1)
+            if carry_out > self.carry_cap:
+                raise RuntimeError("StreamPlan: overlap-add carry exceeds its capacity")
+            out.append(Chunk(t0, kc, self.emitted, e1, p_end, self.carry, carry_out, self.parity))
+            self.k, self.emitted, self.carry = t0 + kc, e1, carry_out
+            self.parity ^= 1
+        return out
+
+    def push(self, n_new: int) -> List[Chunk]:
+        if n_new < 0:
+            raise ValueError("push: negative sample count")
+        k_to = self.frames_ready(self.n + n_new)
+        chunks = self._chunks(k_to, None)
+        self.n += n_new
+        return chunks
+
+    def flush(self) -> List[Chunk]:
+        self.check_flush(self.n)
+        return self._chunks(self.total_frames(self.n), self.n)
+
+
+def check_model(model, batch) -> None:
+    """The construction guards of StreamingDCCRN (host only, before any GPU work)."""
+    from .model.pvae_module import DCCRN_
+    if not isinstance(model, DCCRN_):
+        raise ValueError("StreamingDCCRN takes a model.pvae_module.DCCRN_")
+    net = model.std_DCCRN
+    if not net.causal or any(e.conv._cfg[2][1] != 1 for e in net.encoders):
+        raise ValueError("StreamingDCCRN needs a causal model (encoder time padding 1): with time padding 0 frame t needs x[t+1]")
+    if model.recon_type not in ("mask", "real_imag"):
+        raise ValueError(f"StreamingDCCRN: unknown recon_type {model.recon_type!r} (mask or real_imag)")
+    if isinstance(batch, bool) or not isinstance(batch, int) or batch <= 0:
+        raise ValueError("StreamingDCCRN: batch must be a positive int")
+    if any(not q.is_cuda for q in model.parameters()) or any(not b.is_cuda for b in model.buffers()):
+        raise RuntimeError("StreamingDCCRN runs on the MI355X only: move the model to the GPU first (there is no CPU path)")
+
+
+def check_input(x, batch: int, device=None) -> None:
+    """The guards of StreamingDCCRN.push (host only)."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2:
+        raise ValueError("push: x must be a tensor [batch, n]")
+    if x.shape[0] != batch:
+        raise ValueError(f"push: expected {batch} streams, got {x.shape[0]}")
+    if not x.is_cuda:
+        raise RuntimeError("StreamingDCCRN.push: pass a GPU (ROCm) tensor; there is no CPU path")
+    if device is not None and x.device != device:
+        raise RuntimeError(f"push: input on {x.device}, model on {device}")
+
+
+def _fold_and_slope(block):
+    return block.bn.eval_fold(), block.prelu.weight.detach().reshape(1).float().contiguous()
+
+
+class _ConvPack:
+    __slots__ = ("w", "bias", "fold", "slope", "transposed", "C0", "C1", "Cout", "Fin", "Fout", "nsplit")
+
+
+class StreamingDCCRN:
+    """Lock-step streaming inference of a causal ``DCCRN_`` (DCCRN-CL) for ``batch`` signals.
+
+    ``push(x)`` takes the next ``n >= 0`` samples of every stream (``x``: ``[batch, n]`` float32 on the model's GPU) and returns
+    the ``[batch, m]`` output samples that became final; ``flush()`` ends the signals, returns the rest and resets the streamer for
+    the next signals.  All pushes and the flush together return exactly what ``model(x_full, train=False)[0]`` returns
+    (``hop * floor(L / hop)`` samples, eval-mode semantics with the batch norm folded).  Output sample m is returned by the push
+    that delivers input sample m + 300 ... m + 399 at n_fft 512, win 400, hop 100.
+
+    The streamer always runs in exact fp32, whatever ``ops.PRECISION`` is.  Weights are packed once, at construction: later
+    changes of the model's parameters are not seen by an existing streamer.
+    """
+
+    def __init__(self, model, batch: int, frames_per_launch: int = 64, max_columns: int = 4096):
+        check_model(model, batch)
+        net = model.std_DCCRN
+        params = list(model.parameters())
+        if len(net.lstms) != 1 or not L.lib().idv_stream_lstm_supported(i(net.lstms[0].hidden_size)) or net.lstms[0].num_layer != 2:
+            raise ValueError("StreamingDCCRN: one two-layer ComplexLSTM with hidden size 128 is supported")
+        for blk in list(net.encoders) + list(net.decoders):
+            (blk.conv if hasattr(blk, "conv") else blk.transconv)._check_supported()
+        self.model, self.B = model, batch
+        self.device = params[0].device
+        st = model.stft
+        self.n_fft, self.hop, self.win = st.n_fft, st.hop_length, st.win_length
+        self.F = self.n_fft // 2 + 1
+        self.cap = max(1, min(frames_per_launch, max_columns // batch))
+        self.plan = StreamPlan(self.n_fft, self.hop, self.win, self.cap)
+        self.skip_to_use = list(net.skip_to_use)
+        with torch.no_grad(), torch.cuda.device(self.device):
+            self._pack(model)
+            self._alloc()
+        self.reset()
+
+    # ------------------------------------------------------------------ construction
+    def _conv(self, conv, blk, C0, C1, Fin):
+        cp = _ConvPack()
+        cp.transposed = conv._transposed
+        re, im = conv._re, conv._im
+        cin = conv.in_channel if C1 == 0 else C0 + C1
+        cp.Cout = conv.out_channel
+        cp.C0, cp.C1, cp.Fin = C0, C1, Fin
+        cp.Fout = 2 * Fin - 1 if cp.transposed else (Fin - 1) // 2 + 1
+        L.lib().idv_stream_cconv_wfloats.restype = L._L
+        cp.w = torch.empty(int(L.lib().idv_stream_cconv_wfloats(i(cin), i(cp.Cout))), dtype=torch.float32, device=self.device)
+        cp.bias = torch.empty(2 * cp.Cout, dtype=torch.float32, device=self.device)
+        call("idv_stream_pack_cconv", p(re.weight.detach().float().contiguous()), p(im.weight.detach().float().contiguous()),
+             p(re.bias.detach().float().contiguous()), p(im.bias.detach().float().contiguous()), i(cin), i(cp.Cout),
+             i(1 if cp.transposed else 0), p(cp.w), p(cp.bias), stream_ptr())
+        cp.fold, cp.slope = _fold_and_slope(blk)
+        cp.fold = cp.fold.clone()
+        cp.nsplit = int(L.lib().idv_stream_cconv_splits(i(1 if cp.transposed else 0), i(cin), i(cp.Cout), i(Fin), i(self.B)))
+        if cp.nsplit <= 0:
+            raise ValueError("StreamingDCCRN: unsupported block shape")
+        return cp
+
+    def _pack(self, model):
+        net = model.std_DCCRN
+        F = self.F
+        self.enc = []
+        ch, Fin = 1, F
+        self.enc_shapes = []                       # (C, F) of every encoder output
+        for blk in net.encoders:
+            cp = self._conv(blk.conv, blk, ch, 0, Fin)
+            self.enc.append(cp)
+            ch, Fin = cp.Cout, cp.Fout
+            self.enc_shapes.append((ch, Fin))
+        self.top = (ch, Fin)
+        self.dec = []
+        n = len(net.encoders)
+        dch = net.dense.out_channel // Fin
+        if dch * Fin != net.dense.out_channel:
+            raise ValueError("StreamingDCCRN: dense output does not match the top encoder shape")
+        c, f = dch, Fin
+        for di, blk in enumerate(net.decoders):
+            c1 = self.enc_shapes[n - 1 - di][0] if di in self.skip_to_use else 0
+            if c + c1 != blk.transconv.in_channel:
+                raise ValueError("StreamingDCCRN: decoder input channels do not match")
+            cp = self._conv(blk.transconv, blk, c, c1, f)
+            self.dec.append(cp)
+            c, f = cp.Cout, cp.Fout
+        if (c, f) != (1, F):
+            raise ValueError("StreamingDCCRN: the last decoder must give one channel of n_fft/2 + 1 bins")
+        lstm = net.lstms[0]
+        self.H = lstm.hidden_size
+        self.K = ch * Fin
+        sd = {k: v.detach().float().contiguous() for k, v in lstm.named_parameters()}
+        H, K = self.H, self.K
+        wih = torch.empty(ops.mtiles_alloc(8 * H) * ((K + 7) // 8 * 4) * 64, dtype=torch.float32, device=self.device)
+        bih = torch.empty(ops.mtiles_alloc(8 * H) * 32, dtype=torch.float32, device=self.device)
+        call("idv_pack_lstm_ih", p(sd["lstm_re.weight_ih_l0"]), p(sd["lstm_re.bias_ih_l0"]), p(sd["lstm_re.bias_hh_l0"]),
+             p(sd["lstm_im.weight_ih_l0"]), p(sd["lstm_im.bias_ih_l0"]), p(sd["lstm_im.bias_hh_l0"]), i(H), i(K), p(wih), p(bih),
+             stream_ptr())
+        self.lstm_ih = (wih, bih)
+        mats = []
+        for part in ("lstm_re", "lstm_im"):
+            for name in ("weight_hh_l0", "weight_ih_l1", "weight_hh_l1"):
+                mats.append(sd[f"{part}.{name}"].t().contiguous())
+        self.lstm_wt = torch.stack(mats).contiguous()
+        self.lstm_b1 = torch.stack([sd[f"{part}.bias_ih_l1"] + sd[f"{part}.bias_hh_l1"] for part in ("lstm_re", "lstm_im")]).contiguous()
+        dn = net.dense
+        self.dense = [ops.pack_pw(dn.linear_read.weight.detach().float(), dn.linear_read.bias.detach().float()),
+                      ops.pack_pw(dn.linear_imag.weight.detach().float(), dn.linear_imag.bias.detach().float())]
+        self.dense_out = (dch, Fin)
+        dft = ops.DftPlan(self.n_fft, self.win, self.hop, 1, self.device)
+        self.dft_fwd, self.dft_inv = dft.fwd, dft.inv
+        self.datanorm = model.datanorm
+        if self.datanorm:
+            self.mean = model.data_mean.reshape(-1).float().contiguous().clone()
+            self.std = model.data_std.reshape(-1).float().contiguous().clone()
+        self.recon = model.recon_type
+
+    def _alloc(self):
+        B, dev = self.B, self.device
+        Tp = self.cap + 1
+        self.Jp_max = Planar.jp_for(B, Tp)
+        mk = lambda C, F: Planar.empty(C, F, B, self.cap, Tp, dev, zero=True)
+        self.fr = mk(1, self.win // 2)                       # frames [win][Jp]
+        self.X = mk(1, self.F)
+        self.N = mk(1, self.F) if self.datanorm else self.X
+        self.enc_out = [mk(c, f) for c, f in self.enc_shapes]
+        self.lat = mk(self.H, 1)
+        self.dense_buf = mk(*self.dense_out)
+        self.dec_out = [mk(cp.Cout, cp.Fout) for cp in self.dec]
+        self.pred = mk(1, self.F)
+        self.pred2 = mk(1, self.F) if self.datanorm else None
+        self.pc = torch.empty(B * self.F * self.cap * 2, dtype=torch.float32, device=dev)
+        self.ifr = mk(1, self.win // 2)
+        J = B * self.cap
+        self.G = torch.empty(2 * J * 8 * self.H, dtype=torch.float32, device=dev)
+        self.hout = torch.empty(4 * J * self.H, dtype=torch.float32, device=dev)
+        work = max([cp.nsplit * 2 * cp.Cout * cp.Fout * J for cp in self.enc + self.dec if cp.nsplit > 1] + [0])
+        self.work = torch.empty(max(work, 1), dtype=torch.float32, device=dev)
+        # per-stream state
+        hist = lambda C, F: torch.zeros(2, 2 * C * F * B, dtype=torch.float32, device=dev)
+        self.h_in = hist(1, self.F)
+        self.h_enc = [hist(c, f) for c, f in self.enc_shapes]
+        self.h_dense = hist(*self.dense_out)
+        self.h_dec = [hist(cp.Cout, cp.Fout) for cp in self.dec[:-1]]
+        self.lstm_state = torch.zeros(4 * 4 * B * self.H, dtype=torch.float32, device=dev)
+        self.ring = torch.zeros(B * self.plan.ring, dtype=torch.float32, device=dev)
+        self.carry = torch.zeros(2, B * self.plan.carry_cap, dtype=torch.float32, device=dev)
+        self.state = [self.h_in, self.h_dense, self.lstm_state, self.ring, self.carry] + self.h_enc + self.h_dec
+
+    def reset(self):
+        """Zero every per-stream state buffer and the bookkeeping (done by construction and by flush)."""
+        for t in self.state:
+            t.zero_()
+        self.plan.reset()
+
+    # ------------------------------------------------------------------ push / flush
+    def push(self, x: torch.Tensor) -> torch.Tensor:
+        check_input(x, self.B, self.device)
+        x = x.float()
+        n_new = int(x.shape[1])
+        # the kernels read rows at any pitch (a column slice of a longer signal costs no copy); anything else is made contiguous
+        if (n_new > 1 and x.stride(1) != 1) or (self.B > 1 and x.stride(0) < n_new):
+            x = x.contiguous()
+        ldx = x.stride(0) if self.B > 1 else n_new
+        n_prev = self.plan.n
+        with torch.cuda.device(self.device):
+            chunks = self.plan.push(n_new)
+            y = self._run(chunks, x, ldx, n_new, n_prev, None)
+            if n_new:
+                call("idv_stream_ring", p(self.ring), i(self.plan.ring), p(x), ll(ldx), i(n_new), ll(n_prev), i(self.B), stream_ptr())
+        return y
+
+    def flush(self) -> torch.Tensor:
+        L_total = self.plan.n
+        self.plan.check_flush(L_total)
+        with torch.cuda.device(self.device):
+            chunks = self.plan.flush()
+            y = self._run(chunks, None, 0, 0, L_total, L_total)
+            self.reset()
+        return y
+
+    def _run(self, chunks: List[Chunk], x, ldx: int, n_new: int, n_prev: int, L_end: Optional[int]) -> torch.Tensor:
+        m = (chunks[-1].e1 - chunks[0].e0) if chunks else 0
+        y = torch.empty(self.B, m, dtype=torch.float32, device=self.device)
+        T_total = self.plan.total_frames(L_end) if L_end is not None else -1
+        for c in chunks:
+            if c.k > 0:
+                self._network(c, x, ldx, n_new, n_prev, L_end)
+            pin = c.parity
+            frames = self.ifr if c.k > 0 else None
+            Tp = c.k + 1
+            Jp = Planar.jp_for(self.B, Tp)
+            call("idv_stream_ola", frames.ptr() if frames is not None else p(None), i(Tp), i(Jp), p(self.carry[pin]), i(c.carry_in),
+                 p(self.carry[1 - pin]), i(self.plan.carry_cap), i(self.B), i(self.n_fft), i(self.win), i(self.hop), ll(c.t0), i(c.k),
+                 ll(T_total), ll(c.e0), ll(c.e1), ll(c.p_end), p(y) if m else p(None), i(max(m, 1)), ll(c.e0 - chunks[0].e0),
+                 stream_ptr())
+        return y
+
+    def _network(self, c: Chunk, x, ldx: int, n_new: int, n_prev: int, L_end: Optional[int]):
+        B, k, P = self.B, c.k, c.parity
+        Tp = k + 1
+        Jp = Planar.jp_for(B, Tp)
+        s = stream_ptr()
+        ptr = lambda pl, plane=0: L._P(pl.buf.data_ptr() + 4 * (ops.SLACK + plane * pl.F * Jp))
+        call("idv_stream_frames", p(self.ring), i(self.plan.ring), p(x) if x is not None else p(None), ll(ldx), i(n_new), ll(n_prev),
+             ll(L_end if L_end is not None else -1), i(B), i(self.n_fft), i(self.win), i(self.hop), ll(c.t0), i(k), ptr(self.fr),
+             i(Tp), i(Jp), s)
+        ops.pw_gemm(ptr(self.fr), self.win, self.dft_fwd[0], self.dft_fwd[1], 2 * self.F, B, Tp, Jp, k, ptr(self.X))
+        if self.datanorm:
+            call("idv_datanorm", ptr(self.X), p(self.mean), p(self.std), i(self.F), i(B), i(k), i(Tp), i(Jp), ptr(self.N), s)
+        # encoders
+        src, hsrc = self.N, self.h_in
+        for e, cp in enumerate(self.enc):
+            out = self.enc_out[e]
+            self._conv_call(cp, ptr(src), hsrc[P], None, None, ptr(out), self.h_enc[e][1 - P],
+                            p(self.h_in[1 - P]) if e == 0 else p(None), B, k, Tp, Jp)
+            src, hsrc = out, self.h_enc[e]
+        # LSTM: layer-0 projection of both input parts (idv_pw_gemm as offline), then the stateful recurrence
+        H, K = self.H, self.K
+        wih, bih = self.lstm_ih
+        top = self.enc_out[-1]
+        for z in range(2):
+            ops.pw_gemm(ptr(top, z * top.C), K, wih, bih, 8 * H, B, Tp, Jp, k,
+                        L._P(self.G.data_ptr() + 4 * z * k * B * 8 * H), swap=True, ldo=8 * H)
+        call("idv_stream_clstm", p(self.G), p(self.lstm_wt), p(self.lstm_b1), p(self.lstm_state), p(self.hout), ptr(self.lat), i(H),
+             i(B), i(k), i(Tp), i(Jp), s)
+        # dense
+        dc, df = self.dense_out
+        for ri, pk in enumerate(self.dense):
+            ops.pw_gemm(ptr(self.lat, ri * H), H, pk[0], pk[1], dc * df, B, Tp, Jp, k, ptr(self.dense_buf, ri * dc))
+        # decoders
+        src, hsrc = self.dense_buf, self.h_dense
+        n = len(self.enc)
+        for di, cp in enumerate(self.dec):
+            out = self.dec_out[di]
+            skip = n - 1 - di if di in self.skip_to_use else None
+            x1 = ptr(self.enc_out[skip]) if skip is not None else None
+            h1 = self.h_enc[skip][P] if skip is not None else None
+            hout = self.h_dec[di][1 - P] if di < len(self.h_dec) else None      # nothing reads the last block's history
+            self._conv_call(cp, ptr(src), hsrc[P], x1, h1, ptr(out), hout,
+                            p(self.h_dense[1 - P]) if di == 0 else p(None), B, k, Tp, Jp)
+            if di < len(self.h_dec):
+                src, hsrc = out, self.h_dec[di]
+        mask = self.dec_out[-1]
+        if self.recon == "mask":
+            call("idv_mask_apply", ptr(mask), ptr(self.N), i(1), i(Jp), ptr(self.pred), p(None), i(self.F), i(B), i(k), i(Tp), i(Jp), s)
+            pred = self.pred
+        else:
+            pred = mask
+        if self.datanorm:
+            call("idv_datadenorm", ptr(pred), p(self.mean), p(self.std), i(self.F), i(B), i(k), i(Tp), i(Jp), ptr(self.pred2),
+                 p(self.pc), s)
+            pred = self.pred2
+        ops.pw_gemm(ptr(pred), 2 * self.F, self.dft_inv[0], self.dft_inv[1], self.win, B, Tp, Jp, k, ptr(self.ifr))
+
+    def _conv_call(self, cp: _ConvPack, x0, h0, x1, h1, out, hist_out, x0hist_out, B, k, Tp, Jp):
+        call("idv_stream_cconv", x0, p(h0), i(cp.C0), x1 if x1 is not None else p(None), p(h1), i(cp.C1), p(cp.w), p(cp.bias),
+             p(cp.fold), p(cp.slope), out, p(hist_out), x0hist_out, p(self.work), i(cp.nsplit), i(1 if cp.transposed else 0),
+             i(cp.Cout), i(cp.Fin), i(B), i(k), i(Tp), i(Jp), stream_ptr())

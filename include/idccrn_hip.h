@@ -623,6 +623,44 @@ int idv_cconv2d_tw_fwd(const float* x0, int Cin, const float* wfrag, const float
                        float* out, double* stats, double* stats_work, int stats_rep, int tshift, int Cout, int Fin, int B, int Tp,
                        int Jp, int t_valid_out, void* stream);
 
+/* ---- streaming enhancement (stream_conv.hip, stream_lstm.hip, stream_io.hip; streaming.StreamingDCCRN) ------------------------
+ * One push runs the causal DCCRN over the k frames it completes for B lock-step streams.  Activations use the planar-J layout
+ * with Tp = k + 1; a per-stream history column hist[2][C][F][B] supplies x[t-1] of each stream's first frame.  Exact fp32.
+ *
+ * Complex conv / transposed conv block (causal, kernel (5,2), stride (2,1)): sources x0 (C0 channels, history h0) and x1 (C1
+ * skip channels, history h1; C1 = 0: none), then bias, the folded eval batch norm (fold[Cout][6] or NULL) and PReLU (slope or
+ * NULL).  Writes out (planar [2][Cout][Fout][Jp]) and the last column of each stream to hist_out (or NULL); x0hist_out (or NULL)
+ * receives the last column of x0.  nsplit = idv_stream_cconv_splits(...) K parts, work holds nsplit * 2 * Cout * Fout * B * k
+ * floats when nsplit > 1; the parts are added in a fixed order.  w / bias from idv_stream_pack_cconv (w_*: conv [Cout][Cin][5][2],
+ * transposed [Cin][Cout][5][2]; idv_stream_cconv_wfloats floats of w, 2 * Cout of bias). */
+long long idv_stream_cconv_wfloats(int Cin, int Cout);
+int idv_stream_pack_cconv(const float* w_re, const float* w_im, const float* b_re, const float* b_im, int Cin, int Cout,
+                          int transposed, float* w, float* bias, void* stream);
+int idv_stream_cconv_splits(int transposed, int Cin, int Cout, int Fin, int B);
+int idv_stream_cconv(const float* x0, const float* h0, int C0, const float* x1, const float* h1, int C1, const float* w,
+                     const float* bias, const float* fold, const float* prelu_slope, float* out, float* hist_out, float* x0hist_out,
+                     float* work, int nsplit, int transposed, int Cout, int Fin, int B, int k, int Tp, int Jp, void* stream);
+/* Two-layer complex LSTM over k steps with carried state (H = 128 only; idv_stream_lstm_supported).  G: [2][k*B][8H] layer-0
+ * projections from idv_pw_gemm (idv_pack_lstm_ih fragments, swap = 1, ldo = 8H); wt: [2 sets][W_hh0, W_ih1, W_hh1][H][4H]
+ * (transposed torch weights, set 0 = lstm_re); b1: [2][4H] = b_ih1 + b_hh1; state: [4 runs][2 layers][h, c][B][H], read and
+ * written back; hout: [4][k*B][H] scratch; out: planar [2][H][Jp] (real = rr - ii, imag = ir + ri). */
+int idv_stream_lstm_supported(int H);
+int idv_stream_clstm(const float* G, const float* wt, const float* b1, float* state, float* hout, float* out, int H, int B, int k,
+                     int Tp, int Jp, void* stream);
+/* Framing of frames t0 .. t0+k-1 into frames[win][Jp] (torch.stft centre / reflect convention): samples below n_prev from
+ * ring[B][R] (sample s at s mod R), the others from x[B][n_new] (row stride ldx >= n_new); L_end >= 0 applies the end mirror of
+ * a signal of L_end samples.  idv_stream_ring stores the last R samples of x into the ring. */
+int idv_stream_frames(const float* ring, int R, const float* x, long long ldx, int n_new, long long n_prev, long long L_end, int B,
+                      int n_fft, int win, int hop, long long t0, int k, float* frames, int Tp, int Jp, void* stream);
+int idv_stream_ring(float* ring, int R, const float* x, long long ldx, int n_new, long long n_prev, int B, void* stream);
+/* Overlap-add of the windowed inverse-DFT frames t0 .. t0+k-1 (frames[win][Jp], k may be 0) onto the carried partial sums
+ * carry_in[B][cap] (padded positions n_fft/2 + e0 ...), emission of output samples e0 .. e1-1 divided by the istft envelope of
+ * frames 0 .. T_total-1 (T_total < 0: no end yet) into y[b][y_off ...] (row stride ldy), and the partial sums of positions
+ * n_fft/2 + e1 .. p_end-1 into carry_out. */
+int idv_stream_ola(const float* frames, int Tp, int Jp, const float* carry_in, int carry_in_len, float* carry_out, int cap, int B,
+                   int n_fft, int win, int hop, long long t0, int k, long long T_total, long long e0, long long e1, long long p_end,
+                   float* y, int ldy, long long y_off, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
