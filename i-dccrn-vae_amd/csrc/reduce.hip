@@ -89,6 +89,22 @@ __global__ void sisdr_final_kernel(const double* __restrict__ work, int B, float
     out[b] = (float)(10.0 * log10((eps + sss) / (eps + snn)));
 }
 
+// sisnr_partial_kernel over the first lens[b] samples of row b (clamped to Lmax, the shorter of the two row pitches)
+__global__ __launch_bounds__(256) void sisdr_ragged_partial_kernel(const float* __restrict__ ref, int ref_ld, const float* __restrict__ est,
+                                                                   int est_ld, const int* __restrict__ lens, int Lmax,
+                                                                   double* __restrict__ work) {
+    const int b = blockIdx.y;
+    const float* s = ref + (size_t)b * ref_ld;
+    const float* e = est + (size_t)b * est_ld;
+    const int L = max(0, min(lens[b], Lmax));
+    double E = 0, D = 0, Q = 0;
+    for (int n = blockIdx.x * blockDim.x + threadIdx.x; n < L; n += gridDim.x * blockDim.x) {
+        const float sv = s[n], ev = e[n];
+        E += (double)sv * sv; D += (double)ev * sv; Q += (double)ev * ev;
+    }
+    block_add3(E, D, Q, work + (size_t)b * 3);
+}
+
 // out[b][n] = mean_s x[b*ns + s][n]   (test_se_cvaefinetune.py:309-311: torch.mean over the sampled waveforms)
 __global__ void mean_over_samples_kernel(const float* __restrict__ x, int ns, int B, int L, float* __restrict__ out) {
     const long long n = (long long)B * L;
@@ -225,6 +241,18 @@ extern "C" int idv_sisdr(const float* ref, int ref_ld, const float* est, int est
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(work, 0, sizeof(double) * 3 * B, st) != hipSuccess) return IDV_ELAUNCH;
     hipLaunchKernelGGL(sisnr_partial_kernel, dim3(grid_for(L, 64), B), dim3(256), 0, st, ref, ref_ld, 1, est, est_ld, L, work);
+    hipLaunchKernelGGL(sisdr_final_kernel, dim3((B + 63) / 64), dim3(64), 0, st, work, B, out);
+    return idv_launch_status();
+}
+
+extern "C" int idv_sisdr_ragged(const float* ref, int ref_ld, const float* est, int est_ld, const int* lens, int B, double* work,
+                                float* out, void* stream) {
+    if (!ref || !est || !lens || !work || !out || B <= 0 || B > 65535 || ref_ld <= 0 || est_ld <= 0) return IDV_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(work, 0, sizeof(double) * 3 * B, st) != hipSuccess) return IDV_ELAUNCH;
+    const int Lmax = ref_ld < est_ld ? ref_ld : est_ld;
+    hipLaunchKernelGGL(sisdr_ragged_partial_kernel, dim3(grid_for(Lmax, 64), B), dim3(256), 0, st, ref, ref_ld, est, est_ld, lens, Lmax,
+                       work);
     hipLaunchKernelGGL(sisdr_final_kernel, dim3((B + 63) / 64), dim3(64), 0, st, work, B, out);
     return idv_launch_status();
 }

@@ -3,18 +3,26 @@
   * supervised (supervised_dccrn/test.py:123-137): ``model(noisy, train=False)[0]``;
   * I-DCCRN-VAE (i_dccrn_vae/nsvae_dccrn/test_se_cvaefinetune.py:251-311): noisy encoder (eval) -> fine-tuned decoder with
     the noisy skips (``pad='sig'``) on ``num_samples`` (10 in test_se_cvaefinetune.sh) latent draws -> mean over the sampled
-    waveforms.  The reference feeds one utterance at a time (``tmp_x[None]``); here a batch of equal-length utterances
-    goes through at once (utterances are independent in eval mode: folded batch norm);
+    waveforms.  The reference feeds one utterance at a time (``tmp_x[None]``); here a batch of utterances goes through at
+    once (utterances are independent in eval mode: folded batch norm);
   * the two-latent evaluation (test_se_cvaefinetune.py:261-305, ``latent_to_use == 2``): speech AND noise decoders on their
     latents, then one of the ``outtype`` estimators -- ``clean_direct`` (mean of the sampled speech waveforms),
     ``real_imag_mask`` (:85-101), ``complex_mask`` (:104-116), ``phase_mask`` (:119-135) -- as one HIP kernel
     (``idv_outtype_estimate``) + the ISTFT (``torch.istft`` with the analysis window, :288 etc.);
   * ``compute_sisdr`` (utils/eval_metrics.py:49-64) on the device.  PESQ / ESTOI / DNSMOS are third-party CPU metrics and
     stay out of scope.
+
+Utterances of different lengths (causal models, the ones every shipped recipe builds): every entry point takes ``lengths``
+(a python sequence or a CPU integer tensor, one sample count per row of the zero- or anything-padded ``[B, Lmax]`` batch).  Row
+b of the result then holds the ``hop * (lengths[b] // hop)`` samples the model gives for that utterance alone, followed by zeros up
+to ``hop * (Tmax - 1)``, ``Tmax = 1 + max(lengths) // hop``.  In a causal network frame t depends on frames <= t only, so only the
+STFT framing (each row mirrored at its own end), the ISTFT overlap-add (each row over its own frames and their envelope) and
+``compute_sisdr`` read the lengths.  :func:`enhance_list` takes a list of signals of any lengths, groups them into such batches
+(:func:`plan_ragged_batches`) and returns the enhanced signals in the caller's order.
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import Callable, List, Optional, Sequence
 
 import torch
 
@@ -35,11 +43,14 @@ def mean_over_samples(recon: torch.Tensor, num_samples: int) -> torch.Tensor:
 
 
 @torch.no_grad()
-def enhance_supervised(model, noisy: torch.Tensor, check: bool = True) -> torch.Tensor:
+def enhance_supervised(model, noisy: torch.Tensor, check: bool = True, lengths=None) -> torch.Tensor:
     """DCCRN / DCCRN-CL: [B, L] -> enhanced [B, hop*(T-1)].  ``check`` (all three entry points): synchronise and raise
     ``ops.CoopTimeout`` here, at the operation that owns it, if a cooperative LSTM recurrence of this forward timed out
-    (its outputs would be NaN); ``check=False`` keeps the call asynchronous (call ``ops.coop_check()`` yourself)."""
-    return _checked(model(noisy, train=False)[0], check)
+    (its outputs would be NaN); ``check=False`` keeps the call asynchronous (call ``ops.coop_check()`` yourself).
+    ``lengths`` (all three entry points): per-row sample counts of a padded batch, see the module docstring."""
+    if lengths is None:
+        return _checked(model(noisy, train=False)[0], check)
+    return _checked(model(noisy, train=False, lengths=lengths)[0], check)
 
 
 def _checked(out: torch.Tensor, check: bool) -> torch.Tensor:
@@ -49,16 +60,23 @@ def _checked(out: torch.Tensor, check: bool) -> torch.Tensor:
 
 
 @torch.no_grad()
-def enhance_vae(noisy_encoder, decoder, noisy: torch.Tensor, eps=None, latent: str = "speech", check: bool = True) -> torch.Tensor:
+def enhance_vae(noisy_encoder, decoder, noisy: torch.Tensor, eps=None, latent: str = "speech", check: bool = True,
+                lengths=None) -> torch.Tensor:
     """I-DCCRN-VAE (phase 2, latent_to_use 1): [B, L] -> mean of the num_samples decoded waveforms, [B, hop*(T-1)].
     ``eps``: optional injected Gaussian draws (see the encoder's forward)."""
-    r = noisy_encoder(noisy, train=False, eps=eps)
+    r = _encode(noisy_encoder, noisy, eps, lengths)
     z = r[0] if latent == "speech" else r[4]
     if z is None:
         raise ValueError("this encoder has no noise latent (latent_num == 1)")
     skiper, C, F, stft_x = r[8], r[9], r[10], r[11]
     recon, _ = decoder(stft_x, z, skiper, C, F, train=False, pad="sig")
     return _checked(mean_over_samples(recon, noisy_encoder.num_samples), check)
+
+
+def _encode(noisy_encoder, noisy, eps, lengths):
+    if lengths is None:
+        return noisy_encoder(noisy, train=False, eps=eps)
+    return noisy_encoder(noisy, train=False, eps=eps, lengths=lengths)
 
 
 OUTTYPES = {"real_imag_mask": 0, "complex_mask": 1, "phase_mask": 2}
@@ -92,11 +110,11 @@ def outtype_estimate(predict_noise: torch.Tensor, predict_speech: torch.Tensor, 
 
 @torch.no_grad()
 def enhance_vae_two_latents(noisy_encoder, speech_decoder, noise_decoder, noisy: torch.Tensor, outtype: str = "clean_direct",
-                            phase: int = 2, eps=None, check: bool = True) -> torch.Tensor:
+                            phase: int = 2, eps=None, check: bool = True, lengths=None) -> torch.Tensor:
     """latent_to_use == 2 (test_se_cvaefinetune.py:261-305): the noisy encoder's speech latent through the speech decoder and
     its noise latent through the noise decoder (phase 1: the pre-trained decoders, zero skips, :263-264; phase 2: the
     fine-tuned decoders with the noisy skips, ``pad='sig'``, :295-296), then the ``outtype`` estimator -> enhanced [B, L]."""
-    r = noisy_encoder(noisy, train=False, eps=eps)
+    r = _encode(noisy_encoder, noisy, eps, lengths)
     if r[4] is None:
         raise ValueError("this encoder has no noise latent (latent_num == 1)")
     z_s, z_n, skiper, C, F, stft_x = r[0], r[4], r[8], r[9], r[10], r[11]
@@ -109,16 +127,28 @@ def enhance_vae_two_latents(noisy_encoder, speech_decoder, noise_decoder, noisy:
     spec, _ = outtype_estimate(pred_n, pred_s, stft_x, outtype, ns)
     from .model.pvae_module import dft_plan
     st = noisy_encoder.stft
-    return _checked(ops.istft(spec, dft_plan(st.n_fft, st.win_length, st.hop_length, spec.T, spec.buf.device)), check)
+    return _checked(ops.istft(spec, dft_plan(st.n_fft, st.win_length, st.hop_length, spec.T, spec.buf.device),
+                              lengths=getattr(getattr(stft_x, "_idv", None), "lengths", None)), check)
 
 
-def compute_sisdr(x_est: torch.Tensor, x_ref: torch.Tensor) -> torch.Tensor:
-    """SI-SDR in dB per utterance (utils/eval_metrics.py:49-64); inputs [L] or [B, L] on the GPU -> tensor [B] (or scalar)."""
+def compute_sisdr(x_est: torch.Tensor, x_ref: torch.Tensor, lengths=None) -> torch.Tensor:
+    """SI-SDR in dB per utterance (utils/eval_metrics.py:49-64); inputs [L] or [B, L] on the GPU -> tensor [B] (or scalar).
+    ``lengths``: row b is scored over its first lengths[b] samples only (the two inputs may then differ in padded width)."""
     ops.check_dev_f32(x_est, "x_est")
     ops.check_dev_f32(x_ref, "x_ref", x_est.device)
     single = x_est.dim() == 1
     e = x_est.reshape(1, -1) if single else x_est
     r = x_ref.reshape(1, -1) if single else x_ref
+    if lengths is not None:
+        if e.shape[0] != r.shape[0]:
+            raise ValueError(f"estimate {tuple(e.shape)} and reference {tuple(r.shape)} differ in batch size")
+        lens = ops.Lengths(ops.check_lengths(lengths, e.shape[0], min(e.shape[1], r.shape[1]), None), e.device)
+        e, r = e.float().contiguous(), r.float().contiguous()
+        B = e.shape[0]
+        work = torch.empty(3 * B, dtype=torch.float64, device=e.device)
+        out = torch.empty(B, dtype=torch.float32, device=e.device)
+        call("idv_sisdr_ragged", p(r), i(r.stride(0)), p(e), i(e.stride(0)), p(lens.dev), i(B), p(work), p(out), stream_ptr())
+        return out[0] if single else out
     if e.shape != r.shape:
         raise ValueError(f"estimate {tuple(e.shape)} and reference {tuple(r.shape)} differ")
     e, r = e.float().contiguous(), r.float().contiguous()
@@ -127,3 +157,62 @@ def compute_sisdr(x_est: torch.Tensor, x_ref: torch.Tensor) -> torch.Tensor:
     out = torch.empty(B, dtype=torch.float32, device=e.device)
     call("idv_sisdr", p(r), i(r.stride(0)), p(e), i(e.stride(0)), i(B), i(L), p(work), p(out), stream_ptr())
     return out[0] if single else out
+
+
+def plan_ragged_batches(lengths: Sequence[int], hop: int, max_batch: int = 64, max_columns: int = 64 * 642,
+                        max_waste: float = 0.1) -> List[List[int]]:
+    """Group utterances of ``lengths`` samples into batches for the ``lengths=`` entry points (host only, no device use) ->
+    list of batches, each a list of indices into ``lengths``; every index appears exactly once.
+
+    Utterance b has T_b = 1 + lengths[b] // hop frames; a batch of B utterances is laid out as B * (Tmax + 1) columns, Tmax its
+    longest.  Indices are sorted by length (descending, ties by index) and a batch is filled greedily; it is closed when adding
+    the next utterance would exceed ``max_batch`` utterances, make B * (Tmax + 1) > ``max_columns`` (default: 64 utterances x 642
+    columns, the headline launch shape) or push the padding share 1 - sum_b T_b / (B * Tmax) above ``max_waste``.  A single
+    utterance longer than ``max_columns - 1`` frames gets a batch of its own."""
+    if hop <= 0 or max_batch < 1 or max_columns < 2 or not 0 <= max_waste < 1:
+        raise ValueError("plan_ragged_batches: need hop > 0, max_batch >= 1, max_columns >= 2, 0 <= max_waste < 1")
+    lengths = [int(v) for v in lengths]
+    if any(v < 0 for v in lengths):
+        raise ValueError("plan_ragged_batches: negative length")
+    order = sorted(range(len(lengths)), key=lambda k: (-lengths[k], k))
+    batches: List[List[int]] = []
+    cur: List[int] = []
+    frames = tmax = 0
+    for k in order:
+        t = 1 + lengths[k] // hop
+        if cur:                       # descending order: Tmax stays the first utterance's
+            n = len(cur) + 1
+            if n > max_batch or n * (tmax + 1) > max_columns or 1 - (frames + t) / (n * tmax) > max_waste:
+                batches.append(cur)
+                cur = []
+        if not cur:
+            frames, tmax = 0, t
+        cur.append(k)
+        frames += t
+    if cur:
+        batches.append(cur)
+    return batches
+
+
+@torch.no_grad()
+def enhance_list(enhance: Callable, signals: Sequence[torch.Tensor], hop: int, check: bool = True, **plan_kw) -> List[torch.Tensor]:
+    """Enhance utterances of any lengths at batch throughput.  ``signals``: 1-D float32 GPU tensors; ``enhance``: a callable
+    ``enhance(padded [B, Lmax], lengths=[...], check=False) -> [B, hop*(Tmax-1)]`` -- ``functools.partial(enhance_supervised,
+    model)``, ``functools.partial(enhance_vae, encoder, decoder)``, ... ; ``hop``: the model's hop length; ``plan_kw``: the
+    knobs of :func:`plan_ragged_batches`.  Returns the enhanced signals in the caller's order, signal k exactly
+    ``hop * (len(signals[k]) // hop)`` samples long.  One ``ops.coop_check()`` per batch when ``check``."""
+    for k, sgn in enumerate(signals):
+        if not isinstance(sgn, torch.Tensor) or sgn.dim() != 1:
+            raise ValueError(f"signals[{k}] must be a 1-D tensor")
+        ops.check_dev_f32(sgn, f"signals[{k}]")
+    lens = [int(sgn.shape[0]) for sgn in signals]
+    out: List[Optional[torch.Tensor]] = [None] * len(signals)
+    for batch in plan_ragged_batches(lens, hop, **plan_kw):
+        blens = [lens[k] for k in batch]
+        padded = torch.zeros(len(batch), max(blens), dtype=torch.float32, device=signals[batch[0]].device)
+        for row, k in enumerate(batch):
+            padded[row, :lens[k]] = signals[k]
+        y = _checked(enhance(padded, lengths=blens, check=False), check)
+        for row, k in enumerate(batch):
+            out[k] = y[row, :hop * (lens[k] // hop)].clone()
+    return out

@@ -46,10 +46,14 @@ class STFT(nn.Module):
         super().__init__()
         self.n_fft, self.hop_length, self.win_length = n_fft, hop_length, win_length
 
-    def planar(self, signal: torch.Tensor) -> Planar:
+    def planar(self, signal: torch.Tensor, lengths=None) -> Planar:
         _need_cuda(signal)
         T = 1 + signal.shape[1] // self.hop_length
         plan = dft_plan(self.n_fft, self.win_length, self.hop_length, T, signal.device)
+        if lengths is not None:
+            if AG.grad_mode(signal):
+                raise ValueError("lengths: utterances of different lengths are an eval-mode (train=False) feature")
+            return ops.stft(signal, plan, lengths=lengths)
         if AG.grad_mode(signal):
             sig = signal.float().contiguous()
             buf = AG.StftFn.apply(plan, sig)
@@ -70,11 +74,13 @@ class ISTFT(nn.Module):
         super().__init__()
         self.n_fft, self.hop_length, self.win_length = n_fft, hop_length, win_length
 
-    def planar(self, spec: Planar) -> torch.Tensor:
+    def planar(self, spec: Planar, lengths=None) -> torch.Tensor:
         plan = dft_plan(self.n_fft, self.win_length, self.hop_length, spec.T, spec.buf.device)
         if AG.grad_mode(spec.buf):
+            if lengths is not None:
+                raise ValueError("lengths: utterances of different lengths are an eval-mode (train=False) feature")
             return AG.IstftFn.apply(plan, AG._geom(spec), spec.buf)
-        return ops.istft(spec, plan)
+        return ops.istft(spec, plan, lengths=lengths)
 
     def forward(self, x):
         pl = getattr(x, "_idv", None)
@@ -336,9 +342,32 @@ def _eval_builds_no_graph(what, *inputs):
             "kernels have no backward, the gradient would be cut silently; call with train=True, or detach() the input")
 
 
+def check_ragged(causal, encoders, train, lengths, signal, n_fft) -> list:
+    """The guards of a forward with per-utterance ``lengths`` (host only, before any GPU work) -> the lengths as a list of ints.
+    Only the STFT framing and the ISTFT overlap-add know the lengths, which is right for a causal network alone."""
+    if train:
+        raise ValueError("lengths is accepted with train=False only: train mode computes whole-batch batch-norm moments over "
+                         "all columns, the padded ones included")
+    if not causal or any(e.conv._cfg[2][1] != 1 for e in encoders):
+        raise ValueError("lengths needs a causal model (encoder time padding 1): a non-causal block reads frame t+1, so the "
+                         "padding past an utterance's end would leak into its last valid frame")
+    if not isinstance(signal, torch.Tensor) or signal.dim() != 2:
+        raise ValueError("lengths: the signal must be a padded [B, L] tensor")
+    return ops.check_lengths(lengths, signal.shape[0], signal.shape[1], n_fft)
+
+
+def _ragged_input(signal, host):
+    """(signal trimmed to the longest utterance -- a view, the framing kernel takes the row pitch --, ops.Lengths)."""
+    _need_cuda(signal)
+    return signal[:, :max(host)], ops.Lengths(host, signal.device)
+
+
 class DCCRN_(nn.Module):
     """Supervised DCCRN (DCCRN-CL when causal=True).  reference: model/pvae_module.py:200-255.
-    forward(signal [B, L], train=True) -> (clean [B, hop*(T-1)], predict complex64 [B, F, T])."""
+    forward(signal [B, L], train=True) -> (clean [B, hop*(T-1)], predict complex64 [B, F, T]).
+    ``lengths`` (train=False, causal models): row b of the padded batch holds lengths[b] samples; T is then the longest
+    utterance's frame count, and row b of both outputs equals the forward of that utterance alone over its own
+    hop * (lengths[b] // hop) samples / 1 + lengths[b] // hop frames (zeros / don't-care values past them)."""
 
     def __init__(self, n_fft, hop_len, net_params, causal, device, win_length, skip_to_use, recon_type, resynthesis,
                  data_mean, data_std):
@@ -352,32 +381,41 @@ class DCCRN_(nn.Module):
         self.register_buffer("data_std", data_std)
         self.datanorm = self.data_mean is not None and self.data_std is not None
 
-    def forward(self, signal, train=True):
+    def forward(self, signal, train=True, lengths=None):
         # Eval is per-utterance independent (folded BN): run sub-batches on separate HIP streams so one sub-batch's
         # 16-CU LSTM recurrence and kernel tails overlap the other's conv GEMMs.  Train mode needs whole-batch
         # CBN statistics and stays on one stream.
+        if lengths is not None and not isinstance(lengths, ops.Lengths):      # an ops.Lengths: checked already (the call below)
+            host = check_ragged(self.std_DCCRN.causal, self.std_DCCRN.encoders, train, lengths, signal, self.stft.n_fft)
+            if self.resynthesis and min(host) // self.stft.hop_length * self.stft.hop_length <= self.stft.n_fft // 2:
+                raise ValueError("lengths with resynthesis=True: every enhanced signal (hop * (length // hop) samples) must be "
+                                 "longer than n_fft/2 to be framed again")
+            signal, lengths = _ragged_input(signal, host)
         if not train and torch.is_grad_enabled():
             # eval mode builds no graph: the folded-BN kernels have no backward (module docstring)
             _eval_builds_no_graph(type(self).__name__, signal)
             with torch.no_grad():
-                return self.forward(signal, False)
+                return self.forward(signal, False, lengths)
         n = 1 if train else ops.stream_split(signal.shape[0])
         if n == 1:
-            return self._forward_one(signal, train)
+            return self._forward_one(signal, train, lengths=lengths)
         main = torch.cuda.current_stream(signal.device)
         outs = []
         streams = ops.side_streams(n, signal.device)
         ready = torch.cuda.Event()
         ready.record(main)
         encoded = None                                            # staggered: part k+1 starts when part k enters its LSTM
+        b0 = 0
         for part, st in zip(signal.tensor_split(n), streams):
+            part_lengths = None if lengths is None else lengths.part(b0, b0 + part.shape[0])      # each part its own rows
+            b0 += part.shape[0]
             st.wait_event(ready)
             part.record_stream(st)                                # the input is read on st: its block is not re-used before st is done
             if encoded is not None and ops.STREAM_STAGGER and part.shape[0] < ops.STREAM_STAGGER_BELOW:
                 st.wait_event(encoded)
             encoded = torch.cuda.Event()
             with torch.cuda.stream(st):
-                outs.append(self._forward_one(part, False, encoded.record) + (self.std_DCCRN.latent,))
+                outs.append(self._forward_one(part, False, encoded.record, part_lengths) + (self.std_DCCRN.latent,))
         for st in streams:                                        # join only after every part is enqueued
             main.wait_stream(st)
         # Explicit cross-stream ownership: every part's outputs were allocated from their side stream's pool
@@ -388,16 +426,18 @@ class DCCRN_(nn.Module):
         self.std_DCCRN.latent = latent
         return clean, predict
 
-    def _forward_one(self, signal, train, on_encoded=None):
-        X = self.stft.planar(signal)
+    def _forward_one(self, signal, train, on_encoded=None, lengths=None):
+        X = self.stft.planar(signal, lengths)
         net_in = _apply_datanorm(X, self.data_mean, self.data_std, train) if self.datanorm else X
         out = self.std_DCCRN.forward_planar(net_in, train=train, on_encoded=on_encoded)
         pred, predict = _predict_outputs(self, out, net_in, self.recon_type)
         if self.datanorm:
             pred, predict = _invert_datanorm(pred, self.data_mean, self.data_std)
-        clean = self.istft.planar(pred)
+        clean = self.istft.planar(pred, X.lengths)
         if self.resynthesis:
-            predict = ops.planar_to_complex(self.stft.planar(clean))
+            # the enhanced signals are framed again at their own (output) lengths
+            out_lengths = None if X.lengths is None else X.lengths.outputs(self.stft.hop_length)
+            predict = ops.planar_to_complex(self.stft.planar(clean, out_lengths))
         else:
             predict._idv = pred
         return clean, predict
@@ -450,8 +490,10 @@ class _VAEEncoderBase(nn.Module):
         finally:
             self.num_samples, self.zdim = keep_ns, keep_z
 
-    def _encode(self, x, train):
-        X = self.stft.planar(x)
+    def _encode(self, x, train, lengths=None):
+        if lengths is not None:
+            x, lengths = _ragged_input(x, check_ragged(self.causal, self.encoders, train, lengths, x, self.stft.n_fft))
+        X = self.stft.planar(x, lengths)
         skips = _run_encoders(self.encoders, X, train)
         top = skips[-1]
         lat = top
@@ -465,18 +507,19 @@ class _VAEEncoderBase(nn.Module):
 class pvae_dccrn_encoder_skip_prepare(_VAEEncoderBase):
     """CVAE / NVAE encoder.  reference: model/pvae_module.py:1791-1914.
     forward(x, train=True, eps=None) -> (z, miu, log_sigma, delta, skiper, C, F, stft_x);
-    ``eps=(eps_r, eps_i)`` ([B, ns, T, zdim]) injects the two Gaussian draws (parity tests), default samples on device."""
+    ``eps=(eps_r, eps_i)`` ([B, ns, T, zdim]) injects the two Gaussian draws (parity tests), default samples on device.
+    ``lengths`` (train=False, causal): as DCCRN_.forward; ``stft_x`` carries them to the decoders' ISTFT."""
 
     def __init__(self, net_params, causal, device, zdim, n_fft, hop_len, win_length, num_samples):
         super().__init__()
         self._setup(net_params, causal, device, zdim, n_fft, hop_len, win_length, num_samples, 1)
 
-    def forward(self, x, train=True, eps=None):
+    def forward(self, x, train=True, eps=None, lengths=None):
         if not train and torch.is_grad_enabled():
             _eval_builds_no_graph(type(self).__name__, x)
             with torch.no_grad():                                    # eval mode builds no graph
-                return self.forward(x, False, eps)
-        lat, skiper, C, F, stft_x = self._encode(x, train)
+                return self.forward(x, False, eps, lengths)
+        lat, skiper, C, F, stft_x = self._encode(x, train, lengths)
         z = self.zdim
         return (self._sample(lat, 0, eps), _lstm_out_view(lat, 0, z), _lstm_out_view(lat, z, 2 * z),
                 _lstm_out_view(lat, 2 * z, 3 * z), skiper, C, F, stft_x)
@@ -494,12 +537,12 @@ class nsvae_pvae_dccrn_encoder_twophase(_VAEEncoderBase):
         self.latent_num = latent_num
         self._setup(net_params, causal, device, zdim, n_fft, hop_len, win_length, num_samples, latent_num)
 
-    def forward(self, x, train=True, eps=None):
+    def forward(self, x, train=True, eps=None, lengths=None):
         if not train and torch.is_grad_enabled():
             _eval_builds_no_graph(type(self).__name__, x)
             with torch.no_grad():                                    # eval mode builds no graph
-                return self.forward(x, False, eps)
-        lat, skiper, C, F, stft_x = self._encode(x, train)
+                return self.forward(x, False, eps, lengths)
+        lat, skiper, C, F, stft_x = self._encode(x, train, lengths)
         z = self.zdim
         out = []
         for k in range(2):
@@ -583,8 +626,11 @@ class _VAEDecoderBase(nn.Module):
                 p = dec.forward_planar(p, train)
             outs.append(p)
         X = planar_of(stft_x.unsqueeze(1), zp.Tp) if getattr(stft_x, "_idv", None) is None else stft_x._idv
+        if train and X.lengths is not None:
+            raise ValueError("a stft_x of utterances of different lengths is accepted with train=False only: train mode computes "
+                             "whole-batch batch-norm moments over all columns, the padded ones included")
         pred, predict = _predict_outputs(self, p, X, self.recon_type, x_div=Bn // X.B)
-        recon = self.istft.planar(pred)
+        recon = self.istft.planar(pred, X.lengths)                   # a ragged batch: row b uses the lengths of utterance b // ns
         predict._idv = pred
         return recon, predict, outs
 
@@ -626,5 +672,9 @@ class nsvae_pvae_dccrn_decoder_twophase(_VAEDecoderBase):
     def forward(self, stft_x, z, skiper, C, F, train=True, pad="zero"):
         recon, predict, _ = self._decode(stft_x, z, skiper, C, F, train, pad)
         if self.resynthesis:
-            predict = ops.planar_to_complex(self.stft.planar(recon))
+            lengths = getattr(getattr(stft_x, "_idv", None), "lengths", None)
+            if lengths is not None:                                  # one output length per decoded row
+                ns = recon.shape[0] // len(lengths)
+                lengths = [self.stft.hop_length * (v // self.stft.hop_length) for v in lengths.host for _ in range(ns)]
+            predict = ops.planar_to_complex(self.stft.planar(recon, lengths))
         return recon, predict

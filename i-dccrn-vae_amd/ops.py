@@ -41,12 +41,14 @@ class Planar:
 
     ``T`` is the number of valid frames (t_valid); ``Tp`` = T_stft + 1 columns per utterance.
     ``tensor5()`` exposes it with the reference's shape [B, C, F, T, 2] as a strided view.
+    ``lengths``: the :class:`Lengths` of a batch of utterances of different lengths (set by ``stft(..., lengths=)`` on the
+    spectrum it returns, None everywhere else); ``T`` is then the longest utterance's frame count.
     """
 
-    __slots__ = ("buf", "C", "F", "B", "T", "Tp", "Jp")
+    __slots__ = ("buf", "C", "F", "B", "T", "Tp", "Jp", "lengths")
 
-    def __init__(self, buf, C, F, B, T, Tp, Jp):
-        self.buf, self.C, self.F, self.B, self.T, self.Tp, self.Jp = buf, C, F, B, T, Tp, Jp
+    def __init__(self, buf, C, F, B, T, Tp, Jp, lengths=None):
+        self.buf, self.C, self.F, self.B, self.T, self.Tp, self.Jp, self.lengths = buf, C, F, B, T, Tp, Jp, lengths
 
     @staticmethod
     def jp_for(B: int, Tp: int) -> int:
@@ -773,8 +775,71 @@ class DftPlan:
         return self._inv_T
 
 
-def stft(x: torch.Tensor, plan: DftPlan, Tp: Optional[int] = None) -> Planar:
-    """STFT.forward: x [B, L] -> planar [2][1][F][Jp]."""
+def check_lengths(lengths, B: int, L: int, n_fft: Optional[int]) -> list:
+    """The guards on per-utterance sample counts (host only, no device use) -> list of ints.  ``lengths``: a python sequence
+    or a CPU integer tensor with one entry per row of the padded [B, L] batch, each n_fft/2 < length <= L (n_fft None: a
+    signal that is not framed, 0 < length <= L)."""
+    if isinstance(lengths, Lengths):
+        lengths = lengths.host
+    if isinstance(lengths, torch.Tensor):
+        if lengths.is_cuda:
+            raise ValueError("lengths must be a python sequence or a CPU integer tensor: they size the batch on the host, and "
+                             "a GPU tensor would have to be fetched with a synchronisation")
+        if lengths.dim() != 1 or lengths.is_floating_point() or lengths.is_complex() or lengths.dtype == torch.bool:
+            raise ValueError("lengths must be a 1-D integer tensor")
+        lengths = lengths.tolist()
+    elif isinstance(lengths, (str, bytes)) or not isinstance(lengths, Sequence):
+        raise ValueError("lengths must be a python sequence or a CPU integer tensor")
+    if any(isinstance(v, bool) or not isinstance(v, int) for v in lengths):
+        raise ValueError("lengths must be integers (sample counts)")
+    if len(lengths) != B:
+        raise ValueError(f"{len(lengths)} lengths for a batch of {B} utterances")
+    for b, v in enumerate(lengths):
+        if n_fft is None and v <= 0:
+            raise ValueError(f"lengths[{b}] = {v}: a length must be positive")
+        if n_fft is not None and v <= n_fft // 2:
+            raise ValueError(f"lengths[{b}] = {v}: torch.stft's reflect padding needs more than n_fft/2 = {n_fft // 2} samples")
+        if v > L:
+            raise ValueError(f"lengths[{b}] = {v} exceeds the {L} samples per row of the padded batch")
+    return list(lengths)
+
+
+class Lengths:
+    """Sample counts of a batch of utterances of different lengths: ``host`` (list of ints, sizes the launch) and ``dev``
+    (int32 on the device, read by idv_stft_frames_ragged / idv_istft_ola_ragged / idv_sisdr_ragged)."""
+
+    __slots__ = ("host", "dev")
+
+    def __init__(self, host, device, dev=None):
+        self.host = list(host)
+        self.dev = torch.tensor(self.host, dtype=torch.int32, device=device) if dev is None else dev
+
+    def __len__(self):
+        return len(self.host)
+
+    def part(self, b0: int, b1: int) -> "Lengths":
+        """Rows b0 .. b1-1 (a sub-batch of a stream split); shares the device array."""
+        return Lengths(self.host[b0:b1], None, self.dev[b0:b1])
+
+    def outputs(self, hop: int) -> "Lengths":
+        """The lengths of the enhanced signals, hop * (length // hop)."""
+        return Lengths([hop * (v // hop) for v in self.host], self.dev.device)
+
+
+def _ragged_rows(x: torch.Tensor) -> torch.Tensor:
+    """The padded batch as the ragged framing kernels take it: fp32 rows at any pitch (a column slice of a wider buffer is
+    passed as it is), unit stride inside a row."""
+    if x.dtype != torch.float32 or x.stride(1) != 1 or x.stride(0) < x.shape[1]:
+        x = x.float().contiguous()
+    return x
+
+
+def stft(x: torch.Tensor, plan: DftPlan, Tp: Optional[int] = None, lengths=None) -> Planar:
+    """STFT.forward: x [B, L] -> planar [2][1][F][Jp].  ``lengths`` (a :class:`Lengths`, a python sequence or a CPU integer
+    tensor): row b holds lengths[b] samples and is mirrored at its own end; the frames past its 1 + lengths[b] // hop are
+    zeros (whatever x holds there) and the returned spectrum carries the lengths."""
+    if lengths is not None:
+        return _stft_ragged(x, plan, Tp, lengths)
     B, Lx = x.shape
     T = 1 + Lx // plan.hop
     assert T == plan.T, "DftPlan built for another length"
@@ -797,9 +862,45 @@ def stft(x: torch.Tensor, plan: DftPlan, Tp: Optional[int] = None) -> Planar:
     return out
 
 
-def istft(spec: Planar, plan: DftPlan) -> torch.Tensor:
-    """ISTFT.forward: planar [2][1][F][Jp] -> y [B, hop*(T-1)]."""
+def _stft_ragged(x: torch.Tensor, plan: DftPlan, Tp: Optional[int], lengths) -> Planar:
+    B, Lx = x.shape
+    T = 1 + Lx // plan.hop
+    assert T == plan.T, "DftPlan built for another length"
+    host = check_lengths(lengths, B, Lx, plan.n_fft)
+    if not isinstance(lengths, Lengths):
+        lengths = Lengths(host, x.device)
+    Tp = Tp or T + 1
+    x = _ragged_rows(x)
+    assert plan.win % 2 == 0
+    out = Planar.empty(1, plan.F, B, T, Tp, x.device)
+    out.lengths = lengths
+    if PRECISION == "bf16x3":
+        kimg = KImage((plan.win + 63) // 64 * 64, out.Jp, x.device)
+        call("idv_stft_frames_kimage_ragged", p(x), ll(x.stride(0)), p(lengths.dev), i(B), i(plan.n_fft), i(plan.win), i(plan.hop),
+             i(T), kimg.ptr(), ll(kimg.lo_off), i(Tp), i(out.Jp), stream_ptr())
+        pw_bf16x3(kimg, 0, plan.win, plan.fwd16, None, 2 * plan.F, B, Tp, T, out.ptr())
+        return out
+    fr = Planar.empty(1, plan.win // 2, B, T, Tp, x.device)      # [win][Jp] scratch (2*C*F = win planes)
+    call("idv_stft_frames_ragged", p(x), ll(x.stride(0)), p(lengths.dev), i(B), i(plan.n_fft), i(plan.win), i(plan.hop), i(T),
+         fr.ptr(), i(Tp), i(fr.Jp), stream_ptr())
+    pw_gemm(fr.ptr(), plan.win, plan.fwd[0], plan.fwd[1], 2 * plan.F, B, Tp, fr.Jp, T, out.ptr())
+    return out
+
+
+def istft(spec: Planar, plan: DftPlan, lengths=None) -> torch.Tensor:
+    """ISTFT.forward: planar [2][1][F][Jp] -> y [B, hop*(T-1)].  ``lengths`` (the input signals' sample counts, as for
+    :func:`stft`): row b is the overlap-add of its own 1 + length // hop frames over their own envelope, hop * (length // hop)
+    samples followed by zeros.  Fewer lengths than rows: each serves ``B // len(lengths)`` consecutive rows (the VAE decoders'
+    num_samples rows per utterance)."""
     B, T = spec.B, spec.T
+    if lengths is not None:
+        nl = len(lengths)
+        if nl < 1 or B % nl:
+            raise ValueError(f"{nl} lengths for {B} rows: the row count must be a multiple of the number of lengths")
+        if not isinstance(lengths, Lengths):
+            lengths = Lengths(check_lengths(lengths, nl, plan.hop * T + plan.hop - 1, plan.n_fft), spec.buf.device)
+        if max(lengths.host) // plan.hop + 1 > T:
+            raise ValueError("a length needs more frames than the spectrum holds")
     fr = Planar.empty(1, plan.win // 2, B, T, spec.Tp, spec.buf.device)
     if PRECISION == "bf16x3":
         kimg = KImage.from_planes(spec.ptr(), 2 * plan.F, B * spec.Tp, spec.Jp, spec.buf.device, pad_to=64)
@@ -807,6 +908,10 @@ def istft(spec: Planar, plan: DftPlan) -> torch.Tensor:
     else:
         pw_gemm(spec.ptr(), 2 * plan.F, plan.inv[0], plan.inv[1], plan.win, B, spec.Tp, spec.Jp, T, fr.ptr())
     y = torch.empty(B, plan.hop * (T - 1), dtype=torch.float32, device=spec.buf.device)
+    if lengths is not None:
+        call("idv_istft_ola_ragged", fr.ptr(), p(lengths.dev), i(B // len(lengths)), i(B), i(plan.n_fft), i(plan.win), i(plan.hop),
+             i(T), i(spec.Tp), i(fr.Jp), p(y), ll(y.stride(0)), stream_ptr())
+        return y
     call("idv_istft_ola", fr.ptr(), p(plan.env_inv), i(B), i(plan.n_fft), i(plan.win), i(plan.hop), i(T), i(spec.Tp),
          i(fr.Jp), p(y), stream_ptr())
     return y

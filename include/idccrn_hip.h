@@ -661,6 +661,27 @@ int idv_stream_ola(const float* frames, int Tp, int Jp, const float* carry_in, i
                    int n_fft, int win, int hop, long long t0, int k, long long T_total, long long e0, long long e1, long long p_end,
                    float* y, int ldy, long long y_off, void* stream);
 
+/* ---- batches of utterances of different lengths (ragged.hip, reduce.hip; inference.enhance_* / compute_sisdr with `lengths`) ---
+ * lens: device int32[], samples per utterance.  Utterance b has T_b = 1 + lens[b] / hop frames and hop * (T_b - 1) output samples;
+ * the batch is laid out for Tmax = max_b T_b frames, Tp >= Tmax + 1.  A causal network computes frame t from frames <= t, so only
+ * these signal ends and the metric need the lengths (additive entries: IDV_ABI_VERSION is unchanged).
+ *
+ * idv_stft_frames for x[B][ldx] (row pitch ldx): the end mirror of row b is taken at lens[b] and no sample at or past lens[b] is
+ * read; the columns of frames t >= T_b and the guard column are zeros.  The _kimage form writes the split-bf16 K-major image
+ * (idv_stft_frames_kimage) instead. */
+int idv_stft_frames_ragged(const float* x, long long ldx, const int* lens, int B, int n_fft, int win, int hop, int Tmax, float* frames,
+                           int Tp, int Jp, void* stream);
+int idv_stft_frames_kimage_ragged(const float* x, long long ldx, const int* lens, int B, int n_fft, int win, int hop, int Tmax, void* img,
+                                  long long lo_off_elems, int Tp, int Jp, void* stream);
+/* idv_istft_ola per row: row b uses lens[b / len_div] (len_div = num_samples for the VAE decoders' B * num_samples rows).
+ * Overlap-add of frames 0 .. T_b - 1 only, divided by the envelope of those frames (formed on the fly in double, as idv_make_dft
+ * forms its table), into y[b][s] for s < hop * (T_b - 1); zeros from there to hop * (Tmax - 1).  y rows at pitch ldy. */
+int idv_istft_ola_ragged(const float* frames, const int* lens, int len_div, int B, int n_fft, int win, int hop, int Tmax, int Tp, int Jp,
+                         float* y, long long ldy, void* stream);
+/* idv_sisdr over the first lens[b] samples of each row (clamped to the shorter row pitch); work: 3*B doubles. */
+int idv_sisdr_ragged(const float* ref, int ref_ld, const float* est, int est_ld, const int* lens, int B, double* work, float* out,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif
