@@ -20,8 +20,10 @@
 // 2 p + 1) interleaved per pair (one 8-byte read fetches the operands of two tiles); the FREQUENCY transform A + cb B of cgemm_wino
 // happens at the operand read (two reads + one add).  Weights: cgemm_wino's fragments re-ordered by idv_pack_cconv_tw (lane =
 // channel parity x 32 + co), per (channel pair, wave).  Design notes and measurements: DESIGN.md 3.1e.
+#include <atomic>
 #include <cstdint>
 #include <cstdlib>
+#include <type_traits>
 #include "cgemm.hpp"
 #include "../../include/idccrn_hip.h"
 
@@ -47,6 +49,8 @@ struct TwArgs {
     int add_div, add_Jp;
     int jtiles, ftiles;
     int xcd_split;        // block order: the co tiles of a column block on different XCDs (see the kernel)
+    int cgroups;          // cotiles / NCT: workgroups per (column block, row pair); the block order runs over these
+    int stagger;          // NCT = 2, odd-row phase: waves 4 .. 7 stage one k-step later than their SIMD partners, waves 0 .. 3
 };
 
 constexpr int TW_PACK_CI = 8;      // pack granularity in complex input channels (cgemm_wino's WCIK)
@@ -80,8 +84,12 @@ template <int PH> constexpr int tw_wslots() { return PH == 0 ? 9 : 8; }        /
 
 // DBG (timing experiments only, results wrong): 1 = no staging after the prologue, 2 = no weight re-loads, 4 = no epilogue exchange
 // LEFT: the time taps read (x[t-1], x[t]) (tshift = -1: the extra window column is on the left), else (x[t], x[t+1])
-template <int PH, int CIK, bool LEFT, int DBG = 0, int RDW = 2, bool WVEC = true, bool STATS = false>
-__global__ __launch_bounds__(256, 2) void cconv_tw_kernel(const TwArgs a) {
+// NCT: co tiles per workgroup.  2: eight waves; waves 0 .. 3 run the program of co tile 2 p, waves 4 .. 7 the same program on co tile
+// 2 p + 1 (tiles, weights, K order and epilogue of a co tile are those of NCT = 1: the results are bit-identical), and all 512 threads
+// share ONE staging of the raw rows, which do not depend on the output channel: half the staging work and input fetch per MFMA.  One
+// workgroup per CU, still two waves per SIMD.
+template <int PH, int CIK, bool LEFT, int DBG = 0, int RDW = 2, bool WVEC = true, bool STATS = false, int NCT = 1>
+__global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw_kernel(const TwArgs a) {
     constexpr int NR = tw_nr<PH>(), NT = tw_nt<PH>(), NTP = tw_ntp<PH>(), NTW = tw_ntw<PH>();
     constexpr int NRAW = PH == 0 ? 4 : 3, ROW0 = PH == 0 ? 0 : 1;       // raw patch rows d(ROW0) .. : input rows m0 - 1 + ROW0 ..
     constexpr int KS = CIK / 2;                  // MFMA k-steps (channel pairs) per chunk
@@ -89,15 +97,20 @@ __global__ __launch_bounds__(256, 2) void cconv_tw_kernel(const TwArgs a) {
     constexpr int NE = CIK * RT;
     constexpr int NBUF = 2;
     constexpr int NITEM = CIK * NRAW * 16;       // staging items per chunk: (channel, raw row, 2 column pairs)
-    constexpr int NLD = (NITEM + 255) / 256;
+    constexpr int NTHR = 256 * NCT;
+    constexpr int NLD = (NITEM + NTHR - 1) / NTHR;
+    static_assert(NCT == 1 || NCT == 2, "one or two co tiles per workgroup");
     static_assert(KS % RDW == 0 && NLD <= 2, "weight ring slots are compile-time; at most two staging items per thread");
-    static_assert(NT * 4 * 64 <= NBUF * NE, "the epilogue exchange fits the patch buffers");
+    static_assert(NLD + NCT - 1 < KS, "the staging k-steps (from 1 on, waves 4 .. 7 one later) end before the barrier's k-step");
+    static_assert(NCT * NT * 4 * 64 <= NBUF * NE, "the epilogue exchange (one area per co tile) fits the patch buffers");
 
     extern __shared__ __attribute__((aligned(16))) float smem[];
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // the wave's place in its co tile's program; which co tile of the workgroup
+    const int w4 = NCT == 1 ? wave : wave & 3, cth = NCT == 1 ? 0 : wave >> 2;
     const int half = lane >> 5, l31 = lane & 31;
 
     // block order: all (frequency tile, co tile) workgroups of a 64-column block on ONE XCD (block ids equal mod 8 share an XCD):
@@ -108,18 +121,19 @@ __global__ __launch_bounds__(256, 2) void cconv_tw_kernel(const TwArgs a) {
     if (a.xcd_split) {
         // 2 / 4 / 8 co tiles: co tile ct always on the XCDs = ct (mod cotiles), so that an XCD streams 1 / cotiles of the layer's taps
         // (2 - 5 MB: its L2 holds them) and the raw rows of a column block are read by cotiles XCDs instead of one
-        const int G = 8 / a.cotiles;
-        ct = xcd % a.cotiles;
-        jt = (slot / a.ftiles) * G + xcd / a.cotiles;
+        const int G = 8 / a.cgroups;
+        ct = xcd % a.cgroups;
+        jt = (slot / a.ftiles) * G + xcd / a.cgroups;
         ft = slot - (slot / a.ftiles) * a.ftiles;
     } else {
-        const int per = a.cotiles * a.ftiles;
+        const int per = a.cgroups * a.ftiles;
         jt = (slot / per) * 8 + xcd;
         const int rem = slot - (slot / per) * per;
-        ft = rem / a.cotiles;
-        ct = rem - ft * a.cotiles;
+        ft = rem / a.cgroups;
+        ct = rem - ft * a.cgroups;
     }
     if (jt >= a.jtiles) return;
+    ct = NCT * ct + cth;                          // (ct was the workgroup's group of NCT co tiles)
     const int j0 = jt * 64;
     const int m0 = 2 * ft;
     const int rbase = m0 - 1 + ROW0;
@@ -140,13 +154,13 @@ __global__ __launch_bounds__(256, 2) void cconv_tw_kernel(const TwArgs a) {
     int offA[UNI ? 1 : NPAIR + 1], offB[UNI ? 1 : NPAIR + 1];
     float cbj[UNI ? 1 : NPAIR + 1];
     if (UNI) {
-        cbj[0] = tw_cb<PH>(wave);
-        offA[0] = (tw_ra<PH>(wave) - ROW0) * 288;
-        offB[0] = (tw_rb<PH>(wave) - ROW0) * 288;             // (cb is never 0 in this phase)
+        cbj[0] = tw_cb<PH>(w4);
+        offA[0] = (tw_ra<PH>(w4) - ROW0) * 288;
+        offB[0] = (tw_rb<PH>(w4) - ROW0) * 288;             // (cb is never 0 in this phase)
     } else {
 #pragma unroll
         for (int j = 0; j <= NPAIR; ++j) {
-            int t = tw_tile(PH, wave, j < NPAIR ? 2 * j : NTW - 1);
+            int t = tw_tile(PH, w4, j < NPAIR ? 2 * j : NTW - 1);
             t = t < 0 ? 0 : t;
             const int r = t / 9, plane = t - r * 9;
             cbj[j] = tw_cb<PH>(r);
@@ -166,7 +180,7 @@ __global__ __launch_bounds__(256, 2) void cconv_tw_kernel(const TwArgs a) {
     bool interior[NLD];       // wave-uniform: every lane's item has its row and all five window columns inside the tensor
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
-        const int e = tid + i * 256;
+        const int e = tid + i * NTHR;
         const int c8 = e & 15;
         const int rl = (e >> 4) % NRAW, cl = e / (16 * NRAW);
         item_cl[i] = cl;
@@ -243,8 +257,9 @@ __global__ __launch_bounds__(256, 2) void cconv_tw_kernel(const TwArgs a) {
         const float xd_ = g == 0 ? fr[q0 + 2] + fi[q0 + 2] : (g == 1 ? fr[q0 + 2] : fi[q0 + 2]);
         return tau == 0 ? xa_ - xb_ : (tau == 1 ? xb_ : xb_ - xd_);
     };
-    // an item exists for every thread in the even-row phase (512 items); in the odd-row phase the second item only in waves 0, 1
-    auto item_exists = [&](int i) -> bool { return NITEM >= (i + 1) * 256 || wave * 64 + i * 256 < NITEM; };
+    // an item exists for every thread in the even-row phase (512 items); in the odd-row phase (384) the second item only in waves 0, 1
+    // (NCT = 2: the one item in waves 0 .. 5)
+    auto item_exists = [&](int i) -> bool { return NITEM >= (i + 1) * NTHR || wave * 64 + i * NTHR < NITEM; };
     // LDS layout of a raw row: planes (2 j, 2 j + 1) interleaved per column pair at [j][32 pairs][2], plane 8 at [256 + pair]:
     // a lane fetches the operands of two tiles with one 8-byte read, an item writes two planes x two pairs with one 16-byte write
     auto stage_plane2 = [&](float* dst, int i, int j) {
@@ -267,7 +282,7 @@ __global__ __launch_bounds__(256, 2) void cconv_tw_kernel(const TwArgs a) {
     // odd-row phase two 16-byte loads
     constexpr int WS = tw_wslots<PH>();
     const float* wbase = a.wfrag + ((size_t)(PH == 1 ? (size_t)a.cotiles * a.UP * tw_ntp<0>() : 0) + (size_t)ct * a.UP * NTP) * 64 +
-                         (size_t)wave * WS * 64;
+                         (size_t)w4 * WS * 64;
     const int total_ks = nchunk * KS;
     float a_w[RDW][NTW];
     auto load_w = [&](int g, float (&dst)[NTW]) {
@@ -315,44 +330,55 @@ __global__ __launch_bounds__(256, 2) void cconv_tw_kernel(const TwArgs a) {
     __syncthreads();
 
     load_raw_all(smem + (size_t)half * RT);
-    for (int chunk = 0; chunk < nchunk; ++chunk) {
-        const float* P = smem + (chunk & 1) * NE;
-        float* Pn = smem + ((chunk + 1) & 1) * NE;
-        const int nxt = chunk + 1 < nchunk ? chunk + 1 : chunk, nxt2 = chunk + 2 < nchunk ? chunk + 2 : nchunk - 1;
+    // the main loop; late_ (NCT = 2, odd-row phase only): the copy that stages one k-step later, for waves 4 .. 7, so that SIMD partners
+    // do not stage at the same time.  A copy, not a branch on the wave inside the loop: the staging steps sit between the MFMAs, and
+    // with a wave-uniform branch at each of them the paired kernels were SLOWER than the unpaired ones (dec0-3, B = 64: 36.4 against
+    // 34.2 ms; in this form 33.0).  The even-row phase has no late copy: a second copy of its loop spills 60 - 72 bytes per lane.
+    auto run = [&](auto late_) {
+        constexpr bool LATE = decltype(late_)::value;
+        for (int chunk = 0; chunk < nchunk; ++chunk) {
+            const float* P = smem + (chunk & 1) * NE;
+            float* Pn = smem + ((chunk + 1) & 1) * NE;
+            const int nxt = chunk + 1 < nchunk ? chunk + 1 : chunk, nxt2 = chunk + 2 < nchunk ? chunk + 2 : nchunk - 1;
 #pragma unroll
-        for (int ul = 0; ul < KS; ++ul) {
-            // operands of the next k-step: of this chunk, or (last k-step, after the barrier below) of the next chunk
-            const float* bnext = ul + 1 < KS ? P + (size_t)(2 * (ul + 1) + half) * RT : Pn + (size_t)half * RT;
-            // staging of chunk + 1 rides on k-steps 1 (item 0) and 2 (item 1): the item's registers were loaded one chunk ago, the
-            // other buffer was last read in the previous chunk (a barrier since); the steps of the store are dealt out between MFMAs
-            const int si = ul - 1;
-            const bool staging = !(DBG & 1) && si >= 0 && si < NLD;
+            for (int ul = 0; ul < KS; ++ul) {
+                // operands of the next k-step: of this chunk, or (last k-step, after the barrier below) of the next chunk
+                const float* bnext = ul + 1 < KS ? P + (size_t)(2 * (ul + 1) + half) * RT : Pn + (size_t)half * RT;
+                // staging of chunk + 1 rides on k-steps 1 (item 0) and 2 (item 1): the item's registers were loaded one chunk ago, the
+                // other buffer was last read in the previous chunk (a barrier since); the steps of the store are dealt out between MFMAs
+                const int si = ul - 1 - (LATE ? 1 : 0);
+                const bool staging = !(DBG & 1) && si >= 0 && si < NLD;
 #pragma unroll
-            for (int k = 0; k < NTW; ++k) {
-                const float b = xa[k] + cbj[UNI ? 0 : (k >> 1 < NPAIR ? k >> 1 : NPAIR)] * xb[k];
-                acc[k] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_w[ul % RDW][k], b, acc[k], 0, 0, 0);
-                if (ul == KS - 1 && k == 0) {
-                    // every wave has stored chunk + 1 (k-steps 1, 2) and issued its last reads of P: after this barrier Pn is complete
-                    // and P may be overwritten (from k-step 1 of the next chunk on)
+                for (int k = 0; k < NTW; ++k) {
+                    const float b = xa[k] + cbj[UNI ? 0 : (k >> 1 < NPAIR ? k >> 1 : NPAIR)] * xb[k];
+                    acc[k] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_w[ul % RDW][k], b, acc[k], 0, 0, 0);
+                    if (ul == KS - 1 && k == 0) {
+                        // every wave has stored chunk + 1 (k-steps 1, 2) and issued its last reads of P: after this barrier Pn is complete
+                        // and P may be overwritten (from k-step 1 of the next chunk on)
+                        __builtin_amdgcn_sched_barrier(0);
+                        __syncthreads();
+                    }
+                    // the operand registers of the tiles done so far are free again
+                    if ((k & 1) && (k >> 1) < NPAIR) load_raw2(bnext, k >> 1);
+                    if (k == NTW - 1) load_raw2(bnext, NPAIR);
+                    if (staging) {
+                        // the store's steps between the MFMAs: window at 0, plane pairs at 1, 3, 5 and (7 or, with seven tiles, 6), plane 8 last
+                        if (k == 0) stage_window(nxt, si);
+                        if ((k & 1) && k < 6) stage_plane2(Pn, si, k >> 1);
+                        if (k == (NTW == 9 ? 7 : 6)) stage_plane2(Pn, si, 3);
+                        if (k == NTW - 1) stage_plane2(Pn, si, 4);
+                        if (k == NTW - 1) stage_load(nxt2, si);
+                    }
                     __builtin_amdgcn_sched_barrier(0);
-                    __syncthreads();
                 }
-                // the operand registers of the tiles done so far are free again
-                if ((k & 1) && (k >> 1) < NPAIR) load_raw2(bnext, k >> 1);
-                if (k == NTW - 1) load_raw2(bnext, NPAIR);
-                if (staging) {
-                    // the store's steps between the MFMAs: window at 0, plane pairs at 1, 3, 5 and (7 or, with seven tiles, 6), plane 8 last
-                    if (k == 0) stage_window(nxt, si);
-                    if ((k & 1) && k < 6) stage_plane2(Pn, si, k >> 1);
-                    if (k == (NTW == 9 ? 7 : 6)) stage_plane2(Pn, si, 3);
-                    if (k == NTW - 1) stage_plane2(Pn, si, 4);
-                    if (k == NTW - 1) stage_load(nxt2, si);
-                }
-                __builtin_amdgcn_sched_barrier(0);
+                if (!(DBG & 2)) load_w(chunk * KS + ul + RDW, a_w[ul % RDW]);
             }
-            if (!(DBG & 2)) load_w(chunk * KS + ul + RDW, a_w[ul % RDW]);
         }
-    }
+    };
+    if (NCT == 2 && PH == 1 && a.stagger && cth)
+        run(std::integral_constant<bool, NCT == 2 && PH == 1>{});
+    else
+        run(std::false_type{});
     __syncthreads();                                          // all patch reads done: the buffers become the exchange area
 
     // ------------------------------------------------------------------ epilogue
@@ -360,7 +386,7 @@ __global__ __launch_bounds__(256, 2) void cconv_tw_kernel(const TwArgs a) {
     // 4 s + w of lane l -- output channel co, column pair l31 -- reads ALL tiles there and runs the output transforms
     const float slope = a.slope ? *a.slope : 1.0f;
     const bool has_act = a.slope != nullptr;
-    float* E = smem;
+    float* E = smem + cth * (NT * 4 * 64);                    // one exchange area per co tile
     const int jA = j0 + 2 * l31;                              // the pair's two output columns jA, jA + 1
     bool keep[2], inb[2];
     int ja[2];                                                // the addend's column: utterance b / add_div of its own buffer
@@ -377,7 +403,7 @@ __global__ __launch_bounds__(256, 2) void cconv_tw_kernel(const TwArgs a) {
         if (s > 0) __syncthreads();
 #pragma unroll
         for (int k = 0; k < NTW; ++k) {
-            const int t = tw_tile(PH, wave, k);
+            const int t = tw_tile(PH, w4, k);
             if (t >= 0) {
 #pragma unroll
                 for (int rr = 0; rr < 4; ++rr) E[(t * 4 + rr) * 64 + lane] = acc[k][4 * s + rr];
@@ -386,7 +412,7 @@ __global__ __launch_bounds__(256, 2) void cconv_tw_kernel(const TwArgs a) {
         __syncthreads();
         float v[NT];
 #pragma unroll
-        for (int t = 0; t < NT; ++t) v[t] = E[(t * 4 + wave) * 64 + lane];
+        for (int t = 0; t < NT; ++t) v[t] = E[(t * 4 + w4) * 64 + lane];
         // time, then Gauss: P[r][q][re / im]
         float pr[NR][2], pi[NR][2];
 #pragma unroll
@@ -404,7 +430,7 @@ __global__ __launch_bounds__(256, 2) void cconv_tw_kernel(const TwArgs a) {
                 pi[r][q] = y[0][q] + y[1][q];
             }
         }
-        const int rg = 4 * s + wave;
+        const int rg = 4 * s + w4;
         const int co = ct * 32 + (rg & 3) + 8 * (rg >> 2) + 4 * half;
         const bool cok = co < a.Cout;
         const f32x4 e0 = *(const f32x4*)(a.epi + (size_t)co * 8);
@@ -510,7 +536,7 @@ __global__ void pack_cconv_tw_kernel(const float* __restrict__ wino, int cotiles
     }
 }
 
-template <int PH, int CIK, bool LEFT, int DBG, int RDW, bool WVEC = true, bool STATS = false>
+template <int PH, int CIK, bool LEFT, int DBG, int RDW, bool WVEC = true, bool STATS = false, int NCT = 1>
 int launch_tw_ph_l(const TwArgs& a, hipStream_t st);
 // weight fragments as [64 lanes][4 tiles] groups with 16-byte loads (bit PH set) or slot-major [slot][64 lanes] with 4-byte loads: measured
 // (B = 64, dec0-3) even-row phase 22.0 -> 21.1 ms with the vector form, odd-row phase 14.1 -> 17.8 ms: default 1 = even-row phase only
@@ -522,6 +548,12 @@ inline int tw_wvec_mask() {
 template <int PH, int CIK, int DBG = 0, int RDW = 2>
 int launch_tw_ph(const TwArgs& a, hipStream_t st) {
     const bool wv = (tw_wvec_mask() >> PH) & 1;
+    // two co tiles per workgroup (idv_tw_pair bit PH): an even number of co tiles, default weight layouts
+    if (DBG == 0 && RDW == 2 && wv == (PH == 0) && a.cotiles % 2 == 0 && ((idv_tw_pair(-1) >> PH) & 1)) {
+        constexpr bool WV = PH == 0;
+        if (a.stats) return a.tshift ? launch_tw_ph_l<PH, CIK, true, 0, 2, WV, true, 2>(a, st) : launch_tw_ph_l<PH, CIK, false, 0, 2, WV, true, 2>(a, st);
+        return a.tshift ? launch_tw_ph_l<PH, CIK, true, 0, 2, WV, false, 2>(a, st) : launch_tw_ph_l<PH, CIK, false, 0, 2, WV, false, 2>(a, st);
+    }
     if (DBG == 0 && RDW == 2 && a.stats) {                    // the training forward: default weight layouts only
         constexpr bool WV = PH == 0;
         if (wv != WV) return IDV_EINVAL;
@@ -531,38 +563,62 @@ int launch_tw_ph(const TwArgs& a, hipStream_t st) {
         return a.tshift ? launch_tw_ph_l<PH, CIK, true, 0, 2, false>(a, st) : launch_tw_ph_l<PH, CIK, false, 0, 2, false>(a, st);
     return a.tshift ? launch_tw_ph_l<PH, CIK, true, DBG, RDW>(a, st) : launch_tw_ph_l<PH, CIK, false, DBG, RDW>(a, st);
 }
-template <int PH, int CIK, bool LEFT, int DBG, int RDW, bool WVEC, bool STATS>
+template <int PH, int CIK, bool LEFT, int DBG, int RDW, bool WVEC, bool STATS, int NCT>
 int launch_tw_ph_l(const TwArgs& a, hipStream_t st) {
     constexpr int NE = CIK * (PH == 0 ? 4 : 3) * 9 * 32;
     constexpr size_t smem = 2 * NE * sizeof(float);
-    static_assert(smem * 2 <= 160 * 1024, "the patch buffers of two workgroups must fit the 160 KB of LDS");
+    static_assert(smem * (NCT == 1 ? 2 : 1) <= 160 * 1024, "the patch buffers of two workgroups (NCT = 2: of one) must fit the 160 KB of LDS");
     TwArgs b = a;
     b.jtiles = (a.J + 63) / 64;
     b.ftiles = PH == 1 ? a.Fin / 2 : (a.Fin + 1) / 2;
     if (b.ftiles == 0) return IDV_OK;
     // co tiles on different XCDs: dec0-3 at B = 64 34.7 -> 34.3 ms (dec0, eight co tiles: 9.81 -> 9.54); IDV_TW_XCD_SPLIT=0: one XCD per column block
     static const int xsplit = [] { const char* e = getenv("IDV_TW_XCD_SPLIT"); return e ? atoi(e) : 1; }();
-    b.xcd_split = (xsplit && (b.cotiles == 2 || b.cotiles == 4 || b.cotiles == 8)) ? 1 : 0;
-    long long nblk = (long long)((b.jtiles + 7) / 8) * 8 * b.ftiles * b.cotiles;
+    b.cgroups = b.cotiles / NCT;                              // (NCT = 2: the caller checked that the co-tile count is even)
+    if (b.cgroups * NCT != b.cotiles) return IDV_EINVAL;
+    static const int stag = [] { const char* e = getenv("IDV_TW_PAIR_STAGGER"); return e ? atoi(e) : 1; }();
+    b.stagger = stag;
+    b.xcd_split = (xsplit && (b.cgroups == 2 || b.cgroups == 4 || b.cgroups == 8)) ? 1 : 0;
+    long long nblk = (long long)((b.jtiles + 7) / 8) * 8 * b.ftiles * b.cgroups;
     if (b.xcd_split) {
-        const int G = 8 / b.cotiles;
+        const int G = 8 / b.cgroups;
         nblk = (long long)((b.jtiles + G - 1) / G) * b.ftiles * 8;
     }
     if (nblk > 0x7fffffffLL) return IDV_EINVAL;
-    auto k = cconv_tw_kernel<PH, CIK, LEFT, DBG, RDW, WVEC, STATS>;
-    // (once per instantiation and device: setting it on every launch is host time, a lot of it under a profiler)
-    static bool attr_set[64] = {};
+    auto k = cconv_tw_kernel<PH, CIK, LEFT, DBG, RDW, WVEC, STATS, NCT>;
+    // (once per instantiation and device: setting it on every launch is host time, a lot of it under a profiler.  Two threads that
+    // both find the flag clear both set the same value.)
+    static std::atomic<bool> attr_set[64];
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return IDV_ELAUNCH;
-    if (smem > 64 * 1024 && !attr_set[dev]) {
+    if (smem > 64 * 1024 && !attr_set[dev].load(std::memory_order_acquire)) {
         if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return IDV_ELAUNCH;
-        attr_set[dev] = true;
+        attr_set[dev].store(true, std::memory_order_release);
     }
-    hipLaunchKernelGGL(k, dim3((unsigned)nblk), dim3(256), smem, st, b);
+    hipLaunchKernelGGL(k, dim3((unsigned)nblk), dim3(256 * NCT), smem, st, b);
+    if (NCT > 1) idv_tw_pair_note_launch();
     return idv_launch_status();
 }
 
 }  // namespace
+
+// ---- the switch of the paired form, for this file and cgemm_tw2.hip.  Bits: 1 = transposed form, even-row phase; 2 = transposed form,
+// odd-row phase; 4 = conv form.  IDV_TW_PAIR in the environment is read once; idv_tw_pair(mask >= 0) sets it in-process.
+namespace {
+std::atomic<int>& tw_pair_mask() {
+    static std::atomic<int> v{[] { const char* e = getenv("IDV_TW_PAIR"); return e ? atoi(e) & IDV_TW_PAIR_ALL : IDV_TW_PAIR_DEFAULT; }()};
+    return v;
+}
+std::atomic<long long> tw_pair_launches{0};
+}  // namespace
+void idv_tw_pair_note_launch() { tw_pair_launches.fetch_add(1, std::memory_order_relaxed); }
+extern "C" int idv_tw_pair(int mask) {
+    if (mask < 0) return tw_pair_mask().load(std::memory_order_relaxed);
+    return tw_pair_mask().exchange(mask & IDV_TW_PAIR_ALL, std::memory_order_relaxed);
+}
+extern "C" long long idv_tw_pair_launches(int reset) {
+    return reset ? tw_pair_launches.exchange(0, std::memory_order_relaxed) : tw_pair_launches.load(std::memory_order_relaxed);
+}
 
 // 1 if idv_ctconv2d_tw_fwd serves the layer: a transposed conv that cgemm_gauss serves, with at least two input rows, at least one
 // FULL tile of 32 complex output channels (a workgroup is one co tile x 64 columns, so unlike cgemm_wino's four-co-tile form the

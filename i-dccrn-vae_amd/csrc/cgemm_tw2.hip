@@ -14,6 +14,7 @@
 //     wave 3        = A0, A1, A3 on planes 7, 8 (12 MFMAs) + A2 on planes 6, 7, 8 (3)                     (15 per k-step)
 // Staging, LDS layout (raw rows, planes paired per column pair), weight ring and the epilogue exchange are cgemm_tw.hip's; the
 // frequency transform A + cb B happens at the operand read.  Weights: cgemm_wino's conv fragments re-ordered by idv_pack_cconv_tw2.
+#include <atomic>
 #include <cstdint>
 #include <cstdlib>
 #include <type_traits>
@@ -39,6 +40,8 @@ struct Tw2Args {
     int stats_rep;
     int jtiles, ftiles;
     int xcd_split;
+    int cgroups;          // cotiles / NCT: workgroups per (column block, row pair); the block order runs over these
+    int stagger;          // NCT = 2: waves 4 .. 7 stage eight MFMA slots later than their SIMD partners, waves 0 .. 3
 };
 
 constexpr int TW2_PACK_CI = 8;     // pack granularity in complex input channels (cgemm_wino's WCIK)
@@ -71,39 +74,54 @@ __host__ __device__ inline int tw2_acc_tile(int w, int i) {
 // offset of plane p inside a raw row of the patch buffer (planes (2 j, 2 j + 1) interleaved per column pair, plane 8 apart), lane part
 __device__ __forceinline__ int tw2_poff(int p, int l31) { return p < 8 ? (p >> 1) * 64 + 2 * l31 + (p & 1) : 256 + l31; }
 
-template <bool LEFT, bool STATS, int DBG = 0>
-__global__ __launch_bounds__(256, 2) void cconv_tw2_kernel(const Tw2Args a) {
+// NCT: co tiles per workgroup (cgemm_tw.hip).  2: eight waves, waves 0 .. 3 on co tile 2 p, waves 4 .. 7 the same program on co tile
+// 2 p + 1, one staging of the raw rows for both.  The 448 items of a chunk go to 512 threads, one each; the 64 threads of wave 7 have
+// none and stage a dead item (loads of a valid address, stores to a dump row behind the patch buffer), so that the staging is free of
+// a per-wave branch (with one the register allocator spills three times what NCT = 1 does).
+constexpr int tw2_smem_floats(int nct) {
+    // NCT = 1: two patch buffers; NCT = 2: two patch buffers with a dump row each, or the two exchange areas of the epilogue (larger)
+    return nct == 1 ? 2 * 4 * 7 * 288 : (2 * (4 * 7 * 288 + 288) > 2 * 36 * 4 * 64 ? 2 * (4 * 7 * 288 + 288) : 2 * 36 * 4 * 64);
+}
+template <bool LEFT, bool STATS, int DBG = 0, int NCT = 1>
+__global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw2_kernel(const Tw2Args a) {
     constexpr int NT = 36, NACC = 9, NSLOT = 16;
     constexpr int NRAW = 7, CIK = 4, KS = 2;
     constexpr int RT = NRAW * 288;               // floats per channel in a patch buffer
     constexpr int NE = CIK * RT;
+    constexpr int NEB = NCT == 1 ? NE : NE + 288;    // buffer pitch (NCT = 2: + the dump row of the threads without an item)
     constexpr int NITEM = CIK * NRAW * 16;       // 448 staging items per chunk: (channel, raw row, 2 column pairs)
-    constexpr int NLD = 2;
-    static_assert(NT * 4 * 64 <= 2 * NE, "the epilogue exchange fits the patch buffers");
+    constexpr int NTHR = 256 * NCT;
+    constexpr int NLD = (NITEM + NTHR - 1) / NTHR;
+    static_assert(NCT == 1 || NCT == 2, "one or two co tiles per workgroup");
+    static_assert(2 * NEB <= tw2_smem_floats(NCT) && NCT * NT * 4 * 64 <= tw2_smem_floats(NCT),
+                  "the patch buffers and the epilogue exchange (one area per co tile) fit the allocation");
 
     extern __shared__ __attribute__((aligned(16))) float smem[];
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // the wave's place in its co tile's program; which co tile of the workgroup
+    const int w4 = NCT == 1 ? wave : wave & 3, cth = NCT == 1 ? 0 : wave >> 2;
     const int half = lane >> 5, l31 = lane & 31;
 
     const int bid = blockIdx.x;
     const int xcd = bid & 7, slot = bid >> 3;
     int jt, ft, ct;
     if (a.xcd_split) {                            // co tile ct always on the XCDs = ct (mod cotiles): see cgemm_tw.hip
-        const int G = 8 / a.cotiles;
-        ct = xcd % a.cotiles;
-        jt = (slot / a.ftiles) * G + xcd / a.cotiles;
+        const int G = 8 / a.cgroups;
+        ct = xcd % a.cgroups;
+        jt = (slot / a.ftiles) * G + xcd / a.cgroups;
         ft = slot - (slot / a.ftiles) * a.ftiles;
     } else {
-        const int per = a.cotiles * a.ftiles;
+        const int per = a.cgroups * a.ftiles;
         jt = (slot / per) * 8 + xcd;
         const int rem = slot - (slot / per) * per;
-        ft = rem / a.cotiles;
-        ct = rem - ft * a.cotiles;
+        ft = rem / a.cgroups;
+        ct = rem - ft * a.cgroups;
     }
     if (jt >= a.jtiles) return;
+    ct = NCT * ct + cth;                          // (ct was the workgroup's group of NCT co tiles)
     const int j0 = jt * 64;
     const int m0 = 2 * ft;                        // first OUTPUT row of the pair
     const int rbase = 2 * m0 - 2;                 // raw row r0
@@ -123,12 +141,13 @@ __global__ __launch_bounds__(256, 2) void cconv_tw2_kernel(const Tw2Args a) {
     unsigned off_v[NLD], ldsoff[NLD];
     unsigned okmask[NLD];     // bits 0-4: window column valid; bit 5: row valid
     bool interior[NLD];
-    auto item_cl = [&](int i) -> int { return (tid + i * 256) / (16 * NRAW); };
+    auto item_cl = [&](int i) -> int { return (tid + i * NTHR) / (16 * NRAW); };
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
-        const int e = tid + i * 256;
+        const int e = tid + i * NTHR;
         const int c8 = e & 15;
-        const int rl = (e >> 4) % NRAW, cl = e / (16 * NRAW);
+        // (NCT = 2, no item: channel CIK is dead in every chunk, and its row 0 is the dump row behind the buffer)
+        const int cl = e / (16 * NRAW), rl = (NCT == 2 && e >= NITEM) ? 0 : (e >> 4) % NRAW;
         const int f = rbase + rl;
         const int jc = j0 + 4 * c8;
         const int je = LEFT ? jc - 1 : jc + 4;
@@ -151,7 +170,7 @@ __global__ __launch_bounds__(256, 2) void cconv_tw2_kernel(const Tw2Args a) {
         interior[i] = __builtin_amdgcn_ballot_w64((m & 0x3fu) == 0x3fu) == ~0ull;
         ldsoff[i] = (unsigned)((cl * NRAW + rl) * 288 + 4 * c8);
     }
-    // the second item exists in waves 0 .. 2 only (448 items)
+    // the second item exists in waves 0 .. 2 only (448 items); NCT = 2: one item in every thread (wave 7: a dead one)
     auto item_exists = [&](int i) -> bool { return i == 0 || wave * 64 + 256 < NITEM; };
     auto stage_load = [&](int chunk, int i) {
         if (!item_exists(i)) return;
@@ -215,7 +234,7 @@ __global__ __launch_bounds__(256, 2) void cconv_tw2_kernel(const Tw2Args a) {
     // ---- weights: 16 slots per k-step as four 16-byte loads ([group][64 lanes][4 slots]).  ONE set of registers: group g of the next
     // k-step is fetched right after the four MFMAs that use group g of this one (two sets do not fit beside 144 accumulator, 32
     // operand and 20 staging registers)
-    const float* wbase = a.wfrag + (((size_t)ct * a.UP) * 4 + wave) * 1024 + lane * 4;
+    const float* wbase = a.wfrag + (((size_t)ct * a.UP) * 4 + w4) * 1024 + lane * 4;
     const int total_ks = nchunk * KS;
     float a_w[NSLOT];
     auto load_wg = [&](int g, int grp) {
@@ -227,11 +246,11 @@ __global__ __launch_bounds__(256, 2) void cconv_tw2_kernel(const Tw2Args a) {
 
     // ---- operands.  Waves 0 .. 2: products x, y of the wave's main accumulator on planes 0 .. 6 and product 2 on the plane pair w:
     // six row offsets at run time, plane offsets constant.  Wave 3: every row constant.
-    const int am = tw2_main_acc(wave < 3 ? wave : 0);
+    const int am = tw2_main_acc(w4 < 3 ? w4 : 0);
     const int qxm = tw2_qx(am), qym = tw2_qy(am);
     const int rxa = tw2_ra(qxm) * 288, rxb = tw2_rb(qxm) * 288, rya = tw2_ra(qym) * 288, ryb = tw2_rb(qym) * 288;
     const float cbx = tw2_cb(qxm), cby = tw2_cb(qym);
-    const int r2a = tw2_ra(2) * 288 + wave * 64, r2b = tw2_rb(2) * 288 + wave * 64;     // (+ plane pair j = w of product 2)
+    const int r2a = tw2_ra(2) * 288 + w4 * 64, r2b = tw2_rb(2) * 288 + w4 * 64;     // (+ plane pair j = w of product 2)
     // operands in a rolling window of two groups of four slots: group g of a k-step is fetched while group g - 1 runs.
     // Role A (waves 0 .. 2): group g < 3 = product x planes (2 g, 2 g + 1) on slots 0, 2 and product y on slots 1, 3 (two 8-byte reads per
     // row each); group 3 = plane 6 of x, y (slots 0, 1) and product 2's plane pair (slots 2, 3).  Role B (wave 3): slots 4 g .. 4 g + 3 of
@@ -270,17 +289,17 @@ __global__ __launch_bounds__(256, 2) void cconv_tw2_kernel(const Tw2Args a) {
 #pragma unroll
     for (int i = 0; i < NLD; ++i) stage_load(nchunk > 1 ? 1 : 0, i);
     __syncthreads();
-    if (wave < 3)
+    if (w4 < 3)
         load_grp_a(smem + (size_t)half * RT, 0, xa[0], xb[0]);
     else
         load_grp_b(smem + (size_t)half * RT, 0, xa[0], xb[0]);
 
     // the main loop, once per wave role (the branch is outside the loop: two straight-line loops, each with the workgroup's barriers)
-    auto run = [&](auto role) {
+    auto run = [&](auto role, auto late_) {
         constexpr bool ROLE_B = decltype(role)::value;
         for (int chunk = 0; chunk < nchunk; ++chunk) {
-            const float* P = smem + (chunk & 1) * NE;
-            float* Pn = smem + ((chunk + 1) & 1) * NE;
+            const float* P = smem + (chunk & 1) * NEB;
+            float* Pn = smem + ((chunk + 1) & 1) * NEB;
             const int nxt = chunk + 1 < nchunk ? chunk + 1 : chunk, nxt2 = chunk + 2 < nchunk ? chunk + 2 : nchunk - 1;
 #pragma unroll
             for (int ul = 0; ul < KS; ++ul) {
@@ -321,7 +340,21 @@ __global__ __launch_bounds__(256, 2) void cconv_tw2_kernel(const Tw2Args a) {
                     }
                     // weights of the next k-step, group by group
                     if (((k & 3) == 3 || (ROLE_B && k == NSLOT - 2)) && !(DBG & 2)) load_wg(chunk * KS + ul + 1, k >> 2);
-                    if (staging) {
+                    if constexpr (NCT == 2) if (staging) {
+                        // the one item: slots 0 .. 5 or (waves 4 .. 7 with a.stagger: not while the SIMD partner stages) slots 8 .. 13
+                        constexpr bool late = decltype(late_)::value;
+                        if (k <= 5 && !late) {
+                            if (k == 0) stage_window(nxt, 0);
+                            if (k >= 1) stage_plane2(Pn, 0, k - 1);
+                            if (k == 5) stage_load(nxt2, 0);
+                        }
+                        if (k >= 8 && k <= 13 && late) {
+                            if (k == 8) stage_window(nxt, 0);
+                            if (k >= 9) stage_plane2(Pn, 0, k - 9);
+                            if (k == 13) stage_load(nxt2, 0);
+                        }
+                    }
+                    if constexpr (NCT == 1) if (staging) {
                         // item 0: window at slot 0, plane pairs at 1 .. 4, plane 8 at 5, reload at 5; item 1 (waves 0 .. 2): slots 8 .. 13
                         if (k == 0) stage_window(nxt, 0);
                         if (k >= 1 && k <= 5) stage_plane2(Pn, 0, k - 1);
@@ -337,16 +370,23 @@ __global__ __launch_bounds__(256, 2) void cconv_tw2_kernel(const Tw2Args a) {
             }
         }
     };
-    if (wave < 3)
-        run(std::false_type{});
+    // (NCT = 2 with a.stagger: waves 4 .. 7 run the copies of the loops that stage eight slots later -- a copy, because a branch on the
+    // wave inside the loop costs the register allocator 80 - 90 bytes of scratch per lane)
+    if (NCT == 2 && a.stagger && cth) {
+        if (w4 < 3)
+            run(std::false_type{}, std::integral_constant<bool, NCT == 2>{});
+        else
+            run(std::true_type{}, std::integral_constant<bool, NCT == 2>{});
+    } else if (w4 < 3)
+        run(std::false_type{}, std::false_type{});
     else
-        run(std::true_type{});
+        run(std::true_type{}, std::false_type{});
     __syncthreads();                                          // all patch reads done: the buffers become the exchange area
 
     // ------------------------------------------------------------------ epilogue (cgemm_tw.hip's, 36 tiles)
     const float slope = a.slope ? *a.slope : 1.0f;
     const bool has_act = a.slope != nullptr;
-    float* E = smem;
+    float* E = smem + cth * (NT * 4 * 64);                    // one exchange area per co tile
     const int jA = j0 + 2 * l31;
     bool keep[2], inb[2];
 #pragma unroll
@@ -361,14 +401,14 @@ __global__ __launch_bounds__(256, 2) void cconv_tw2_kernel(const Tw2Args a) {
         if (s > 0) __syncthreads();
 #pragma unroll
         for (int k = 0; k < NACC; ++k) {
-            const int t = tw2_acc_tile(wave, k);
+            const int t = tw2_acc_tile(w4, k);
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) E[(t * 4 + rr) * 64 + lane] = acc[k][4 * s + rr];
         }
         __syncthreads();
         float v[NT];
 #pragma unroll
-        for (int t = 0; t < NT; ++t) v[t] = E[(t * 4 + wave) * 64 + lane];
+        for (int t = 0; t < NT; ++t) v[t] = E[(t * 4 + w4) * 64 + lane];
         float pr[4][2], pi[4][2];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -385,7 +425,7 @@ __global__ __launch_bounds__(256, 2) void cconv_tw2_kernel(const Tw2Args a) {
                 pi[r][q] = y[0][q] + y[1][q];
             }
         }
-        const int rg = 4 * s + wave;
+        const int rg = 4 * s + w4;
         const int co = ct * 32 + (rg & 3) + 8 * (rg >> 2) + 4 * half;
         const bool cok = co < a.Cout;
         const f32x4 e0 = *(const f32x4*)(a.epi + (size_t)co * 8);
@@ -469,31 +509,37 @@ __global__ void pack_cconv_tw2_kernel(const float* __restrict__ wino, int cotile
     }
 }
 
-template <bool LEFT, bool STATS, int DBG>
+template <bool LEFT, bool STATS, int DBG, int NCT = 1>
 int launch_tw2(const Tw2Args& a, hipStream_t st) {
-    constexpr size_t smem = 2 * 4 * 7 * 288 * sizeof(float);
-    static_assert(smem * 2 <= 160 * 1024, "the patch buffers of two workgroups must fit the 160 KB of LDS");
+    constexpr size_t smem = tw2_smem_floats(NCT) * sizeof(float);
+    static_assert(smem * (NCT == 1 ? 2 : 1) <= 160 * 1024, "the patch buffers of two workgroups (NCT = 2: of one) must fit the 160 KB of LDS");
     Tw2Args b = a;
     b.jtiles = (a.J + 63) / 64;
     b.ftiles = (a.Fout + 1) / 2;
     static const int xsplit = [] { const char* e = getenv("IDV_TW_XCD_SPLIT"); return e ? atoi(e) : 1; }();
-    b.xcd_split = (xsplit && (b.cotiles == 2 || b.cotiles == 4 || b.cotiles == 8)) ? 1 : 0;
-    long long nblk = (long long)((b.jtiles + 7) / 8) * 8 * b.ftiles * b.cotiles;
+    b.cgroups = b.cotiles / NCT;                              // (NCT = 2: the caller checked that the co-tile count is even)
+    if (b.cgroups * NCT != b.cotiles) return IDV_EINVAL;
+    static const int stag = [] { const char* e = getenv("IDV_TW_PAIR_STAGGER"); return e ? atoi(e) : 1; }();
+    b.stagger = stag;
+    b.xcd_split = (xsplit && (b.cgroups == 2 || b.cgroups == 4 || b.cgroups == 8)) ? 1 : 0;
+    long long nblk = (long long)((b.jtiles + 7) / 8) * 8 * b.ftiles * b.cgroups;
     if (b.xcd_split) {
-        const int G = 8 / b.cotiles;
+        const int G = 8 / b.cgroups;
         nblk = (long long)((b.jtiles + G - 1) / G) * b.ftiles * 8;
     }
     if (nblk > 0x7fffffffLL) return IDV_EINVAL;
-    auto k = cconv_tw2_kernel<LEFT, STATS, DBG>;
-    // (once per instantiation and device: setting it on every launch is host time, a lot of it under a profiler)
-    static bool attr_set[64] = {};
+    auto k = cconv_tw2_kernel<LEFT, STATS, DBG, NCT>;
+    // (once per instantiation and device: setting it on every launch is host time, a lot of it under a profiler.  Two threads that
+    // both find the flag clear both set the same value.)
+    static std::atomic<bool> attr_set[64];
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return IDV_ELAUNCH;
-    if (smem > 64 * 1024 && !attr_set[dev]) {
+    if (smem > 64 * 1024 && !attr_set[dev].load(std::memory_order_acquire)) {
         if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return IDV_ELAUNCH;
-        attr_set[dev] = true;
+        attr_set[dev].store(true, std::memory_order_release);
     }
-    hipLaunchKernelGGL(k, dim3((unsigned)nblk), dim3(256), smem, st, b);
+    hipLaunchKernelGGL(k, dim3((unsigned)nblk), dim3(256 * NCT), smem, st, b);
+    if (NCT > 1) idv_tw_pair_note_launch();
     return idv_launch_status();
 }
 
@@ -558,8 +604,14 @@ extern "C" int idv_cconv2d_tw_fwd(const float* x0, int Cin, const float* wfrag, 
     if (!stats && dbg == 2) return tshift ? launch_tw2<true, false, 2>(a, st) : launch_tw2<false, false, 2>(a, st);
     if (!stats && dbg == 3) return tshift ? launch_tw2<true, false, 3>(a, st) : launch_tw2<false, false, 3>(a, st);
 #endif
-    if (stats)
+    // two co tiles per workgroup (idv_tw_pair bit IDV_TW_PAIR_CONV): an even number of co tiles
+    const bool pair = a.cotiles % 2 == 0 && (idv_tw_pair(-1) & IDV_TW_PAIR_CONV);
+    if (stats && pair)
+        rc = tshift ? launch_tw2<true, true, 0, 2>(a, st) : launch_tw2<false, true, 0, 2>(a, st);
+    else if (stats)
         rc = tshift ? launch_tw2<true, true, 0>(a, st) : launch_tw2<false, true, 0>(a, st);
+    else if (pair)
+        rc = tshift ? launch_tw2<true, false, 0, 2>(a, st) : launch_tw2<false, false, 0, 2>(a, st);
     else
         rc = tshift ? launch_tw2<true, false, 0>(a, st) : launch_tw2<false, false, 0>(a, st);
     if (rc || !(stats && stats_work)) return rc;

@@ -31,6 +31,7 @@
 // (F(2,2): 3 x 3 = 9 tiles, 3 transformed rows).  Per wave: 32 complex output channels x 2 output rows x ONE 32-column tile.
 // Weights: 4 floats per (channel, plane) and lane as ONE 16-byte load -- one vector-memory instruction per 4 / 3 MFMAs
 // (cgemm_gauss: five per ten).
+#include <atomic>
 #include <cstdlib>
 #include "cgemm.hpp"
 #include "../../include/idccrn_hip.h"
@@ -465,8 +466,14 @@ int launch_wino_ph(const WinoArgs& a, hipStream_t st) {
     auto k = cconv_wino_kernel<PH, WM, WN, CIK, NBUF, STATS, OCC, RD>;
     // OCC 1: more than half a CU's LDS, i.e. one workgroup per CU whatever the register count says
     const size_t smem_req = OCC == 1 ? (smem > 84 * 1024 ? smem : 84 * 1024) : smem;
-    if (smem_req > 64 * 1024 &&
-        hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_req) != hipSuccess) return IDV_ELAUNCH;
+    // (once per instantiation and device, as in cgemm_tw.hip: smem_req is a constant of the instantiation)
+    static std::atomic<bool> attr_set[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return IDV_ELAUNCH;
+    if (smem_req > 64 * 1024 && !attr_set[dev].load(std::memory_order_acquire)) {
+        if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_req) != hipSuccess) return IDV_ELAUNCH;
+        attr_set[dev].store(true, std::memory_order_release);
+    }
     hipLaunchKernelGGL(k, dim3((unsigned)nblk), dim3(WM * WN * 64), smem_req, st, b);
     return idv_launch_status();
 }

@@ -49,4 +49,6 @@ __device__ __forceinline__ float tanhf_(float x) {
 // ~10^4 workgroups the same-address atomics cost more than the contraction (enc1, B = 32: 4.1 ms against 1.65) -- and this
 // kernel folds the replicas into stats[C][5] (+=, fixed order).  elementwise.hip
 int idv_launch_stats_collapse(const double* work, int rep, int n, double* stats, hipStream_t st);
+// one more launch of a time-Winograd kernel with two co tiles per workgroup (the count behind idv_tw_pair_launches).  cgemm_tw.hip
+void idv_tw_pair_note_launch();
 

@@ -290,6 +290,27 @@ def _pack_wino(w_re, w_im, cout: int, cin_total: int, cin_used: int, transposed:
 TW = os.environ.get("IDV_TW", "1") != "0"
 TW_CONV = os.environ.get("IDV_TW_CONV", "1") != "0"      # the conv form (csrc/cgemm_tw2.hip); 0: cgemm_wino's conv form
 TW_CFG = 5000000                 # LAUNCH_LOG ids of a launch on the time-Winograd kernels: TW_CFG (+ 1: taps (x[t-1], x[t]); + 2: the conv form)
+# Two co tiles per workgroup in the time-Winograd kernels (one staging of the raw rows for both; bit-identical outputs).  A bit mask:
+# 1 = transposed form, even-row phase; 2 = transposed form, odd-row phase; 4 = conv form; 0 = one co tile per workgroup everywhere.
+# None: the library's value (IDV_TW_PAIR in the environment, default all).  Assigning it takes effect at the next launch.
+TW_PAIR = None
+_tw_pair_lib = None              # the library's own value, read before the first assignment reaches it
+_tw_pair_pushed = None
+
+
+def _sync_tw_pair():
+    global _tw_pair_lib, _tw_pair_pushed
+    if TW_PAIR == _tw_pair_pushed:
+        return
+    if _tw_pair_lib is None:
+        _tw_pair_lib = int(L.lib().idv_tw_pair(-1))
+    L.lib().idv_tw_pair(_tw_pair_lib if TW_PAIR is None else int(TW_PAIR))
+    _tw_pair_pushed = TW_PAIR
+
+
+def tw_pair_launches(reset: bool = False) -> int:
+    """Launches of the paired time-Winograd kernels by this process so far."""
+    return int(L.lib().idv_tw_pair_launches(1 if reset else 0))
 
 
 def _pack_wino_tw(w_re, w_im, cout: int, cin_total: int, cin_used: int, transposed: bool, conj: int):
@@ -571,6 +592,7 @@ def cconv2d(x: Planar, wfrag, bias, cout: int, *, transposed=False, causal=True,
         if LAUNCH_LOG is not None:
             cfg = TW_CFG + (1 if tshift else 0)
         swork = _stats_work(stats, cout)
+        _sync_tw_pair()
         call("idv_ctconv2d_tw_fwd", x.ptr(), i(x.C), skip.ptr() if skip is not None else p(None), i(c1), p(gauss[4]), p(gauss[1]),
              i(gauss[2]), p(slope), out.ptr(), p(stats), p(swork), i(STATS_REP), i(tshift), i(cout), i(x.F), i(x.B), i(x.Tp), i(x.Jp),
              i(t_out), addend.ptr() if addend is not None else p(None), i(addend_div), i(addend.Jp if addend is not None else 0),
@@ -580,6 +602,7 @@ def cconv2d(x: Planar, wfrag, bias, cout: int, *, transposed=False, causal=True,
         if LAUNCH_LOG is not None:
             cfg = TW_CFG + 2 + (1 if tshift else 0)
         swork = _stats_work(stats, cout)
+        _sync_tw_pair()
         call("idv_cconv2d_tw_fwd", x.ptr(), i(x.C), p(gauss[4]), p(gauss[1]), i(gauss[2]), p(slope), out.ptr(), p(stats), p(swork),
              i(STATS_REP), i(tshift), i(cout), i(x.F), i(x.B), i(x.Tp), i(x.Jp), i(t_out), stream_ptr())
     elif skip_div == 1 and _wino_ok(gauss, transposed, x, c1, cout, skip.Jp if skip is not None else None):
@@ -1141,11 +1164,13 @@ def cconv_dgrad(dy: Planar, wfrag, bias, cout_adj: int, fwd_transposed: bool, ca
     if wfrag_bf16 is None and adj_transposed and _tw_ok(gauss, dy, 0, cout_adj, None):
         if LAUNCH_LOG is not None:
             cfg = TW_CFG + (1 if tshift_adj else 0)
+        _sync_tw_pair()
         call("idv_ctconv2d_tw_fwd", dy.ptr(), i(dy.C), p(None), i(0), p(gauss[4]), p(gauss[1]), i(0), p(None), out.ptr(), p(None), p(None),
              i(0), i(tshift_adj), i(cout_adj), i(dy.F), i(dy.B), i(dy.Tp), i(dy.Jp), i(t_out), p(None), i(1), i(0), stream_ptr())
     elif wfrag_bf16 is None and not adj_transposed and _tw2_ok(gauss, dy, 0, cout_adj):
         if LAUNCH_LOG is not None:
             cfg = TW_CFG + 2 + (1 if tshift_adj else 0)
+        _sync_tw_pair()
         call("idv_cconv2d_tw_fwd", dy.ptr(), i(dy.C), p(gauss[4]), p(gauss[1]), i(0), p(None), out.ptr(), p(None), p(None), i(0),
              i(tshift_adj), i(cout_adj), i(dy.F), i(dy.B), i(dy.Tp), i(dy.Jp), i(t_out), stream_ptr())
     elif wfrag_bf16 is None and _wino_ok(gauss, adj_transposed, dy, 0, cout_adj, None):

@@ -682,6 +682,20 @@ int idv_istft_ola_ragged(const float* frames, const int* lens, int len_div, int 
 int idv_sisdr_ragged(const float* ref, int ref_ld, const float* est, int est_ld, const int* lens, int B, double* work, float* out,
                      void* stream);
 
+/* ---- time-Winograd convs with two co tiles per workgroup (cgemm_tw.hip, cgemm_tw2.hip; additive entries: IDV_ABI_VERSION is
+ * unchanged).  A layer with an even number of 32-channel co tiles runs workgroups of eight waves that stage the raw input rows once
+ * for two co tiles; the outputs are bit-identical to the one-co-tile kernels (the train-mode moment sums within the rounding of a
+ * reordered double sum).  The switch is a bit mask, read once from IDV_TW_PAIR in the environment. */
+#define IDV_TW_PAIR_T_EVEN 1   /* transposed conv (idv_ctconv2d_tw_fwd), even-row phase */
+#define IDV_TW_PAIR_T_ODD 2    /* transposed conv, odd-row phase */
+#define IDV_TW_PAIR_CONV 4     /* conv (idv_cconv2d_tw_fwd) */
+#define IDV_TW_PAIR_ALL 7
+#define IDV_TW_PAIR_DEFAULT 7   /* the paired form is faster in all three */
+/* mask >= 0: sets the switch (atomically; launches issued afterwards see it) and returns the previous value; mask < 0: returns it. */
+int idv_tw_pair(int mask);
+/* Number of paired kernel launches of this process so far; reset != 0 also sets the count back to 0. */
+long long idv_tw_pair_launches(int reset);
+
 #ifdef __cplusplus
 }
 #endif
