@@ -24,15 +24,11 @@ struct BCoopArgs {
     const float* whhT;    // idv_pack_lstm_hh_bwd: [set][unit tile][blk][lane][4]
     float* hx;            // exchange [2 parity][4 runs][Bpad][4H] fp32: dA_t, row-major in the gate-column order colp
     unsigned hx_bytes;
-    unsigned* sync;       // [abort flag: 256 B][group = run * tiles + tile][replica][256 B]
-    int nrep;
+    CoopSync cs;          // group = run * tiles + tile
     int B, T, Bpad, tiles;
-    unsigned* status;     // host-mapped sticky status word (coop.hpp) or nullptr
-    int fault;
 };
 
 constexpr int H = 128, NSL = 4;
-constexpr unsigned long long SPIN_LIMIT_TICKS = 40000000ull;     // 0.4 s of the 100 MHz wall clock
 
 __global__ __launch_bounds__(256, 1) void lstm_bptt_coop_f32_kernel(const BCoopArgs a) {
     extern __shared__ __attribute__((aligned(16))) float red[];                // [4 waves][2 tiles][4 r][64 lanes]
@@ -45,9 +41,9 @@ __global__ __launch_bounds__(256, 1) void lstm_bptt_coop_f32_kernel(const BCoopA
     const int z = run >> 1, s = run & 1;
     const int col = lane & 15, rq = lane >> 4;
     const int b0 = tile * 16;
-    unsigned* abortf = a.sync;
-    unsigned* counter0 = a.sync + 64 + (size_t)((run * a.tiles + tile) * a.nrep) * 64;
-    unsigned* counter = counter0 + (size_t)(sl & (a.nrep - 1)) * 64;
+    unsigned* abortf = idv_coop_abort_flag(a.cs);
+    unsigned* counter0 = idv_coop_counter(a.cs, run * a.tiles + tile);
+    unsigned* counter = idv_coop_replica(a.cs, counter0, sl);
     const size_t TBH = (size_t)a.T * a.B * H;
     float* g = a.g + z * a.g_run_z + s * a.g_run_s;
     const float* cst = a.c + (size_t)run * TBH;
@@ -78,7 +74,7 @@ __global__ __launch_bounds__(256, 1) void lstm_bptt_coop_f32_kernel(const BCoopA
 
     bool aborted = false;
     if (tid == 0) abort_sh = 0;
-    if (a.fault && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) return;      // injected failure (tests only)
+    if (idv_coop_withheld(a.cs)) return;
     for (int t = a.T - 1; t >= 0; --t) {
         const int step = a.T - 1 - t;                // 0, 1, ...
         // inputs of the cell backward (independent of the contraction): issue first
@@ -99,22 +95,7 @@ __global__ __launch_bounds__(256, 1) void lstm_bptt_coop_f32_kernel(const BCoopA
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc[u][r] = 0.f;
         if (step > 0) {
-            if (tid == 0) {
-                const unsigned want = (unsigned)step * (unsigned)NSL;
-                const unsigned long long t0 = wall_clock64();
-                unsigned long long spins = 0;
-                while (__hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want) {
-                    __builtin_amdgcn_s_sleep(1);
-                    if ((++spins & 1023) == 0) {
-                        if (__hip_atomic_load(abortf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) { abort_sh = 1; break; }
-                        if (wall_clock64() - t0 > SPIN_LIMIT_TICKS) {
-                            __hip_atomic_store(abortf, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            abort_sh = 1;
-                            break;
-                        }
-                    }
-                }
-            }
+            if (tid == 0) idv_coop_wait(counter, (unsigned)step * (unsigned)NSL, abortf, &abort_sh);
             __syncthreads();                 // the polling wave joins after its match; every load below is sc1
             if (abort_sh) { aborted = true; break; }
             // dA_{t+1} of the whole group: row = lane & 15, 8 consecutive gate columns per lane and chunk
@@ -181,11 +162,11 @@ __global__ __launch_bounds__(256, 1) void lstm_bptt_coop_f32_kernel(const BCoopA
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        if (tid < a.nrep) __hip_atomic_fetch_add(counter0 + (size_t)tid * 64, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        idv_coop_arrive(a.cs, counter0, tid);
     }
     if (aborted) {
         // poison this workgroup's gate gradients: a timed-out BPTT must never look like a result
-        if (tid == 0) idv_coop_raise(a.status);
+        if (tid == 0) idv_coop_raise(a.cs.status);
         const float qnan = __builtin_nanf("");
         for (long long e = tid; e < (long long)a.T * 16 * 128; e += 256) {
             const int cidx = (int)(e & 127), br = (int)((e >> 7) & 15);
@@ -195,7 +176,7 @@ __global__ __launch_bounds__(256, 1) void lstm_bptt_coop_f32_kernel(const BCoopA
     }
 }
 
-constexpr int SYNC_BYTES = 256 + 64 * 8 * 256;
+constexpr int SYNC_BYTES = idv_coop_sync_bytes(64);      // <= 64 groups
 
 }  // namespace idv_bcoop
 
@@ -219,23 +200,13 @@ extern "C" int idv_lstm_bptt_coop(float* gates, long long g_run_z, long long g_r
     hipStream_t st = (hipStream_t)stream;
     const int tiles = (B + 15) / 16;
     const long long Bpad = 16LL * tiles;
-    if (hipMemsetAsync(work, 0, SYNC_BYTES, st) != hipSuccess) return IDV_ELAUNCH;
     BCoopArgs a{};
     a.g = gates; a.g_run_z = g_run_z; a.g_run_s = g_run_s; a.ldg = ldg;
     a.c = cstates; a.dhout = dhout; a.whhT = whhT;
-    a.sync = (unsigned*)work;
     a.hx = (float*)((char*)work + SYNC_BYTES);
     a.hx_bytes = (unsigned)(2LL * 4 * Bpad * 4 * H * 4);
-    a.nrep = 4;
+    a.cs.nrep = 4;
     a.B = B; a.T = T; a.Bpad = (int)Bpad; a.tiles = tiles;
-    { const char* e = getenv("IDV_COOP_FAULT"); a.fault = (e && e[0] == '1') ? 1 : 0; }
-    a.status = idv_coop_status_word();
     const size_t smem = 84 * 1024;                   // one workgroup per CU
-    if (hipFuncSetAttribute((const void*)lstm_bptt_coop_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-        return IDV_ELAUNCH;
-    int rc = idv_coop_chain_begin(st);
-    if (rc) return rc;
-    hipLaunchKernelGGL(lstm_bptt_coop_f32_kernel, dim3(NSL, 4, tiles), dim3(256), smem, st, a);
-    if ((rc = idv_coop_chain_end(st))) return rc;
-    return idv_launch_status();
+    return idv_coop_launch(lstm_bptt_coop_f32_kernel, dim3(NSL, 4, tiles), smem, st, work, SYNC_BYTES, a);
 }

@@ -37,41 +37,13 @@ struct Args {
     const float* whhT0;
     float* hx;            // exchange [2 layers][2 parity][4 runs][Bpad][4H] fp32: dA_t, row-major in the gate-column order
     unsigned hx_bytes;
-    unsigned* sync;       // [abort flag: 256 B][layer slot][group = run * tiles + tile][replica][256 B]
-    int nrep;
+    CoopSync cs;          // group = layer slot * 4 * tiles + run * tiles + tile
     int B, T, Bpad, tiles;
-    unsigned* status;
-    int fault;
 };
 
 constexpr int H = 128, NSL = 4;
-constexpr unsigned long long SPIN_LIMIT_TICKS = 40000000ull;     // 0.4 s of the 100 MHz wall clock
 constexpr int MAX_GROUPS = 64, MAX_REP = 8;
-constexpr int SYNC_BYTES = 256 + 2 * MAX_GROUPS * MAX_REP * 256;
-
-// thread 0: wait until *counter >= want (bounded); (other, other_seen): a second counter read ONCE if the first check fails
-__device__ __forceinline__ void wait_for(unsigned* counter, unsigned want, unsigned* abortf, int* abort_sh, unsigned* seen = nullptr,
-                                         unsigned* other = nullptr, unsigned* other_seen = nullptr) {
-    const unsigned long long t0 = wall_clock64();
-    unsigned long long spins = 0;
-    unsigned v;
-    while ((v = __hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) < want) {
-        if (other) {
-            *other_seen = __hip_atomic_load(other, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            other = nullptr;
-        }
-        __builtin_amdgcn_s_sleep(1);
-        if ((++spins & 1023) == 0) {
-            if (__hip_atomic_load(abortf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) { *abort_sh = 1; break; }
-            if (wall_clock64() - t0 > SPIN_LIMIT_TICKS) {
-                __hip_atomic_store(abortf, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                *abort_sh = 1;
-                break;
-            }
-        }
-    }
-    if (seen) *seen = v;
-}
+constexpr int SYNC_BYTES = idv_coop_sync_bytes(2 * MAX_GROUPS, MAX_REP);
 
 __global__ __launch_bounds__(256, 1) void lstm_bptt_stack2_f32_kernel(const Args a) {
     extern __shared__ __attribute__((aligned(16))) float red[];                // [4 waves][2 tiles][4 r][64 lanes]
@@ -87,12 +59,11 @@ __global__ __launch_bounds__(256, 1) void lstm_bptt_stack2_f32_kernel(const Args
     const int z = run >> 1, s = run & 1;
     const int col = lane & 15, rq = lane >> 4;
     const int b0 = tile * 16;
-    unsigned* abortf = a.sync;
+    unsigned* abortf = idv_coop_abort_flag(a.cs);
     const int groups = 4 * a.tiles, grp = run * a.tiles + tile;
-    unsigned* cntA = a.sync + 64 + (size_t)((0 * groups + grp) * a.nrep) * 64;          // layer-1 arrivals of this (run, tile)
-    unsigned* cntB = a.sync + 64 + (size_t)((1 * groups + grp) * a.nrep) * 64;          // layer-0 arrivals
+    unsigned* cntA = idv_coop_counter(a.cs, 0 * groups + grp);          // layer-1 arrivals of this (run, tile)
+    unsigned* cntB = idv_coop_counter(a.cs, 1 * groups + grp);          // layer-0 arrivals
     unsigned* mine = low ? cntB : cntA;
-    const int rep = sl & (a.nrep - 1);
     const size_t TB = (size_t)a.T * a.B, TBH = TB * H;
     // this layer's gate buffer, cell states and incoming gradient
     float* g = low ? a.g0 + z * a.g0_run_z + s * a.g0_run_s : a.g1 + (size_t)run * TB * 4 * H;
@@ -129,7 +100,7 @@ __global__ __launch_bounds__(256, 1) void lstm_bptt_stack2_f32_kernel(const Args
 
     bool aborted = false;
     if (tid == 0) { abort_sh = 0; seen1_sh = 0; }
-    if (a.fault && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) return;      // injected failure (tests only)
+    if (idv_coop_withheld(a.cs)) return;
     __syncthreads();
 
     // layer 0: rows of dA1 for time t (all 4H gate columns of this (run, tile); this wave's 128 of them) from the G1 buffer
@@ -143,7 +114,7 @@ __global__ __launch_bounds__(256, 1) void lstm_bptt_stack2_f32_kernel(const Args
         }
     };
     auto in_late = [&](int step, int t, f32x4 (&v)[4][2]) -> bool {            // poll layer 1, then load
-        if (tid == 0) wait_for(cntA + (size_t)rep * 64, (unsigned)(step + 1) * (unsigned)NSL, abortf, &abort_sh, &seen1_sh);
+        if (tid == 0) idv_coop_wait(idv_coop_replica(a.cs, cntA, sl), (unsigned)(step + 1) * (unsigned)NSL, abortf, &abort_sh, &seen1_sh);
         __syncthreads();
         if (abort_sh) return false;
         in_load(t, v);
@@ -189,8 +160,8 @@ __global__ __launch_bounds__(256, 1) void lstm_bptt_stack2_f32_kernel(const Args
         if (low && step == 0) contract(cur, ireg);             // dh0[T-1] = dA1[T-1] W_ih1 (no recurrent term yet)
         if (step > 0) {
             if (tid == 0)       // (layer 0: the view of layer 1's progress is refreshed while waiting for the siblings, if it waits)
-                wait_for(mine + (size_t)rep * 64, (unsigned)step * (unsigned)NSL, abortf, &abort_sh, nullptr,
-                         low ? cntA + (size_t)rep * 64 : nullptr, &seen1_sh);
+                idv_coop_wait(idv_coop_replica(a.cs, mine, sl), (unsigned)step * (unsigned)NSL, abortf, &abort_sh, nullptr,
+                              low ? idv_coop_replica(a.cs, cntA, sl) : nullptr, &seen1_sh);
             __syncthreads();                 // the polling wave joins after its match; every load below is sc1
             if (abort_sh) { aborted = true; break; }
             // dA_{t+1} of this layer's group: row = lane & 15, 8 consecutive gate columns per lane and chunk
@@ -261,7 +232,7 @@ __global__ __launch_bounds__(256, 1) void lstm_bptt_stack2_f32_kernel(const Args
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        if (tid < a.nrep) __hip_atomic_fetch_add(mine + (size_t)tid * 64, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        idv_coop_arrive(a.cs, mine, tid);
         // layer 0: the next step's input rows, the late way, if they were not requested above
         if (low && t > 0) {
             if (!early && !in_late(step + 1, t - 1, nx)) aborted = true;
@@ -273,7 +244,7 @@ __global__ __launch_bounds__(256, 1) void lstm_bptt_stack2_f32_kernel(const Args
     }
     if (aborted) {
         // poison this workgroup's gate gradients: a timed-out BPTT must never look like a result
-        if (tid == 0) idv_coop_raise(a.status);
+        if (tid == 0) idv_coop_raise(a.cs.status);
         const float qnan = __builtin_nanf("");
         for (long long e = tid; e < (long long)a.T * 16 * 128; e += 256) {
             const int cidx = (int)(e & 127), br = (int)((e >> 7) & 15);
@@ -314,25 +285,15 @@ extern "C" int idv_lstm_bptt_stack2(float* g1, float* g0, long long g0_run_z, lo
     hipStream_t st = (hipStream_t)stream;
     const int tiles = (B + 15) / 16;
     const long long Bpad = 16LL * tiles;
-    if (hipMemsetAsync(work, 0, SYNC_BYTES, st) != hipSuccess) return IDV_ELAUNCH;
     Args a{};
     a.g1 = g1; a.g1_bytes = (unsigned)g1_bytes;
     a.g0 = g0; a.g0_run_z = g0_run_z; a.g0_run_s = g0_run_s; a.ldg0 = ldg0;
     a.c1 = c1; a.c0 = c0; a.dhout = dhout1;
     a.whhT1 = whhT1; a.wihT1 = wihT1; a.whhT0 = whhT0;
-    a.sync = (unsigned*)work;
     a.hx = (float*)((char*)work + SYNC_BYTES);
     a.hx_bytes = (unsigned)(2LL * 2 * 4 * Bpad * 4 * H * 4);
-    a.nrep = 4;
+    a.cs.nrep = 4;
     a.B = B; a.T = T; a.Bpad = (int)Bpad; a.tiles = tiles;
-    { const char* e = getenv("IDV_COOP_FAULT"); a.fault = (e && e[0] == '1') ? 1 : 0; }
-    a.status = idv_coop_status_word();
     const size_t smem = 84 * 1024;                   // one workgroup per CU
-    if (hipFuncSetAttribute((const void*)lstm_bptt_stack2_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-        return IDV_ELAUNCH;
-    int rc = idv_coop_chain_begin(st);
-    if (rc) return rc;
-    hipLaunchKernelGGL(lstm_bptt_stack2_f32_kernel, dim3(2 * NSL, 4, tiles), dim3(256), smem, st, a);
-    if ((rc = idv_coop_chain_end(st))) return rc;
-    return idv_launch_status();
+    return idv_coop_launch(lstm_bptt_stack2_f32_kernel, dim3(2 * NSL, 4, tiles), smem, st, work, SYNC_BYTES, a);
 }

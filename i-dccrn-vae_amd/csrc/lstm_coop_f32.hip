@@ -10,7 +10,6 @@
 // loads behind the poll and the barrier; one workgroup per CU (84 KB of LDS requested); bounded spins, NaN poison on time-out.
 // Per step: 0.85 us of MFMA + ~2 us of hand-off latencies instead of 6 us.
 #include <cstdlib>
-#include <mutex>
 #include "common.hpp"
 #include "coop.hpp"
 #include "../../include/idccrn_hip.h"
@@ -29,15 +28,11 @@ struct CoopArgs {
     float* csave;             // training: cell states [4 runs][T*B][H], or nullptr
     float* hx;                // exchange [2 parity][4 runs][Bpad][H] fp32
     unsigned hx_bytes;
-    unsigned* sync;           // [abort flag: 256 B][group = run * tiles + tile][replica][256 B]
-    int nrep;
+    CoopSync cs;              // group = run * tiles + tile
     int B, T, Bpad, tiles;
-    unsigned* status;         // host-mapped sticky status word (coop.hpp) or nullptr
-    int fault;                // test hook (IDV_COOP_FAULT=1): workgroup (0, 0, 0) never arrives -> the bounded spins must abort
 };
 
 constexpr int H = 128, NSL = 4, UPW = 32;          // hidden size, workgroups per group, units per workgroup
-constexpr unsigned long long SPIN_LIMIT_TICKS = 40000000ull;     // 0.4 s of the 100 MHz wall clock
 
 __global__ __launch_bounds__(256, 1) void lstm_coop_f32_kernel(const CoopArgs a) {
     extern __shared__ __attribute__((aligned(16))) float red[];                // [4 waves][8 tiles][4 r][64 lanes]
@@ -50,9 +45,9 @@ __global__ __launch_bounds__(256, 1) void lstm_coop_f32_kernel(const CoopArgs a)
     const int z = run >> 1, s = run & 1;
     const int col = lane & 15, rq = lane >> 4;
     const int b0 = tile * 16;
-    unsigned* abortf = a.sync;
-    unsigned* counter0 = a.sync + 64 + (size_t)((run * a.tiles + tile) * a.nrep) * 64;
-    unsigned* counter = counter0 + (size_t)(sl & (a.nrep - 1)) * 64;
+    unsigned* abortf = idv_coop_abort_flag(a.cs);
+    unsigned* counter0 = idv_coop_counter(a.cs, run * a.tiles + tile);
+    unsigned* counter = idv_coop_replica(a.cs, counter0, sl);
     const size_t TBH = (size_t)a.T * a.B * H;
     const float* g = a.g + z * a.g_run_z + s * a.g_run_s;
     float* gsv = a.gsave ? a.gsave + z * a.g_run_z + s * a.g_run_s : nullptr;
@@ -82,7 +77,7 @@ __global__ __launch_bounds__(256, 1) void lstm_coop_f32_kernel(const CoopArgs a)
 
     bool aborted = false;
     if (tid == 0) abort_sh = 0;
-    if (a.fault && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) return;      // injected failure (tests only)
+    if (idv_coop_withheld(a.cs)) return;
     for (int t = 0; t < a.T; ++t) {
         float gpre[2][4];
         {
@@ -98,22 +93,7 @@ __global__ __launch_bounds__(256, 1) void lstm_coop_f32_kernel(const CoopArgs a)
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc[t8][r] = 0.f;
         if (t > 0) {
-            if (tid == 0) {
-                const unsigned want = (unsigned)t * (unsigned)NSL;
-                const unsigned long long t0 = wall_clock64();
-                unsigned long long spins = 0;
-                while (__hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want) {
-                    __builtin_amdgcn_s_sleep(1);
-                    if ((++spins & 1023) == 0) {
-                        if (__hip_atomic_load(abortf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) { abort_sh = 1; break; }
-                        if (wall_clock64() - t0 > SPIN_LIMIT_TICKS) {
-                            __hip_atomic_store(abortf, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            abort_sh = 1;
-                            break;
-                        }
-                    }
-                }
-            }
+            if (tid == 0) idv_coop_wait(counter, (unsigned)t * (unsigned)NSL, abortf, &abort_sh);
             __syncthreads();                 // the polling wave joins after its match; every load below is sc1
             if (abort_sh) { aborted = true; break; }
             const unsigned par_r = (unsigned)((t - 1) & 1) * 4u * (unsigned)a.Bpad * (unsigned)H * 4u;
@@ -173,10 +153,10 @@ __global__ __launch_bounds__(256, 1) void lstm_coop_f32_kernel(const CoopArgs a)
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        if (tid < a.nrep) __hip_atomic_fetch_add(counter0 + (size_t)tid * 64, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        idv_coop_arrive(a.cs, counter0, tid);
     }
     if (aborted) {
-        if (tid == 0) idv_coop_raise(a.status);
+        if (tid == 0) idv_coop_raise(a.cs.status);
         const float qnan = __builtin_nanf("");
         for (long long e = tid; e < (long long)a.T * 16 * UPW; e += 256) {
             const int u = (int)(e % UPW), br = (int)((e / UPW) & 15);
@@ -186,7 +166,7 @@ __global__ __launch_bounds__(256, 1) void lstm_coop_f32_kernel(const CoopArgs a)
     }
 }
 
-constexpr int SYNC_BYTES = 256 + 64 * 8 * 256;      // abort flag + (<= 64 groups) x 8 replicas x 256 B
+constexpr int SYNC_BYTES = idv_coop_sync_bytes(64);      // <= 64 groups
 
 }  // namespace idv_coop
 
@@ -213,23 +193,13 @@ extern "C" int idv_lstm_rec_coop_f32(const float* g, long long g_run_z, long lon
     hipStream_t st = (hipStream_t)stream;
     const int tiles = (B + 15) / 16;
     const long long Bpad = 16LL * tiles;
-    if (hipMemsetAsync(work, 0, SYNC_BYTES, st) != hipSuccess) return IDV_ELAUNCH;
     CoopArgs a{};
     a.g = g; a.g_run_z = g_run_z; a.g_run_s = g_run_s; a.ldg = ldg;
     a.whh = whh_frag; a.hout = hout; a.gsave = gsave; a.csave = csave;
-    a.sync = (unsigned*)work;
     a.hx = (float*)((char*)work + SYNC_BYTES);
     a.hx_bytes = (unsigned)(2LL * 4 * Bpad * H * 4);
-    a.nrep = 4;
+    a.cs.nrep = 4;
     a.B = B; a.T = T; a.Bpad = (int)Bpad; a.tiles = tiles;
-    { const char* e = getenv("IDV_COOP_FAULT"); a.fault = (e && e[0] == '1') ? 1 : 0; }
-    a.status = idv_coop_status_word();
     const size_t smem = 84 * 1024;                   // > half a CU's LDS: one workgroup per CU (red[] needs 32 KB)
-    if (hipFuncSetAttribute((const void*)lstm_coop_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-        return IDV_ELAUNCH;
-    int rc = idv_coop_chain_begin(st);
-    if (rc) return rc;
-    hipLaunchKernelGGL(lstm_coop_f32_kernel, dim3(NSL, 4, tiles), dim3(256), smem, st, a);
-    if ((rc = idv_coop_chain_end(st))) return rc;
-    return idv_launch_status();
+    return idv_coop_launch(lstm_coop_f32_kernel, dim3(NSL, 4, tiles), smem, st, work, SYNC_BYTES, a);
 }

@@ -17,7 +17,6 @@
 // Every spin is bounded: a workgroup that waits longer than ~0.4 s raises the abort flag, all workgroups drain, and the
 // outputs are poisoned with NaN (no hang; results never silently wrong).
 #include <cstdlib>
-#include <mutex>
 #include "common.hpp"
 #include "coop.hpp"
 #include "../../include/idccrn_hip.h"
@@ -40,15 +39,10 @@ struct PersArgs {
     int Tp, Jp;
     unsigned short* hx;       // exchange [2 parity][4 runs][Bpad][H/8][hi 8 x bf16 | lo 8 x bf16]
     unsigned hx_bytes;
-    unsigned* sync;           // [abort flag: 256 B][group = set * chunks + chunk][replica][256 B] arrive counters
-    int nrep;                 // replicas of each arrive counter (1, 2, 4 or 8), each on a 256-byte block of its own
+    CoopSync cs;              // group = set * chunks + chunk
     int H, B, T, Bpad, nchunks;
-    int fault;                // test hook (IDV_COOP_FAULT=1): workgroup (0, 0, 0) never arrives -> the bounded spins must abort
-    unsigned* status;         // host-mapped sticky status word (coop.hpp) or nullptr
     unsigned long long* prof; // diagnostic build only: [workgroup][8] accumulated phase cycles, [7] = XCC id
 };
-
-constexpr unsigned long long SPIN_LIMIT_CYCLES = 1000000000ull;     // ~0.4 s at 2.4 GHz
 
 #define IDV_STAMP(i)                                                       \
     if (PROF && pw) {                                                      \
@@ -73,13 +67,9 @@ __global__ __launch_bounds__(256, 1) void lstm_pers_kernel(const PersArgs a) {
     const int col = lane & 15, rq = lane >> 4;
     const int KB = H / 32;
     const int TPR = a.Bpad / 16, NT = 2 * TPR;
-    // every arriving workgroup adds to ALL replicas of its group's counter (one wave instruction, one lane per replica);
-    // a workgroup polls ONE replica: 1/nrep of the pollers per word, and no two groups share a memory channel (with the four
-    // group counters in one 16-byte block the poll round trip grew by 28 ns per polling workgroup of the LAUNCH: 2.8 us of
-    // a 6.2 us step at 96 workgroups)
-    unsigned* abortf = a.sync;
-    unsigned* counter0 = a.sync + 64 + (size_t)((s * a.nchunks + ch) * a.nrep) * 64;
-    unsigned* counter = counter0 + (size_t)(sl & (a.nrep - 1)) * 64;
+    unsigned* abortf = idv_coop_abort_flag(a.cs);
+    unsigned* counter0 = idv_coop_counter(a.cs, s * a.nchunks + ch);
+    unsigned* counter = idv_coop_replica(a.cs, counter0, sl);
     const size_t TBH = (size_t)a.T * a.B * H;
 
     // this workgroup's tiles: run (2 z + s), first row, validity (the last chunk of an odd tile count is ragged)
@@ -116,7 +106,7 @@ __global__ __launch_bounds__(256, 1) void lstm_pers_kernel(const PersArgs a) {
 
     bool aborted = false;
     if (tid == 0) abort_sh = 0;
-    if (a.fault && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) return;      // injected failure (tests only)
+    if (idv_coop_withheld(a.cs)) return;
     const bool pw = PROF && wave == 0;
     unsigned long long pacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, plast = 0;
     if (PROF && pw) plast = __builtin_readcyclecounter();
@@ -144,20 +134,7 @@ __global__ __launch_bounds__(256, 1) void lstm_pers_kernel(const PersArgs a) {
         if (t > 0) {
             // ---- wait for h_{t-1} of the whole group
             if (tid == 0) {
-                const unsigned want = (unsigned)t * (unsigned)nslice;
-                const unsigned long long t0 = wall_clock64();
-                unsigned long long spins = 0;
-                while (__hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want) {
-                    __builtin_amdgcn_s_sleep(1);
-                    if ((++spins & 1023) == 0) {
-                        if (__hip_atomic_load(abortf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) { abort_sh = 1; break; }
-                        if (wall_clock64() - t0 > SPIN_LIMIT_CYCLES / 24) {     // wall_clock64 ticks at 100 MHz
-                            __hip_atomic_store(abortf, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            abort_sh = 1;
-                            break;
-                        }
-                    }
-                }
+                idv_coop_wait(counter, (unsigned)t * (unsigned)nslice, abortf, &abort_sh);
                 IDV_STAMP(0)                                 // gpre issue + spin
             }
             // no acquire fence: every byte of the exchange buffer was stored sc1 and drained before the arrive, and every
@@ -272,7 +249,7 @@ __global__ __launch_bounds__(256, 1) void lstm_pers_kernel(const PersArgs a) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         IDV_STAMP(5)                                         // store drain + barrier
-        if (tid < a.nrep) __hip_atomic_fetch_add(counter0 + (size_t)tid * 64, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        idv_coop_arrive(a.cs, counter0, tid);
     }
     if (PROF && pw && lane == 0) {
         const int wg = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
@@ -282,7 +259,7 @@ __global__ __launch_bounds__(256, 1) void lstm_pers_kernel(const PersArgs a) {
     if (aborted) {
         // poison this workgroup's outputs: a timed-out recurrence must never look like a result; the host learns it through
         // the sticky status word (the next cooperative entry / idv_coop_last_status returns IDV_ECOOP)
-        if (tid == 0) idv_coop_raise(a.status);
+        if (tid == 0) idv_coop_raise(a.cs.status);
         const float qnan = __builtin_nanf("");
         for (int rt = 0; rt < NRT; ++rt) {
             if (!t_ok[rt]) continue;
@@ -321,113 +298,11 @@ extern "C" int idv_lstm_pers_supported(int H, int B) {
     return idv_pers::nrt_for(H, B) > 0;
 }
 
-static constexpr int SYNC_BYTES = 256 + 20 * 8 * 256;     // abort flag + (<= 20 groups) x (<= 8 replicas) x 256 B
+static constexpr int SYNC_BYTES = idv_coop_sync_bytes(20);     // <= 20 groups
 
 extern "C" long long idv_lstm_pers_work_bytes(int H, int B) {
     const long long Bpad = (B + 15) / 16 * 16;
     return SYNC_BYTES + 2LL * 4 * Bpad * H * 4;       // [abort flag + arrive counters, zeroed per call][exchange]
-}
-
-// ---- per-device process state of the cooperative kernels (coop.hpp) ------------------------------------------------------
-// Two cooperative launches must never share the chip: each needs ALL its workgroups resident (it spins on its siblings), and
-// two half-resident launches on different streams would wait for each other until the spin bound poisons both.  Launches
-// from different streams of one device are therefore chained through an event (other kernels may still overlap them).
-static std::mutex g_pers_mu;
-static hipEvent_t g_pers_done[16] = {};
-static hipStream_t g_pers_stream[16] = {};
-static int g_max_wg[16] = {};                 // 0: not queried yet
-static unsigned* g_status_host[16] = {};      // host-mapped sticky status words
-static unsigned* g_status_dev[16] = {};
-static bool g_status_tried[16] = {};
-
-static int cur_dev() {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return -1;
-    return dev;
-}
-
-extern "C" int idv_coop_max_workgroups(void) {
-    // no device visible (sizing queries in the build container): the MI355X figure, 256 CUs - 16
-    const int dev = cur_dev();
-    if (dev < 0) { (void)hipGetLastError(); return 240; }
-    std::lock_guard<std::mutex> lk(g_pers_mu);
-    if (g_max_wg[dev] == 0) {
-        hipDeviceProp_t pr;
-        if (hipGetDeviceProperties(&pr, dev) != hipSuccess || pr.multiProcessorCount <= 0) {
-            (void)hipGetLastError();
-            g_max_wg[dev] = 240;
-        } else {
-            // one workgroup per CU (every cooperative launch requests > half a CU's LDS); 1/16 of the CUs stay free so that a
-            // kernel of another stream still finds a CU and never delays the start of a sibling workgroup indefinitely
-            const int cu = pr.multiProcessorCount;
-            int n = cu - cu / 16;
-            const char* e = getenv("IDV_COOP_MAX_WG");              // experiments / CU-masked devices
-            if (e && atoi(e) > 0 && atoi(e) < n) n = atoi(e);
-            g_max_wg[dev] = n;
-        }
-    }
-    return g_max_wg[dev];
-}
-
-unsigned* idv_coop_status_word() {
-    const int dev = cur_dev();
-    if (dev < 0) return nullptr;
-    std::lock_guard<std::mutex> lk(g_pers_mu);
-    if (!g_status_tried[dev]) {
-        g_status_tried[dev] = true;
-        void* h = nullptr;
-        void* d = nullptr;
-        if (hipHostMalloc(&h, 256, hipHostMallocMapped) == hipSuccess) {
-            *(volatile unsigned*)h = 0u;
-            if (hipHostGetDevicePointer(&d, h, 0) == hipSuccess) {
-                g_status_host[dev] = (unsigned*)h;
-                g_status_dev[dev] = (unsigned*)d;
-            } else {
-                (void)hipHostFree(h);
-            }
-        }
-        (void)hipGetLastError();
-    }
-    return g_status_dev[dev];
-}
-
-// IDV_ECOOP if a cooperative kernel of the current device has timed out since the status was last cleared (its outputs are
-// NaN-poisoned); clear != 0 acknowledges and resets it -- until then every cooperative entry of the device refuses with IDV_ECOOP.  The word is written by the device when the kernel aborts, so a launch that is
-// still queued is not covered: synchronise the stream first for a definite answer.
-extern "C" int idv_coop_last_status(int clear) {
-    const int dev = cur_dev();
-    if (dev < 0) return IDV_ELAUNCH;
-    (void)idv_coop_status_word();
-    std::lock_guard<std::mutex> lk(g_pers_mu);
-    volatile unsigned* w = g_status_host[dev];
-    if (!w || !*w) return IDV_OK;
-    if (clear) *w = 0u;
-    return IDV_ECOOP;
-}
-
-int idv_coop_chain_begin(hipStream_t st) {
-    const int dev = cur_dev();
-    if (dev < 0) return IDV_ELAUNCH;
-    g_pers_mu.lock();
-    volatile unsigned* w = g_status_host[dev];
-    if (w && *w) {                       // an earlier cooperative launch timed out and nobody has acknowledged it: refuse, like a
-        g_pers_mu.unlock();              // sticky device error, until idv_coop_last_status(1) -- the status is NOT consumed here,
-        return IDV_ECOOP;                // so an unrelated caller cannot swallow it
-    }
-    if (g_pers_done[dev] && g_pers_stream[dev] != st && hipStreamWaitEvent(st, g_pers_done[dev], 0) != hipSuccess) {
-        g_pers_mu.unlock();
-        return IDV_ELAUNCH;
-    }
-    return IDV_OK;
-}
-int idv_coop_chain_end(hipStream_t st) {
-    const int dev = cur_dev();
-    int rc = dev < 0 ? IDV_ELAUNCH : IDV_OK;
-    if (!rc && !g_pers_done[dev] && hipEventCreateWithFlags(&g_pers_done[dev], hipEventDisableTiming) != hipSuccess) rc = IDV_ELAUNCH;
-    if (!rc && hipEventRecord(g_pers_done[dev], st) != hipSuccess) rc = IDV_ELAUNCH;
-    if (!rc) g_pers_stream[dev] = st;
-    g_pers_mu.unlock();
-    return rc;
 }
 
 static unsigned long long* g_prof = nullptr;
@@ -460,8 +335,6 @@ extern "C" int idv_lstm_rec_pers(const float* g, long long g_run_z, long long g_
     const long long Bpad = (long long)TPR * 16;
     const size_t hx_bytes = (size_t)2 * 4 * Bpad * H * 4;
     if (2 * chunks > 20) return IDV_EINVAL;
-    // only the polled words are zeroed: every row of the exchange buffer a step reads was written by the step before
-    if (hipMemsetAsync(work, 0, SYNC_BYTES, st) != hipSuccess) return IDV_ELAUNCH;
     static const int nrep = [] {
         const char* e = getenv("IDV_PERS_REPL");
         const int v = e ? atoi(e) : 8;
@@ -473,19 +346,15 @@ extern "C" int idv_lstm_rec_pers(const float* g, long long g_run_z, long long g_
     a.hout = hout;
     a.kimg = (uint4*)kimg; a.kimg_lo = kimg_lo_slots; a.Tp = Tp; a.Jp = Jp;
     a.gsave = gsave; a.csave = csave;
-    a.sync = (unsigned*)work;
     a.hx = (unsigned short*)((char*)work + SYNC_BYTES);
     a.hx_bytes = (unsigned)hx_bytes;
-    a.nrep = nrep;
+    a.cs.nrep = nrep;
     a.H = H; a.B = B; a.T = T; a.Bpad = (int)Bpad; a.nchunks = chunks; a.prof = prof;
-    { const char* e = getenv("IDV_COOP_FAULT"); a.fault = (e && e[0] == '1') ? 1 : 0; }
     dim3 grid(H / 16, 2, chunks);
     // at least 84 KB of LDS per workgroup: ONE workgroup per CU whatever the register count (the hand-off form above is the
     // one measured for one workgroup per CU, and co-located workgroups would share one CU's miss bandwidth)
     size_t smem = (size_t)4 * nrt * 4 * 4 * 64 * sizeof(float);
     if (smem < 84 * 1024) smem = 84 * 1024;
-    a.status = idv_coop_status_word();
-    // the kernel is chosen and its LDS attribute set BEFORE the chain lock is taken: no early return may hold the lock
     typedef void (*kern_t)(const PersArgs);
     kern_t k = nullptr;
 #define IDV_PERS_PICK(KBW, NRT) k = prof ? (kern_t)lstm_pers_kernel<KBW, NRT, true> : (kern_t)lstm_pers_kernel<KBW, NRT, false>
@@ -495,11 +364,5 @@ extern "C" int idv_lstm_rec_pers(const float* g, long long g_run_z, long long g_
         if (nrt == 1) IDV_PERS_PICK(6, 1); else if (nrt == 2) IDV_PERS_PICK(6, 2); else IDV_PERS_PICK(6, 4);
     }
 #undef IDV_PERS_PICK
-    if (smem > 48 * 1024 && hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-        return IDV_ELAUNCH;
-    int rc = idv_coop_chain_begin(st);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k, grid, dim3(256), smem, st, a);
-    if ((rc = idv_coop_chain_end(st))) return rc;
-    return idv_launch_status();
+    return idv_coop_launch(k, grid, smem, st, work, SYNC_BYTES, a);
 }

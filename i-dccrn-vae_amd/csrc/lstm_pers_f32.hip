@@ -33,14 +33,9 @@ struct Pers32Args {
     float* csave;             // training: cell state per step [4 runs][T*B][H], or nullptr
     float* hx;                // exchange [2 parity][4 runs][Bpad][H] fp32
     unsigned hx_bytes;
-    unsigned* sync;           // [abort flag: 256 B][group = set * chunks + chunk][replica][256 B] arrive counters
-    int nrep;
+    CoopSync cs;              // group = set * chunks + chunk
     int H, B, T, Bpad, nchunks;
-    int fault;                // test hook (IDV_COOP_FAULT=1): workgroup (0, 0, 0) never arrives -> the bounded spins must abort
-    unsigned* status;         // host-mapped sticky status word (coop.hpp) or nullptr
 };
-
-constexpr unsigned long long SPIN_LIMIT_TICKS = 40000000ull;     // 0.4 s of the 100 MHz wall clock
 
 template <int KBW, int NRT>     // 32-k blocks per wave = H/128; 16-row tiles per workgroup
 __global__ __launch_bounds__(256, 1) void lstm_pers_f32_kernel(const Pers32Args a) {
@@ -55,9 +50,9 @@ __global__ __launch_bounds__(256, 1) void lstm_pers_f32_kernel(const Pers32Args 
     const int nslice = gridDim.x;
     const int col = lane & 15, rq = lane >> 4;
     const int TPR = a.Bpad / 16, NT = 2 * TPR;
-    unsigned* abortf = a.sync;
-    unsigned* counter0 = a.sync + 64 + (size_t)((s * a.nchunks + ch) * a.nrep) * 64;
-    unsigned* counter = counter0 + (size_t)(sl & (a.nrep - 1)) * 64;
+    unsigned* abortf = idv_coop_abort_flag(a.cs);
+    unsigned* counter0 = idv_coop_counter(a.cs, s * a.nchunks + ch);
+    unsigned* counter = idv_coop_replica(a.cs, counter0, sl);
     const size_t TBH = (size_t)a.T * a.B * H;
 
     // this workgroup's tiles of the (2 runs of the weight set) x ceil(B/16) tile space: run (2 z + s), first row, validity
@@ -97,7 +92,7 @@ __global__ __launch_bounds__(256, 1) void lstm_pers_f32_kernel(const Pers32Args 
 
     bool aborted = false;
     if (tid == 0) abort_sh = 0;
-    if (a.fault && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) return;      // injected failure (tests only)
+    if (idv_coop_withheld(a.cs)) return;
     for (int t = 0; t < a.T; ++t) {
         // ---- inputs of the cell update (independent of h): issue first
         float gpre[NRT][4];
@@ -121,22 +116,7 @@ __global__ __launch_bounds__(256, 1) void lstm_pers_f32_kernel(const Pers32Args 
 
         if (t > 0) {
             // ---- wait for h_{t-1} of the whole group
-            if (tid == 0) {
-                const unsigned want = (unsigned)t * (unsigned)nslice;
-                const unsigned long long t0 = wall_clock64();
-                unsigned long long spins = 0;
-                while (__hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want) {
-                    __builtin_amdgcn_s_sleep(1);
-                    if ((++spins & 1023) == 0) {
-                        if (__hip_atomic_load(abortf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) { abort_sh = 1; break; }
-                        if (wall_clock64() - t0 > SPIN_LIMIT_TICKS) {
-                            __hip_atomic_store(abortf, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            abort_sh = 1;
-                            break;
-                        }
-                    }
-                }
-            }
+            if (tid == 0) idv_coop_wait(counter, (unsigned)t * (unsigned)nslice, abortf, &abort_sh);
             // no acquire fence: every byte of the exchange buffer was stored sc1 and drained before the arrive, and every
             // load of it below is an sc1 buffer load issued after this barrier, which the polling wave joins after its match
             __syncthreads();
@@ -224,11 +204,11 @@ __global__ __launch_bounds__(256, 1) void lstm_pers_f32_kernel(const Pers32Args 
         // ---- publish: every storing wave drains its stores, the workgroup meets, ONE wave instruction arrives
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        if (tid < a.nrep) __hip_atomic_fetch_add(counter0 + (size_t)tid * 64, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        idv_coop_arrive(a.cs, counter0, tid);
     }
     if (aborted) {
         // poison this workgroup's outputs: a timed-out recurrence must never look like a result
-        if (tid == 0) idv_coop_raise(a.status);
+        if (tid == 0) idv_coop_raise(a.cs.status);
         const float qnan = __builtin_nanf("");
         for (int rt = 0; rt < NRT; ++rt) {
             if (!t_ok[rt]) continue;
@@ -250,7 +230,7 @@ inline int nrt_for(int H, int B) {
     return 0;
 }
 
-constexpr int SYNC_BYTES = 256 + 20 * 8 * 256;     // as lstm_pers.hip: abort flag + (<= 20 groups) x (<= 8 replicas) x 256 B
+constexpr int SYNC_BYTES = idv_coop_sync_bytes(20);     // <= 20 groups
 
 }  // namespace idv_pers32
 
@@ -283,13 +263,10 @@ extern "C" int idv_lstm_rec_pers_f32(const float* g, long long g_run_z, long lon
     Pers32Args a{};
     a.g = g; a.g_run_z = g_run_z; a.g_run_s = g_run_s; a.ldg = ldg;
     a.whh = whh_frag; a.hout = hout; a.gsave = gsave; a.csave = csave;
-    a.sync = (unsigned*)work;
     a.hx = (float*)((char*)work + SYNC_BYTES);
     a.hx_bytes = (unsigned)(2LL * 4 * Bpad * H * 4);
-    a.nrep = 8;
+    a.cs.nrep = 8;
     a.H = H; a.B = B; a.T = T; a.Bpad = (int)Bpad; a.nchunks = chunks;
-    { const char* e = getenv("IDV_COOP_FAULT"); a.fault = (e && e[0] == '1') ? 1 : 0; }
-    a.status = idv_coop_status_word();
     typedef void (*kern_t)(const Pers32Args);
     kern_t k;
     if (H == 384) k = nrt == 1 ? (kern_t)lstm_pers_f32_kernel<3, 1> : (nrt == 2 ? (kern_t)lstm_pers_f32_kernel<3, 2> : (kern_t)lstm_pers_f32_kernel<3, 4>);
@@ -297,11 +274,5 @@ extern "C" int idv_lstm_rec_pers_f32(const float* g, long long g_run_z, long lon
     // at least 84 KB of LDS per workgroup: ONE workgroup per CU whatever the register count
     size_t smem = (size_t)4 * nrt * 4 * 4 * 64 * sizeof(float);
     if (smem < 84 * 1024) smem = 84 * 1024;
-    if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return IDV_ELAUNCH;
-    if (hipMemsetAsync(work, 0, SYNC_BYTES, st) != hipSuccess) return IDV_ELAUNCH;
-    int rc = idv_coop_chain_begin(st);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k, dim3(H / 16, 2, chunks), dim3(256), smem, st, a);
-    if ((rc = idv_coop_chain_end(st))) return rc;
-    return idv_launch_status();
+    return idv_coop_launch(k, dim3(H / 16, 2, chunks), smem, st, work, SYNC_BYTES, a);
 }

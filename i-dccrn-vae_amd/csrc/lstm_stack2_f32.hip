@@ -16,7 +16,6 @@
 // idv_lstm_stack2_f32_supported checks the count against idv_coop_max_workgroups()); bounded spins, NaN poison and the sticky
 // status word on time-out (coop.hpp).
 #include <cstdlib>
-#include <mutex>
 #include "common.hpp"
 #include "coop.hpp"
 #include "../../include/idccrn_hip.h"
@@ -41,43 +40,13 @@ struct Args {
     float* csave1;
     float* hx;                // exchange [2 layers][2 parity][4 runs][Bpad][H] fp32
     unsigned hx_bytes;
-    unsigned* sync;           // [abort flag: 256 B][layer][group = run * tiles + tile][replica][256 B]
-    int nrep;
+    CoopSync cs;              // group = layer * 4 * tiles + run * tiles + tile
     int B, T, Bpad, tiles;
-    unsigned* status;         // host-mapped sticky status word (coop.hpp) or nullptr
-    int fault;                // test hook (IDV_COOP_FAULT=1): workgroup (0, 0, 0) never arrives -> the bounded spins must abort
 };
 
 constexpr int H = 128, NSL = 4, UPW = 32;          // hidden size, workgroups per (layer, group), units per workgroup
-constexpr unsigned long long SPIN_LIMIT_TICKS = 40000000ull;     // 0.4 s of the 100 MHz wall clock
 constexpr int MAX_GROUPS = 64, MAX_REP = 8;
-constexpr int SYNC_BYTES = 256 + 2 * MAX_GROUPS * MAX_REP * 256;
-
-// thread 0 of the workgroup: wait until *counter >= want (bounded); 1 in *abort_sh when the launch is being abandoned;
-// *seen (if given) <- the last value read
-// (other, other_seen): a second counter read ONCE if the first check fails, i.e. only when there is time to spare
-__device__ __forceinline__ void wait_for(unsigned* counter, unsigned want, unsigned* abortf, int* abort_sh, unsigned* seen = nullptr,
-                                         unsigned* other = nullptr, unsigned* other_seen = nullptr) {
-    const unsigned long long t0 = wall_clock64();
-    unsigned long long spins = 0;
-    unsigned v;
-    while ((v = __hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) < want) {
-        if (other) {
-            *other_seen = __hip_atomic_load(other, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            other = nullptr;
-        }
-        __builtin_amdgcn_s_sleep(1);
-        if ((++spins & 1023) == 0) {
-            if (__hip_atomic_load(abortf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) { *abort_sh = 1; break; }
-            if (wall_clock64() - t0 > SPIN_LIMIT_TICKS) {
-                __hip_atomic_store(abortf, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                *abort_sh = 1;
-                break;
-            }
-        }
-    }
-    if (seen) *seen = v;
-}
+constexpr int SYNC_BYTES = idv_coop_sync_bytes(2 * MAX_GROUPS, MAX_REP);
 
 __global__ __launch_bounds__(256, 1) void lstm_stack2_f32_kernel(const Args a) {
     extern __shared__ __attribute__((aligned(16))) float red[];                // [4 waves][8 tiles][4 r][64 lanes]
@@ -92,12 +61,11 @@ __global__ __launch_bounds__(256, 1) void lstm_stack2_f32_kernel(const Args a) {
     const int z = run >> 1, s = run & 1;
     const int col = lane & 15, rq = lane >> 4;
     const int b0 = tile * 16;
-    unsigned* abortf = a.sync;
+    unsigned* abortf = idv_coop_abort_flag(a.cs);
     const int groups = 4 * a.tiles, grp = run * a.tiles + tile;
-    unsigned* cnt0 = a.sync + 64 + (size_t)((0 * groups + grp) * a.nrep) * 64;          // layer-0 arrivals of this (run, tile)
-    unsigned* cnt1 = a.sync + 64 + (size_t)((1 * groups + grp) * a.nrep) * 64;
+    unsigned* cnt0 = idv_coop_counter(a.cs, 0 * groups + grp);          // layer-0 arrivals of this (run, tile)
+    unsigned* cnt1 = idv_coop_counter(a.cs, 1 * groups + grp);
     unsigned* mine = layer ? cnt1 : cnt0;
-    const int rep = sl & (a.nrep - 1);
     const size_t TB = (size_t)a.T * a.B, TBH = TB * H;
     // exchange regions: [layer][parity][run][Bpad][H]
     const unsigned hx_layer = (unsigned)layer * 2u * 4u * (unsigned)a.Bpad * (unsigned)H * 4u;
@@ -141,7 +109,7 @@ __global__ __launch_bounds__(256, 1) void lstm_stack2_f32_kernel(const Args a) {
 
     bool aborted = false;
     if (tid == 0) { abort_sh = 0; seen0_sh = 0; }
-    if (a.fault && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) return;      // injected failure (tests only)
+    if (idv_coop_withheld(a.cs)) return;
     __syncthreads();
 
     // layer 1: the rows of h0[t] for the CURRENT step sit in registers (cur0, cur1) when the step starts; W_ih h0[t] is
@@ -155,7 +123,7 @@ __global__ __launch_bounds__(256, 1) void lstm_stack2_f32_kernel(const Args a) {
         a1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(h0r, off + 16u, 0, 16));
     };
     auto input_late = [&](int tt, f32x4& a0, f32x4& a1) -> bool {            // poll layer 0, then load
-        if (tid == 0) wait_for(cnt0 + (size_t)rep * 64, (unsigned)(tt + 1) * (unsigned)NSL, abortf, &abort_sh, &seen0_sh);
+        if (tid == 0) idv_coop_wait(idv_coop_replica(a.cs, cnt0, sl), (unsigned)(tt + 1) * (unsigned)NSL, abortf, &abort_sh, &seen0_sh);
         __syncthreads();
         if (abort_sh) return false;
         input_load(tt, a0, a1);
@@ -199,8 +167,8 @@ __global__ __launch_bounds__(256, 1) void lstm_stack2_f32_kernel(const Args a) {
         if (layer && t == 0) input_mfma();
         if (t > 0) {
             if (tid == 0)       // (layer 1: the view of layer 0's progress is refreshed while waiting for the siblings, if it waits)
-                wait_for(mine + (size_t)rep * 64, (unsigned)t * (unsigned)NSL, abortf, &abort_sh, nullptr,
-                         layer ? cnt0 + (size_t)rep * 64 : nullptr, &seen0_sh);
+                idv_coop_wait(idv_coop_replica(a.cs, mine, sl), (unsigned)t * (unsigned)NSL, abortf, &abort_sh, nullptr,
+                              layer ? idv_coop_replica(a.cs, cnt0, sl) : nullptr, &seen0_sh);
             __syncthreads();                 // the polling wave joins after its match; every load below is sc1
             if (abort_sh) { aborted = true; break; }
             const unsigned par_r = hx_layer + (unsigned)((t - 1) & 1) * hx_par;
@@ -268,7 +236,7 @@ __global__ __launch_bounds__(256, 1) void lstm_stack2_f32_kernel(const Args a) {
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        if (tid < a.nrep) __hip_atomic_fetch_add(mine + (size_t)tid * 64, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        idv_coop_arrive(a.cs, mine, tid);
         // layer 1: the next step's input rows, the late way, if they were not requested above
         if (layer && t + 1 < a.T) {
             if (!early && !input_late(t + 1, nx0, nx1)) aborted = true;
@@ -276,7 +244,7 @@ __global__ __launch_bounds__(256, 1) void lstm_stack2_f32_kernel(const Args a) {
         }
     }
     if (aborted) {
-        if (tid == 0) idv_coop_raise(a.status);
+        if (tid == 0) idv_coop_raise(a.cs.status);
         if (layer) {
             const float qnan = __builtin_nanf("");
             for (long long e = tid; e < (long long)a.T * 16 * UPW; e += 256) {
@@ -322,25 +290,15 @@ extern "C" int idv_lstm_stack2_f32(const float* g, long long g_run_z, long long 
     hipStream_t st = (hipStream_t)stream;
     const int tiles = (B + 15) / 16;
     const long long Bpad = 16LL * tiles;
-    if (hipMemsetAsync(work, 0, SYNC_BYTES, st) != hipSuccess) return IDV_ELAUNCH;
     Args a{};
     a.g = g; a.g_run_z = g_run_z; a.g_run_s = g_run_s; a.ldg = ldg;
     a.whh0 = whh0; a.wih1 = wih1_hh; a.whh1 = whh1; a.bias1 = bias1;
     a.h0 = h0; a.h0_bytes = (unsigned)h0_bytes; a.hout = hout;
     a.gsave1 = gsave1; a.csave0 = csave0; a.csave1 = csave1;
-    a.sync = (unsigned*)work;
     a.hx = (float*)((char*)work + SYNC_BYTES);
     a.hx_bytes = (unsigned)(2LL * 2 * 4 * Bpad * H * 4);
-    a.nrep = 4;
+    a.cs.nrep = 4;
     a.B = B; a.T = T; a.Bpad = (int)Bpad; a.tiles = tiles;
-    { const char* e = getenv("IDV_COOP_FAULT"); a.fault = (e && e[0] == '1') ? 1 : 0; }
-    a.status = idv_coop_status_word();
     const size_t smem = 84 * 1024;                   // > half a CU's LDS: one workgroup per CU (red[] needs 32 KB)
-    if (hipFuncSetAttribute((const void*)lstm_stack2_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-        return IDV_ELAUNCH;
-    int rc = idv_coop_chain_begin(st);
-    if (rc) return rc;
-    hipLaunchKernelGGL(lstm_stack2_f32_kernel, dim3(2 * NSL, 4, tiles), dim3(256), smem, st, a);
-    if ((rc = idv_coop_chain_end(st))) return rc;
-    return idv_launch_status();
+    return idv_coop_launch(lstm_stack2_f32_kernel, dim3(2 * NSL, 4, tiles), smem, st, work, SYNC_BYTES, a);
 }
