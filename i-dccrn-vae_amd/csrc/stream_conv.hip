@@ -30,7 +30,24 @@ struct SconvArgs {
     int transposed, Cout, Fin, Fout, B, k, Tp, Jp, nsplit, cps;
 };
 
-__device__ __forceinline__ void epilogue(const SconvArgs& a, int co, int fo, int b, int t, float vr, float vi) {
+// The per-row entry (idv_stream_cconv_rows): k above is k_launch, h0 / h1 / hist_out / x0hist_out are the bases of both parity
+// halves, and slot b reads half parity_b, writes half 1 - parity_b from its column k_b - 1 (nothing when k_b = 0).
+struct SconvRows {
+    const long long* rows;
+    size_t h0_half, h1_half, out_half;      // floats per parity half of h0 / h1 / hist_out (x0hist_out: h0_half)
+};
+
+struct RowOf {
+    int k, parity;
+};
+
+__device__ __forceinline__ RowOf row_of(const SconvRows& r, int b) {
+    const long long* q = r.rows + (size_t)b * IDV_STREAM_ROW_FIELDS;
+    return RowOf{(int)q[IDV_ROW_K], (int)q[IDV_ROW_PARITY]};
+}
+
+// t_hist: the column that goes to hist (the slot's last one)
+__device__ __forceinline__ void epilogue(const SconvArgs& a, int co, int fo, int b, int t, float vr, float vi, float* hist, int t_hist) {
     vr += a.bias[2 * co];
     vi += a.bias[2 * co + 1];
     if (a.fold) {
@@ -48,16 +65,16 @@ __device__ __forceinline__ void epilogue(const SconvArgs& a, int co, int fo, int
     const size_t o = (size_t)co * plane + (size_t)fo * a.Jp + (size_t)b * a.Tp + 1 + t;
     a.out[o] = vr;
     a.out[(size_t)a.Cout * plane + o] = vi;
-    if (a.hist_out && t == a.k - 1) {
+    if (hist && t == t_hist) {
         const size_t h = ((size_t)co * a.Fout + fo) * a.B + b;
-        a.hist_out[h] = vr;
-        a.hist_out[(size_t)a.Cout * a.Fout * a.B + h] = vi;
+        hist[h] = vr;
+        hist[(size_t)a.Cout * a.Fout * a.B + h] = vi;
     }
 }
 
 // grid: x = position blocks, y = co tiles, z = split * (transposed ? 2 : 1) + output-bin parity
-template <int CO_T>
-__global__ __launch_bounds__(SC_THREADS) void stream_cconv_kernel(const SconvArgs a) {
+template <int CO_T, bool ROWS>
+__device__ __forceinline__ void cconv_body(const SconvArgs& a, const SconvRows& r) {
     const int J = a.B * a.k;
     const int par = a.transposed ? (int)(blockIdx.z & 1) : 0;
     const int split = a.transposed ? (int)(blockIdx.z >> 1) : (int)blockIdx.z;
@@ -70,7 +87,12 @@ __global__ __launch_bounds__(SC_THREADS) void stream_cconv_kernel(const SconvArg
         for (long long e = blockIdx.x * (long long)SC_THREADS + threadIdx.x; e < n; e += (long long)gridDim.x * SC_THREADS) {
             const int b = (int)(e % a.B);
             const long long pf = e / a.B;                     // (ri * C0 + ci) * Fin + fi
-            a.x0hist_out[e] = a.x0[pf * a.Jp + (long long)b * a.Tp + a.k];
+            if (ROWS) {
+                const RowOf rw = row_of(r, b);
+                if (rw.k > 0) a.x0hist_out[(size_t)(1 - rw.parity) * r.h0_half + e] = a.x0[pf * a.Jp + (long long)b * a.Tp + rw.k];
+            } else {
+                a.x0hist_out[e] = a.x0[pf * a.Jp + (long long)b * a.Tp + a.k];
+            }
         }
     }
 
@@ -81,6 +103,10 @@ __global__ __launch_bounds__(SC_THREADS) void stream_cconv_kernel(const SconvArg
     const int b = j / a.k, t = j - b * a.k;
     const int fo = a.transposed ? 2 * fq + par : fq;
     const int ci0 = split * a.cps, ci1 = min(Cin, ci0 + a.cps);
+    RowOf rw{a.k, 0};
+    if (ROWS) rw = row_of(r, b);
+    const float* h0 = a.h0 + (ROWS ? (size_t)rw.parity * r.h0_half : 0);
+    const float* h1 = a.h1 + (ROWS ? (size_t)rw.parity * r.h1_half : 0);
 
     float accr[CO_T], acci[CO_T];
 #pragma unroll
@@ -90,7 +116,7 @@ __global__ __launch_bounds__(SC_THREADS) void stream_cconv_kernel(const SconvArg
     for (int ci = ci0; ci < ci1; ++ci) {
         const bool second = ci >= a.C0;
         const float* x = second ? a.x1 : a.x0;
-        const float* hs = second ? a.h1 : a.h0;
+        const float* hs = second ? h1 : h0;
         const int C = second ? a.C1 : a.C0;
         const int cl = second ? ci - a.C0 : ci;
         const size_t pr = (size_t)cl * a.Fin, pi = (size_t)(C + cl) * a.Fin;
@@ -131,7 +157,8 @@ __global__ __launch_bounds__(SC_THREADS) void stream_cconv_kernel(const SconvArg
         const int co = cot * CO_T + c;
         if (co >= a.Cout) break;
         if (a.nsplit == 1) {
-            epilogue(a, co, fo, b, t, accr[c], acci[c]);
+            epilogue(a, co, fo, b, t, accr[c], acci[c],
+                     ROWS && a.hist_out ? a.hist_out + (size_t)(1 - rw.parity) * r.out_half : a.hist_out, rw.k - 1);
         } else {
             const size_t slab = (size_t)a.Cout * a.Fout * J;
             const size_t o = (size_t)split * 2 * slab + ((size_t)co * a.Fout + fo) * J + j;
@@ -141,7 +168,18 @@ __global__ __launch_bounds__(SC_THREADS) void stream_cconv_kernel(const SconvArg
     }
 }
 
-__global__ void stream_cconv_combine_kernel(const SconvArgs a) {
+template <int CO_T>
+__global__ __launch_bounds__(SC_THREADS) void stream_cconv_kernel(const SconvArgs a) {
+    cconv_body<CO_T, false>(a, SconvRows{});
+}
+
+template <int CO_T>
+__global__ __launch_bounds__(SC_THREADS) void stream_cconv_rows_kernel(const SconvArgs a, const SconvRows r) {
+    cconv_body<CO_T, true>(a, r);
+}
+
+template <bool ROWS>
+__device__ __forceinline__ void combine_body(const SconvArgs& a, const SconvRows& r) {
     const int J = a.B * a.k;
     const long long n = (long long)a.Cout * a.Fout * J;
     const size_t slab = (size_t)n;
@@ -154,9 +192,17 @@ __global__ void stream_cconv_combine_kernel(const SconvArgs a) {
             vr += a.work[(size_t)s * 2 * slab + e];
             vi += a.work[(size_t)s * 2 * slab + slab + e];
         }
-        epilogue(a, co, fo, j / a.k, j % a.k, vr, vi);
+        const int b = j / a.k;
+        RowOf rw{a.k, 0};
+        if (ROWS) rw = row_of(r, b);
+        epilogue(a, co, fo, b, j % a.k, vr, vi, ROWS && a.hist_out ? a.hist_out + (size_t)(1 - rw.parity) * r.out_half : a.hist_out,
+                 rw.k - 1);
     }
 }
+
+__global__ void stream_cconv_combine_kernel(const SconvArgs a) { combine_body<false>(a, SconvRows{}); }
+
+__global__ void stream_cconv_combine_rows_kernel(const SconvArgs a, const SconvRows r) { combine_body<true>(a, r); }
 
 // w_re / w_im: conv [Cout][Cin][5][2], transposed [Cin][Cout][5][2]; taps reordered to (x[t-1], x[t])
 __global__ void stream_pack_cconv_kernel(const float* __restrict__ w_re, const float* __restrict__ w_im,
@@ -222,10 +268,11 @@ extern "C" int idv_stream_cconv_splits(int transposed, int Cin, int Cout, int Fi
     return s < 1 ? 1 : (int)s;
 }
 
-extern "C" int idv_stream_cconv(const float* x0, const float* h0, int C0, const float* x1, const float* h1, int C1,
-                                const float* w, const float* bias, const float* fold, const float* prelu_slope, float* out,
-                                float* hist_out, float* x0hist_out, float* work, int nsplit, int transposed, int Cout, int Fin,
-                                int B, int k, int Tp, int Jp, void* stream) {
+// rows NULL: the lock-step entry
+static int launch_cconv(const float* x0, const float* h0, int C0, const float* x1, const float* h1, int C1, const float* w,
+                        const float* bias, const float* fold, const float* prelu_slope, float* out, float* hist_out, float* x0hist_out,
+                        float* work, int nsplit, int transposed, int Cout, int Fin, int B, int k, int Tp, int Jp, const long long* rows,
+                        void* stream) {
     if (!x0 || !h0 || C0 <= 0 || C1 < 0 || (C1 > 0 && (!x1 || !h1)) || !w || !bias || !out || Cout <= 0 ||
         Fin <= 0 || B <= 0 || k <= 0 || Tp < k + 1 || Jp < B * Tp || nsplit <= 0 || (nsplit > 1 && !work))
         return IDV_EINVAL;
@@ -245,7 +292,12 @@ extern "C" int idv_stream_cconv(const float* x0, const float* h0, int C0, const 
     dim3 grid((unsigned)((pos + SC_THREADS - 1) / SC_THREADS), (unsigned)((Cout + ct - 1) / ct),
               (unsigned)(nsplit * (a.transposed ? 2 : 1)));
     hipStream_t st = (hipStream_t)stream;
-    if (ct == 16)
+    const SconvRows r{rows, (size_t)2 * C0 * Fin * B, (size_t)2 * C1 * Fin * B, (size_t)2 * Cout * a.Fout * B};
+    if (rows && ct == 16)
+        hipLaunchKernelGGL(stream_cconv_rows_kernel<16>, grid, dim3(SC_THREADS), 0, st, a, r);
+    else if (rows)
+        hipLaunchKernelGGL(stream_cconv_rows_kernel<1>, grid, dim3(SC_THREADS), 0, st, a, r);
+    else if (ct == 16)
         hipLaunchKernelGGL(stream_cconv_kernel<16>, grid, dim3(SC_THREADS), 0, st, a);
     else
         hipLaunchKernelGGL(stream_cconv_kernel<1>, grid, dim3(SC_THREADS), 0, st, a);
@@ -253,6 +305,26 @@ extern "C" int idv_stream_cconv(const float* x0, const float* h0, int C0, const 
     if (rc || nsplit == 1) return rc;
     long long g = ((long long)Cout * a.Fout * J + 255) / 256;
     g = g > 4096 ? 4096 : (g < 1 ? 1 : g);
-    hipLaunchKernelGGL(stream_cconv_combine_kernel, dim3((unsigned)g), dim3(256), 0, st, a);
+    if (rows)
+        hipLaunchKernelGGL(stream_cconv_combine_rows_kernel, dim3((unsigned)g), dim3(256), 0, st, a, r);
+    else
+        hipLaunchKernelGGL(stream_cconv_combine_kernel, dim3((unsigned)g), dim3(256), 0, st, a);
     return idv_launch_status();
+}
+
+extern "C" int idv_stream_cconv(const float* x0, const float* h0, int C0, const float* x1, const float* h1, int C1,
+                                const float* w, const float* bias, const float* fold, const float* prelu_slope, float* out,
+                                float* hist_out, float* x0hist_out, float* work, int nsplit, int transposed, int Cout, int Fin,
+                                int B, int k, int Tp, int Jp, void* stream) {
+    return launch_cconv(x0, h0, C0, x1, h1, C1, w, bias, fold, prelu_slope, out, hist_out, x0hist_out, work, nsplit, transposed, Cout,
+                        Fin, B, k, Tp, Jp, nullptr, stream);
+}
+
+extern "C" int idv_stream_cconv_rows(const float* x0, const float* h0, int C0, const float* x1, const float* h1, int C1,
+                                     const float* w, const float* bias, const float* fold, const float* prelu_slope, float* out,
+                                     float* hist, float* x0hist, float* work, int nsplit, int transposed, int Cout, int Fin, int B,
+                                     int k_launch, int Tp, int Jp, const long long* rows, void* stream) {
+    if (!rows) return IDV_EINVAL;
+    return launch_cconv(x0, h0, C0, x1, h1, C1, w, bias, fold, prelu_slope, out, hist, x0hist, work, nsplit, transposed, Cout, Fin, B,
+                        k_launch, Tp, Jp, rows, stream);
 }

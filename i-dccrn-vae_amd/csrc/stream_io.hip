@@ -87,6 +87,101 @@ __global__ void stream_ola_kernel(const float* __restrict__ frames, int Tp, int 
     }
 }
 
+// ---- per-row variants (streaming.StreamingSessions): every slot b takes its ranges from row b of a table of
+// IDV_STREAM_ROW_FIELDS long longs per slot (include/idccrn_hip.h).  The table is indexed by b, which differs from lane to lane.
+#define ROW(b, f) rows[(size_t)(b) * IDV_STREAM_ROW_FIELDS + (f)]
+
+// columns tl >= k_b of a slot are zeroed: the kernels downstream run over all k_launch columns and must not meet stale data
+__global__ void stream_frames_rows_kernel(const float* __restrict__ ring, int R, const float* __restrict__ x, long long ldx,
+                                          const long long* __restrict__ rows, int B, int n_fft, int win, int hop, int k_launch,
+                                          float* __restrict__ frames, int Tp, int Jp) {
+    const int left = (n_fft - win) / 2, half = n_fft / 2;
+    const long long n = (long long)win * B * k_launch;
+    for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
+        const int tl = (int)(e % k_launch);
+        const int b = (int)((e / k_launch) % B);
+        const int i = (int)(e / ((long long)k_launch * B));
+        float v = 0.f;
+        if (tl < ROW(b, IDV_ROW_K)) {
+            const long long n_prev = ROW(b, IDV_ROW_N_PREV), L_end = ROW(b, IDV_ROW_L_END);
+            long long s = (long long)hop * (ROW(b, IDV_ROW_T0) + tl) + left - half + i;
+            if (s < 0) s = -s;
+            if (L_end >= 0 && s >= L_end) s = 2 * (L_end - 1) - s;
+            v = s >= n_prev ? x[(size_t)b * ldx + (size_t)(s - n_prev)] : ring[(size_t)b * R + (size_t)(s % R)];
+        }
+        frames[(size_t)i * Jp + (size_t)b * Tp + 1 + tl] = v;
+    }
+}
+
+// the last min(count_b, R) of the count_b new samples of slot b go to the ring at the slot's own position
+__global__ void stream_ring_rows_kernel(float* __restrict__ ring, int R, const float* __restrict__ x, long long ldx, int n_max,
+                                        const long long* __restrict__ rows, int B) {
+    const long long n = (long long)n_max * B;
+    for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
+        const int b = (int)(e / n_max);
+        const long long j = e % n_max, count = ROW(b, IDV_ROW_COUNT);
+        const long long first = count > R ? count - R : 0;              // index into x[b] of the oldest sample kept
+        if (first + j >= count) continue;
+        const long long s = ROW(b, IDV_ROW_N_PREV) + first + j;
+        ring[(size_t)b * R + (size_t)(s % R)] = x[(size_t)b * ldx + (size_t)(first + j)];
+    }
+}
+
+// stream_ola_kernel with the ranges, the carry parity and the output offset of each slot; the same sums in the same order
+__global__ void stream_ola_rows_kernel(const float* __restrict__ frames, int Tp, int Jp, float* __restrict__ carry, int cap,
+                                       const long long* __restrict__ rows, int B, int n_fft, int win, int hop, long long span_max,
+                                       float* __restrict__ y, long long ldy) {
+    const int left = (n_fft - win) / 2, half = n_fft / 2;
+    const long long n = span_max * B;
+    const double two_pi = 6.283185307179586476925286766559;
+    for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
+        const int b = (int)(e / span_max);
+        const long long e0 = ROW(b, IDV_ROW_E0), e1 = ROW(b, IDV_ROW_E1);
+        const int k = (int)ROW(b, IDV_ROW_K);
+        if (k == 0 && e0 == e1) continue;                               // the slot sits this group out: its carry stays where it is
+        const long long p_start = half + e0, p_new = half + e1;
+        const long long P = p_start + e % span_max;
+        if (P >= ROW(b, IDV_ROW_P_END)) continue;
+        const long long t0 = ROW(b, IDV_ROW_T0), T_total = ROW(b, IDV_ROW_T_TOTAL);
+        const int parity = (int)ROW(b, IDV_ROW_PARITY);
+        const float* cin = carry + (size_t)parity * B * cap;
+        float* cout_ = carry + (size_t)(1 - parity) * B * cap;
+        float v = (P - p_start < ROW(b, IDV_ROW_CARRY_IN)) ? cin[(size_t)b * cap + (size_t)(P - p_start)] : 0.f;
+        for (int tl = 0; tl < k; ++tl) {
+            const long long i = P - (long long)hop * (t0 + tl) - left;
+            if (i >= 0 && i < win) v += frames[(size_t)i * Jp + (size_t)b * Tp + 1 + tl];
+        }
+        if (P < p_new) {
+            double env = 0.0;
+            long long t_hi = (P - left) / hop;
+            if (T_total >= 0 && t_hi > T_total - 1) t_hi = T_total - 1;
+            long long t_lo = P - left - win >= 0 ? (P - left - win) / hop + 1 : 0;
+            for (long long t = t_lo; t <= t_hi; ++t) {
+                const long long i = P - (long long)hop * t - left;
+                if (i >= 0 && i < win) {
+                    const double wn = 0.5 - 0.5 * cos(two_pi * i / win);
+                    env += wn * wn;
+                }
+            }
+            const float inv = env > 1e-11 ? (float)(1.0 / env) : 0.f;
+            y[(size_t)b * ldy + (size_t)(ROW(b, IDV_ROW_Y_OFF) + P - p_start)] = v * inv;
+        } else {
+            cout_[(size_t)b * cap + (size_t)(P - p_new)] = v;
+        }
+    }
+}
+
+// buf viewed as [outer][B][inner]: zero the slots listed
+__global__ void stream_zero_rows_kernel(float* __restrict__ buf, long long outer, int B, long long inner,
+                                        const long long* __restrict__ slots, int n_slots) {
+    const long long per = outer * inner, n = per * n_slots;
+    for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
+        const long long b = slots[e / per], r = e % per;
+        buf[((size_t)(r / inner) * B + (size_t)b) * inner + (size_t)(r % inner)] = 0.f;
+    }
+}
+#undef ROW
+
 }  // namespace
 
 extern "C" int idv_stream_frames(const float* ring, int R, const float* x, long long ldx, int n_new, long long n_prev, long long L_end,
@@ -131,5 +226,78 @@ extern "C" int idv_stream_ola(const float* frames, int Tp, int Jp, const float* 
     if (p_end <= p_start) return IDV_OK;
     hipLaunchKernelGGL(stream_ola_kernel, dim3(grid_of((p_end - p_start) * B)), dim3(256), 0, (hipStream_t)stream, frames, Tp, Jp,
                        carry_in, carry_in_len, carry_out, cap, B, n_fft, win, hop, t0, k, T_total, e0, e1, p_end, y, ldy, y_off);
+    return idv_launch_status();
+}
+
+extern "C" int idv_stream_row_fields(void) { return IDV_STREAM_ROW_FIELDS; }
+
+extern "C" int idv_stream_rows_check(const long long* host_rows, int B, int R, int n_x, int n_fft, int win, int hop, int cap,
+                                     int k_launch, int Tp, long long ldy, long long span_max) {
+    if (!host_rows || B <= 0 || R <= 0 || n_x < 0 || n_fft <= 0 || win <= 0 || win > n_fft || hop <= 0 || cap <= 0 || k_launch < 0 ||
+        Tp < k_launch + 1 || ldy < 0 || span_max < 0)
+        return IDV_EINVAL;
+    const int left = (n_fft - win) / 2, half = n_fft / 2;
+    for (int b = 0; b < B; ++b) {
+        const long long* r = host_rows + (size_t)b * IDV_STREAM_ROW_FIELDS;
+        const long long n_prev = r[IDV_ROW_N_PREV], count = r[IDV_ROW_COUNT], L_end = r[IDV_ROW_L_END], t0 = r[IDV_ROW_T0],
+                        k = r[IDV_ROW_K], parity = r[IDV_ROW_PARITY], e0 = r[IDV_ROW_E0], e1 = r[IDV_ROW_E1], p_end = r[IDV_ROW_P_END],
+                        carry_in = r[IDV_ROW_CARRY_IN], T_total = r[IDV_ROW_T_TOTAL], y_off = r[IDV_ROW_Y_OFF];
+        if (n_prev < 0 || count < 0 || count > n_x || L_end < -1 || t0 < 0 || k < 0 || k > k_launch || (parity != 0 && parity != 1) ||
+            e0 < 0 || e1 < e0 || carry_in < 0 || carry_in > cap || y_off < 0 || y_off + (e1 - e0) > ldy || (L_end < 0) != (T_total < 0))
+            return IDV_EINVAL;
+        if (k > 0) {   // every sample a frame reads is in the ring or in x[b, :count]; the start mirror is there (as idv_stream_frames)
+            const long long first = hop * t0 + left - half, last = hop * (t0 + k - 1) + left - half + win - 1;
+            const long long lo_read = first < 0 ? 0 : first;
+            const long long hi_read = (L_end >= 0 && last >= L_end) ? L_end - 1 : last;
+            if (hi_read >= n_prev + count || (lo_read < n_prev && n_prev - lo_read > R) || (first < 0 && -first >= n_prev + count) ||
+                (first < 0 && n_prev > R))
+                return IDV_EINVAL;
+        }
+        if (k == 0 && e0 == e1) continue;
+        const long long p_start = half + e0;                 // as idv_stream_ola
+        if (p_end < half + e1 || p_end - p_start < carry_in || p_end - (half + e1) > cap || p_end - p_start > span_max ||
+            (k > 0 && hop * (t0 + k - 1) + left + win > p_end))
+            return IDV_EINVAL;
+    }
+    return IDV_OK;
+}
+
+extern "C" int idv_stream_frames_rows(const float* ring, int R, const float* x, long long ldx, const long long* rows, int B, int n_fft,
+                                      int win, int hop, int k_launch, float* frames, int Tp, int Jp, void* stream) {
+    if (!ring || R <= 0 || ldx < 0 || !rows || B <= 0 || n_fft <= 0 || win <= 0 || win > n_fft || hop <= 0 || k_launch <= 0 || !frames ||
+        Tp < k_launch + 1 || Jp < B * Tp)
+        return IDV_EINVAL;
+    hipLaunchKernelGGL(stream_frames_rows_kernel, dim3(grid_of((long long)win * B * k_launch)), dim3(256), 0, (hipStream_t)stream, ring,
+                       R, x, ldx, rows, B, n_fft, win, hop, k_launch, frames, Tp, Jp);
+    return idv_launch_status();
+}
+
+extern "C" int idv_stream_ring_rows(float* ring, int R, const float* x, long long ldx, int n_x, const long long* rows, int B,
+                                    void* stream) {
+    if (!ring || R <= 0 || n_x < 0 || (n_x > 0 && (!x || ldx < n_x)) || !rows || B <= 0) return IDV_EINVAL;
+    if (n_x == 0) return IDV_OK;
+    const int n_max = n_x < R ? n_x : R;
+    hipLaunchKernelGGL(stream_ring_rows_kernel, dim3(grid_of((long long)n_max * B)), dim3(256), 0, (hipStream_t)stream, ring, R, x, ldx,
+                       n_max, rows, B);
+    return idv_launch_status();
+}
+
+extern "C" int idv_stream_ola_rows(const float* frames, int Tp, int Jp, float* carry, int cap, const long long* rows, int B, int n_fft,
+                                   int win, int hop, int k_launch, long long span_max, float* y, long long ldy, void* stream) {
+    if ((k_launch > 0 && !frames) || k_launch < 0 || !carry || cap <= 0 || !rows || B <= 0 || n_fft <= 0 || win <= 0 || win > n_fft ||
+        hop <= 0 || span_max < 0 || ldy < 0 || (ldy > 0 && !y) || (k_launch > 0 && (Tp < k_launch + 1 || Jp < B * Tp)))
+        return IDV_EINVAL;
+    if (span_max == 0) return IDV_OK;
+    hipLaunchKernelGGL(stream_ola_rows_kernel, dim3(grid_of(span_max * B)), dim3(256), 0, (hipStream_t)stream, frames, Tp, Jp, carry, cap,
+                       rows, B, n_fft, win, hop, span_max, y, ldy);
+    return idv_launch_status();
+}
+
+extern "C" int idv_stream_zero_rows(float* buf, long long outer, int B, long long inner, const long long* slots, int n_slots,
+                                    void* stream) {
+    if (!buf || outer <= 0 || B <= 0 || inner <= 0 || !slots || n_slots < 0 || n_slots > B) return IDV_EINVAL;
+    if (n_slots == 0) return IDV_OK;
+    hipLaunchKernelGGL(stream_zero_rows_kernel, dim3(grid_of(outer * inner * n_slots)), dim3(256), 0, (hipStream_t)stream, buf, outer, B,
+                       inner, slots, n_slots);
     return idv_launch_status();
 }

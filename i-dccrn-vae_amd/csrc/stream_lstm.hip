@@ -14,14 +14,36 @@ namespace {
 constexpr int SL_H = 128;
 constexpr int SL_SB = 8;
 
-__global__ __launch_bounds__(4 * SL_H) void stream_lstm_kernel(const float* __restrict__ G, const float* __restrict__ wt,
-                                                               const float* __restrict__ b1, float* __restrict__ state,
-                                                               float* __restrict__ hout, int B, int k) {
+// ROWS (idv_stream_clstm_rows): k is k_launch and stream b runs only its first k_b = rows[b][IDV_ROW_K] steps; from step k_b on
+// its h and c of both layers stay as they are, in LDS, in registers and in state, and its rows of hout are zero.
+template <bool ROWS>
+__device__ __forceinline__ void lstm_body(const float* __restrict__ G, const float* __restrict__ wt, const float* __restrict__ b1,
+                                          float* __restrict__ state, float* __restrict__ hout, int B, int k,
+                                          const long long* __restrict__ rows) {
     constexpr int H = SL_H, SB = SL_SB, G4 = 4 * H;
     __shared__ float hs0[SB][H], hs1[SB][H], gs[SB][G4];
     const int r = threadIdx.x;
     const int run = blockIdx.y, z = run >> 1, s = run & 1;
     const int b0 = blockIdx.x * SB;
+    constexpr int PAIRS = SB * H / G4;              // (stream, unit) pairs whose cells this thread updates
+    int kq[PAIRS];                                  // steps of the stream of pair q
+    int ksteps = k;                                 // steps this workgroup runs: the most any of its streams has
+    if (ROWS) {
+        ksteps = 0;
+        for (int sb = 0; sb < SB; ++sb)
+            if (b0 + sb < B) ksteps = max(ksteps, (int)rows[(size_t)(b0 + sb) * IDV_STREAM_ROW_FIELDS + IDV_ROW_K]);
+#pragma unroll
+        for (int q = 0; q < PAIRS; ++q) {
+            const int b = b0 + (r + q * G4) / H;
+            kq[q] = b < B ? (int)rows[(size_t)b * IDV_STREAM_ROW_FIELDS + IDV_ROW_K] : 0;
+            for (int t = kq[q]; t < k; ++t)
+                if (b < B) hout[((size_t)run * k * B + (size_t)t * B + b) * H + (r + q * G4) % H] = 0.f;
+        }
+        if (ksteps == 0) return;                    // the same for every thread of the workgroup
+    } else {
+#pragma unroll
+        for (int q = 0; q < PAIRS; ++q) kq[q] = k;
+    }
     const float* w_hh0 = wt + (size_t)(s * 3 + 0) * H * G4;
     const float* w_ih1 = wt + (size_t)(s * 3 + 1) * H * G4;
     const float* w_hh1 = wt + (size_t)(s * 3 + 2) * H * G4;
@@ -30,7 +52,6 @@ __global__ __launch_bounds__(4 * SL_H) void stream_lstm_kernel(const float* __re
     float* st = state + (size_t)run * 4 * B * H;
     const size_t sz = (size_t)B * H;
 
-    constexpr int PAIRS = SB * H / G4;              // (stream, unit) pairs whose cells this thread updates
     float c0[PAIRS], c1[PAIRS];
 #pragma unroll
     for (int q = 0; q < PAIRS; ++q) {
@@ -46,7 +67,7 @@ __global__ __launch_bounds__(4 * SL_H) void stream_lstm_kernel(const float* __re
     const int colp = s * G4 + ((u_r >> 4) * 4 + g_r) * 16 + (u_r & 15);
     __syncthreads();
 
-    for (int t = 0; t < k; ++t) {
+    for (int t = 0; t < ksteps; ++t) {
         float acc[SB];
 #pragma unroll
         for (int sb = 0; sb < SB; ++sb) {
@@ -64,6 +85,7 @@ __global__ __launch_bounds__(4 * SL_H) void stream_lstm_kernel(const float* __re
 #pragma unroll
         for (int q = 0; q < PAIRS; ++q) {
             const int e = r + q * G4, sb = e / H, u = e % H;
+            if (ROWS && t >= kq[q]) continue;
             const float ig = sigmoidf_(gs[sb][u]), fg = sigmoidf_(gs[sb][H + u]);
             const float gg = tanhf_(gs[sb][2 * H + u]), og = sigmoidf_(gs[sb][3 * H + u]);
             c0[q] = fg * c0[q] + ig * gg;
@@ -88,6 +110,7 @@ __global__ __launch_bounds__(4 * SL_H) void stream_lstm_kernel(const float* __re
 #pragma unroll
         for (int q = 0; q < PAIRS; ++q) {
             const int e = r + q * G4, sb = e / H, u = e % H, b = b0 + sb;
+            if (ROWS && t >= kq[q]) continue;
             const float ig = sigmoidf_(gs[sb][u]), fg = sigmoidf_(gs[sb][H + u]);
             const float gg = tanhf_(gs[sb][2 * H + u]), og = sigmoidf_(gs[sb][3 * H + u]);
             c1[q] = fg * c1[q] + ig * gg;
@@ -106,6 +129,19 @@ __global__ __launch_bounds__(4 * SL_H) void stream_lstm_kernel(const float* __re
         st[2 * sz + (size_t)b * H + u] = hs1[sb][u];
         st[3 * sz + (size_t)b * H + u] = c1[q];
     }
+}
+
+__global__ __launch_bounds__(4 * SL_H) void stream_lstm_kernel(const float* __restrict__ G, const float* __restrict__ wt,
+                                                               const float* __restrict__ b1, float* __restrict__ state,
+                                                               float* __restrict__ hout, int B, int k) {
+    lstm_body<false>(G, wt, b1, state, hout, B, k, nullptr);
+}
+
+__global__ __launch_bounds__(4 * SL_H) void stream_lstm_rows_kernel(const float* __restrict__ G, const float* __restrict__ wt,
+                                                                    const float* __restrict__ b1, float* __restrict__ state,
+                                                                    float* __restrict__ hout, int B, int k,
+                                                                    const long long* __restrict__ rows) {
+    lstm_body<true>(G, wt, b1, state, hout, B, k, rows);
 }
 
 // real = rr - ii, imag = ir + ri (runs 0, 3, 2, 1) -> planar [2][H][Jp] at column b*Tp + 1 + t
@@ -127,17 +163,32 @@ __global__ void stream_lstm_combine_kernel(const float* __restrict__ h, int H, i
 
 extern "C" int idv_stream_lstm_supported(int H) { return H == SL_H ? 1 : 0; }
 
-extern "C" int idv_stream_clstm(const float* G, const float* wt, const float* b1, float* state, float* hout, float* out, int H, int B,
-                                int k, int Tp, int Jp, void* stream) {
+// rows NULL: the lock-step entry
+static int launch_clstm(const float* G, const float* wt, const float* b1, float* state, float* hout, float* out, int H, int B, int k,
+                        int Tp, int Jp, const long long* rows, void* stream) {
     if (!G || !wt || !b1 || !state || !hout || !out || B <= 0 || k <= 0 || Tp < k + 1 || Jp < B * Tp) return IDV_EINVAL;
     if (!idv_stream_lstm_supported(H)) return IDV_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(stream_lstm_kernel, dim3((unsigned)((B + SL_SB - 1) / SL_SB), 4), dim3(4 * SL_H), 0, st, G, wt, b1, state, hout,
-                       B, k);
+    const dim3 grid((unsigned)((B + SL_SB - 1) / SL_SB), 4);
+    if (rows)
+        hipLaunchKernelGGL(stream_lstm_rows_kernel, grid, dim3(4 * SL_H), 0, st, G, wt, b1, state, hout, B, k, rows);
+    else
+        hipLaunchKernelGGL(stream_lstm_kernel, grid, dim3(4 * SL_H), 0, st, G, wt, b1, state, hout, B, k);
     int rc = idv_launch_status();
     if (rc) return rc;
     long long g = ((long long)H * B * k + 255) / 256;
     g = g > 4096 ? 4096 : (g < 1 ? 1 : g);
     hipLaunchKernelGGL(stream_lstm_combine_kernel, dim3((unsigned)g), dim3(256), 0, st, hout, H, B, k, Tp, Jp, out);
     return idv_launch_status();
+}
+
+extern "C" int idv_stream_clstm(const float* G, const float* wt, const float* b1, float* state, float* hout, float* out, int H, int B,
+                                int k, int Tp, int Jp, void* stream) {
+    return launch_clstm(G, wt, b1, state, hout, out, H, B, k, Tp, Jp, nullptr, stream);
+}
+
+extern "C" int idv_stream_clstm_rows(const float* G, const float* wt, const float* b1, float* state, float* hout, float* out, int H,
+                                     int B, int k_launch, int Tp, int Jp, const long long* rows, void* stream) {
+    if (!rows) return IDV_EINVAL;
+    return launch_clstm(G, wt, b1, state, hout, out, H, B, k_launch, Tp, Jp, rows, stream);
 }

@@ -11,6 +11,7 @@ emission bookkeeping from which every kernel launch takes its ranges.
 """
 from __future__ import annotations
 
+from collections.abc import Iterable, Sequence
 from typing import List, NamedTuple, Optional
 
 import torch
@@ -118,6 +119,109 @@ class StreamPlan:
         return self._chunks(self.total_frames(self.n), self.n)
 
 
+# One row of a launch group's table, as include/idccrn_hip.h lays it out (IDV_ROW_*)
+ROW_FIELDS = ("n_prev", "count", "L_end", "t0", "k", "parity", "e0", "e1", "p_end", "carry_in", "T_total", "y_off")
+NF = len(ROW_FIELDS)
+
+
+class Group(NamedTuple):
+    """One launch group of a sessions push: ``rows[b]`` is slot b's row of the table (ROW_FIELDS), ``k`` = max_b k_b sizes the
+    launches (Tp = k + 1), ``span`` = the longest overlap-add range of a slot, ``flush``: the group reads from the ring only."""
+    rows: List[List[int]]
+    k: int
+    span: int
+    flush: bool
+
+
+class SessionCall(NamedTuple):
+    """What one ``push(counts, end)`` does: the launch groups (push phase first; the ring update follows the push phase), the
+    number of output samples of each slot and the slots whose state is zeroed at the end."""
+    groups: List[Group]
+    m: List[int]
+    zero: List[int]
+
+
+class SessionPlan:
+    """Host-side bookkeeping of ``slots`` independent streams in one batch (no tensors): every slot owns a :class:`StreamPlan`.
+
+    Group g of the push phase holds chunk g of every slot that has one; after the ring update, the flush phase holds the flush
+    chunks of the slots that end, read from the ring only (n_prev = L).  A slot without work in a group has k = 0 and e0 = e1:
+    the kernels read and write nothing of it, and its parity does not flip, so no history has to be copied through."""
+
+    def __init__(self, slots: int, n_fft: int, hop: int, win: int, cap: int = 64):
+        if isinstance(slots, bool) or not isinstance(slots, int) or slots <= 0:
+            raise ValueError("SessionPlan: slots must be a positive int")
+        self.plans = [StreamPlan(n_fft, hop, win, cap) for _ in range(slots)]
+
+    @property
+    def positions(self) -> List[int]:
+        return [pl.n for pl in self.plans]
+
+    def snapshot(self):
+        return [(pl.n, pl.k, pl.emitted, pl.carry, pl.parity) for pl in self.plans]
+
+    def restore(self, snap):
+        for pl, v in zip(self.plans, snap):
+            pl.n, pl.k, pl.emitted, pl.carry, pl.parity = v
+
+    def check(self, counts: List[int], end: List[int]):
+        """Every guard of a push, before anything changes."""
+        for b in end:
+            L_total = self.plans[b].n + counts[b]
+            if L_total > 0:
+                self.plans[b].check_flush(L_total)
+
+    def push(self, counts: List[int], end: List[int]) -> SessionCall:
+        self.check(counts, end)
+        snap = self.snapshot()
+        try:
+            return self._push(counts, end)
+        except Exception:
+            self.restore(snap)
+            raise
+
+    def drop(self, slots: List[int]):
+        for b in slots:
+            self.plans[b].reset()
+
+    def _group(self, chunks, n_prev, counts, ends, y_off, flush: bool) -> Group:
+        rows, k, span = [], 0, 0
+        for b, pl in enumerate(self.plans):
+            c = chunks[b]
+            if c is None:       # the slot sits this group out; its row states where it stands
+                rows.append([n_prev[b], counts[b], -1, pl.k, 0, pl.parity, pl.emitted, pl.emitted, pl.half + pl.emitted + pl.carry,
+                             pl.carry, -1, y_off[b]])
+                continue
+            if c.k == 0 and c.e0 == c.e1:
+                raise RuntimeError("SessionPlan: a chunk without frames and without output")
+            L_end = ends[b] if flush else -1
+            rows.append([n_prev[b], counts[b], L_end, c.t0, c.k, c.parity, c.e0, c.e1, c.p_end, c.carry_in,
+                         pl.total_frames(L_end) if flush else -1, y_off[b]])
+            y_off[b] += c.e1 - c.e0
+            k = max(k, c.k)
+            span = max(span, c.p_end - (pl.half + c.e0))
+        return Group(rows, k, span, flush)
+
+    def _push(self, counts, end) -> SessionCall:
+        S = len(self.plans)
+        n_prev = [pl.n for pl in self.plans]
+        chunks = [pl.push(counts[b]) for b, pl in enumerate(self.plans)]
+        y_off = [0] * S
+        groups = []
+        # a call that brings samples has a push group even when no frame completes: the ring update reads its table
+        for g in range(max(max(len(c) for c in chunks), 1 if any(counts) else 0)):
+            groups.append(self._group([c[g] if g < len(c) else None for c in chunks], n_prev, counts, None, y_off, False))
+        ending = sorted(b for b in set(end) if self.plans[b].n > 0)
+        if ending:
+            L_total = [pl.n for pl in self.plans]
+            fl = [self.plans[b].flush() if b in ending else [] for b in range(S)]
+            for g in range(max(len(c) for c in fl)):
+                groups.append(self._group([c[g] if g < len(c) else None for c in fl], L_total, [0] * S, L_total, y_off, True))
+            for b in ending:
+                self.plans[b].reset()
+        return SessionCall(groups, y_off, ending)
+
+
 def check_model(model, batch) -> None:
     """The construction guards of StreamingDCCRN (host only, before any GPU work)."""
     from .model.pvae_module import DCCRN_
@@ -146,6 +250,39 @@ def check_input(x, batch: int, device=None) -> None:
         raise RuntimeError(f"push: input on {x.device}, model on {device}")
 
 
+def check_counts(counts, slots: int, n: int) -> List[int]:
+    """The guards on the per-slot sample counts of StreamingSessions.push (host only) -> list of ints."""
+    if counts is None:
+        return [n] * slots
+    if isinstance(counts, torch.Tensor):
+        if counts.is_cuda:
+            raise ValueError("counts must be a python sequence or a CPU integer tensor: they plan the launches on the host, and a "
+                             "GPU tensor would have to be fetched with a synchronisation")
+        if counts.dim() != 1 or counts.is_floating_point() or counts.is_complex() or counts.dtype == torch.bool:
+            raise ValueError("counts must be a 1-D integer tensor")
+        counts = counts.tolist()
+    elif isinstance(counts, (str, bytes)) or not isinstance(counts, Sequence):
+        raise ValueError("counts must be a python sequence or a CPU integer tensor")
+    if any(isinstance(v, bool) or not isinstance(v, int) for v in counts):
+        raise ValueError("counts must be integers (sample counts)")
+    if len(counts) != slots:
+        raise ValueError(f"{len(counts)} counts for {slots} slots")
+    for b, v in enumerate(counts):
+        if not 0 <= v <= n:
+            raise ValueError(f"counts[{b}] = {v}: a count lies in 0 .. {n}, the width of x")
+    return list(counts)
+
+
+def check_slots(which, slots: int) -> List[int]:
+    """A collection of slot numbers (``end=`` / ``drop``) -> sorted list without repeats (host only)."""
+    if isinstance(which, torch.Tensor) or isinstance(which, (str, bytes)) or not isinstance(which, Iterable):
+        raise ValueError("slots must be given as a python collection of ints")
+    which = list(which)
+    if any(isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < slots for v in which):
+        raise ValueError(f"slot numbers lie in 0 .. {slots - 1}")
+    return sorted(set(which))
+
+
 def _fold_and_slope(block):
     return block.bn.eval_fold(), block.prelu.weight.detach().reshape(1).float().contiguous()
 
@@ -154,18 +291,16 @@ class _ConvPack:
     __slots__ = ("w", "bias", "fold", "slope", "transposed", "C0", "C1", "Cout", "Fin", "Fout", "nsplit")
 
 
-class StreamingDCCRN:
-    """Lock-step streaming inference of a causal ``DCCRN_`` (DCCRN-CL) for ``batch`` signals.
+class _Launch(NamedTuple):
+    """What the network needs of a sessions launch group: k_launch and the device pointer of its row table."""
+    k: int
+    rows: object
 
-    ``push(x)`` takes the next ``n >= 0`` samples of every stream (``x``: ``[batch, n]`` float32 on the model's GPU) and returns
-    the ``[batch, m]`` output samples that became final; ``flush()`` ends the signals, returns the rest and resets the streamer for
-    the next signals.  All pushes and the flush together return exactly what ``model(x_full, train=False)[0]`` returns
-    (``hop * floor(L / hop)`` samples, eval-mode semantics with the batch norm folded).  Output sample m is returned by the push
-    that delivers input sample m + 300 ... m + 399 at n_fft 512, win 400, hop 100.
 
-    The streamer always runs in exact fp32, whatever ``ops.PRECISION`` is.  Weights are packed once, at construction: later
-    changes of the model's parameters are not seen by an existing streamer.
-    """
+class _Streamer:
+    """What both streamers share: the construction guards, the packed weights, the activation and state buffers, and the network
+    over the frames of one launch group.  A subclass supplies the framing, the conv block and the LSTM of its kind (scalars for
+    lock-step streams, a row table for sessions)."""
 
     def __init__(self, model, batch: int, frames_per_launch: int = 64, max_columns: int = 4096):
         check_model(model, batch)
@@ -299,9 +434,80 @@ class StreamingDCCRN:
         self.state = [self.h_in, self.h_dense, self.lstm_state, self.ring, self.carry] + self.h_enc + self.h_dec
 
     def reset(self):
-        """Zero every per-stream state buffer and the bookkeeping (done by construction and by flush)."""
         for t in self.state:
             t.zero_()
+
+    # ------------------------------------------------------------------ the network over one launch group
+    def _network(self, c, io):
+        """Frames -> spectrum -> encoders -> LSTM -> dense -> decoders -> mask -> windowed inverse-DFT frames (self.ifr) for the
+        c.k columns per stream of launch group c; ``io`` is what the subclass's framing needs."""
+        B, k = self.B, c.k
+        Tp = k + 1
+        Jp = Planar.jp_for(B, Tp)
+        s = stream_ptr()
+        ptr = lambda pl, plane=0: L._P(pl.buf.data_ptr() + 4 * (ops.SLACK + plane * pl.F * Jp))
+        self._frames(c, io, ptr(self.fr), Tp, Jp)
+        ops.pw_gemm(ptr(self.fr), self.win, self.dft_fwd[0], self.dft_fwd[1], 2 * self.F, B, Tp, Jp, k, ptr(self.X))
+        if self.datanorm:
+            call("idv_datanorm", ptr(self.X), p(self.mean), p(self.std), i(self.F), i(B), i(k), i(Tp), i(Jp), ptr(self.N), s)
+        # encoders
+        src, hsrc = self.N, self.h_in
+        for e, cp in enumerate(self.enc):
+            out = self.enc_out[e]
+            self._block(cp, c, ptr(src), hsrc, None, None, ptr(out), self.h_enc[e], self.h_in if e == 0 else None, Tp, Jp)
+            src, hsrc = out, self.h_enc[e]
+        # LSTM: layer-0 projection of both input parts (idv_pw_gemm as offline), then the stateful recurrence
+        H, K = self.H, self.K
+        wih, bih = self.lstm_ih
+        top = self.enc_out[-1]
+        for z in range(2):
+            ops.pw_gemm(ptr(top, z * top.C), K, wih, bih, 8 * H, B, Tp, Jp, k,
+                        L._P(self.G.data_ptr() + 4 * z * k * B * 8 * H), swap=True, ldo=8 * H)
+        self._lstm(c, ptr(self.lat), Tp, Jp)
+        # dense
+        dc, df = self.dense_out
+        for ri, pk in enumerate(self.dense):
+            ops.pw_gemm(ptr(self.lat, ri * H), H, pk[0], pk[1], dc * df, B, Tp, Jp, k, ptr(self.dense_buf, ri * dc))
+        # decoders
+        src, hsrc = self.dense_buf, self.h_dense
+        n = len(self.enc)
+        for di, cp in enumerate(self.dec):
+            out = self.dec_out[di]
+            skip = n - 1 - di if di in self.skip_to_use else None
+            x1 = ptr(self.enc_out[skip]) if skip is not None else None
+            h1 = self.h_enc[skip] if skip is not None else None
+            hout = self.h_dec[di] if di < len(self.h_dec) else None      # nothing reads the last block's history
+            self._block(cp, c, ptr(src), hsrc, x1, h1, ptr(out), hout, self.h_dense if di == 0 else None, Tp, Jp)
+            if di < len(self.h_dec):
+                src, hsrc = out, self.h_dec[di]
+        mask = self.dec_out[-1]
+        if self.recon == "mask":
+            call("idv_mask_apply", ptr(mask), ptr(self.N), i(1), i(Jp), ptr(self.pred), p(None), i(self.F), i(B), i(k), i(Tp), i(Jp), s)
+            pred = self.pred
+        else:
+            pred = mask
+        if self.datanorm:
+            call("idv_datadenorm", ptr(pred), p(self.mean), p(self.std), i(self.F), i(B), i(k), i(Tp), i(Jp), ptr(self.pred2),
+                 p(self.pc), s)
+            pred = self.pred2
+        ops.pw_gemm(ptr(pred), 2 * self.F, self.dft_inv[0], self.dft_inv[1], self.win, B, Tp, Jp, k, ptr(self.ifr))
+
+class StreamingDCCRN(_Streamer):
+    """Lock-step streaming inference of a causal ``DCCRN_`` (DCCRN-CL) for ``batch`` signals.
+
+    ``push(x)`` takes the next ``n >= 0`` samples of every stream (``x``: ``[batch, n]`` float32 on the model's GPU) and returns
+    the ``[batch, m]`` output samples that became final; ``flush()`` ends the signals, returns the rest and resets the streamer for
+    the next signals.  All pushes and the flush together return exactly what ``model(x_full, train=False)[0]`` returns
+    (``hop * floor(L / hop)`` samples, eval-mode semantics with the batch norm folded).  Output sample m is returned by the push
+    that delivers input sample m + 300 ... m + 399 at n_fft 512, win 400, hop 100.
+
+    The streamer always runs in exact fp32, whatever ``ops.PRECISION`` is.  Weights are packed once, at construction: later
+    changes of the model's parameters are not seen by an existing streamer.
+    """
+
+    def reset(self):
+        """Zero every per-stream state buffer and the bookkeeping (done by construction and by flush)."""
+        super().reset()
         self.plan.reset()
 
     # ------------------------------------------------------------------ push / flush
@@ -336,7 +542,7 @@ class StreamingDCCRN:
         T_total = self.plan.total_frames(L_end) if L_end is not None else -1
         for c in chunks:
             if c.k > 0:
-                self._network(c, x, ldx, n_new, n_prev, L_end)
+                self._network(c, (x, ldx, n_new, n_prev, L_end))
             pin = c.parity
             frames = self.ifr if c.k > 0 else None
             Tp = c.k + 1
@@ -347,64 +553,159 @@ class StreamingDCCRN:
                  stream_ptr())
         return y
 
-    def _network(self, c: Chunk, x, ldx: int, n_new: int, n_prev: int, L_end: Optional[int]):
-        B, k, P = self.B, c.k, c.parity
-        Tp = k + 1
-        Jp = Planar.jp_for(B, Tp)
-        s = stream_ptr()
-        ptr = lambda pl, plane=0: L._P(pl.buf.data_ptr() + 4 * (ops.SLACK + plane * pl.F * Jp))
+    # ------------------------------------------------------------------ the lock-step kernels of the network
+    def _frames(self, c: Chunk, io, frames, Tp: int, Jp: int):
+        x, ldx, n_new, n_prev, L_end = io
         call("idv_stream_frames", p(self.ring), i(self.plan.ring), p(x) if x is not None else p(None), ll(ldx), i(n_new), ll(n_prev),
-             ll(L_end if L_end is not None else -1), i(B), i(self.n_fft), i(self.win), i(self.hop), ll(c.t0), i(k), ptr(self.fr),
-             i(Tp), i(Jp), s)
-        ops.pw_gemm(ptr(self.fr), self.win, self.dft_fwd[0], self.dft_fwd[1], 2 * self.F, B, Tp, Jp, k, ptr(self.X))
-        if self.datanorm:
-            call("idv_datanorm", ptr(self.X), p(self.mean), p(self.std), i(self.F), i(B), i(k), i(Tp), i(Jp), ptr(self.N), s)
-        # encoders
-        src, hsrc = self.N, self.h_in
-        for e, cp in enumerate(self.enc):
-            out = self.enc_out[e]
-            self._conv_call(cp, ptr(src), hsrc[P], None, None, ptr(out), self.h_enc[e][1 - P],
-                            p(self.h_in[1 - P]) if e == 0 else p(None), B, k, Tp, Jp)
-            src, hsrc = out, self.h_enc[e]
-        # LSTM: layer-0 projection of both input parts (idv_pw_gemm as offline), then the stateful recurrence
-        H, K = self.H, self.K
-        wih, bih = self.lstm_ih
-        top = self.enc_out[-1]
-        for z in range(2):
-            ops.pw_gemm(ptr(top, z * top.C), K, wih, bih, 8 * H, B, Tp, Jp, k,
-                        L._P(self.G.data_ptr() + 4 * z * k * B * 8 * H), swap=True, ldo=8 * H)
-        call("idv_stream_clstm", p(self.G), p(self.lstm_wt), p(self.lstm_b1), p(self.lstm_state), p(self.hout), ptr(self.lat), i(H),
-             i(B), i(k), i(Tp), i(Jp), s)
-        # dense
-        dc, df = self.dense_out
-        for ri, pk in enumerate(self.dense):
-            ops.pw_gemm(ptr(self.lat, ri * H), H, pk[0], pk[1], dc * df, B, Tp, Jp, k, ptr(self.dense_buf, ri * dc))
-        # decoders
-        src, hsrc = self.dense_buf, self.h_dense
-        n = len(self.enc)
-        for di, cp in enumerate(self.dec):
-            out = self.dec_out[di]
-            skip = n - 1 - di if di in self.skip_to_use else None
-            x1 = ptr(self.enc_out[skip]) if skip is not None else None
-            h1 = self.h_enc[skip][P] if skip is not None else None
-            hout = self.h_dec[di][1 - P] if di < len(self.h_dec) else None      # nothing reads the last block's history
-            self._conv_call(cp, ptr(src), hsrc[P], x1, h1, ptr(out), hout,
-                            p(self.h_dense[1 - P]) if di == 0 else p(None), B, k, Tp, Jp)
-            if di < len(self.h_dec):
-                src, hsrc = out, self.h_dec[di]
-        mask = self.dec_out[-1]
-        if self.recon == "mask":
-            call("idv_mask_apply", ptr(mask), ptr(self.N), i(1), i(Jp), ptr(self.pred), p(None), i(self.F), i(B), i(k), i(Tp), i(Jp), s)
-            pred = self.pred
-        else:
-            pred = mask
-        if self.datanorm:
-            call("idv_datadenorm", ptr(pred), p(self.mean), p(self.std), i(self.F), i(B), i(k), i(Tp), i(Jp), ptr(self.pred2),
-                 p(self.pc), s)
-            pred = self.pred2
-        ops.pw_gemm(ptr(pred), 2 * self.F, self.dft_inv[0], self.dft_inv[1], self.win, B, Tp, Jp, k, ptr(self.ifr))
+             ll(L_end if L_end is not None else -1), i(self.B), i(self.n_fft), i(self.win), i(self.hop), ll(c.t0), i(c.k), frames,
+             i(Tp), i(Jp), stream_ptr())
+
+    def _block(self, cp: _ConvPack, c: Chunk, x0, h0, x1, h1, out, hist, x0hist, Tp: int, Jp: int):
+        """One conv block: histories are read from half c.parity of the [2][...] buffers and written to the other half."""
+        P = c.parity
+        self._conv_call(cp, x0, h0[P], x1, h1[P] if h1 is not None else None, out, hist[1 - P] if hist is not None else None,
+                        p(x0hist[1 - P]) if x0hist is not None else p(None), self.B, c.k, Tp, Jp)
+
+    def _lstm(self, c: Chunk, out, Tp: int, Jp: int):
+        call("idv_stream_clstm", p(self.G), p(self.lstm_wt), p(self.lstm_b1), p(self.lstm_state), p(self.hout), out, i(self.H),
+             i(self.B), i(c.k), i(Tp), i(Jp), stream_ptr())
 
     def _conv_call(self, cp: _ConvPack, x0, h0, x1, h1, out, hist_out, x0hist_out, B, k, Tp, Jp):
         call("idv_stream_cconv", x0, p(h0), i(cp.C0), x1 if x1 is not None else p(None), p(h1), i(cp.C1), p(cp.w), p(cp.bias),
              p(cp.fold), p(cp.slope), out, p(hist_out), x0hist_out, p(self.work), i(cp.nsplit), i(1 if cp.transposed else 0),
              i(cp.Cout), i(cp.Fin), i(B), i(k), i(Tp), i(Jp), stream_ptr())
+
+
+class StreamingSessions(_Streamer):
+    """Streaming inference of a causal ``DCCRN_`` for ``slots`` independent signals in one batch: every slot starts, receives
+    samples and ends on its own.
+
+        y, m = st.push(x, counts=None, end=())   # x: [slots, n] float32 on the model's GPU
+        st.drop(slots)                           # abandon the signals of these slots: no output, state zeroed
+        st.positions                             # samples received per slot for its current signal (host list)
+
+    ``counts[b]`` (host ints, 0 .. n; None: n for all) says how many leading samples of row b are new for slot b; nothing at or
+    past ``x[b, counts[b]]`` is read.  ``end`` names the slots whose signal ends after this call's samples ("push, then flush"):
+    over its calls a signal of L samples returns ``hop * floor(L / hop)`` samples, the slot is zeroed on the device and its next
+    samples begin a new signal.  Ending a slot that has received nothing is a no-op; ending one with 0 < L <= n_fft/2 raises
+    ``ValueError``.  Every guard runs on the host before any GPU work and before any bookkeeping changes.
+
+    ``y`` is ``[slots, max(m)]`` with ``m[b]`` valid samples in row b and zeros behind them; ``m`` comes from the host plan.
+    A slot's samples are bit-identical to what ``StreamingDCCRN(model, batch=slots)`` returns for the same signal in the same
+    slot, whatever the other slots do.  One table per launch group tells the kernels what each slot does (:class:`SessionPlan`);
+    all tables of a call go to the device in one copy from a pinned staging buffer, whose reuse waits on the event of the copy
+    that last read it (two buffers alternate, so that copy is two calls back).
+    """
+
+    def __init__(self, model, slots: int, frames_per_launch: int = 64, max_columns: int = 4096):
+        super().__init__(model, slots, frames_per_launch, max_columns)
+        if int(L.lib().idv_stream_row_fields()) != NF:
+            raise L.IdvError("libidccrn_hip.so and streaming.ROW_FIELDS disagree about the row table")
+        self.sessions = SessionPlan(slots, self.n_fft, self.hop, self.win, self.cap)
+        # state buffers as [outer][slots][inner] for idv_stream_zero_rows
+        self._zero_views = [(self.ring, 1, self.plan.ring), (self.carry, 2, self.plan.carry_cap), (self.lstm_state, 16, self.H)]
+        self._zero_views += [(h, h.numel() // slots, 1) for h in [self.h_in, self.h_dense] + self.h_enc + self.h_dec]
+        self._table = None          # device int64 buffer of the call's tables
+        self._staging = []          # [(pinned int64 buffer, event of the copy that last read it)] * 2
+        self._turn = 0
+
+    @property
+    def positions(self) -> List[int]:
+        return self.sessions.positions
+
+    def reset(self):
+        """Zero every slot's state and bookkeeping."""
+        super().reset()
+        if hasattr(self, "sessions"):
+            self.sessions.drop(range(self.B))
+
+    # ------------------------------------------------------------------ push / drop
+    def push(self, x: torch.Tensor, counts=None, end=()):
+        check_input(x, self.B, self.device)
+        n = int(x.shape[1])
+        counts = check_counts(counts, self.B, n)
+        end = check_slots(end, self.B)
+        snap = self.sessions.snapshot()
+        plan = self.sessions.push(counts, end)
+        ldy = max(plan.m)
+        x = x.float()
+        if (n > 1 and x.stride(1) != 1) or (self.B > 1 and x.stride(0) < n):       # the pitch rules of StreamingDCCRN.push
+            x = x.contiguous()
+        ldx = x.stride(0) if self.B > 1 else n
+        cap = self.plan.carry_cap
+        host = torch.tensor([v for g in plan.groups for r in g.rows for v in r] + plan.zero, dtype=torch.int64)
+        for gi, g in enumerate(plan.groups):         # a bad table never reaches a kernel
+            rc = L.lib().idv_stream_rows_check(L._P(host.data_ptr() + 8 * gi * self.B * NF), self.B, self.plan.ring,
+                                               0 if g.flush else n, self.n_fft, self.win, self.hop, cap, g.k, g.k + 1, ldy, g.span)
+            if rc != 0:
+                self.sessions.restore(snap)
+                raise L.IdvError(f"idv_stream_rows_check refused the table of launch group {gi} (status {rc})")
+        with torch.cuda.device(self.device):
+            s = stream_ptr()
+            y = torch.zeros(self.B, ldy, dtype=torch.float32, device=self.device)
+            if host.numel() == 0:
+                return y, plan.m
+            table = self._upload(host)
+            rows_of = lambda gi: L._P(table.data_ptr() + 8 * gi * self.B * NF)
+            ring_due = any(counts)
+            for gi, g in enumerate(plan.groups):
+                if g.flush and ring_due:             # the flush phase reads this call's samples from the ring
+                    call("idv_stream_ring_rows", p(self.ring), i(self.plan.ring), p(x), ll(ldx), i(n), rows_of(0), i(self.B), s)
+                    ring_due = False
+                c = _Launch(g.k, rows_of(gi))
+                if g.k > 0:
+                    self._network(c, (None, 0) if g.flush else (x if n else None, ldx))
+                Tp = g.k + 1
+                call("idv_stream_ola_rows", self.ifr.ptr() if g.k > 0 else p(None), i(Tp), i(Planar.jp_for(self.B, Tp)), p(self.carry),
+                     i(cap), c.rows, i(self.B), i(self.n_fft), i(self.win), i(self.hop), i(g.k), ll(g.span), p(y) if ldy else p(None),
+                     ll(ldy), s)
+            if ring_due:
+                call("idv_stream_ring_rows", p(self.ring), i(self.plan.ring), p(x), ll(ldx), i(n), rows_of(0), i(self.B), s)
+            self._zero(L._P(table.data_ptr() + 8 * len(plan.groups) * self.B * NF), len(plan.zero))
+        return y, plan.m
+
+    def drop(self, slots):
+        """Abandon the signals of these slots: nothing is returned for them and their state is zeroed; their next samples begin
+        a new signal."""
+        slots = check_slots(slots, self.B)
+        if not slots:
+            return
+        self.sessions.drop(slots)
+        with torch.cuda.device(self.device):
+            table = self._upload(torch.tensor(slots, dtype=torch.int64))
+            self._zero(L._P(table.data_ptr()), len(slots))
+
+    def _upload(self, host: torch.Tensor) -> torch.Tensor:
+        """One host-to-device copy of a call's tables through a pinned staging buffer."""
+        n = host.numel()
+        if self._table is None or self._table.numel() < n:
+            size = max(1 << (n - 1).bit_length(), 4 * self.B * NF)
+            self._table = torch.empty(size, dtype=torch.int64, device=self.device)
+            self._staging = [(torch.empty(size, dtype=torch.int64).pin_memory(), torch.cuda.Event()) for _ in range(2)]
+        stage, ev = self._staging[self._turn]
+        self._turn ^= 1
+        ev.synchronize()            # the copy that read this buffer two calls ago; an event never recorded does not wait
+        stage[:n].copy_(host)
+        self._table[:n].copy_(stage[:n], non_blocking=True)
+        ev.record()
+        return self._table
+
+    def _zero(self, slots_ptr, n: int):
+        if n:
+            for buf, outer, inner in self._zero_views:
+                call("idv_stream_zero_rows", p(buf), ll(outer), i(self.B), ll(inner), slots_ptr, i(n), stream_ptr())
+
+    # ------------------------------------------------------------------ the per-row kernels of the network
+    def _frames(self, c, io, frames, Tp: int, Jp: int):
+        x, ldx = io
+        call("idv_stream_frames_rows", p(self.ring), i(self.plan.ring), p(x), ll(ldx), c.rows, i(self.B), i(self.n_fft), i(self.win),
+             i(self.hop), i(c.k), frames, i(Tp), i(Jp), stream_ptr())
+
+    def _block(self, cp: _ConvPack, c, x0, h0, x1, h1, out, hist, x0hist, Tp: int, Jp: int):
+        call("idv_stream_cconv_rows", x0, p(h0), i(cp.C0), x1 if x1 is not None else p(None), p(h1), i(cp.C1), p(cp.w), p(cp.bias),
+             p(cp.fold), p(cp.slope), out, p(hist), p(x0hist), p(self.work), i(cp.nsplit), i(1 if cp.transposed else 0), i(cp.Cout),
+             i(cp.Fin), i(self.B), i(c.k), i(Tp), i(Jp), c.rows, stream_ptr())
+
+    def _lstm(self, c, out, Tp: int, Jp: int):
+        call("idv_stream_clstm_rows", p(self.G), p(self.lstm_wt), p(self.lstm_b1), p(self.lstm_state), p(self.hout), out, i(self.H),
+             i(self.B), i(c.k), i(Tp), i(Jp), c.rows, stream_ptr())

@@ -661,6 +661,58 @@ int idv_stream_ola(const float* frames, int Tp, int Jp, const float* carry_in, i
                    int n_fft, int win, int hop, long long t0, int k, long long T_total, long long e0, long long e1, long long p_end,
                    float* y, int ldy, long long y_off, void* stream);
 
+/* ---- streaming sessions: per-slot start, push length and end (stream_io.hip, stream_conv.hip, stream_lstm.hip;
+ * streaming.StreamingSessions; additive entries: IDV_ABI_VERSION is unchanged).  Each entry takes a device table
+ * rows[B][IDV_STREAM_ROW_FIELDS] of long long where the lock-step entry takes scalars; row b describes what slot b does in this
+ * launch group.  k_launch = max_b k_b sizes the planar layout (Tp >= k_launch + 1) and the pointwise kernels; the columns of a
+ * slot past its k_b hold zeros (frames) or values nobody reads.  A slot with k = 0 and e0 = e1 sits the group out: nothing of its
+ * state is read or written.  hist / carry buffers are given whole ([2 parities][...]): slot b reads half parity_b and writes half
+ * 1 - parity_b.  The arithmetic of a column is that of the lock-step entry, in the same order. */
+#define IDV_STREAM_ROW_FIELDS 12
+#define IDV_ROW_N_PREV 0    /* samples of the slot's signal before this call (held by the ring) */
+#define IDV_ROW_COUNT 1     /* new samples x[b][0 .. count-1]; nothing at or past x[b][count] is read */
+#define IDV_ROW_L_END 2     /* length of the signal when its end is known (end mirror), else -1 */
+#define IDV_ROW_T0 3        /* first frame of the group */
+#define IDV_ROW_K 4         /* frames of the group, 0 <= k <= k_launch */
+#define IDV_ROW_PARITY 5    /* history / carry half read; 1 - parity is written */
+#define IDV_ROW_E0 6        /* output samples e0 .. e1-1 become final */
+#define IDV_ROW_E1 7
+#define IDV_ROW_P_END 8     /* one past the last padded overlap-add position touched */
+#define IDV_ROW_CARRY_IN 9  /* carried overlap-add positions */
+#define IDV_ROW_T_TOTAL 10  /* frames of the whole signal when its end is known, else -1 */
+#define IDV_ROW_Y_OFF 11    /* column of y that receives sample e0 */
+int idv_stream_row_fields(void);   /* IDV_STREAM_ROW_FIELDS of the library */
+/* Host only, launches nothing: validates a HOST copy of a group's table against what idv_stream_frames and idv_stream_ola check
+ * for scalars: every sample a frame reads lies in the ring's reach or in x[b][0 .. count-1] (count <= n_x), the start mirror is
+ * there, carry_in and the outgoing carry <= cap, k <= k_launch <= Tp - 1, y_off + e1 - e0 <= ldy, p_end - (n_fft/2 + e0) <=
+ * span_max, parity in {0, 1}.  IDV_EINVAL otherwise.  Call it before the table is uploaded: the entries below cannot look. */
+int idv_stream_rows_check(const long long* host_rows, int B, int R, int n_x, int n_fft, int win, int hop, int cap, int k_launch, int Tp,
+                          long long ldy, long long span_max);
+/* idv_stream_frames with n_prev, count, L_end, t0 and k of each slot; columns tl >= k_b are zeroed.  x may be NULL when every
+ * count is 0. */
+int idv_stream_frames_rows(const float* ring, int R, const float* x, long long ldx, const long long* rows, int B, int n_fft, int win,
+                           int hop, int k_launch, float* frames, int Tp, int Jp, void* stream);
+/* Appends the count_b samples x[b][0 .. count_b-1] (x: [B][n_x], row stride ldx) to the ring of slot b at position n_prev_b. */
+int idv_stream_ring_rows(float* ring, int R, const float* x, long long ldx, int n_x, const long long* rows, int B, void* stream);
+/* idv_stream_ola per slot: carry[2][B][cap] by parity_b, t0 / k / e0 / e1 / p_end / carry_in / T_total / y_off from the row; the
+ * same order of sums (carry, then frames in increasing t) and the same double-precision envelope.  span_max >= the longest
+ * p_end - (n_fft/2 + e0) of the slots that take part. */
+int idv_stream_ola_rows(const float* frames, int Tp, int Jp, float* carry, int cap, const long long* rows, int B, int n_fft, int win,
+                        int hop, int k_launch, long long span_max, float* y, long long ldy, void* stream);
+/* idv_stream_cconv per slot: h0 / h1 / hist / x0hist are [2 parities][2][C][F][B]; x[t-1] of column 0 comes from half parity_b;
+ * column k_b - 1 of out goes to hist (or NULL) and column k_b of x0 to x0hist (or NULL), half 1 - parity_b, only when k_b > 0.
+ * nsplit and work as idv_stream_cconv with k = k_launch. */
+int idv_stream_cconv_rows(const float* x0, const float* h0, int C0, const float* x1, const float* h1, int C1, const float* w,
+                          const float* bias, const float* fold, const float* prelu_slope, float* out, float* hist, float* x0hist,
+                          float* work, int nsplit, int transposed, int Cout, int Fin, int B, int k_launch, int Tp, int Jp,
+                          const long long* rows, void* stream);
+/* idv_stream_clstm per slot (G: [2][k_launch*B][8H], hout: [4][k_launch*B][H]): steps t >= k_b leave h and c of both layers of
+ * slot b as they are; its columns of out from k_b on are zero. */
+int idv_stream_clstm_rows(const float* G, const float* wt, const float* b1, float* state, float* hout, float* out, int H, int B,
+                          int k_launch, int Tp, int Jp, const long long* rows, void* stream);
+/* buf viewed as [outer][B][inner]: zeroes the n_slots slots listed in the device array slots (each in [0, B)). */
+int idv_stream_zero_rows(float* buf, long long outer, int B, long long inner, const long long* slots, int n_slots, void* stream);
+
 /* ---- batches of utterances of different lengths (ragged.hip, reduce.hip; inference.enhance_* / compute_sisdr with `lengths`) ---
  * lens: device int32[], samples per utterance.  Utterance b has T_b = 1 + lens[b] / hop frames and hop * (T_b - 1) output samples;
  * the batch is laid out for Tmax = max_b T_b frames, Tp >= Tmax + 1.  A causal network computes frame t from frames <= t, so only

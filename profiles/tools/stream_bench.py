@@ -1,12 +1,15 @@
 """Streaming enhancement benchmark: one JSON line per batch of lock-step streams, one hop (100 samples) per push.
 
-    python profiles/tools/stream_bench.py [--batches 1,16,128,512,1024] [--seconds 2] [--catchup] [--far-seconds 3600]
+    python profiles/tools/stream_bench.py [--batches 1,16,128,512,1024] [--seconds 2] [--catchup] [--far-seconds 3600] [--sessions]
 
 Per line: device time per push (HIP events around >= --seconds of pushes after warm-up), host wall time per push (synchronised),
 the real-time factor (hop / 16 kHz = 6.25 ms over the wall time) and the algorithmic GFLOP per push (4 real products per complex
 product of every block at its kept positions, LSTM and dense, the DFTs), computed from the shapes.  --catchup adds one line of
 4000-sample pushes at B = 64 in utterances (4 s) per second.  --far-seconds S adds one line at B = 1 measured after S seconds of
 audio went through the streamer in 1 s pushes, with no flush: time per push must not depend on the stream's position.  The
+--sessions measures streaming.StreamingSessions
+instead (metric "sessions_push"): every slot active, slot b 13 * (b % 7) samples ahead of slot 0, so the slots stand at staggered
+positions and each hop push still completes one frame per slot; counts are passed as a host list on every push.  The
 streams are never flushed; pushes are column slices of a 4 s signal taken round-robin (no copy).  Full-width DCCRN-CL,
 synthetic weights.
 """
@@ -39,7 +42,7 @@ def gflop_per_frame(st) -> float:
     return 2 * macs / 1e9
 
 
-def build(B):
+def build(B, sessions=False):
     pm = importlib.import_module("i-dccrn-vae_amd.model.pvae_module")
     S = importlib.import_module("i-dccrn-vae_amd.streaming")
     from oracle import idccrn_oracle as O
@@ -47,18 +50,22 @@ def build(B):
     m = pm.DCCRN_(NFFT, HOP, np_, True, "cuda", WIN, [0, 1, 2, 3, 4, 5], "mask", False, None, None)
     m.load_state_dict(O.synth_state_dict({k: tuple(v.shape) for k, v in m.state_dict().items()}, 7))
     m = m.cuda()
-    return S.StreamingDCCRN(m, batch=B)
+    return S.StreamingSessions(m, slots=B) if sessions else S.StreamingDCCRN(m, batch=B)
 
 
-def run(B, seconds, n=HOP, far_seconds=0):
-    st = build(B)
+def run(B, seconds, n=HOP, far_seconds=0, sessions=False):
+    st = build(B, sessions)
     x = torch.randn(B, 64000, device="cuda") * 0.1
     pos = 0
+    if sessions:                                # stagger the slots: slot b starts 13 * (b % 7) samples ahead
+        st.push(x[:, :13 * 6], counts=[13 * (b % 7) for b in range(B)])
+    counts = [n] * B
 
     def push(m=n):
         nonlocal pos
         assert x.shape[1] % m == 0
-        y = st.push(x[:, pos % x.shape[1]:pos % x.shape[1] + m])
+        xs = x[:, pos % x.shape[1]:pos % x.shape[1] + m]
+        y = st.push(xs, counts)[0] if sessions else st.push(xs)
         pos += m
         return y
 
@@ -95,13 +102,15 @@ def main():
     ap.add_argument("--seconds", type=float, default=2.0)
     ap.add_argument("--catchup", action="store_true")
     ap.add_argument("--far-seconds", type=int, default=0)
+    ap.add_argument("--sessions", action="store_true")
     a = ap.parse_args()
     torch.set_grad_enabled(False)
     budget = 1e3 * HOP / SR
     for B in [int(v) for v in a.batches.split(",") if v]:
-        st, dev_ms, wall_ms, _ = run(B, a.seconds)
+        st, dev_ms, wall_ms, _ = run(B, a.seconds, sessions=a.sessions)
         gf = gflop_per_frame(st) * B
-        print(json.dumps({"metric": "stream_push", "B": B, "hop": HOP, "device_ms_per_push": round(dev_ms, 4),
+        print(json.dumps({"metric": "sessions_push" if a.sessions else "stream_push", "B": B, "hop": HOP,
+                          "device_ms_per_push": round(dev_ms, 4),
                           "wall_ms_per_push": round(wall_ms, 4), "rtf": round(budget / wall_ms, 3),
                           "device_rtf": round(budget / dev_ms, 3), "gflop_per_push": round(gf, 3),
                           "tflops_device": round(gf / dev_ms, 2), "frames_per_launch": st.cap}), flush=True)
