@@ -357,14 +357,14 @@ class LstmFn(torch.autograd.Function):
         if flags & 1:
             # input projections on the bf16 MFMA as in eval: layer 0 from the K-major split image of x, layer 1 from the
             # image of h0 the persistent recurrence writes (H = 384 / 768)
-            if p0[3] is not None:
+            if p0.wih16 is not None:
                 kimg = ops.KImage.from_planes(x.ptr(), 2 * K, x.B * x.Tp, x.Jp, xbuf.device)
-                call("idv_lstm_proj_bf16x3", kimg.ptr(), ll(kimg.lo_slots), i(K), p(p0[3]), p(p0[1]), p(work), i(H), i(x.B), i(x.T),
+                call("idv_lstm_proj_bf16x3", kimg.ptr(), ll(kimg.lo_slots), i(K), p(p0.wih16), p(p0.bih), p(work), i(H), i(x.B), i(x.T),
                      i(x.Tp), i(x.Jp), stream_ptr())
                 flags |= 2
-            wih1_16 = p1[3]
-        call("idv_clstm_fwd2", x.ptr(), i(K), p(p0[0]), p(p0[1]), p(p0[2]), p(p1[0]), p(p1[1]), p(p1[2]),
-             p(p1[4] if (ops.LSTM_STACK2 and len(p1) > 4) else None), i(H), i(x.B), i(x.T), i(x.Tp), i(x.Jp), p(work), out.ptr(),
+            wih1_16 = p1.wih16
+        call("idv_clstm_fwd2", x.ptr(), i(K), p(p0.wih), p(p0.bih), p(p0.whh), p(p1.wih), p(p1.bih), p(p1.whh),
+             p(p1.wih_hh if ops.LSTM_STACK2 else None), i(H), i(x.B), i(x.T), i(x.Tp), i(x.Jp), p(work), out.ptr(),
              i(flags), p(wih1_16), stream_ptr())
         ctx.save_for_backward(xbuf, work, *params)
         ctx.mod, ctx.geom, ctx.ogeom = mod, geom, _geom(out)

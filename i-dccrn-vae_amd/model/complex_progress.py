@@ -153,7 +153,8 @@ class _ComplexConvBase(nn.Module):
             re.weight.detach(), im.weight.detach(), re.bias.detach(), im.bias.detach(), fold, cin_used, self._transposed))
 
     def packed_gauss(self, fold: Optional[torch.Tensor], cin_used: Optional[int] = None):
-        """(wfrag3, epi, has_fold) of the three-product fp32 kernel (ops.pack_cconv_gauss); fold is applied by its epilogue."""
+        """ops.GaussPack (wfrag3, epi, has_fold, wino, tw) of the exact-fp32 kernels (ops.pack_cconv_gauss); fold is applied by their
+        epilogue."""
         re, im = self._re, self._im
         return self._cache_gauss.get((re.weight, im.weight, re.bias, im.bias, fold), cin_used, lambda: ops.pack_cconv_gauss(
             re.weight.detach(), im.weight.detach(), re.bias.detach(), im.bias.detach(), fold, cin_used, self._transposed))

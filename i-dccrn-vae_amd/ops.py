@@ -4,7 +4,7 @@ path happens inside libidccrn_hip.so."""
 from __future__ import annotations
 
 import os
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import torch
 
@@ -176,7 +176,6 @@ class KImage:
 
 def pack_pw_bf16(w):
     M, K = w.shape
-    L.lib().idv_pw_bf16_wfrag_bytes.restype = L._L
     wf = torch.empty(int(L.lib().idv_pw_bf16_wfrag_bytes(i(M), i(K))), dtype=torch.uint8, device=w.device)
     call("idv_pack_pw_bf16", p(w.contiguous()), i(M), i(K), p(wf), stream_ptr())
     return wf
@@ -210,13 +209,16 @@ def cbn_fold(moments, g_rr, g_ri, g_ii, b_r, b_i):
     return fold
 
 
+def _conv_channels(w_re, cin_used: Optional[int], transposed: bool):
+    """-> (cout, cin_total, cin_used) of a conv weight [Cout][Cin][5][2] / transposed conv weight [Cin][Cout][5][2]; cin_used None:
+    all input channels."""
+    cin_total, cout = (w_re.shape[0], w_re.shape[1]) if transposed else (w_re.shape[1], w_re.shape[0])
+    return cout, cin_total, cin_total if cin_used is None else cin_used
+
+
 def pack_cconv(w_re, w_im, b_re, b_im, fold, cin_used: Optional[int] = None, transposed=False):
     """-> (wfrag, bias) for idv_cconv2d_fwd."""
-    if transposed:
-        cin_total, cout = w_re.shape[0], w_re.shape[1]
-    else:
-        cout, cin_total = w_re.shape[0], w_re.shape[1]
-    cin_used = cin_total if cin_used is None else cin_used
+    cout, cin_total, cin_used = _conv_channels(w_re, cin_used, transposed)
     cck = L.lib().idv_cconv_cck(cin_used)
     ccp = (2 * cin_used + cck - 1) // cck * cck
     mt = mtiles_alloc(2 * cout)
@@ -239,19 +241,23 @@ def gauss_supported(c0: int, c1: int, cout: int, bwd: bool = False) -> bool:
     return bool(L.lib().idv_cconv_gauss_supported(i(c0), i(c1), i(cout)))
 
 
-def pack_cconv_gauss(w_re, w_im, b_re, b_im, fold, cin_used: Optional[int] = None, transposed=False, *, adjoint_of=None):
-    """-> (wfrag3, epi, has_fold) for idv_cconv2d_gauss_fwd.  adjoint_of=(cout_adj, cin_total_adj, cin_used_adj, adj_transposed):
+class GaussPack(NamedTuple):
+    """Operands of one exact-fp32 conv / transposed conv for the kernels that take the three-product (Gauss) form."""
+    wfrag3: torch.Tensor             # three-product fragments (idv_cconv2d_gauss_fwd)
+    epi: torch.Tensor                # epilogue table: bias and, with has_fold, the folded batch norm
+    has_fold: int
+    wino: Optional[torch.Tensor]     # Winograd fragments (idv_cconv2d_wino_fwd), None: not packed (WINO off)
+    tw: Optional[torch.Tensor]       # time-Winograd fragments of the operator's form (idv_ctconv2d_tw_fwd / idv_cconv2d_tw_fwd) or None
+
+
+def pack_cconv_gauss(w_re, w_im, b_re, b_im, fold, cin_used: Optional[int] = None, transposed=False, *, adjoint_of=None) -> GaussPack:
+    """-> GaussPack for cconv2d(gauss=) / cconv_dgrad(gauss=).  adjoint_of=(cout_adj, cin_total_adj, cin_used_adj, adj_transposed):
     the data-gradient operator (conjugate-transposed weights, no bias), arguments describing the adjoint as pack_cconv_adjoint."""
     if adjoint_of is not None:
         cout, cin_total, cin_used, transposed = adjoint_of
     else:
-        if transposed:
-            cin_total, cout = w_re.shape[0], w_re.shape[1]
-        else:
-            cout, cin_total = w_re.shape[0], w_re.shape[1]
-        cin_used = cin_total if cin_used is None else cin_used
+        cout, cin_total, cin_used = _conv_channels(w_re, cin_used, transposed)
     lib = L.lib()
-    lib.idv_cconv_gauss_wfrag_floats.restype = L._L
     wfrag = torch.empty(int(lib.idv_cconv_gauss_wfrag_floats(i(cout), i(cin_used))), dtype=torch.float32, device=w_re.device)
     epi = torch.empty(int(lib.idv_cconv_gauss_epi_rows(i(cout))) * 8, dtype=torch.float32, device=w_re.device)
     if adjoint_of is not None:
@@ -259,11 +265,11 @@ def pack_cconv_gauss(w_re, w_im, b_re, b_im, fold, cin_used: Optional[int] = Non
         # versa: same memory, the other interpretation, W_i negated (idv_pack_cconv_adjoint does the same)
         call("idv_pack_cconv_gauss", p(w_re), p(w_im), p(None), p(None), p(None), i(cout), i(cin_total), i(cin_used),
              i(1 if transposed else 0), i(1), p(wfrag), p(epi), stream_ptr())
-        return (wfrag, epi, 0) + _pack_wino_tw(w_re, w_im, cout, cin_total, cin_used, transposed, 1)
+        return GaussPack(wfrag, epi, 0, *_pack_wino_tw(w_re, w_im, cout, cin_total, cin_used, transposed, 1))
     w_re, w_im = w_re.contiguous(), w_im.contiguous()
     call("idv_pack_cconv_gauss", p(w_re), p(w_im), p(b_re.contiguous()), p(b_im.contiguous()), p(fold),
          i(cout), i(cin_total), i(cin_used), i(1 if transposed else 0), i(0), p(wfrag), p(epi), stream_ptr())
-    return (wfrag, epi, (1 if fold is not None else 0)) + _pack_wino_tw(w_re, w_im, cout, cin_total, cin_used, transposed, 0)
+    return GaussPack(wfrag, epi, 1 if fold is not None else 0, *_pack_wino_tw(w_re, w_im, cout, cin_total, cin_used, transposed, 0))
 
 
 # fp32 convs / transposed convs with Winograd-transformed frequency taps on top of the three-product form (csrc/cgemm_wino.hip):
@@ -314,8 +320,8 @@ def tw_pair_launches(reset: bool = False) -> int:
 
 
 def _pack_wino_tw(w_re, w_im, cout: int, cin_total: int, cin_used: int, transposed: bool, conj: int):
-    """-> (wino fragments | None, time-Winograd fragments | None): the tail of a gauss pack tuple (the time-Winograd fragments are
-    those of the OPERATOR's form: csrc/cgemm_tw.hip for a transposed conv, csrc/cgemm_tw2.hip for a conv)."""
+    """-> (wino fragments | None, time-Winograd fragments | None): the `wino` and `tw` fields of a GaussPack (the time-Winograd fragments
+    are those of the OPERATOR's form: csrc/cgemm_tw.hip for a transposed conv, csrc/cgemm_tw2.hip for a conv)."""
     wf = _pack_wino(w_re, w_im, cout, cin_total, cin_used, transposed, conj)
     if wf is None or not TW or (not transposed and not TW_CONV):
         return wf, None
@@ -329,17 +335,17 @@ def _pack_wino_tw(w_re, w_im, cout: int, cin_total: int, cin_used: int, transpos
 
 
 def _tw2_ok(gauss, x: Planar, c1: int, cout: int) -> bool:
-    return (gauss is not None and TW and TW_CONV and WINO and c1 == 0 and len(gauss) > 4 and gauss[4] is not None and x.Jp % 4 == 0
+    return (gauss is not None and TW and TW_CONV and WINO and c1 == 0 and gauss.tw is not None and x.Jp % 4 == 0
             and bool(L.lib().idv_cconv_tw2_supported(i(x.C), i(cout), i(x.F))))
 
 
 def _tw_ok(gauss, x: Planar, c1: int, cout: int, skip_jp: Optional[int]) -> bool:
-    return (gauss is not None and TW and WINO and len(gauss) > 4 and gauss[4] is not None and x.Jp % 4 == 0
+    return (gauss is not None and TW and WINO and gauss.tw is not None and x.Jp % 4 == 0
             and (skip_jp is None or skip_jp == x.Jp) and bool(L.lib().idv_cconv_tw_supported(i(x.C), i(c1), i(cout), i(x.F))))
 
 
 def _wino_ok(gauss, transposed: bool, x: Planar, c1: int, cout: int, skip_jp: Optional[int]) -> bool:
-    return (gauss is not None and WINO and len(gauss) > 3 and gauss[3] is not None and x.Jp % 4 == 0
+    return (gauss is not None and WINO and gauss.wino is not None and x.Jp % 4 == 0
             and (skip_jp is None or skip_jp == x.Jp)
             and bool(L.lib().idv_cconv_wino_supported(i(1 if transposed else 0), i(x.C), i(c1), i(cout), i(x.F))))
 
@@ -348,14 +354,13 @@ def pack_cconv_gauss_skip_part(w_re, w_im, c0: int):
     """Gauss operands of the SKIP half of a transposed conv [Cin][Cout][5][2] (input channels c0 .. Cin), no bias, no fold:
     the once-per-utterance addend of the repeated-skip decoder (see cconv2d(addend=...))."""
     wr, wi = w_re[c0:].contiguous(), w_im[c0:].contiguous()
-    cin, cout = wr.shape[0], wr.shape[1]
+    cout, cin, _ = _conv_channels(wr, None, True)
     lib = L.lib()
-    lib.idv_cconv_gauss_wfrag_floats.restype = L._L
     wfrag = torch.empty(int(lib.idv_cconv_gauss_wfrag_floats(i(cout), i(cin))), dtype=torch.float32, device=wr.device)
     epi = torch.empty(int(lib.idv_cconv_gauss_epi_rows(i(cout))) * 8, dtype=torch.float32, device=wr.device)
     call("idv_pack_cconv_gauss", p(wr), p(wi), p(None), p(None), p(None), i(cout), i(cin), i(cin), i(1), i(0), p(wfrag), p(epi),
          stream_ptr())
-    return (wfrag, epi, 0) + _pack_wino_tw(wr, wi, cout, cin, cin, True, 0)
+    return GaussPack(wfrag, epi, 0, *_pack_wino_tw(wr, wi, cout, cin, cin, True, 0))
 
 
 def bf16_supported(transposed: bool, c0: int, c1: int, skip_div: int, cout: int) -> bool:
@@ -364,12 +369,7 @@ def bf16_supported(transposed: bool, c0: int, c1: int, skip_div: int, cout: int)
 
 def pack_cconv_bf16(w_re, w_im, fold, cin_used: Optional[int] = None, transposed=False):
     """-> split-bf16 weight fragments (uint8 tensor) for idv_cconv2d_bf16x3_fwd."""
-    if transposed:
-        cin_total, cout = w_re.shape[0], w_re.shape[1]
-    else:
-        cout, cin_total = w_re.shape[0], w_re.shape[1]
-    cin_used = cin_total if cin_used is None else cin_used
-    L.lib().idv_cconv_bf16_wfrag_bytes.restype = L._L
+    cout, cin_total, cin_used = _conv_channels(w_re, cin_used, transposed)
     nbytes = L.lib().idv_cconv_bf16_wfrag_bytes(i(cout), i(cin_used))
     wfrag = torch.empty(int(nbytes), dtype=torch.uint8, device=w_re.device)
     call("idv_pack_cconv_bf16", p(w_re.contiguous()), p(w_im.contiguous()), p(fold), i(cout), i(cin_total), i(cin_used),
@@ -379,9 +379,7 @@ def pack_cconv_bf16(w_re, w_im, fold, cin_used: Optional[int] = None, transposed
 
 def pack_ctconv_c1(w_re, w_im, fold, cin_used: Optional[int] = None):
     """Split-bf16 fragments for the Cout = 1 transposed conv (idv_ctconv_c1_bf16x3_fwd)."""
-    cin_total = w_re.shape[0]
-    cin_used = cin_total if cin_used is None else cin_used
-    L.lib().idv_ctconv_c1_wfrag_bytes.restype = L._L
+    _, cin_total, cin_used = _conv_channels(w_re, cin_used, True)
     wfrag = torch.empty(int(L.lib().idv_ctconv_c1_wfrag_bytes(i(cin_used))), dtype=torch.uint8, device=w_re.device)
     call("idv_pack_ctconv_c1_bf16", p(w_re.contiguous()), p(w_im.contiguous()), p(fold), i(cin_total), i(cin_used), p(wfrag),
          stream_ptr())
@@ -392,10 +390,7 @@ def ctconv_c1(x, wfrag_c1, bias, *, slope=None, skip=None) -> Planar:
     """Causal transposed conv with one output channel on the split-bf16 path; x / skip both Planar or both Image."""
     out = Planar.empty(1, 2 * x.F - 1, x.B, x.T, x.Tp, x.buf.device)
     c1 = skip.C if skip is not None else 0
-    if LAUNCH_LOG is not None:
-        macs = 4 * (x.C + c1) * 10 * x.B * x.T * x.F
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    timer = _launch_timer()
     if isinstance(x, Image):
         if skip is not None and not isinstance(skip, Image):
             raise RuntimeError("ctconv_c1: x and skip must have the same format")
@@ -406,9 +401,8 @@ def ctconv_c1(x, wfrag_c1, bias, *, slope=None, skip=None) -> Planar:
         call("idv_ctconv_c1_bf16x3_fwd", x.ptr(), i(x.C), skip.ptr() if skip is not None else p(None), i(c1),
              i(skip.Jp if skip is not None else 0), p(wfrag_c1), p(bias), p(slope), out.ptr(), i(x.F), i(x.B), i(x.Tp), i(x.Jp),
              i(x.T), stream_ptr())
-    if LAUNCH_LOG is not None:
-        ev1.record()
-        LAUNCH_LOG.append((-98 if isinstance(x, Image) else -99, macs, ev0, ev1))
+    if timer is not None:
+        _launch_logged(timer, -98 if isinstance(x, Image) else -99, 4 * (x.C + c1) * 10 * x.B * x.T * x.F)
     return out
 
 
@@ -427,6 +421,39 @@ def pack_pw(w, bias):
 # When set to a list, every cconv2d launch appends (config id, algorithmic MACs, start event, end event);
 # bench.py uses it to time the dominant kernel with events on the launching stream.
 LAUNCH_LOG = None
+
+
+def _launch_timer():
+    """Start of the timed span of one LAUNCH_LOG entry: its (start, end) events, the start recorded on the current stream; None (and
+    nothing created) when launches are not logged."""
+    if LAUNCH_LOG is None:
+        return None
+    timer = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    timer[0].record()
+    return timer
+
+
+def _launch_logged(timer, cfg: int, macs: int):
+    """End of the span `timer` started: LAUNCH_LOG gets (config id, algorithmic MACs, start event, end event)."""
+    timer[1].record()
+    LAUNCH_LOG.append((cfg, macs, timer[0], timer[1]))
+
+
+def _conv_macs(cin: int, cout: int, x, transposed: bool, Fout: int) -> int:
+    """Algorithmic MACs of a complex conv: 4 real convolutions of the reference, kernel 5x2, per kept output position
+    (transposed: per INPUT position, each input feeds 5x2 taps)."""
+    return 4 * cin * cout * 10 * x.B * x.T * (x.F if transposed else Fout)
+
+
+def _conv_geometry(F: int, T: int, transposed: bool, causal: bool, adjoint: bool = False):
+    """-> (Fout, t_out, tshift) of a conv / transposed conv over F rows and T frames.  tshift -1: the time taps read (x[t-1], x[t]);
+    0: (x[t], x[t+1]).  adjoint: the operator is the data gradient of a block; of a causal one it has the time taps reversed (tshift 0)
+    and keeps all T frames (x[T] is the next utterance's zero guard column), of a non-causal one it is the operator's own form."""
+    Fout = 2 * F - 1 if transposed else (F - 1) // 2 + 1
+    t_out = T if causal else (T + 1 if transposed else T - 1)
+    tshift = -1 if (causal or transposed) else 0
+    return Fout, t_out, 0 if (adjoint and causal) else tshift
+
 
 # Eval-mode sub-batch pipelining (model/pvae_module.py DCCRN_.forward): number of HIP streams a batch is split over.
 # Concurrent queues are only safe because the library is built without packed-fp32 VALU code (__graft_entry__.build,
@@ -546,17 +573,9 @@ def cconv2d(x: Planar, wfrag, bias, cout: int, *, transposed=False, causal=True,
             addend: Optional[Planar] = None, addend_div: int = 1):
     """(causal_)ComplexConv2d / (causal_)ComplexConvTranspose2d forward on planar activations.
     image="also" / "only": the exact-fp32 kernel additionally / only writes a split-bf16 image -> (Planar|None, Image)."""
-    Fout = 2 * x.F - 1 if transposed else (x.F - 1) // 2 + 1
-    if causal:
-        t_out = x.T
-    else:
-        t_out = x.T + 1 if transposed else x.T - 1
-    tshift = -1 if (causal or transposed) else 0
-    if adjoint_time:
-        # transposed conv reading (x[t+1], x[t]): with conjugate-transposed weights the adjoint (data gradient) of
-        # the causal conv; all T frames are produced (x[T] is the next utterance's zero guard column)
-        assert transposed and causal
-        tshift = 0
+    # adjoint_time: the transposed conv reading (x[t+1], x[t]); with conjugate-transposed weights the data gradient of the causal conv
+    assert not adjoint_time or (transposed and causal)
+    Fout, t_out, tshift = _conv_geometry(x.F, x.T, transposed, causal, adjoint_time)
     if out is None and image != "only":
         out = Planar.empty(cout, Fout, x.B, t_out, x.Tp, x.buf.device)
     c1 = skip.C if skip is not None else 0
@@ -568,70 +587,78 @@ def cconv2d(x: Planar, wfrag, bias, cout: int, *, transposed=False, causal=True,
              img.ptr(), ll(img.lo_off), i(1 if transposed else 0), i(tshift), i(cout), i(x.F), i(x.B), i(x.Tp), i(x.Jp),
              i(t_out), stream_ptr())
         return out, img
-    if LAUNCH_LOG is not None:
-        cfg = L.lib().idv_cconv_config(i(1 if transposed else 0), i(x.C + c1), i(cout), i(x.F))
-        # algorithmic MACs: 4 real convolutions of the reference, kernel 5x2, per kept output position
-        # (transposed: per INPUT position, each input feeds 5x2 taps)
-        pos = x.B * x.T * (x.F if transposed else Fout)
-        macs = 4 * (x.C + c1) * cout * 10 * pos
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    timer = _launch_timer()
     if wfrag_bf16 is not None:
-        if LAUNCH_LOG is not None:
-            cfg = -(1000000 + L.lib().idv_cconv_bf16_config(i(1 if transposed else 0), i(cout), i(x.F)))
         swork = _stats_work(stats, cout)
         call("idv_cconv2d_bf16x3_fwd", x.ptr(), i(x.C), skip.ptr() if skip is not None else p(None), i(c1),
              i(skip.Jp if skip is not None else 0), i(skip_div), p(wfrag_bf16), p(bias), p(slope), out.ptr(), p(stats), p(swork),
              i(STATS_REP), i(1 if transposed else 0), i(tshift), i(cout), i(x.F), i(x.B), i(x.Tp), i(x.Jp), i(t_out), stream_ptr())
-        if LAUNCH_LOG is not None:
-            ev1.record()
-            LAUNCH_LOG.append((cfg, macs, ev0, ev1))
-        return out
-    if transposed and skip_div == 1 and _tw_ok(gauss, x, c1, cout, skip.Jp if skip is not None else None):
-        # fp32: Winograd-transformed frequency and time taps (csrc/cgemm_tw.hip)
-        if LAUNCH_LOG is not None:
+        cfg = _bf16_cfg(transposed, cout, x.F) if timer is not None else None
+    else:
+        cfg = _cconv2d_fp32(x, out, wfrag, bias, gauss, cout, transposed=transposed, tshift=tshift, t_out=t_out,
+                            has_fold=gauss.has_fold if gauss is not None else 0, stats_rep=STATS_REP, slope=slope, skip=skip,
+                            skip_div=skip_div, stats=stats, addend=addend, addend_div=addend_div)
+    if timer is not None:
+        _launch_logged(timer, cfg, _conv_macs(x.C + c1, cout, x, transposed, Fout))
+    return out
+
+
+def _bf16_cfg(transposed: bool, cout: int, F: int) -> int:
+    """LAUNCH_LOG id of a launch of idv_cconv2d_bf16x3_fwd."""
+    return -(1000000 + L.lib().idv_cconv_bf16_config(i(1 if transposed else 0), i(cout), i(F)))
+
+
+def _cconv2d_fp32(x: Planar, out: Planar, wfrag, bias, gauss: Optional[GaussPack], cout: int, *, transposed: bool, tshift: int,
+                  t_out: int, has_fold: int, stats_rep: int, slope, skip: Optional[Planar], skip_div: int, stats,
+                  addend: Optional[Planar], addend_div: int) -> Optional[int]:
+    """The one launch of an exact-fp32 conv / transposed conv, forward or data gradient, on the first kernel of the ladder
+    time-Winograd -> Winograd -> three products -> plain  that serves it (gauss None: the plain kernel on wfrag / bias).  has_fold and
+    stats_rep are the caller's to say: the data gradient runs without the pack's fold and without moment sums.
+    -> the LAUNCH_LOG id of the kernel taken (None when launches are not logged)."""
+    log = LAUNCH_LOG is not None
+    cfg = None
+    c1 = skip.C if skip is not None else 0
+    skip_jp = skip.Jp if skip is not None else None
+    swork = _stats_work(stats, cout)
+    if transposed and skip_div == 1 and _tw_ok(gauss, x, c1, cout, skip_jp):
+        # Winograd-transformed frequency and time taps (csrc/cgemm_tw.hip)
+        if log:
             cfg = TW_CFG + (1 if tshift else 0)
-        swork = _stats_work(stats, cout)
         _sync_tw_pair()
-        call("idv_ctconv2d_tw_fwd", x.ptr(), i(x.C), skip.ptr() if skip is not None else p(None), i(c1), p(gauss[4]), p(gauss[1]),
-             i(gauss[2]), p(slope), out.ptr(), p(stats), p(swork), i(STATS_REP), i(tshift), i(cout), i(x.F), i(x.B), i(x.Tp), i(x.Jp),
+        call("idv_ctconv2d_tw_fwd", x.ptr(), i(x.C), skip.ptr() if skip is not None else p(None), i(c1), p(gauss.tw), p(gauss.epi),
+             i(has_fold), p(slope), out.ptr(), p(stats), p(swork), i(stats_rep), i(tshift), i(cout), i(x.F), i(x.B), i(x.Tp), i(x.Jp),
              i(t_out), addend.ptr() if addend is not None else p(None), i(addend_div), i(addend.Jp if addend is not None else 0),
              stream_ptr())
     elif not transposed and addend is None and _tw2_ok(gauss, x, c1, cout):
-        # fp32 conv: Winograd-transformed frequency and time taps (csrc/cgemm_tw2.hip)
-        if LAUNCH_LOG is not None:
+        # conv: Winograd-transformed frequency and time taps (csrc/cgemm_tw2.hip)
+        if log:
             cfg = TW_CFG + 2 + (1 if tshift else 0)
-        swork = _stats_work(stats, cout)
         _sync_tw_pair()
-        call("idv_cconv2d_tw_fwd", x.ptr(), i(x.C), p(gauss[4]), p(gauss[1]), i(gauss[2]), p(slope), out.ptr(), p(stats), p(swork),
-             i(STATS_REP), i(tshift), i(cout), i(x.F), i(x.B), i(x.Tp), i(x.Jp), i(t_out), stream_ptr())
-    elif skip_div == 1 and _wino_ok(gauss, transposed, x, c1, cout, skip.Jp if skip is not None else None):
-        # fp32: Winograd-transformed frequency taps on top of the three products (csrc/cgemm_wino.hip)
-        if LAUNCH_LOG is not None:
+        call("idv_cconv2d_tw_fwd", x.ptr(), i(x.C), p(gauss.tw), p(gauss.epi), i(has_fold), p(slope), out.ptr(), p(stats), p(swork),
+             i(stats_rep), i(tshift), i(cout), i(x.F), i(x.B), i(x.Tp), i(x.Jp), i(t_out), stream_ptr())
+    elif skip_div == 1 and _wino_ok(gauss, transposed, x, c1, cout, skip_jp):
+        # Winograd-transformed frequency taps on top of the three products (csrc/cgemm_wino.hip)
+        if log:
             cfg = WINO_CFG + (1000 if transposed else 0) + L.lib().idv_cconv_wino_config(i(1 if transposed else 0), i(x.C + c1), i(cout))
-        swork = _stats_work(stats, cout)
-        call("idv_cconv2d_wino_fwd", x.ptr(), i(x.C), skip.ptr() if skip is not None else p(None), i(c1), p(gauss[3]), p(gauss[1]),
-             i(gauss[2]), p(slope), out.ptr(), p(stats), p(swork), i(STATS_REP), i(1 if transposed else 0), i(tshift), i(cout), i(x.F),
+        call("idv_cconv2d_wino_fwd", x.ptr(), i(x.C), skip.ptr() if skip is not None else p(None), i(c1), p(gauss.wino), p(gauss.epi),
+             i(has_fold), p(slope), out.ptr(), p(stats), p(swork), i(stats_rep), i(1 if transposed else 0), i(tshift), i(cout), i(x.F),
              i(x.B), i(x.Tp), i(x.Jp), i(t_out), addend.ptr() if addend is not None else p(None), i(addend_div),
              i(addend.Jp if addend is not None else 0), stream_ptr())
     elif gauss is not None:
-        # fp32: three real products per complex product (csrc/cgemm_gauss.hip); gauss = (wfrag3, epi, has_fold[, wino fragments])
-        if LAUNCH_LOG is not None:
+        # three real products per complex product (csrc/cgemm_gauss.hip)
+        if log:
             cfg = L.lib().idv_cconv_gauss_config(i(1 if transposed else 0), i(x.C + c1), i(cout), i(x.F))
-        swork = _stats_work(stats, cout)
         call("idv_cconv2d_gauss_fwd", x.ptr(), i(x.C), skip.ptr() if skip is not None else p(None), i(c1),
-             i(skip.Jp if skip is not None else 0), i(skip_div), p(gauss[0]), p(gauss[1]), i(gauss[2]), p(slope), out.ptr(),
-             p(stats), p(swork), i(STATS_REP), i(1 if transposed else 0), i(tshift), i(cout), i(x.F), i(x.B), i(x.Tp), i(x.Jp), i(t_out),
+             i(skip.Jp if skip is not None else 0), i(skip_div), p(gauss.wfrag3), p(gauss.epi), i(has_fold), p(slope), out.ptr(),
+             p(stats), p(swork), i(stats_rep), i(1 if transposed else 0), i(tshift), i(cout), i(x.F), i(x.B), i(x.Tp), i(x.Jp), i(t_out),
              addend.ptr() if addend is not None else p(None), i(addend_div), i(addend.Jp if addend is not None else 0), stream_ptr())
     else:
-        swork = _stats_work(stats, cout)
+        if log:
+            cfg = L.lib().idv_cconv_config(i(1 if transposed else 0), i(x.C + c1), i(cout), i(x.F))
         call("idv_cconv2d_fwd", x.ptr(), i(x.C), skip.ptr() if skip is not None else p(None), i(c1),
              i(skip.Jp if skip is not None else 0), i(skip_div), p(wfrag), p(bias), p(slope), out.ptr(), p(stats), p(swork),
-             i(STATS_REP), i(1 if transposed else 0), i(tshift), i(cout), i(x.F), i(x.B), i(x.Tp), i(x.Jp), i(t_out), stream_ptr())
-    if LAUNCH_LOG is not None:
-        ev1.record()
-        LAUNCH_LOG.append((cfg, macs, ev0, ev1))
-    return out
+             i(stats_rep), i(1 if transposed else 0), i(tshift), i(cout), i(x.F), i(x.B), i(x.Tp), i(x.Jp), i(t_out), stream_ptr())
+    return cfg
 
 
 def cconv2d_img(x, wfrag_bf16, bias, cout: int, *, transposed=False, causal=True, slope=None, skip=None,
@@ -642,51 +669,40 @@ def cconv2d_img(x, wfrag_bf16, bias, cout: int, *, transposed=False, causal=True
     src_img = isinstance(x, Image)
     if skip is not None and isinstance(skip, Image) != src_img:
         raise RuntimeError("cconv2d_img: x and skip must have the same format")
-    Fout = 2 * x.F - 1 if transposed else (x.F - 1) // 2 + 1
-    t_out = x.T if causal else (x.T + 1 if transposed else x.T - 1)
-    tshift = -1 if (causal or transposed) else 0
-    if adjoint:
-        assert causal
-        tshift, t_out = 0, x.T
+    assert causal or not adjoint
+    Fout, t_out, tshift = _conv_geometry(x.F, x.T, transposed, causal, adjoint)
     dev = x.buf.device
     outp = Planar.empty(cout, Fout, x.B, t_out, x.Tp, dev) if want_planar else None
     outi = Image.empty(cout, Fout, x.B, t_out, x.Tp, dev) if want_image else None
     c1 = skip.C if skip is not None else 0
-    if LAUNCH_LOG is not None:
-        cfg = -(100000000 + L.lib().idv_cconv_img_config(i(1 if src_img else 0), i(1 if transposed else 0), i(x.C + c1),
-                                                          i(cout), i(x.F)))
-        pos = x.B * x.T * (x.F if transposed else Fout)
-        macs = 4 * (x.C + c1) * cout * 10 * pos
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    timer = _launch_timer()
     call("idv_cconv2d_img_fwd", i(1 if src_img else 0), x.ptr(), ll(x.lo_slots if src_img else 0), i(x.C),
          skip.ptr() if skip is not None else p(None), ll(skip.lo_slots if (skip is not None and src_img) else 0), i(c1),
          p(wfrag_bf16), p(bias), p(slope), outp.ptr() if outp is not None else p(None),
          outi.ptr() if outi is not None else p(None), ll(outi.lo_off if outi is not None else 0),
          i(1 if transposed else 0), i(tshift), i(cout), i(x.F), i(x.B), i(x.Tp), i(x.Jp), i(t_out), stream_ptr())
-    if LAUNCH_LOG is not None:
-        ev1.record()
-        LAUNCH_LOG.append((cfg, macs, ev0, ev1))
+    if timer is not None:
+        _launch_logged(timer, _img_cfg(src_img, transposed, x.C + c1, cout, x.F), _conv_macs(x.C + c1, cout, x, transposed, Fout))
     return outp, outi
+
+
+def _img_cfg(src_img: bool, transposed: bool, cin: int, cout: int, F: int) -> int:
+    """LAUNCH_LOG id of a launch of the split-image conv kernels."""
+    return -(100000000 + L.lib().idv_cconv_img_config(i(1 if src_img else 0), i(1 if transposed else 0), i(cin), i(cout), i(F)))
 
 
 def cconv2d_img_train(x: Image, wfrag_bf16, bias, cout: int, stats, *, transposed=False, skip: Optional[Image] = None) -> Planar:
     """Training forward of a causal conv block from split images: planar fp32 y + the batch-norm moments (`stats`)."""
-    Fout = 2 * x.F - 1 if transposed else (x.F - 1) // 2 + 1
+    Fout, _, _ = _conv_geometry(x.F, x.T, transposed, True)
     out = Planar.empty(cout, Fout, x.B, x.T, x.Tp, x.buf.device)
     c1 = skip.C if skip is not None else 0
-    if LAUNCH_LOG is not None:
-        cfg = -(100000000 + L.lib().idv_cconv_img_config(i(1), i(1 if transposed else 0), i(x.C + c1), i(cout), i(x.F)))
-        macs = 4 * (x.C + c1) * cout * 10 * x.B * x.T * (x.F if transposed else Fout)
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    timer = _launch_timer()
     swork = _stats_work(stats, cout)
     call("idv_cconv2d_img_train_fwd", x.ptr(), ll(x.lo_slots), i(x.C), skip.ptr() if skip is not None else p(None),
          ll(skip.lo_slots if skip is not None else 0), i(c1), p(wfrag_bf16), p(bias), out.ptr(), p(stats), p(swork), i(STATS_REP),
          i(1 if transposed else 0), i(cout), i(x.F), i(x.B), i(x.Tp), i(x.Jp), i(x.T), stream_ptr())
-    if LAUNCH_LOG is not None:
-        ev1.record()
-        LAUNCH_LOG.append((cfg, macs, ev0, ev1))
+    if timer is not None:
+        _launch_logged(timer, _img_cfg(True, transposed, x.C + c1, cout, x.F), _conv_macs(x.C + c1, cout, x, transposed, Fout))
     return out
 
 
@@ -696,8 +712,17 @@ def pw_gemm(x_ptr, K: int, wfrag, bias, M: int, B: int, Tp: int, Jp: int, t_vali
          i(1 if swap else 0), i(ldo), stream_ptr())
 
 
-def pack_lstm(sd_get, H: int, K: int, layer: int, device):
-    """sd_get(name) -> tensor for names like 'lstm_re.weight_ih_l0'.  Returns (wih, bih, whh)."""
+class LstmPack(NamedTuple):
+    """Packed weights of one layer of a ComplexLSTM (both parts)."""
+    wih: torch.Tensor                # W_ih fragments for idv_pw_gemm
+    bih: torch.Tensor                # b_ih + b_hh
+    whh: torch.Tensor                # W_hh in the recurrence's fragment order
+    wih16: Optional[torch.Tensor]    # split-bf16 W_ih (bf16x3 input projection) or None
+    wih_hh: Optional[torch.Tensor]   # layer 1, H = 128: W_ih in the recurrence's fragment order (two-layer launch) or None
+
+
+def pack_lstm(sd_get, H: int, K: int, layer: int, device) -> LstmPack:
+    """sd_get(name) -> tensor for names like 'lstm_re.weight_ih_l0'."""
     g = lambda n: sd_get(n).contiguous()
     l = layer
     M = 8 * H
@@ -712,7 +737,6 @@ def pack_lstm(sd_get, H: int, K: int, layer: int, device):
     call("idv_pack_lstm_hh", p(g(f"lstm_re.weight_hh_l{l}")), p(g(f"lstm_im.weight_hh_l{l}")), i(H), p(whh), stream_ptr())
     wih16 = None
     if L.lib().idv_lstm_proj_bf16_supported(i(H), i(K)) and (layer == 0 or (4 * H) % 256 == 0):
-        L.lib().idv_lstm_ih_bf16_bytes.restype = L._L
         wih16 = torch.empty(int(L.lib().idv_lstm_ih_bf16_bytes(i(H), i(K))), dtype=torch.uint8, device=device)
         call("idv_pack_lstm_ih_bf16", p(g(f"lstm_re.weight_ih_l{l}")), p(g(f"lstm_im.weight_ih_l{l}")), i(H), i(K), p(wih16),
              stream_ptr())
@@ -722,7 +746,7 @@ def pack_lstm(sd_get, H: int, K: int, layer: int, device):
     if layer == 1 and K == H and H == 128:
         wih_hh = torch.empty(4 * 4 * H * H, dtype=torch.float32, device=device)
         call("idv_pack_lstm_hh", p(g(f"lstm_re.weight_ih_l{l}")), p(g(f"lstm_im.weight_ih_l{l}")), i(H), p(wih_hh), stream_ptr())
-    return wih, bih, whh, wih16, wih_hh
+    return LstmPack(wih, bih, whh, wih16, wih_hh)
 
 
 # bf16x3 mode, H = 384 / 768: one persistent cooperative launch per layer (csrc/lstm_pers.hip) instead of one launch per
@@ -732,7 +756,7 @@ LSTM_PERSISTENT = os.environ.get("IDV_LSTM_PERSISTENT", "1") != "0"
 LSTM_STACK2 = os.environ.get("IDV_LSTM_STACK2", "1") != "0"
 
 
-def clstm(x: Planar, packed0, packed1, H: int) -> Planar:
+def clstm(x: Planar, packed0: LstmPack, packed1: LstmPack, H: int) -> Planar:
     """ComplexLSTM forward: x planar with C*F = K feature planes per part -> planar [2][H][Jp] (F = 1)."""
     K = x.C * x.F
     out = Planar.empty(H, 1, x.B, x.T, x.Tp, x.buf.device)
@@ -741,15 +765,15 @@ def clstm(x: Planar, packed0, packed1, H: int) -> Planar:
     flags = 1 if PRECISION == "bf16x3" else 0
     if not LSTM_PERSISTENT:
         flags |= 8
-    if (flags & 1) and packed0[3] is not None:
+    if (flags & 1) and packed0.wih16 is not None:
         # layer-0 input projection on the bf16 MFMA: K-major split image of the 2K input planes, then G into `work`
         kimg = KImage.from_planes(x.ptr(), 2 * K, x.B * x.Tp, x.Jp, x.buf.device)
-        call("idv_lstm_proj_bf16x3", kimg.ptr(), ll(kimg.lo_slots), i(K), p(packed0[3]), p(packed0[1]), p(work), i(H), i(x.B),
+        call("idv_lstm_proj_bf16x3", kimg.ptr(), ll(kimg.lo_slots), i(K), p(packed0.wih16), p(packed0.bih), p(work), i(H), i(x.B),
              i(x.T), i(x.Tp), i(x.Jp), stream_ptr())
         flags |= 2
-    call("idv_clstm_fwd2", x.ptr(), i(K), p(packed0[0]), p(packed0[1]), p(packed0[2]), p(packed1[0]), p(packed1[1]),
-         p(packed1[2]), p(packed1[4] if (LSTM_STACK2 and len(packed1) > 4) else None), i(H), i(x.B), i(x.T), i(x.Tp), i(x.Jp), p(work), out.ptr(),
-         i(flags), p(packed1[3] if (flags & 1) else None), stream_ptr())
+    call("idv_clstm_fwd2", x.ptr(), i(K), p(packed0.wih), p(packed0.bih), p(packed0.whh), p(packed1.wih), p(packed1.bih),
+         p(packed1.whh), p(packed1.wih_hh if LSTM_STACK2 else None), i(H), i(x.B), i(x.T), i(x.Tp), i(x.Jp), p(work), out.ptr(),
+         i(flags), p(packed1.wih16 if (flags & 1) else None), stream_ptr())
     return out
 
 
@@ -1046,7 +1070,6 @@ def ckl(q1: Planar, off1, q2: Optional[Planar], off2, zdim: int, eps: float) -> 
 def mi_estimate(lat: Planar, off, z: Planar, zdim: int, ns: int, eps: float):
     """Minibatch mutual information (pretrain_pvaes_loss.py:129-159) -> (scalar, work); `work` holds d MI / d log q for mi_bwd."""
     lib = L.lib()
-    lib.idv_mi_work_floats.restype = L._L
     if (z.C, z.B, z.T, z.Tp) != (zdim, lat.B * ns, lat.T, lat.Tp):
         raise ValueError(f"mutual_information: samples {(z.C, z.B, z.T)} do not belong to a posterior {(zdim, lat.B, lat.T)} x {ns}")
     work = torch.empty(int(lib.idv_mi_work_floats(i(lat.B), i(ns), i(lat.T), i(zdim))), dtype=torch.float32, device=lat.buf.device)
@@ -1086,13 +1109,11 @@ def cbn_apply(act: Planar, fold: torch.Tensor, slope=None):
 
 # ----------------------------------------------------------------------------- backward (gradient) operators
 # Thin wrappers over the idv_*_bwd entries; autograd.py strings them into torch.autograd.Function classes.
-_LL = L._L
 
 
 def _ll_fn(name):
-    fn = getattr(L.lib(), name)
-    fn.restype = _LL
-    return fn
+    """A size query of the library by name; _lib.lib() has set its `long long` return type from the header's prototype."""
+    return getattr(L.lib(), name)
 
 
 def like(x: Planar, C: Optional[int] = None, F: Optional[int] = None, zero=False) -> Planar:
@@ -1118,7 +1139,6 @@ def pack_cconv_adjoint(w_re, w_im, cout: int, cin_total: int, cin_used: int, tra
 
 def pack_cconv_bf16_adjoint(w_re, w_im, cout: int, cin_total: int, cin_used: int, transposed: bool):
     """Split-bf16 fragments of the adjoint operator (bf16x3 training), see idv_pack_cconv_bf16_adjoint."""
-    L.lib().idv_cconv_bf16_wfrag_bytes.restype = L._L
     wfrag = torch.empty(int(L.lib().idv_cconv_bf16_wfrag_bytes(i(cout), i(cin_used))), dtype=torch.uint8, device=w_re.device)
     call("idv_pack_cconv_bf16_adjoint", p(w_re), p(w_im), i(cout), i(cin_total), i(cin_used), i(1 if transposed else 0),
          p(wfrag), stream_ptr())
@@ -1141,61 +1161,25 @@ def cconv_dgrad(dy: Planar, wfrag, bias, cout_adj: int, fwd_transposed: bool, ca
     (transposed conv reading (dy[t+1], dy[t]) / conv reading (dy[t], dy[t+1]); all T frames kept: column T+1 is the next
     utterance's zero guard column).  wfrag_bf16: run it on the split-bf16 kernel instead (bf16x3 training mode)."""
     adj_transposed = not fwd_transposed
-    Fout = 2 * dy.F - 1 if adj_transposed else (dy.F - 1) // 2 + 1
     # causal blocks: time taps reversed (tshift 0), T frames in, T frames out.  Non-causal blocks (padding (2, 0)): the adjoint of
     # the conv (T -> T - 1 frames) is the transposed conv's own tap order (dx[t] = W0' dy[t] + W1' dy[t-1], tshift -1) on T frames;
     # the adjoint of the transposed conv (T -> T + 1) is the non-causal conv's (dx[t] = W0' dy[t] + W1' dy[t+1], tshift 0) on T frames
-    if causal:
-        tshift_adj, t_out = 0, dy.T
-    elif adj_transposed:
-        tshift_adj, t_out = -1, dy.T + 1
-    else:
-        tshift_adj, t_out = 0, dy.T - 1
+    Fout, t_out, tshift_adj = _conv_geometry(dy.F, dy.T, adj_transposed, causal, adjoint=True)
     if t_out + 1 > dy.Tp:
         raise RuntimeError("cconv_dgrad: the input of the block had more frames than the buffer's columns per utterance")
     out = Planar.empty(cout_adj, Fout, dy.B, t_out, dy.Tp, dy.buf.device)
-    if LAUNCH_LOG is not None:
-        cfg = L.lib().idv_cconv_config(i(1 if adj_transposed else 0), i(dy.C), i(cout_adj), i(dy.F))
-        macs = 4 * dy.C * cout_adj * 10 * dy.B * dy.T * (dy.F if adj_transposed else Fout)
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        if wfrag_bf16 is not None:
-            cfg = -(1000000 + L.lib().idv_cconv_bf16_config(i(1 if adj_transposed else 0), i(cout_adj), i(dy.F)))
-        ev0.record()
-    if wfrag_bf16 is None and adj_transposed and _tw_ok(gauss, dy, 0, cout_adj, None):
-        if LAUNCH_LOG is not None:
-            cfg = TW_CFG + (1 if tshift_adj else 0)
-        _sync_tw_pair()
-        call("idv_ctconv2d_tw_fwd", dy.ptr(), i(dy.C), p(None), i(0), p(gauss[4]), p(gauss[1]), i(0), p(None), out.ptr(), p(None), p(None),
-             i(0), i(tshift_adj), i(cout_adj), i(dy.F), i(dy.B), i(dy.Tp), i(dy.Jp), i(t_out), p(None), i(1), i(0), stream_ptr())
-    elif wfrag_bf16 is None and not adj_transposed and _tw2_ok(gauss, dy, 0, cout_adj):
-        if LAUNCH_LOG is not None:
-            cfg = TW_CFG + 2 + (1 if tshift_adj else 0)
-        _sync_tw_pair()
-        call("idv_cconv2d_tw_fwd", dy.ptr(), i(dy.C), p(gauss[4]), p(gauss[1]), i(0), p(None), out.ptr(), p(None), p(None), i(0),
-             i(tshift_adj), i(cout_adj), i(dy.F), i(dy.B), i(dy.Tp), i(dy.Jp), i(t_out), stream_ptr())
-    elif wfrag_bf16 is None and _wino_ok(gauss, adj_transposed, dy, 0, cout_adj, None):
-        # the data gradient on the Winograd kernels (csrc/cgemm_wino.hip): adjoint of a conv = a transposed conv and vice versa
-        if LAUNCH_LOG is not None:
-            cfg = WINO_CFG + (1000 if adj_transposed else 0) + L.lib().idv_cconv_wino_config(i(1 if adj_transposed else 0), i(dy.C), i(cout_adj))
-        call("idv_cconv2d_wino_fwd", dy.ptr(), i(dy.C), p(None), i(0), p(gauss[3]), p(gauss[1]), i(0), p(None), out.ptr(), p(None), p(None),
-             i(0), i(1 if adj_transposed else 0), i(tshift_adj), i(cout_adj), i(dy.F), i(dy.B), i(dy.Tp), i(dy.Jp), i(t_out), p(None), i(1),
-             i(0), stream_ptr())
-    elif gauss is not None and wfrag_bf16 is None:
-        if LAUNCH_LOG is not None:
-            cfg = L.lib().idv_cconv_gauss_config(i(1 if adj_transposed else 0), i(dy.C), i(cout_adj), i(dy.F))
-        call("idv_cconv2d_gauss_fwd", dy.ptr(), i(dy.C), p(None), i(0), i(0), i(1), p(gauss[0]), p(gauss[1]), i(0), p(None),
-             out.ptr(), p(None), p(None), i(0), i(1 if adj_transposed else 0), i(tshift_adj), i(cout_adj), i(dy.F), i(dy.B), i(dy.Tp),
-             i(dy.Jp), i(t_out), p(None), i(1), i(0), stream_ptr())
-    elif wfrag_bf16 is not None:
+    timer = _launch_timer()
+    if wfrag_bf16 is not None:
         call("idv_cconv2d_bf16x3_fwd", dy.ptr(), i(dy.C), p(None), i(0), i(0), i(1), p(wfrag_bf16), p(bias), p(None), out.ptr(), p(None),
              p(None), i(0), i(1 if adj_transposed else 0), i(tshift_adj), i(cout_adj), i(dy.F), i(dy.B), i(dy.Tp), i(dy.Jp), i(t_out),
              stream_ptr())
+        cfg = _bf16_cfg(adj_transposed, cout_adj, dy.F) if timer is not None else None
     else:
-        call("idv_cconv2d_fwd", dy.ptr(), i(dy.C), p(None), i(0), i(0), i(1), p(wfrag), p(bias), p(None), out.ptr(), p(None), p(None),
-             i(0), i(1 if adj_transposed else 0), i(tshift_adj), i(cout_adj), i(dy.F), i(dy.B), i(dy.Tp), i(dy.Jp), i(t_out), stream_ptr())
-    if LAUNCH_LOG is not None:
-        ev1.record()
-        LAUNCH_LOG.append((cfg, macs, ev0, ev1))
+        # no skip, addend, slope or moment sums, and never the pack's fold: the adjoint of the contraction alone
+        cfg = _cconv2d_fp32(dy, out, wfrag, bias, gauss, cout_adj, transposed=adj_transposed, tshift=tshift_adj, t_out=t_out, has_fold=0,
+                            stats_rep=0, slope=None, skip=None, skip_div=1, stats=None, addend=None, addend_div=1)
+    if timer is not None:
+        _launch_logged(timer, cfg, _conv_macs(dy.C, cout_adj, dy, adj_transposed, Fout))
     return out
 
 
@@ -1230,16 +1214,13 @@ def cconv_wgrad(x: Planar, ci_off: int, dy: Planar, cout: int, cin_total: int, t
     else:
         n = int(_ll_fn("idv_cconv_wgrad_bf16_work_floats" if bf16 else "idv_cconv_wgrad_work_floats")(i(cs), i(cl), i(x.B), i(x.Tp)))
     work = _scratch(n, x.buf.device)
-    if LAUNCH_LOG is not None:
-        macs = 4 * x.C * cout * 10 * x.B * x.T * (x.F if transposed else dy.F)
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    timer = _launch_timer()
     call("idv_cconv2d_bwd_weight_bf16x3" if bf16 else ("idv_cconv2d_bwd_weight_gauss" if gauss else "idv_cconv2d_bwd_weight"),
          x.ptr(), i(x.C), i(ci_off), dy.ptr(), i(cout), i(cin_total), i(1 if transposed else 0),
          i(tshift), i(x.F), i(x.B), i(x.Tp), i(x.Jp), i(dy.Jp), p(work), ll(work.numel()), p(dw_re), p(dw_im), stream_ptr())
-    if LAUNCH_LOG is not None:
-        ev1.record()
-        LAUNCH_LOG.append((WGRAD_BF16_CFG if bf16 else (WGRAD_GAUSS_CFG if gauss else WGRAD_CFG), macs, ev0, ev1))
+    if timer is not None:
+        _launch_logged(timer, WGRAD_BF16_CFG if bf16 else (WGRAD_GAUSS_CFG if gauss else WGRAD_CFG),
+                       _conv_macs(x.C, cout, x, transposed, dy.F))
 
 
 def cconv_bias_grad(dy: Planar):
