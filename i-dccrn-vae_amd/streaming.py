@@ -283,12 +283,23 @@ def check_slots(which, slots: int) -> List[int]:
     return sorted(set(which))
 
 
+CONV_ENGINES = ("valu", "mfma")
+
+
+def check_conv(conv) -> str:
+    """The guard on the ``conv=`` argument of both streamers (host only): the engine of the conv blocks."""
+    if not isinstance(conv, str) or conv not in CONV_ENGINES:
+        raise ValueError(f"conv must be one of {CONV_ENGINES} (vector-ALU or fp32-MFMA streaming conv), got {conv!r}")
+    return conv
+
+
 def _fold_and_slope(block):
     return block.bn.eval_fold(), block.prelu.weight.detach().reshape(1).float().contiguous()
 
 
 class _ConvPack:
-    __slots__ = ("w", "bias", "fold", "slope", "transposed", "C0", "C1", "Cout", "Fin", "Fout", "nsplit")
+    # engine: "valu" (idv_stream_cconv*) or "mfma" (idv_stream_cconv_mfma*); w is the weight pack of that engine
+    __slots__ = ("w", "bias", "fold", "slope", "transposed", "C0", "C1", "Cout", "Fin", "Fout", "nsplit", "engine")
 
 
 class _Launch(NamedTuple):
@@ -302,7 +313,8 @@ class _Streamer:
     over the frames of one launch group.  A subclass supplies the framing, the conv block and the LSTM of its kind (scalars for
     lock-step streams, a row table for sessions)."""
 
-    def __init__(self, model, batch: int, frames_per_launch: int = 64, max_columns: int = 4096):
+    def __init__(self, model, batch: int, frames_per_launch: int = 64, max_columns: int = 4096, conv: str = "valu"):
+        self.conv = check_conv(conv)
         check_model(model, batch)
         net = model.std_DCCRN
         params = list(model.parameters())
@@ -332,12 +344,21 @@ class _Streamer:
         cp.Cout = conv.out_channel
         cp.C0, cp.C1, cp.Fin = C0, C1, Fin
         cp.Fout = 2 * Fin - 1 if cp.transposed else (Fin - 1) // 2 + 1
-        L.lib().idv_stream_cconv_wfloats.restype = L._L
-        cp.w = torch.empty(int(L.lib().idv_stream_cconv_wfloats(i(cin), i(cp.Cout))), dtype=torch.float32, device=self.device)
+        # the engine of a block is fixed here, from the constructor's choice and the block's shape alone
+        mfma = self.conv == "mfma" and L.lib().idv_stream_cconv_mfma_supported(i(1 if cp.transposed else 0), i(cin), i(cp.Cout)) == 1
+        cp.engine = "mfma" if mfma else "valu"
         cp.bias = torch.empty(2 * cp.Cout, dtype=torch.float32, device=self.device)
-        call("idv_stream_pack_cconv", p(re.weight.detach().float().contiguous()), p(im.weight.detach().float().contiguous()),
-             p(re.bias.detach().float().contiguous()), p(im.bias.detach().float().contiguous()), i(cin), i(cp.Cout),
-             i(1 if cp.transposed else 0), p(cp.w), p(cp.bias), stream_ptr())
+        wsrc = (p(re.weight.detach().float().contiguous()), p(im.weight.detach().float().contiguous()),
+                p(re.bias.detach().float().contiguous()), p(im.bias.detach().float().contiguous()))
+        if mfma:
+            cp.w = torch.empty(int(L.lib().idv_stream_cconv_mfma_wfloats(i(cin), i(cp.Cout))), dtype=torch.float32, device=self.device)
+            call("idv_stream_pack_cconv_mfma", wsrc[0], wsrc[1], wsrc[2], wsrc[3], i(cin), i(cp.Cout), i(1 if cp.transposed else 0),
+                 p(cp.w), p(cp.bias), stream_ptr())
+        else:
+            L.lib().idv_stream_cconv_wfloats.restype = L._L
+            cp.w = torch.empty(int(L.lib().idv_stream_cconv_wfloats(i(cin), i(cp.Cout))), dtype=torch.float32, device=self.device)
+            call("idv_stream_pack_cconv", wsrc[0], wsrc[1], wsrc[2], wsrc[3], i(cin), i(cp.Cout), i(1 if cp.transposed else 0),
+                 p(cp.w), p(cp.bias), stream_ptr())
         cp.fold, cp.slope = _fold_and_slope(blk)
         cp.fold = cp.fold.clone()
         cp.nsplit = int(L.lib().idv_stream_cconv_splits(i(1 if cp.transposed else 0), i(cin), i(cp.Cout), i(Fin), i(self.B)))
@@ -372,6 +393,7 @@ class _Streamer:
             c, f = cp.Cout, cp.Fout
         if (c, f) != (1, F):
             raise ValueError("StreamingDCCRN: the last decoder must give one channel of n_fft/2 + 1 bins")
+        self.conv_engines = [cp.engine for cp in self.enc + self.dec]      # enc0 .. then dec0 ..: nothing falls back unseen
         lstm = net.lstms[0]
         self.H = lstm.hidden_size
         self.K = ch * Fin
@@ -501,6 +523,10 @@ class StreamingDCCRN(_Streamer):
     (``hop * floor(L / hop)`` samples, eval-mode semantics with the batch norm folded).  Output sample m is returned by the push
     that delivers input sample m + 300 ... m + 399 at n_fft 512, win 400, hop 100.
 
+    ``conv`` names the engine of the conv blocks: ``"valu"`` (default, vector ALU) or ``"mfma"`` (fp32 matrix cores for every
+    block with at least 16 output channels, the others stay on the vector ALU; ``conv_engines`` lists the engine per block,
+    enc0 .. then dec0 ..).  The engine is fixed at construction and both give the same bits, so outputs of the two can be mixed.
+
     The streamer always runs in exact fp32, whatever ``ops.PRECISION`` is.  Weights are packed once, at construction: later
     changes of the model's parameters are not seen by an existing streamer.
     """
@@ -571,6 +597,13 @@ class StreamingDCCRN(_Streamer):
              i(self.B), i(c.k), i(Tp), i(Jp), stream_ptr())
 
     def _conv_call(self, cp: _ConvPack, x0, h0, x1, h1, out, hist_out, x0hist_out, B, k, Tp, Jp):
+        # one call per engine, each with its entry's name as a literal: the static check of the call sites against the header
+        # (tests/test_host_cpu.py) reads literal names only, and a name picked at run time would go unchecked
+        if cp.engine == "mfma":
+            call("idv_stream_cconv_mfma", x0, p(h0), i(cp.C0), x1 if x1 is not None else p(None), p(h1), i(cp.C1), p(cp.w), p(cp.bias),
+                 p(cp.fold), p(cp.slope), out, p(hist_out), x0hist_out, p(self.work), i(cp.nsplit), i(1 if cp.transposed else 0),
+                 i(cp.Cout), i(cp.Fin), i(B), i(k), i(Tp), i(Jp), stream_ptr())
+            return
         call("idv_stream_cconv", x0, p(h0), i(cp.C0), x1 if x1 is not None else p(None), p(h1), i(cp.C1), p(cp.w), p(cp.bias),
              p(cp.fold), p(cp.slope), out, p(hist_out), x0hist_out, p(self.work), i(cp.nsplit), i(1 if cp.transposed else 0),
              i(cp.Cout), i(cp.Fin), i(B), i(k), i(Tp), i(Jp), stream_ptr())
@@ -597,8 +630,8 @@ class StreamingSessions(_Streamer):
     that last read it (two buffers alternate, so that copy is two calls back).
     """
 
-    def __init__(self, model, slots: int, frames_per_launch: int = 64, max_columns: int = 4096):
-        super().__init__(model, slots, frames_per_launch, max_columns)
+    def __init__(self, model, slots: int, frames_per_launch: int = 64, max_columns: int = 4096, conv: str = "valu"):
+        super().__init__(model, slots, frames_per_launch, max_columns, conv)
         if int(L.lib().idv_stream_row_fields()) != NF:
             raise L.IdvError("libidccrn_hip.so and streaming.ROW_FIELDS disagree about the row table")
         self.sessions = SessionPlan(slots, self.n_fft, self.hop, self.win, self.cap)
@@ -702,6 +735,11 @@ class StreamingSessions(_Streamer):
              i(self.hop), i(c.k), frames, i(Tp), i(Jp), stream_ptr())
 
     def _block(self, cp: _ConvPack, c, x0, h0, x1, h1, out, hist, x0hist, Tp: int, Jp: int):
+        if cp.engine == "mfma":                  # two literal call sites, as in StreamingDCCRN._conv_call
+            call("idv_stream_cconv_mfma_rows", x0, p(h0), i(cp.C0), x1 if x1 is not None else p(None), p(h1), i(cp.C1), p(cp.w),
+                 p(cp.bias), p(cp.fold), p(cp.slope), out, p(hist), p(x0hist), p(self.work), i(cp.nsplit),
+                 i(1 if cp.transposed else 0), i(cp.Cout), i(cp.Fin), i(self.B), i(c.k), i(Tp), i(Jp), c.rows, stream_ptr())
+            return
         call("idv_stream_cconv_rows", x0, p(h0), i(cp.C0), x1 if x1 is not None else p(None), p(h1), i(cp.C1), p(cp.w), p(cp.bias),
              p(cp.fold), p(cp.slope), out, p(hist), p(x0hist), p(self.work), i(cp.nsplit), i(1 if cp.transposed else 0), i(cp.Cout),
              i(cp.Fin), i(self.B), i(c.k), i(Tp), i(Jp), c.rows, stream_ptr())

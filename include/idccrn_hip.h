@@ -713,6 +713,29 @@ int idv_stream_clstm_rows(const float* G, const float* wt, const float* b1, floa
 /* buf viewed as [outer][B][inner]: zeroes the n_slots slots listed in the device array slots (each in [0, B)). */
 int idv_stream_zero_rows(float* buf, long long outer, int B, long long inner, const long long* slots, int n_slots, void* stream);
 
+/* ---- streaming conv on the fp32 matrix cores (stream_conv_mfma.hip; streaming.Streaming*(conv="mfma"); additive entries:
+ * IDV_ABI_VERSION is unchanged).  The same function as idv_stream_cconv / idv_stream_cconv_rows and, bit for bit, the same
+ * result: v_mfma_f32_32x32x2_f32 is fed the products of the vector-ALU kernel in its order, with the same K parts (nsplit from
+ * idv_stream_cconv_splits, the same work layout and combine) and the same epilogue.  Blocks with Cout >= 16 only. */
+/* Floats of the MFMA weight pack: [co tiles of 32][Cin][5][4 fragments][64 lanes]. */
+long long idv_stream_cconv_mfma_wfloats(int Cin, int Cout);
+/* Inputs and bias as idv_stream_pack_cconv; w in MFMA fragment order (lane = output channel and k; -w_im is formed here, rows
+ * past Cout are zero). */
+int idv_stream_pack_cconv_mfma(const float* w_re, const float* w_im, const float* b_re, const float* b_im, int Cin, int Cout,
+                               int transposed, float* w, float* bias, void* stream);
+/* Host only, launches nothing: 1 when the MFMA entries serve the block (Cin >= 1 and Cout >= 16), 0 when it stays on
+ * idv_stream_cconv, -1 for a non-positive Cin or Cout. */
+int idv_stream_cconv_mfma_supported(int transposed, int Cin, int Cout);
+/* idv_stream_cconv with w from idv_stream_pack_cconv_mfma; IDV_EINVAL for an unsupported shape. */
+int idv_stream_cconv_mfma(const float* x0, const float* h0, int C0, const float* x1, const float* h1, int C1, const float* w,
+                          const float* bias, const float* fold, const float* prelu_slope, float* out, float* hist_out, float* x0hist_out,
+                          float* work, int nsplit, int transposed, int Cout, int Fin, int B, int k, int Tp, int Jp, void* stream);
+/* idv_stream_cconv_rows with w from idv_stream_pack_cconv_mfma; IDV_EINVAL for an unsupported shape. */
+int idv_stream_cconv_mfma_rows(const float* x0, const float* h0, int C0, const float* x1, const float* h1, int C1, const float* w,
+                               const float* bias, const float* fold, const float* prelu_slope, float* out, float* hist, float* x0hist,
+                               float* work, int nsplit, int transposed, int Cout, int Fin, int B, int k_launch, int Tp, int Jp,
+                               const long long* rows, void* stream);
+
 /* ---- batches of utterances of different lengths (ragged.hip, reduce.hip; inference.enhance_* / compute_sisdr with `lengths`) ---
  * lens: device int32[], samples per utterance.  Utterance b has T_b = 1 + lens[b] / hop frames and hop * (T_b - 1) output samples;
  * the batch is laid out for Tmax = max_b T_b frames, Tp >= Tmax + 1.  A causal network computes frame t from frames <= t, so only

@@ -1,13 +1,15 @@
 """Streaming enhancement benchmark: one JSON line per batch of lock-step streams, one hop (100 samples) per push.
 
     python profiles/tools/stream_bench.py [--batches 1,16,128,512,1024] [--seconds 2] [--catchup] [--far-seconds 3600] [--sessions]
+                                           [--conv valu|mfma|both]
 
 Per line: device time per push (HIP events around >= --seconds of pushes after warm-up), host wall time per push (synchronised),
 the real-time factor (hop / 16 kHz = 6.25 ms over the wall time) and the algorithmic GFLOP per push (4 real products per complex
 product of every block at its kept positions, LSTM and dense, the DFTs), computed from the shapes.  --catchup adds one line of
 4000-sample pushes at B = 64 in utterances (4 s) per second.  --far-seconds S adds one line at B = 1 measured after S seconds of
-audio went through the streamer in 1 s pushes, with no flush: time per push must not depend on the stream's position.  The
---sessions measures streaming.StreamingSessions
+audio went through the streamer in 1 s pushes, with no flush: time per push must not depend on the stream's position.  --conv names the engine
+of the conv blocks (streaming.check_conv); "both" measures the two engines in turn, twice, in one process per batch size, so
+that they share the card and its clocks (field "round").  --sessions measures streaming.StreamingSessions
 instead (metric "sessions_push"): every slot active, slot b 13 * (b % 7) samples ahead of slot 0, so the slots stand at staggered
 positions and each hop push still completes one frame per slot; counts are passed as a host list on every push.  The
 streams are never flushed; pushes are column slices of a 4 s signal taken round-robin (no copy).  Full-width DCCRN-CL,
@@ -42,7 +44,7 @@ def gflop_per_frame(st) -> float:
     return 2 * macs / 1e9
 
 
-def build(B, sessions=False):
+def build(B, sessions=False, conv="valu"):
     pm = importlib.import_module("i-dccrn-vae_amd.model.pvae_module")
     S = importlib.import_module("i-dccrn-vae_amd.streaming")
     from oracle import idccrn_oracle as O
@@ -50,11 +52,11 @@ def build(B, sessions=False):
     m = pm.DCCRN_(NFFT, HOP, np_, True, "cuda", WIN, [0, 1, 2, 3, 4, 5], "mask", False, None, None)
     m.load_state_dict(O.synth_state_dict({k: tuple(v.shape) for k, v in m.state_dict().items()}, 7))
     m = m.cuda()
-    return S.StreamingSessions(m, slots=B) if sessions else S.StreamingDCCRN(m, batch=B)
+    return S.StreamingSessions(m, slots=B, conv=conv) if sessions else S.StreamingDCCRN(m, batch=B, conv=conv)
 
 
-def run(B, seconds, n=HOP, far_seconds=0, sessions=False):
-    st = build(B, sessions)
+def run(B, seconds, n=HOP, far_seconds=0, sessions=False, conv="valu"):
+    st = build(B, sessions, conv)
     x = torch.randn(B, 64000, device="cuda") * 0.1
     pos = 0
     if sessions:                                # stagger the slots: slot b starts 13 * (b % 7) samples ahead
@@ -103,31 +105,36 @@ def main():
     ap.add_argument("--catchup", action="store_true")
     ap.add_argument("--far-seconds", type=int, default=0)
     ap.add_argument("--sessions", action="store_true")
+    ap.add_argument("--conv", choices=["valu", "mfma", "both"], default="valu")
     a = ap.parse_args()
     torch.set_grad_enabled(False)
     budget = 1e3 * HOP / SR
+    turns = [("valu", 0), ("mfma", 0), ("valu", 1), ("mfma", 1)] if a.conv == "both" else [(a.conv, 0)]
+    conv1 = "mfma" if a.conv == "both" else a.conv            # the single-engine lines below
     for B in [int(v) for v in a.batches.split(",") if v]:
-        st, dev_ms, wall_ms, _ = run(B, a.seconds, sessions=a.sessions)
-        gf = gflop_per_frame(st) * B
-        print(json.dumps({"metric": "sessions_push" if a.sessions else "stream_push", "B": B, "hop": HOP,
-                          "device_ms_per_push": round(dev_ms, 4),
-                          "wall_ms_per_push": round(wall_ms, 4), "rtf": round(budget / wall_ms, 3),
-                          "device_rtf": round(budget / dev_ms, 3), "gflop_per_push": round(gf, 3),
-                          "tflops_device": round(gf / dev_ms, 2), "frames_per_launch": st.cap}), flush=True)
-        del st
-        torch.cuda.empty_cache()
+        for conv, rnd in turns:
+            st, dev_ms, wall_ms, _ = run(B, a.seconds, sessions=a.sessions, conv=conv)
+            gf = gflop_per_frame(st) * B
+            print(json.dumps({"metric": "sessions_push" if a.sessions else "stream_push", "B": B, "hop": HOP,
+                              "device_ms_per_push": round(dev_ms, 4),
+                              "wall_ms_per_push": round(wall_ms, 4), "rtf": round(budget / wall_ms, 3),
+                              "device_rtf": round(budget / dev_ms, 3), "gflop_per_push": round(gf, 3),
+                              "tflops_device": round(gf / dev_ms, 2), "frames_per_launch": st.cap, "conv": conv,
+                              "conv_engines": st.conv_engines.count("mfma"), "round": rnd}), flush=True)
+            del st
+            torch.cuda.empty_cache()
     if a.catchup:
         B, n = 64, 4000
-        st, dev_ms, wall_ms, _ = run(B, a.seconds, n)
+        st, dev_ms, wall_ms, _ = run(B, a.seconds, n, conv=conv1)
         utt = B * n / (4 * SR)                      # 4 s utterances per push
         print(json.dumps({"metric": "stream_catchup", "B": B, "samples_per_push": n, "wall_ms_per_push": round(wall_ms, 3),
                           "device_ms_per_push": round(dev_ms, 3), "utt_per_s": round(utt / (wall_ms / 1e3), 1),
-                          "offline_utt_per_s": 901}), flush=True)
+                          "offline_utt_per_s": 901, "conv": conv1}), flush=True)
     if a.far_seconds:
-        st, dev_ms, wall_ms, pos = run(1, a.seconds, HOP, a.far_seconds)
+        st, dev_ms, wall_ms, pos = run(1, a.seconds, HOP, a.far_seconds, conv=conv1)
         print(json.dumps({"metric": "stream_push_far", "B": 1, "hop": HOP, "position_s": round(pos / SR, 1),
                           "device_ms_per_push": round(dev_ms, 4), "wall_ms_per_push": round(wall_ms, 4),
-                          "rtf": round(budget / wall_ms, 3)}), flush=True)
+                          "rtf": round(budget / wall_ms, 3), "conv": conv1}), flush=True)
 
 
 if __name__ == "__main__":
