@@ -21,8 +21,7 @@ int launch_vec(const CgemmArgs& a, hipStream_t st) {
     const long long tiles = (long long)b.jtiles * b.ftiles;
     // transposed conv: all frequency tiles of a column block on ONE XCD (they share 2 of their 5 input rows through its L2):
     // -27 % L2-miss traffic on dec1-3 at unchanged speed; the conv mode lost 1 % with it and keeps the tile-major order
-    static const bool map_ft = [] { const char* e = getenv("IDV_MAP_FT"); return !e || e[0] != '0'; }();
-    b.map_ft = (map_ft && MODE == IDV_TCONV) ? 1 : 0;
+    b.map_ft = MODE == IDV_TCONV ? 1 : 0;
     const long long nblk = b.map_ft ? (long long)((b.jtiles + 7) / 8) * 8 * b.ftiles * b.mblocks : ((tiles + 7) / 8) * 8 * b.mblocks;
     if (nblk > 0x7fffffffLL) return IDV_EINVAL;
     dim3 grid((unsigned)nblk);
@@ -147,30 +146,12 @@ extern "C" int idv_pw_gemm(const float* x, int K, const float* wfrag, const floa
     a.tshift = 0; a.t_valid = t_valid; a.stats = nullptr; a.ldo = ldo; a.nB = B;
     if (Jp < a.J) return IDV_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    // IDV_PW_CFG (experiments): 1 = four column tiles per wave, 2 = four row tiles per wave (rows in whole 256-row blocks only:
-    // the fragment buffer is allocated in 128-row blocks)
-    static const int pwcfg = [] { const char* e = getenv("IDV_PW_CFG"); return e ? atoi(e) : 0; }();
-    if (pwcfg == 1) {
-        if (swap) return launch_cfg<IDV_PW, 2, 2, 2, 1, 4, 8, true, false>(a, st);
-        return launch_cfg<IDV_PW, 2, 2, 2, 1, 4, 8, false, false>(a, st);
-    }
-    if (pwcfg == 2 && a.Mtiles % 8 == 0) {
-        if (swap) return launch_cfg<IDV_PW, 2, 2, 4, 1, 2, 8, true, false>(a, st);
-        return launch_cfg<IDV_PW, 2, 2, 4, 1, 2, 8, false, false>(a, st);
-    }
     // four row-tile pairs x ONE column group per workgroup where the rows come in whole 256-row blocks (the LSTM input
     // projections: M = 8H): a 72-column patch per workgroup instead of 136, as for the wide transposed conv (cgemm_gauss.hip):
-    // M = 1024 / 3072 / 6144, K = 1280, B = 64: 1.20 / 3.08 / 5.88 -> 1.16 / 2.97 / 5.60 ms.  IDV_PW_CFG=7 keeps 2 x 2.
-    // experiments: 16 / 32 planes per K chunk (a quarter of the barriers per MFMA); K in whole chunks only
-    if ((pwcfg == 16 || pwcfg == 32) && a.Mtiles % 8 == 0 && K % pwcfg == 0) {
-        if (pwcfg == 16) {
-            if (swap) return launch_cfg<IDV_PW, 4, 1, 2, 1, 2, 16, true, false>(a, st);
-            return launch_cfg<IDV_PW, 4, 1, 2, 1, 2, 16, false, false>(a, st);
-        }
-        if (swap) return launch_cfg<IDV_PW, 4, 1, 2, 1, 2, 32, true, false>(a, st);
-        return launch_cfg<IDV_PW, 4, 1, 2, 1, 2, 32, false, false>(a, st);
-    }
-    if (pwcfg != 7 && a.Mtiles % 8 == 0) {
+    // M = 1024 / 3072 / 6144, K = 1280, B = 64: 1.20 / 3.08 / 5.88 -> 1.16 / 2.97 / 5.60 ms against the 2 x 2 form, which the
+    // other row counts keep.  Measured and removed: four column tiles per wave, four row tiles per wave, and 16 / 32
+    // planes per K chunk (a quarter of the barriers per MFMA).
+    if (a.Mtiles % 8 == 0) {
         if (swap) return launch_cfg<IDV_PW, 4, 1, 2, 1, 2, 8, true, false>(a, st);
         return launch_cfg<IDV_PW, 4, 1, 2, 1, 2, 8, false, false>(a, st);
     }

@@ -500,11 +500,9 @@ int launch_bf16(const CgemmArgs& a, hipStream_t st) {
     b.jtiles = (a.J + JT - 1) / JT;
     b.ftiles = (rows + FO_T - 1) / FO_T;
     b.mblocks = ((a.M + 31) / 32 + WM * MT_W - 1) / (WM * MT_W);
-    const long long tiles = (long long)b.jtiles * b.ftiles;
     // all frequency tiles of a column block on one XCD (cgemm.hpp): -25 % L2-miss traffic in both modes at unchanged speed
-    static const int map_ft = [] { const char* e = getenv("IDV_MAP_FT_BF16"); return e ? atoi(e) : 2; }();   // 0 off, 1: TCONV, 2: both
-    b.map_ft = ((map_ft == 1 && MODE == IDV_TCONV) || map_ft == 2) ? 1 : 0;
-    const long long nblk = b.map_ft ? (long long)((b.jtiles + 7) / 8) * 8 * b.ftiles * b.mblocks : ((tiles + 7) / 8) * 8 * b.mblocks;
+    b.map_ft = 1;
+    const long long nblk = (long long)((b.jtiles + 7) / 8) * 8 * b.ftiles * b.mblocks;
     if (nblk > 0x7fffffffLL) return IDV_EINVAL;
     auto k = cgemm_bf16_kernel<MODE, WM, WN, FO_T, JC_W, STATS, MT_W, IMGIN, AD>;
     if (smem > 64 * 1024 &&

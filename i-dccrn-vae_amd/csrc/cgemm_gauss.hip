@@ -433,8 +433,7 @@ int launch_gauss_v(const GaussArgs& a, hipStream_t st) {
     b.jtiles = (a.J + JT - 1) / JT;
     b.ftiles = (rows + FO_T - 1) / FO_T;
     b.mblocks = (a.cotiles + WM - 1) / WM;
-    static const bool map_ft = [] { const char* e = getenv("IDV_MAP_FT"); return !e || e[0] != '0'; }();
-    b.map_ft = (map_ft && MODE == IDV_TCONV) ? 1 : 0;
+    b.map_ft = MODE == IDV_TCONV ? 1 : 0;                     // block order as cgemm.hip's
     const long long tiles = (long long)b.jtiles * b.ftiles;
     const long long nblk = b.map_ft ? (long long)((b.jtiles + 7) / 8) * 8 * b.ftiles * b.mblocks : ((tiles + 7) / 8) * 8 * b.mblocks;
     if (nblk > 0x7fffffffLL) return IDV_EINVAL;
@@ -455,18 +454,15 @@ int launch_gauss(const GaussArgs& a, hipStream_t st) {
     return launch_gauss_v<MODE, WM, WN, FO_T, JC_W, CIK, STATS, false, OCC>(a, st);
 }
 
-inline int waste(int n, int t) { return ((n + t - 1) / t) * t - n; }
-
 constexpr int CIK = 4;        // complex input channels per K chunk (wfrag / supported() granularity); the kernels' own chunk
-constexpr int CIK5 = 2;       // the 5-row conv tile (15 accumulator tiles = 240 registers) and the 1-row x 4-column-tile conv
-                              // (13 / 5 patch rows of 72 / 264 .. 520 columns per channel) stage 2 channels per chunk
+constexpr int CIK5 = 2;       // the one-co-tile conv form stages 2 channels per chunk (its patch: 5 rows of 264 columns per channel)
 
 // Two workgroups per CU (6 accumulator tiles per wave, < 256 registers, accumulators in VGPRs) so that one workgroup's prologue
 // (first patch, weight ring) and epilogue overlap the other's MFMAs; per layer, tests/tools/gauss_layers_probe.py, B = 64:
-//   * conv: one output row x two column tiles per wave beats the 12 / 9 / 15-tile one-workgroup forms on EVERY encoder layer
-//     (enc1 3.44 -> 3.24 ms, enc2 6.32 -> 5.78, enc3 6.13 -> 5.84, enc4 6.40 -> 6.23, enc5 7.03 -> 6.94): no frequency-tile
-//     waste, and the short-K layers (32 .. 128 input channels) gain most.  IDV_GAUSS_CCFG=0 restores the old forms,
-//     IDV_GAUSS_CCFG=N limits the new one to <= N input channels;
+//   * conv: one output row x two column tiles per wave beats the 12 / 9 / 15-tile one-workgroup forms (five, three or one output
+//     rows per tile, chosen by the least frequency-tile waste) on EVERY encoder layer (enc1 3.44 -> 3.24 ms, enc2 6.32 -> 5.78,
+//     enc3 6.13 -> 5.84, enc4 6.40 -> 6.23, enc5 7.03 -> 6.94): no frequency-tile waste, and the short-K layers (32 .. 128 input
+//     channels) gain most.  The one-workgroup forms are removed;
 //   * transposed conv: one column tile per wave wins at <= 128 input channels (dec4 6.78 -> 6.13 ms) and loses at 256 / 512
 //     (dec3 11.75 -> 11.89 ms; all wide layers 659 -> 653 utt/s), where the 12-tile form amortises its patch reads over two
 //     column tiles.  IDV_GAUSS_OCC2_MAXC moves the boundary.
@@ -474,65 +470,31 @@ inline int occ2_max_cin() {
     static const int v = [] { const char* e = getenv("IDV_GAUSS_OCC2_MAXC"); return e ? atoi(e) : 128; }();
     return v;
 }
-inline bool tconv_wm4() {
-    static const bool v = [] { const char* e = getenv("IDV_GAUSS_TWM"); return !(e && atoi(e) == 2); }();
-    return v;
-}
-inline bool conv_cik2() {
-    static const bool v = [] { const char* e = getenv("IDV_GAUSS_CCIK"); return e && atoi(e) == 2; }();
-    return v;
-}
-inline int conv_occ2_max_cin() {
-    static const int v = [] { const char* e = getenv("IDV_GAUSS_CCFG"); return e ? atoi(e) : (1 << 30); }();
-    return v;
-}
 
 // configuration id: 3 MODE WM WN FO_T JC_W OCC as decimal digits (leading 3 = the three-product kernel)
-int gauss_config(int transposed, int Cin, int Cout, int rows) {
+int gauss_config(int transposed, int Cin, int Cout) {
     const int wide = Cout > 32;                       // two co tiles per workgroup where the layer has them
-    if (transposed) {
-        const bool occ2 = Cin <= occ2_max_cin();
-        // four co tiles x ONE column group per workgroup where the layer has four co tiles (a 72-column patch instead of 136
-        // per workgroup: dec0 13.63 -> 13.16 ms, dec1 12.61 -> 11.81, dec2 11.96 -> 11.52 at B = 64; IDV_GAUSS_TWM=2 restores 2 x 2)
-        if (!occ2 && Cout >= 128 && tconv_wm4()) return 3141121;
-        return wide ? (occ2 ? 3122112 : 3122121) : (occ2 ? 3114112 : 3114121);
-    }
-    if (Cin <= conv_occ2_max_cin()) return wide ? 3022122 : 3014122;
-    int fo = 5;
-    if (waste(rows, 3) < waste(rows, fo)) fo = 3;
-    if (waste(rows, 1) < waste(rows, fo)) fo = 1;
-    const int jc = fo == 1 ? 4 : 1;
-    return (300000 + (wide ? 2200 : 1400) + fo * 10 + jc) * 10 + 1;
+    if (!transposed) return wide ? 3022122 : 3014122;
+    const bool occ2 = Cin <= occ2_max_cin();
+    // four co tiles x ONE column group per workgroup where the layer has four co tiles (a 72-column patch instead of 136
+    // per workgroup: dec0 13.63 -> 13.16 ms, dec1 12.61 -> 11.81, dec2 11.96 -> 11.52 at B = 64 against 2 x 2)
+    if (!occ2 && Cout >= 128) return 3141121;
+    return wide ? (occ2 ? 3122112 : 3122121) : (occ2 ? 3114112 : 3114121);
 }
 
 template <bool STATS>
 int launch_cfg(const GaussArgs& a, int transposed, hipStream_t st) {
-    const int rows = transposed ? a.Fin : a.Fout;
-    // experiments (IDV_GAUSS_TCFG): 1 = one co tile x four column groups per workgroup, 2 = two workgroups per CU whatever the K
-    static const int tcfg = [] { const char* e = getenv("IDV_GAUSS_TCFG"); return e ? atoi(e) : 0; }();
-    if (transposed && a.Cout > 32 && !STATS) {
-        if (tcfg == 1) return launch_gauss<IDV_TCONV, 1, 4, 1, 2, CIK, STATS>(a, st);
-        if (tcfg == 2) return launch_gauss<IDV_TCONV, 2, 2, 1, 1, CIK, STATS, 2>(a, st);
-    }
-    switch (gauss_config(transposed, a.C0 + a.C1, a.Cout, rows)) {
+    switch (gauss_config(transposed, a.C0 + a.C1, a.Cout)) {
         // (eight channels per K chunk -- half the barriers -- change nothing here: three patch buffers already hide them)
         case 3141121: return launch_gauss<IDV_TCONV, 4, 1, 1, 2, CIK, STATS>(a, st);
         case 3122121: return launch_gauss<IDV_TCONV, 2, 2, 1, 2, CIK, STATS>(a, st);
         case 3122112: return launch_gauss<IDV_TCONV, 2, 2, 1, 1, CIK, STATS, 2>(a, st);
         case 3114121: return launch_gauss<IDV_TCONV, 1, 4, 1, 2, CIK, STATS>(a, st);
         case 3114112: return launch_gauss<IDV_TCONV, 1, 4, 1, 1, CIK, STATS, 2>(a, st);
-        // (four channels per K chunk on two patch buffers beat two channels on three: 28.1 -> 27.1 ms over enc1-5, B = 64;
-        //  IDV_GAUSS_CCIK=2 restores the latter)
-        case 3022122: return conv_cik2() ? launch_gauss<IDV_CONV, 2, 2, 1, 2, CIK5, STATS, 2>(a, st)
-                                         : launch_gauss<IDV_CONV, 2, 2, 1, 2, CIK, STATS, 2>(a, st);
+        // (four channels per K chunk on two patch buffers beat two channels on three: 28.1 -> 27.1 ms over enc1-5, B = 64)
+        case 3022122: return launch_gauss<IDV_CONV, 2, 2, 1, 2, CIK, STATS, 2>(a, st);
         // (one co tile x four column groups: a 264-column patch -- four channels per chunk would not leave room for two workgroups)
         case 3014122: return launch_gauss<IDV_CONV, 1, 4, 1, 2, CIK5, STATS, 2>(a, st);
-        case 3022511: return launch_gauss<IDV_CONV, 2, 2, 5, 1, CIK5, STATS>(a, st);
-        case 3022311: return launch_gauss<IDV_CONV, 2, 2, 3, 1, CIK, STATS>(a, st);
-        case 3022141: return launch_gauss<IDV_CONV, 2, 2, 1, 4, CIK5, STATS>(a, st);
-        case 3014511: return launch_gauss<IDV_CONV, 1, 4, 5, 1, CIK5, STATS>(a, st);
-        case 3014311: return launch_gauss<IDV_CONV, 1, 4, 3, 1, CIK, STATS>(a, st);
-        case 3014141: return launch_gauss<IDV_CONV, 1, 4, 1, 4, CIK5, STATS>(a, st);
         default: return IDV_EINVAL;
     }
 }
@@ -557,8 +519,8 @@ extern "C" long long idv_cconv_gauss_wfrag_floats(int Cout, int cin_used) {
 extern "C" int idv_cconv_gauss_epi_rows(int Cout) { return (Cout + 31) / 32 * 32; }
 
 extern "C" int idv_cconv_gauss_config(int transposed, int Cin, int Cout, int Fin) {
-    const int rows = transposed ? Fin : (Fin - 1) / 2 + 1;
-    return gauss_config(transposed, Cin, Cout, rows);
+    (void)Fin;                                        // (no form depends on the row count any more)
+    return gauss_config(transposed, Cin, Cout);
 }
 
 // Pack ComplexConv2d / ComplexConvTranspose2d weights (layouts as idv_pack_cconv) into the three Gauss planes

@@ -54,6 +54,14 @@ struct TwArgs {
 };
 
 constexpr int TW_PACK_CI = 8;      // pack granularity in complex input channels (cgemm_wino's WCIK)
+// weight fragments as [64 lanes][4 tiles] groups with 16-byte loads (bit PH set) or slot-major [slot][64 lanes] with 4-byte loads: measured
+// (B = 64, dec0-3) even-row phase 22.0 -> 21.1 ms with the vector form, odd-row phase 14.1 -> 17.8 ms: the even-row phase only.  Read by
+// the pack kernel and the conv kernels alike.
+constexpr int TW_WVEC_MASK = 1;
+// co tiles on different XCDs: dec0-3 at B = 64 34.7 -> 34.3 ms (dec0, eight co tiles: 9.81 -> 9.54) against one XCD per column block
+constexpr int TW_XCD_SPLIT = 1;
+// two co tiles per workgroup, odd-row phase: waves 4 .. 7 stage one k-step later than their SIMD partners (see the kernel's main loop)
+constexpr int TW_PAIR_STAGGER = 1;
 
 // frequency transforms: cgemm_wino.hip's tables (transformed row r = raw row ra + cb * raw row rb of d0..d3 = input rows m0 - 1 .. m0 + 2)
 template <int PH> __device__ __forceinline__ int tw_ra(int r) {
@@ -82,13 +90,12 @@ __host__ __device__ inline int tw_tile(int ph, int w, int k) {
 }
 template <int PH> constexpr int tw_wslots() { return PH == 0 ? 9 : 8; }        // packed weight slots per (channel pair, wave)
 
-// DBG (timing experiments only, results wrong): 1 = no staging after the prologue, 2 = no weight re-loads, 4 = no epilogue exchange
 // LEFT: the time taps read (x[t-1], x[t]) (tshift = -1: the extra window column is on the left), else (x[t], x[t+1])
 // NCT: co tiles per workgroup.  2: eight waves; waves 0 .. 3 run the program of co tile 2 p, waves 4 .. 7 the same program on co tile
 // 2 p + 1 (tiles, weights, K order and epilogue of a co tile are those of NCT = 1: the results are bit-identical), and all 512 threads
 // share ONE staging of the raw rows, which do not depend on the output channel: half the staging work and input fetch per MFMA.  One
 // workgroup per CU, still two waves per SIMD.
-template <int PH, int CIK, bool LEFT, int DBG = 0, int RDW = 2, bool WVEC = true, bool STATS = false, int NCT = 1>
+template <int PH, int CIK, bool LEFT, bool STATS = false, int NCT = 1>
 __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw_kernel(const TwArgs a) {
     constexpr int NR = tw_nr<PH>(), NT = tw_nt<PH>(), NTP = tw_ntp<PH>(), NTW = tw_ntw<PH>();
     constexpr int NRAW = PH == 0 ? 4 : 3, ROW0 = PH == 0 ? 0 : 1;       // raw patch rows d(ROW0) .. : input rows m0 - 1 + ROW0 ..
@@ -96,6 +103,8 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw_kernel(c
     constexpr int RT = NRAW * 9 * 32;            // floats per channel in a patch buffer: per raw row 9 (Gauss, time) planes of 32 pairs
     constexpr int NE = CIK * RT;
     constexpr int NBUF = 2;
+    constexpr int RDW = 2;                       // weight ring depth in k-steps
+    constexpr bool WVEC = (TW_WVEC_MASK >> PH) & 1;
     constexpr int NITEM = CIK * NRAW * 16;       // staging items per chunk: (channel, raw row, 2 column pairs)
     constexpr int NTHR = 256 * NCT;
     constexpr int NLD = (NITEM + NTHR - 1) / NTHR;
@@ -296,7 +305,7 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw_kernel(c
                 if (4 + k < NTW) dst[4 + k] = w1[k];
             }
             if (NTW == 9) dst[NTW - 1] = ws[512 + lane];
-        } else {                                              // (experiments) slot-major [slot][64 lanes]: one 4-byte load per tile
+        } else {                                              // slot-major [slot][64 lanes]: one 4-byte load per tile
 #pragma unroll
             for (int k = 0; k < NTW; ++k) dst[k] = ws[k * 64 + lane];
         }
@@ -347,7 +356,7 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw_kernel(c
                 // staging of chunk + 1 rides on k-steps 1 (item 0) and 2 (item 1): the item's registers were loaded one chunk ago, the
                 // other buffer was last read in the previous chunk (a barrier since); the steps of the store are dealt out between MFMAs
                 const int si = ul - 1 - (LATE ? 1 : 0);
-                const bool staging = !(DBG & 1) && si >= 0 && si < NLD;
+                const bool staging = si >= 0 && si < NLD;
 #pragma unroll
                 for (int k = 0; k < NTW; ++k) {
                     const float b = xa[k] + cbj[UNI ? 0 : (k >> 1 < NPAIR ? k >> 1 : NPAIR)] * xb[k];
@@ -371,7 +380,7 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw_kernel(c
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                if (!(DBG & 2)) load_w(chunk * KS + ul + RDW, a_w[ul % RDW]);
+                load_w(chunk * KS + ul + RDW, a_w[ul % RDW]);
             }
         }
     };
@@ -399,7 +408,7 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw_kernel(c
         ja[q] = j - (bj - bj / a.add_div) * a.Tp;
     }
 #pragma unroll
-    for (int s = 0; s < ((DBG & 4) ? 1 : 4); ++s) {
+    for (int s = 0; s < 4; ++s) {
         if (s > 0) __syncthreads();
 #pragma unroll
         for (int k = 0; k < NTW; ++k) {
@@ -536,34 +545,7 @@ __global__ void pack_cconv_tw_kernel(const float* __restrict__ wino, int cotiles
     }
 }
 
-template <int PH, int CIK, bool LEFT, int DBG, int RDW, bool WVEC = true, bool STATS = false, int NCT = 1>
-int launch_tw_ph_l(const TwArgs& a, hipStream_t st);
-// weight fragments as [64 lanes][4 tiles] groups with 16-byte loads (bit PH set) or slot-major [slot][64 lanes] with 4-byte loads: measured
-// (B = 64, dec0-3) even-row phase 22.0 -> 21.1 ms with the vector form, odd-row phase 14.1 -> 17.8 ms: default 1 = even-row phase only
-// (IDV_TW_WVEC=0 .. 3 for experiments; read by the pack kernel and the launcher alike)
-inline int tw_wvec_mask() {
-    static const int v = [] { const char* e = getenv("IDV_TW_WVEC"); return e ? atoi(e) : 1; }();
-    return v;
-}
-template <int PH, int CIK, int DBG = 0, int RDW = 2>
-int launch_tw_ph(const TwArgs& a, hipStream_t st) {
-    const bool wv = (tw_wvec_mask() >> PH) & 1;
-    // two co tiles per workgroup (idv_tw_pair bit PH): an even number of co tiles, default weight layouts
-    if (DBG == 0 && RDW == 2 && wv == (PH == 0) && a.cotiles % 2 == 0 && ((idv_tw_pair(-1) >> PH) & 1)) {
-        constexpr bool WV = PH == 0;
-        if (a.stats) return a.tshift ? launch_tw_ph_l<PH, CIK, true, 0, 2, WV, true, 2>(a, st) : launch_tw_ph_l<PH, CIK, false, 0, 2, WV, true, 2>(a, st);
-        return a.tshift ? launch_tw_ph_l<PH, CIK, true, 0, 2, WV, false, 2>(a, st) : launch_tw_ph_l<PH, CIK, false, 0, 2, WV, false, 2>(a, st);
-    }
-    if (DBG == 0 && RDW == 2 && a.stats) {                    // the training forward: default weight layouts only
-        constexpr bool WV = PH == 0;
-        if (wv != WV) return IDV_EINVAL;
-        return a.tshift ? launch_tw_ph_l<PH, CIK, true, 0, 2, WV, true>(a, st) : launch_tw_ph_l<PH, CIK, false, 0, 2, WV, true>(a, st);
-    }
-    if (DBG == 0 && RDW == 2 && !wv)
-        return a.tshift ? launch_tw_ph_l<PH, CIK, true, 0, 2, false>(a, st) : launch_tw_ph_l<PH, CIK, false, 0, 2, false>(a, st);
-    return a.tshift ? launch_tw_ph_l<PH, CIK, true, DBG, RDW>(a, st) : launch_tw_ph_l<PH, CIK, false, DBG, RDW>(a, st);
-}
-template <int PH, int CIK, bool LEFT, int DBG, int RDW, bool WVEC, bool STATS, int NCT>
+template <int PH, int CIK, bool LEFT, bool STATS, int NCT>
 int launch_tw_ph_l(const TwArgs& a, hipStream_t st) {
     constexpr int NE = CIK * (PH == 0 ? 4 : 3) * 9 * 32;
     constexpr size_t smem = 2 * NE * sizeof(float);
@@ -572,20 +554,17 @@ int launch_tw_ph_l(const TwArgs& a, hipStream_t st) {
     b.jtiles = (a.J + 63) / 64;
     b.ftiles = PH == 1 ? a.Fin / 2 : (a.Fin + 1) / 2;
     if (b.ftiles == 0) return IDV_OK;
-    // co tiles on different XCDs: dec0-3 at B = 64 34.7 -> 34.3 ms (dec0, eight co tiles: 9.81 -> 9.54); IDV_TW_XCD_SPLIT=0: one XCD per column block
-    static const int xsplit = [] { const char* e = getenv("IDV_TW_XCD_SPLIT"); return e ? atoi(e) : 1; }();
     b.cgroups = b.cotiles / NCT;                              // (NCT = 2: the caller checked that the co-tile count is even)
     if (b.cgroups * NCT != b.cotiles) return IDV_EINVAL;
-    static const int stag = [] { const char* e = getenv("IDV_TW_PAIR_STAGGER"); return e ? atoi(e) : 1; }();
-    b.stagger = stag;
-    b.xcd_split = (xsplit && (b.cgroups == 2 || b.cgroups == 4 || b.cgroups == 8)) ? 1 : 0;
+    b.stagger = TW_PAIR_STAGGER;
+    b.xcd_split = (TW_XCD_SPLIT && (b.cgroups == 2 || b.cgroups == 4 || b.cgroups == 8)) ? 1 : 0;
     long long nblk = (long long)((b.jtiles + 7) / 8) * 8 * b.ftiles * b.cgroups;
     if (b.xcd_split) {
         const int G = 8 / b.cgroups;
         nblk = (long long)((b.jtiles + G - 1) / G) * b.ftiles * 8;
     }
     if (nblk > 0x7fffffffLL) return IDV_EINVAL;
-    auto k = cconv_tw_kernel<PH, CIK, LEFT, DBG, RDW, WVEC, STATS, NCT>;
+    auto k = cconv_tw_kernel<PH, CIK, LEFT, STATS, NCT>;
     // (once per instantiation and device: setting it on every launch is host time, a lot of it under a profiler.  Two threads that
     // both find the flag clear both set the same value.)
     static std::atomic<bool> attr_set[64];
@@ -598,6 +577,23 @@ int launch_tw_ph_l(const TwArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(k, dim3((unsigned)nblk), dim3(256 * NCT), smem, st, b);
     if (NCT > 1) idv_tw_pair_note_launch();
     return idv_launch_status();
+}
+
+// one choice over (statistics, two co tiles per workgroup, side of the time taps).  Two co tiles per workgroup (idv_tw_pair bit PH)
+// need an even number of co tiles.
+template <int PH, int CIK>
+int launch_tw_ph(const TwArgs& a, hipStream_t st) {
+    const bool pair = a.cotiles % 2 == 0 && ((idv_tw_pair(-1) >> PH) & 1);
+    switch ((a.stats ? 4 : 0) | (pair ? 2 : 0) | (a.tshift ? 1 : 0)) {
+        case 0: return launch_tw_ph_l<PH, CIK, false, false, 1>(a, st);
+        case 1: return launch_tw_ph_l<PH, CIK, true, false, 1>(a, st);
+        case 2: return launch_tw_ph_l<PH, CIK, false, false, 2>(a, st);
+        case 3: return launch_tw_ph_l<PH, CIK, true, false, 2>(a, st);
+        case 4: return launch_tw_ph_l<PH, CIK, false, true, 1>(a, st);
+        case 5: return launch_tw_ph_l<PH, CIK, true, true, 1>(a, st);
+        case 6: return launch_tw_ph_l<PH, CIK, false, true, 2>(a, st);
+        default: return launch_tw_ph_l<PH, CIK, true, true, 2>(a, st);
+    }
 }
 
 }  // namespace
@@ -644,7 +640,7 @@ extern "C" int idv_pack_cconv_tw(const float* wino_frag, int Cout, int cin_used,
     const long long n = idv_cconv_tw_wfrag_floats(Cout, cin_used);
     const unsigned blocks = (unsigned)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256);
     hipLaunchKernelGGL(pack_cconv_tw_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, wino_frag, cotiles, cpad * 3, cpad / 2,
-                       tw_wvec_mask(), tw_frag);
+                       TW_WVEC_MASK, tw_frag);
     return idv_launch_status();
 }
 
@@ -680,19 +676,6 @@ extern "C" int idv_ctconv2d_tw_fwd(const float* x0, int C0, const float* x1, int
     a.stats = stats;
     if (stats && stats_work) { a.stats = stats_work; a.stats_rep = stats_rep; }       // replicated sums, folded afterwards (common.hpp)
     int rc = 0;
-#ifdef IDV_TW_EXPERIMENTS
-    // timing experiments (WRONG results by construction; compiled in only with -DIDV_TW_EXPERIMENTS): IDV_TW_DBG = the kernel's DBG bits
-    // (1: no staging after the prologue, 2: no weight re-loads), IDV_TW_ONLY = 1 / 2: one phase only
-    static const int dbg = [] { const char* e = getenv("IDV_TW_DBG"); return e ? atoi(e) : 0; }();
-    static const int only = [] { const char* e = getenv("IDV_TW_ONLY"); return e ? atoi(e) : 0; }();
-    if (dbg && !stats) {
-        if (only != 2) rc = dbg == 1 ? launch_tw_ph<0, 8, 1>(a, st) : (dbg == 2 ? launch_tw_ph<0, 8, 2>(a, st) : launch_tw_ph<0, 8, 3>(a, st));
-        if (rc) return rc;
-        if (only != 1) rc = dbg == 1 ? launch_tw_ph<1, 8, 1>(a, st) : (dbg == 2 ? launch_tw_ph<1, 8, 2>(a, st) : launch_tw_ph<1, 8, 3>(a, st));
-        return rc;
-    }
-    if (only) return only == 1 ? launch_tw_ph<0, 8>(a, st) : launch_tw_ph<1, 8>(a, st);
-#endif
     rc = launch_tw_ph<0, 8>(a, st);
     if (!rc) rc = launch_tw_ph<1, 8>(a, st);
     if (rc || !(stats && stats_work)) return rc;

@@ -45,6 +45,10 @@ struct Tw2Args {
 };
 
 constexpr int TW2_PACK_CI = 8;     // pack granularity in complex input channels (cgemm_wino's WCIK)
+// block order and staging stagger as cgemm_tw.hip measured them: co tiles on different XCDs; with two co tiles per workgroup waves 4 .. 7
+// stage later than their SIMD partners
+constexpr int TW2_XCD_SPLIT = 1;
+constexpr int TW2_PAIR_STAGGER = 1;
 
 // product q of the conv form: raw rows (ra, rb), factor cb, accumulator
 __host__ __device__ constexpr int tw2_ra(int q) { return q == 0 ? 0 : (q == 1 ? 2 : (q == 2 ? 4 : (q == 3 ? 2 : (q == 4 ? 1 : 3)))); }
@@ -82,7 +86,7 @@ constexpr int tw2_smem_floats(int nct) {
     // NCT = 1: two patch buffers; NCT = 2: two patch buffers with a dump row each, or the two exchange areas of the epilogue (larger)
     return nct == 1 ? 2 * 4 * 7 * 288 : (2 * (4 * 7 * 288 + 288) > 2 * 36 * 4 * 64 ? 2 * (4 * 7 * 288 + 288) : 2 * 36 * 4 * 64);
 }
-template <bool LEFT, bool STATS, int DBG = 0, int NCT = 1>
+template <bool LEFT, bool STATS, int NCT = 1>
 __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw2_kernel(const Tw2Args a) {
     constexpr int NT = 36, NACC = 9, NSLOT = 16;
     constexpr int NRAW = 7, CIK = 4, KS = 2;
@@ -304,7 +308,7 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw2_kernel(
 #pragma unroll
             for (int ul = 0; ul < KS; ++ul) {
                 const float* bnext = ul + 1 < KS ? P + (size_t)(2 * (ul + 1) + half) * RT : Pn + (size_t)half * RT;
-                const bool staging = !(DBG & 1) && ul == 0;  // both items ride on k-step 0; the barrier sits in k-step 1
+                const bool staging = ul == 0;           // both items ride on k-step 0; the barrier sits in k-step 1
 #pragma unroll
                 for (int k = 0; k < (ROLE_B ? NSLOT - 1 : NSLOT); ++k) {
                     const int g = k >> 2, s4 = k & 3;
@@ -339,7 +343,7 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw2_kernel(
                         else load_grp_a(bnext, 0, xa[0], xb[0]);
                     }
                     // weights of the next k-step, group by group
-                    if (((k & 3) == 3 || (ROLE_B && k == NSLOT - 2)) && !(DBG & 2)) load_wg(chunk * KS + ul + 1, k >> 2);
+                    if ((k & 3) == 3 || (ROLE_B && k == NSLOT - 2)) load_wg(chunk * KS + ul + 1, k >> 2);
                     if constexpr (NCT == 2) if (staging) {
                         // the one item: slots 0 .. 5 or (waves 4 .. 7 with a.stagger: not while the SIMD partner stages) slots 8 .. 13
                         constexpr bool late = decltype(late_)::value;
@@ -509,26 +513,24 @@ __global__ void pack_cconv_tw2_kernel(const float* __restrict__ wino, int cotile
     }
 }
 
-template <bool LEFT, bool STATS, int DBG, int NCT = 1>
+template <bool LEFT, bool STATS, int NCT>
 int launch_tw2(const Tw2Args& a, hipStream_t st) {
     constexpr size_t smem = tw2_smem_floats(NCT) * sizeof(float);
     static_assert(smem * (NCT == 1 ? 2 : 1) <= 160 * 1024, "the patch buffers of two workgroups (NCT = 2: of one) must fit the 160 KB of LDS");
     Tw2Args b = a;
     b.jtiles = (a.J + 63) / 64;
     b.ftiles = (a.Fout + 1) / 2;
-    static const int xsplit = [] { const char* e = getenv("IDV_TW_XCD_SPLIT"); return e ? atoi(e) : 1; }();
     b.cgroups = b.cotiles / NCT;                              // (NCT = 2: the caller checked that the co-tile count is even)
     if (b.cgroups * NCT != b.cotiles) return IDV_EINVAL;
-    static const int stag = [] { const char* e = getenv("IDV_TW_PAIR_STAGGER"); return e ? atoi(e) : 1; }();
-    b.stagger = stag;
-    b.xcd_split = (xsplit && (b.cgroups == 2 || b.cgroups == 4 || b.cgroups == 8)) ? 1 : 0;
+    b.stagger = TW2_PAIR_STAGGER;
+    b.xcd_split = (TW2_XCD_SPLIT && (b.cgroups == 2 || b.cgroups == 4 || b.cgroups == 8)) ? 1 : 0;
     long long nblk = (long long)((b.jtiles + 7) / 8) * 8 * b.ftiles * b.cgroups;
     if (b.xcd_split) {
         const int G = 8 / b.cgroups;
         nblk = (long long)((b.jtiles + G - 1) / G) * b.ftiles * 8;
     }
     if (nblk > 0x7fffffffLL) return IDV_EINVAL;
-    auto k = cconv_tw2_kernel<LEFT, STATS, DBG, NCT>;
+    auto k = cconv_tw2_kernel<LEFT, STATS, NCT>;
     // (once per instantiation and device: setting it on every launch is host time, a lot of it under a profiler.  Two threads that
     // both find the flag clear both set the same value.)
     static std::atomic<bool> attr_set[64];
@@ -597,23 +599,18 @@ extern "C" int idv_cconv2d_tw_fwd(const float* x0, int Cin, const float* wfrag, 
     a.stats = stats;
     if (stats && stats_work) { a.stats = stats_work; a.stats_rep = stats_rep; }
     int rc;
-#ifdef IDV_TW_EXPERIMENTS
-    // timing experiments (WRONG results by construction; compiled in only with -DIDV_TW_EXPERIMENTS): IDV_TW_DBG = the kernel's DBG bits
-    static const int dbg = [] { const char* e = getenv("IDV_TW_DBG"); return e ? atoi(e) : 0; }();
-    if (!stats && dbg == 1) return tshift ? launch_tw2<true, false, 1>(a, st) : launch_tw2<false, false, 1>(a, st);
-    if (!stats && dbg == 2) return tshift ? launch_tw2<true, false, 2>(a, st) : launch_tw2<false, false, 2>(a, st);
-    if (!stats && dbg == 3) return tshift ? launch_tw2<true, false, 3>(a, st) : launch_tw2<false, false, 3>(a, st);
-#endif
     // two co tiles per workgroup (idv_tw_pair bit IDV_TW_PAIR_CONV): an even number of co tiles
     const bool pair = a.cotiles % 2 == 0 && (idv_tw_pair(-1) & IDV_TW_PAIR_CONV);
-    if (stats && pair)
-        rc = tshift ? launch_tw2<true, true, 0, 2>(a, st) : launch_tw2<false, true, 0, 2>(a, st);
-    else if (stats)
-        rc = tshift ? launch_tw2<true, true, 0>(a, st) : launch_tw2<false, true, 0>(a, st);
-    else if (pair)
-        rc = tshift ? launch_tw2<true, false, 0, 2>(a, st) : launch_tw2<false, false, 0, 2>(a, st);
-    else
-        rc = tshift ? launch_tw2<true, false, 0>(a, st) : launch_tw2<false, false, 0>(a, st);
+    switch ((stats ? 4 : 0) | (pair ? 2 : 0) | (tshift ? 1 : 0)) {
+        case 0: rc = launch_tw2<false, false, 1>(a, st); break;
+        case 1: rc = launch_tw2<true, false, 1>(a, st); break;
+        case 2: rc = launch_tw2<false, false, 2>(a, st); break;
+        case 3: rc = launch_tw2<true, false, 2>(a, st); break;
+        case 4: rc = launch_tw2<false, true, 1>(a, st); break;
+        case 5: rc = launch_tw2<true, true, 1>(a, st); break;
+        case 6: rc = launch_tw2<false, true, 2>(a, st); break;
+        default: rc = launch_tw2<true, true, 2>(a, st); break;
+    }
     if (rc || !(stats && stats_work)) return rc;
     return idv_launch_stats_collapse(stats_work, stats_rep, Cout * 5, stats, st);
 }

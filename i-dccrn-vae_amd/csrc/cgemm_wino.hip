@@ -61,6 +61,7 @@ struct WinoArgs {
     int xcd_split;        // block order: co-tile blocks on different XCDs (see the kernel)
 };
 
+constexpr int WINO_XCD_SPLIT = 1;   // block order (launch_wino_ph)
 constexpr int WCIK = 8;          // pack granularity in complex input channels (= cgemm_gauss's: shared `supported` rule); the kernel's K
                                  // chunk CIK divides it (2: the weight ring of a chunk is 48 registers beside 336 accumulator registers)
 // transformed row tq = A + cb B of the raw patch rows (transposed conv: d0..d3 = input rows m0 - 1 .. m0 + 2; conv: r0..r6 = input
@@ -454,9 +455,8 @@ int launch_wino_ph(const WinoArgs& a, hipStream_t st) {
     b.mblocks = (a.cotiles + WM - 1) / WM;
     if (b.ftiles == 0) return IDV_OK;
     // co-tile blocks on different XCDs where a layer has 2 / 4 / 8 of them: dec0 (8 co tiles = 2 blocks) 10.75 -> 10.45 ms, no
-    // change elsewhere (the L2-miss traffic is not what bounds these kernels); IDV_WINO_XCD_SPLIT=0: all blocks of a tile on one XCD
-    static const int xsplit = [] { const char* e = getenv("IDV_WINO_XCD_SPLIT"); return e ? atoi(e) : 1; }();
-    b.xcd_split = (xsplit && (b.mblocks == 2 || b.mblocks == 4 || b.mblocks == 8)) ? 1 : 0;
+    // change elsewhere (the L2-miss traffic is not what bounds these kernels) against all blocks of a tile on one XCD
+    b.xcd_split = (WINO_XCD_SPLIT && (b.mblocks == 2 || b.mblocks == 4 || b.mblocks == 8)) ? 1 : 0;
     long long nblk = (long long)((b.jtiles + 7) / 8) * 8 * b.ftiles * b.mblocks;
     if (b.xcd_split) {
         const int G = 8 / b.mblocks;
@@ -478,40 +478,31 @@ int launch_wino_ph(const WinoArgs& a, hipStream_t st) {
     return idv_launch_status();
 }
 
+// conv: one launch at TWO workgroups per CU: two channels per chunk (one staging item per thread), a weight ring of three units
+// (7 fragments per unit): 253 registers, accumulators in VGPRs.  The one-workgroup form with eight channels per chunk and a ring
+// of half a chunk measured slower (enc3 5.35 -> 5.04 ms, enc4 5.66 -> 5.44) and is removed.
+template <int WM, int WN>
+int launch_wino_conv(const WinoArgs& a, hipStream_t st) {
+    return a.stats ? launch_wino_ph<2, WM, WN, 2, true, 2, 3>(a, st) : launch_wino_ph<2, WM, WN, 2, false, 2, 3>(a, st);
+}
+
 // transposed conv: even rows, then odd rows: two launches per layer (the second reads the same raw rows from the L2 / Infinity
-// Cache).  IDV_WINO_PH1 (experiments): 0 = the odd-row phase as the even one (one workgroup per CU, ring = a chunk); default: two
-// workgroups per CU with a ring of 8 units (9 accumulator tiles = 144 registers leave room for it).  conv: one launch, the weight
-// ring half a chunk deep (7 fragments per unit).
+// Cache), both at two workgroups per CU (the one-workgroup forms of either phase, ring = a chunk, are removed):
+//   * even rows where they fit 256 registers (accumulators in VGPRs): the four-co-tile form with four channels per chunk and a
+//     weight ring of four units (249 registers): dec0 11.09 -> 10.49 ms, dec1 10.13 -> 9.62, dec2 9.67 -> 9.03 (B = 64); the 2 x 2
+//     form with two channels per chunk (one staging item per thread; with four it needs two and spills) and a ring of three:
+//     dec3 10.37 -> 9.99;
+//   * odd rows (9 accumulator tiles = 144 registers) with CIK channels per chunk and a ring of 8 units (6 where a chunk's 12
+//     units are no multiple of 8).
 template <int WM, int WN, int CIK, bool STATS>
-int launch_wino_s(const WinoArgs& a, int transposed, hipStream_t st) {
-    if (!transposed) {
-        // two channels per chunk: the conv form at TWO workgroups per CU (one staging item per thread, ring of three units: 253
-        // registers, accumulators in VGPRs)
-        if constexpr (CIK == 2) return launch_wino_ph<2, WM, WN, 2, STATS, 2, 3>(a, st);
-        else return launch_wino_ph<2, WM, WN, CIK, STATS, 1, (CIK * 3) / 2>(a, st);
-    }
-    if constexpr (CIK == 2) return IDV_EINVAL;                 // (the transposed form picks its own chunk sizes below)
-    else {
-    static const int ph1 = [] { const char* e = getenv("IDV_WINO_PH1"); return e ? atoi(e) : 1; }();
-    // the even-row phase runs at two workgroups per CU too where it fits 256 registers (accumulators in VGPRs): the four-co-tile
-    // form with four channels per chunk and a weight ring of four units (249 registers): dec0 11.09 -> 10.49 ms, dec1 10.13 -> 9.62,
-    // dec2 9.67 -> 9.03 (B = 64); the 2 x 2 form with two channels per chunk (one staging item per thread; with four it needs two
-    // and spills) and a ring of three: dec3 10.37 -> 9.99.  IDV_WINO_PH0=1: one workgroup per CU
-    static const int ph0 = [] { const char* e = getenv("IDV_WINO_PH0"); return e ? atoi(e) : 2; }();
-    if (ph0 == 2 && WM == 4 && WN == 1) {
-        if (int rc = launch_wino_ph<0, 4, 1, 4, STATS, 2, 4>(a, st)) return rc;
-    } else if (ph0 == 2 && WM == 2 && WN == 2) {
-        if (int rc = launch_wino_ph<0, 2, 2, 2, STATS, 2, 3>(a, st)) return rc;
-    } else if (ph0 == 2 && WM == 1 && WN == 4) {          // one co tile x four column groups: two channels per chunk (5 registers spilled)
-        if (int rc = launch_wino_ph<0, 1, 4, 2, STATS, 2, 3>(a, st)) return rc;
-    } else if (int rc = launch_wino_ph<0, WM, WN, CIK, STATS>(a, st)) return rc;
-    if (ph1 == 0) return launch_wino_ph<1, WM, WN, CIK, STATS>(a, st);
+int launch_wino_tconv_s(const WinoArgs& a, hipStream_t st) {
+    constexpr int CIK0 = WM == 4 ? 4 : 2;
+    if (int rc = launch_wino_ph<0, WM, WN, CIK0, STATS, 2, CIK0 == 4 ? 4 : 3>(a, st)) return rc;
     return launch_wino_ph<1, WM, WN, CIK, STATS, 2, (CIK * 3) % 8 == 0 ? 8 : 6>(a, st);
-    }
 }
 template <int WM, int WN, int CIK>
-int launch_wino(const WinoArgs& a, int transposed, hipStream_t st) {
-    return a.stats ? launch_wino_s<WM, WN, CIK, true>(a, transposed, st) : launch_wino_s<WM, WN, CIK, false>(a, transposed, st);
+int launch_wino_tconv(const WinoArgs& a, hipStream_t st) {
+    return a.stats ? launch_wino_tconv_s<WM, WN, CIK, true>(a, st) : launch_wino_tconv_s<WM, WN, CIK, false>(a, st);
 }
 
 const bool USE_WINO = [] { const char* e = getenv("IDV_WINO"); return !e || e[0] != '0'; }();
@@ -528,6 +519,7 @@ extern "C" int idv_cconv_wino_supported(int transposed, int C0, int C1, int Cout
     static const int min_cout = [] { const char* e = getenv("IDV_WINO_MIN_COUT"); return e ? atoi(e) : 33; }();
     static const int conv_min = [] { const char* e = getenv("IDV_WINO_CONV_MINC"); return e ? atoi(e) : 32; }();
     if (!USE_WINO || (!transposed && !USE_WINO_CONV) || Cout < min_cout) return 0;
+    if (transposed && Cout <= 32) return 0;          // whatever IDV_WINO_MIN_COUT says: the one-co-tile transposed form is removed
     static const int conv_mincout = [] { const char* e = getenv("IDV_WINO_CONV_MINCOUT"); return e ? atoi(e) : 64; }();
     if (transposed ? Fin < 2 : ((Fin - 1) / 2 + 1 < 2 || Cout < conv_mincout || C0 + C1 < conv_min)) return 0;
     return idv_cconv_gauss_supported(C0, C1, Cout);
@@ -594,22 +586,18 @@ extern "C" int idv_cconv2d_wino_fwd(const float* x0, int C0, const float* x1, in
     a.stats = stats;
     if (stats && stats_work) { a.stats = stats_work; a.stats_rep = stats_rep; }       // replicated sums, folded afterwards (common.hpp)
     int rc;
-    // experiments: IDV_WINO_CFG / IDV_WINO_CCFG = WM WN CIK as decimal digits for the transposed conv / the conv
-    static const int xcfg = [] { const char* e = getenv("IDV_WINO_CFG"); return e ? atoi(e) : 0; }();
-    static const int xccfg = [] { const char* e = getenv("IDV_WINO_CCFG"); return e ? atoi(e) : 0; }();
-    int cfg = transposed ? xcfg : xccfg;
-    if (!cfg) cfg = idv_cconv_wino_config(transposed, C0 + C1, Cout);
-    if (C1 > 0 && C0 % (cfg % 10)) cfg = cfg / 10 * 10 + 4;
-    if (transposed && cfg % 10 == 2) return IDV_EINVAL;          // a K chunk must not straddle the two sources (C0 % 4 == 0 holds)
+    int cfg = idv_cconv_wino_config(transposed, C0 + C1, Cout);
+    // transposed conv, second source: a K chunk of the odd-row phase must not straddle the two sources: where C0 is no multiple of
+    // 8 the 4-channel chunk (C0 % 4 == 0 holds: idv_cconv_gauss_supported).  The conv's 2-channel chunk always divides C0.
+    if (transposed && C1 > 0 && C0 % (cfg % 10)) cfg = cfg / 10 * 10 + 4;
     switch (cfg) {
-        case 412: rc = launch_wino<4, 1, 2>(a, transposed, st); break;
-        case 414: rc = launch_wino<4, 1, 4>(a, transposed, st); break;
-        case 418: rc = launch_wino<4, 1, 8>(a, transposed, st); break;
-        case 222: rc = launch_wino<2, 2, 2>(a, transposed, st); break;
-        case 224: rc = launch_wino<2, 2, 4>(a, transposed, st); break;
-        case 228: rc = launch_wino<2, 2, 8>(a, transposed, st); break;
-        case 144: rc = launch_wino<1, 4, 4>(a, transposed, st); break;
-        default: return IDV_EINVAL;
+        case 412: rc = launch_wino_conv<4, 1>(a, st); break;
+        case 222: rc = launch_wino_conv<2, 2>(a, st); break;
+        case 414: rc = launch_wino_tconv<4, 1, 4>(a, st); break;
+        case 418: rc = launch_wino_tconv<4, 1, 8>(a, st); break;
+        case 224: rc = launch_wino_tconv<2, 2, 4>(a, st); break;
+        case 228: rc = launch_wino_tconv<2, 2, 8>(a, st); break;
+        default: return IDV_EINVAL;       // (144, one co tile: idv_cconv_wino_supported refuses it; measured 3 % slower than cgemm_gauss)
     }
     if (rc || !(stats && stats_work)) return rc;
     return idv_launch_stats_collapse(stats_work, stats_rep, Cout * 5, stats, st);

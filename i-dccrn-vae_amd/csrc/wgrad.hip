@@ -778,11 +778,8 @@ const bool WGRAD_GAUSS = [] { const char* e = getenv("IDV_WGRAD_GAUSS"); return 
 // four S variants written to the LDS and 16-column steps, gained 4 % only.
 const bool WGRAD_WINO = [] { const char* e = getenv("IDV_WGRAD_WINO"); return !e || e[0] != '0'; }();
 // columns per step of the Winograd kernels: 32 (half the barriers per MFMA; the even-tap kernel then sits at 256 registers with 11
-// spilled: still faster -- all layers 47.05 -> 45.31 ms at B = 32); IDV_WGRAD_WINO_JT=16: 16-column steps
-inline int wgrad_wino_jt() {
-    static const int v = [] { const char* e = getenv("IDV_WGRAD_WINO_JT"); return (e && atoi(e) == 16) ? 16 : 32; }();
-    return v;
-}
+// spilled: still faster than 16-column steps -- all layers 47.05 -> 45.31 ms at B = 32; the 16-column form is removed)
+constexpr int WINO_JT = 32;
 inline bool wgrad_wino_for(int Fs) {
     static const int min_rows = [] { const char* e = getenv("IDV_WGRAD_WINO_MINF"); return e ? atoi(e) : 8; }();
     return WGRAD_WINO && Fs >= min_rows;
@@ -792,7 +789,7 @@ inline GaussPlan gauss_plan(int Cs, int Cl, int Fs, int Fl, int J, int JpS, int 
     GaussPlan g;
     // Winograd form: a step is a PAIR of S rows, 8 + 6 partial product planes per split instead of 10 tap planes
     const bool wino = wgrad_wino_for(Fs);
-    g.p = make_plan_rounds(Cs, Cl, J, CONV_MS, CONV_ML, wino ? wgrad_wino_jt() : CONV_JT, 3, 2, wino ? (Fs + 1) / 2 : Fs);
+    g.p = make_plan_rounds(Cs, Cl, J, CONV_MS, CONV_ML, wino ? WINO_JT : CONV_JT, 3, 2, wino ? (Fs + 1) / 2 : Fs);
     g.prod_stride = (long long)g.p.nsplit * (wino ? 14 : 10) * g.p.SpPad * g.p.LpPad;
     g.part_floats = 3 * g.prod_stride;
     g.s_comb = ((long long)Cs * Fs * JpS + 63) / 64 * 64;
@@ -864,13 +861,8 @@ extern "C" int idv_cconv2d_bwd_weight_gauss(const float* x, int Cx, int ci_off, 
     const dim3 grid(g.p.nsplit, g.p.tilesS, 3 * g.p.tilesL);
     if (wgrad_wino_for(a.Fs)) {
         a.steps_total = (long long)g.p.jtiles * ((a.Fs + 1) / 2);
-        if (wgrad_wino_jt() == 32) {
-            hipLaunchKernelGGL((wgrad_wino_kernel<0, 2, 32>), grid, dim3(256), 0, st, a);
-            hipLaunchKernelGGL((wgrad_wino_kernel<1, 2, 32>), grid, dim3(256), 0, st, a);
-        } else {
-            hipLaunchKernelGGL((wgrad_wino_kernel<0, 2, 16>), grid, dim3(256), 0, st, a);
-            hipLaunchKernelGGL((wgrad_wino_kernel<1, 2, 16>), grid, dim3(256), 0, st, a);
-        }
+        hipLaunchKernelGGL((wgrad_wino_kernel<0, 2, WINO_JT>), grid, dim3(256), 0, st, a);
+        hipLaunchKernelGGL((wgrad_wino_kernel<1, 2, WINO_JT>), grid, dim3(256), 0, st, a);
         hipLaunchKernelGGL(wgrad_unpack_gauss_wino_kernel, dim3(grid_for((long long)Cout * Cx * 10)), dim3(256), 0, st, work,
                            g.prod_stride, g.p.nsplit, g.p.SpPad, g.p.LpPad, Cout, Cx, Cin_total, ci_off, transposed, dw_re, dw_im);
         return idv_launch_status();

@@ -119,6 +119,7 @@ def test_cconv_gauss(ops, causal, transposed, cin, cout, F, T, B, skip_c, skip_d
     (True, False, 6, 40, 9, 9, 2, 0, False, None),        # non-causal taps (T + 1 output frames)
     (True, True, 32, 64, 33, 645, 2, 32, False, 0.25),    # utterance-length columns, Tp = 646, column tail
     (True, True, 256, 64, 17, 70, 2, 0, True, 0.25),      # a real layer width (dec3's channels)
+    (True, True, 12, 64, 5, 9, 2, 12, False, None),       # second source behind 12 channels (C0 % 8 == 4): the odd-row phase's 4-channel chunk
     (False, True, 32, 64, 129, 70, 2, 0, False, None),    # conv: two co tiles x two column groups, odd output row count (65)
     (False, True, 8, 40, 65, 33, 2, 0, True, 0.2),        # conv: ragged second co tile, fold + PReLU
     (False, True, 72, 128, 17, 40, 3, 0, False, None),    # conv: four co tiles x one column group, 72 input channels (served from 64)

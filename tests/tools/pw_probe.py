@@ -1,4 +1,4 @@
-"""Timing of the point-wise contraction (LSTM input projections) at the NSVAE shapes.  IDV_PW_CFG selects experimental tiles."""
+"""Timing of the point-wise contraction (LSTM input projections) at the NSVAE shapes."""
 import importlib, os, sys, torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 amd = importlib.import_module("i-dccrn-vae_amd"); ops = amd.ops
@@ -24,4 +24,4 @@ for (M, K) in ((6144, 1280), (3072, 1280), (3072, 768), (1024, 1280)):
     e1.record(); torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / 5
     line.append(f"M={M} K={K}: {ms:.3f} ms {2*M*K*B*T/ms/1e9:.1f} TF")
-print(f"[pw cfg {os.environ.get('IDV_PW_CFG','default')}] " + " | ".join(line), flush=True)
+print("[pw] " + " | ".join(line), flush=True)

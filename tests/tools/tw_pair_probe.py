@@ -1,8 +1,7 @@
 """Per-layer timing of the time-Winograd convs with two co tiles per workgroup (ops.TW_PAIR) beside the one-co-tile kernels, at the
 DCCRN-CL evaluation shapes: dec0 .. dec3 (csrc/cgemm_tw.hip; pair masks 0, 1 = even-row phase, 2 = odd-row phase, 3 = both) and
 enc2 .. enc5 (csrc/cgemm_tw2.hip; masks 0, 4).  Prints the time per layer and mask and the largest output difference to mask 0,
-which must be 0.     python tests/tools/tw_pair_probe.py [B] [repeats]      (GPU box)
-IDV_TW_PAIR_STAGGER=0: waves 4 .. 7 stage at the same time as their SIMD partners; IDV_TW_XCD_SPLIT as in tw_layers_probe.py."""
+which must be 0.     python tests/tools/tw_pair_probe.py [B] [repeats]      (GPU box)"""
 import importlib
 import os
 import sys

@@ -1,6 +1,5 @@
 """Per-layer timing of the DCCRN-CL decoder's transposed convs (dec0 .. dec4 at B utterances of 4 s) on the Winograd kernel
-(csrc/cgemm_wino.hip) beside cgemm_gauss_kernel.  IDV_WINO_CFG=<WM WN CIK digits> selects an experimental workgroup shape
-(read once per process).   python tests/tools/wino_layers_probe.py [B]      (GPU box)"""
+(csrc/cgemm_wino.hip) beside cgemm_gauss_kernel.   python tests/tools/wino_layers_probe.py [B]      (GPU box)"""
 import importlib
 import os
 import sys
@@ -21,7 +20,6 @@ g = torch.Generator().manual_seed(0)
 slope = torch.tensor([0.25], device=dev)
 tot = [0.0, 0.0]
 line = []
-tag = os.environ.get("IDV_WINO_CFG", "default") + "/" + os.environ.get("IDV_WINO_CCFG", "default")
 for tr, layers in ((False, ENC), (True, DEC)):
     for k, (cin, cout) in enumerate(layers):
         fin = FE[6 - k] if tr else FE[k + 1]
@@ -49,4 +47,4 @@ for tr, layers in ((False, ENC), (True, DEC)):
         tot[1] += res[1]
         line.append(f"{'dec' if tr else 'enc'}{k if tr else k + 1} {res[0]:6.2f} -> {res[1]:6.2f}")
         del x, y
-print(f"[wino cfg {tag}] " + " | ".join(line) + f" | total {tot[0]:.2f} -> {tot[1]:.2f} ms", flush=True)
+print("[wino] " + " | ".join(line) + f" | total {tot[0]:.2f} -> {tot[1]:.2f} ms", flush=True)
