@@ -182,7 +182,82 @@ __global__ void stream_zero_rows_kernel(float* __restrict__ buf, long long outer
 }
 #undef ROW
 
+// ---- streaming.StreamingVAE: the Gaussian draws of the reparameterisation and the skips at batch B * ns
+
+// Philox4x32-10 (Salmon et al., SC'11): ten rounds of two 32x32 -> 64 multiplies, the key bumped by the Weyl constants
+__device__ __forceinline__ void philox4x32_10(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
+                                              uint32_t& w0, uint32_t& w1) {
+#pragma unroll
+    for (int round = 0; round < 10; ++round) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1;
+        c3 = (uint32_t)p0;
+        c0 = n0;
+        c2 = n2;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    w0 = c0;
+    w1 = c1;
+}
+
+// eps_r, eps_i [B][ns][k][zdim] for frames t0 .. t0+k-1: counter (t low, t high, b*ns + s, u), key (seed low, seed high); words
+// 0 and 1 through Box-Muller.  A draw depends on (seed, b, s, t, u) only.
+__global__ void stream_eps_kernel(unsigned long long seed, long long t0, int k, int Bn, int zdim, float* __restrict__ eps_r,
+                                  float* __restrict__ eps_i) {
+    const long long n = (long long)Bn * k * zdim;
+    for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
+        const uint32_t u = (uint32_t)(e % zdim);
+        const long long tl = (e / zdim) % k;
+        const uint32_t bs = (uint32_t)(e / ((long long)zdim * k));
+        const unsigned long long t = (unsigned long long)(t0 + tl);
+        uint32_t w0, w1;
+        philox4x32_10((uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)t, (uint32_t)(t >> 32), bs, u, w0, w1);
+        const float u1 = (float)((w0 >> 8) + 1u) * 0x1p-24f;                  // (0, 1]
+        const float th = 6.283185307179586476925286766559f * ((float)(w1 >> 8) * 0x1p-24f);
+        const float rad = sqrtf(-2.0f * logf(u1));
+        eps_r[e] = rad * cosf(th);
+        eps_i[e] = rad * sinf(th);
+    }
+}
+
+// rows of x (pitch Jp, column b*Tp + 1 + tl, tl < k) -> xn (pitch Jpn, column (b*ns + s)*Tp + 1 + tl); hist[rows][B] -> histn[rows][B*ns]
+__global__ void stream_repeat_kernel(const float* __restrict__ x, const float* __restrict__ hist, long long rows, int B, int ns, int k,
+                                     int Tp, int Jp, float* __restrict__ xn, float* __restrict__ histn, int Jpn) {
+    const int Bn = B * ns, kc = k + 1;                                        // column kc - 1 of a row's span stands for the history
+    const long long n = rows * Bn * kc;
+    for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
+        const int tl = (int)(e % kc);
+        const int bn = (int)((e / kc) % Bn);
+        const long long row = e / ((long long)kc * Bn);
+        const int b = bn / ns;
+        if (tl < k)
+            xn[(size_t)row * Jpn + (size_t)bn * Tp + 1 + tl] = x[(size_t)row * Jp + (size_t)b * Tp + 1 + tl];
+        else if (hist)
+            histn[(size_t)row * Bn + bn] = hist[(size_t)row * B + b];
+    }
+}
+
 }  // namespace
+
+extern "C" int idv_stream_eps(long long seed, long long t0, int k, int B, int ns, int zdim, float* eps_r, float* eps_i, void* stream) {
+    if (t0 < 0 || k <= 0 || B <= 0 || ns <= 0 || zdim <= 0 || !eps_r || !eps_i || (long long)B * ns > 0x7fffffffLL) return IDV_EINVAL;
+    hipLaunchKernelGGL(stream_eps_kernel, dim3(grid_of((long long)B * ns * k * zdim)), dim3(256), 0, (hipStream_t)stream,
+                       (unsigned long long)seed, t0, k, B * ns, zdim, eps_r, eps_i);
+    return idv_launch_status();
+}
+
+extern "C" int idv_stream_repeat(const float* x, const float* hist, int C, int F, int B, int ns, int k, int Tp, int Jp, float* xn,
+                                 float* histn, int Jpn, void* stream) {
+    if (!x || !xn || (hist != nullptr) != (histn != nullptr) || C <= 0 || F <= 0 || B <= 0 || ns <= 0 || k <= 0 || Tp < k + 1 ||
+        Jp < B * Tp || (long long)B * ns * Tp > Jpn)
+        return IDV_EINVAL;
+    const long long rows = 2LL * C * F;
+    hipLaunchKernelGGL(stream_repeat_kernel, dim3(grid_of(rows * B * ns * (k + 1))), dim3(256), 0, (hipStream_t)stream, x, hist, rows, B,
+                       ns, k, Tp, Jp, xn, histn, Jpn);
+    return idv_launch_status();
+}
 
 extern "C" int idv_stream_frames(const float* ring, int R, const float* x, long long ldx, int n_new, long long n_prev, long long L_end,
                                  int B, int n_fft, int win, int hop, long long t0, int k, float* frames, int Tp, int Jp, void* stream) {

@@ -159,9 +159,160 @@ __global__ void stream_lstm_combine_kernel(const float* __restrict__ h, int H, i
     }
 }
 
+// ---- wide form (idv_stream_clstm_wide): H up to 768, the hidden sizes of the VAE encoders (3 * zdim * latent_num).
+// One launch per layer per step; the stream orders the steps, nothing waits on another workgroup inside a launch.  A workgroup
+// (one wave) owns WL_U hidden units of one run for WL_SB streams: thread r holds gate row (r / WL_U) * H + u0 + r % WL_U, so
+// all four gates of a unit meet in the workgroup and the cell update is local.  A launch reads h of ALL units of the previous
+// step (or of this step's layer 0) while its sibling workgroups write this step's h, so h is never updated in place: step t
+// reads the row step t - 1 wrote into hstep (step 0: state) and writes its own row; wide_carry_kernel copies the last rows to
+// state afterwards.  c belongs to the unit's workgroup alone and is updated in state.
+// Every pre-activation is one fmaf chain in a thread: G (layer 0) or b1 (layer 1) first, then the products in increasing k
+// (layer 1: W_ih1 h0, then W_hh1 h1), whatever k, t or the stream's place in its tile is.
+constexpr int WL_U = 16;
+constexpr int WL_SB = 8;
+constexpr int WL_ROWS = 4 * WL_U;
+constexpr int WL_HMAX = 768;
+constexpr int WL_KB = 16;                            // k per weight block; divides H
+
+// hstep: [2 layers][4 runs][k][B][H]
+template <int LAYER>
+__global__ __launch_bounds__(WL_ROWS) void wide_step_kernel(const float* __restrict__ G, const float* __restrict__ wt,
+                                                            const float* __restrict__ b1, float* __restrict__ state,
+                                                            float* __restrict__ hstep, int H, int B, int k, int t) {
+    extern __shared__ __attribute__((aligned(16))) float wl_lds[];
+    const int KT = (LAYER + 1) * H;                 // layer 0: h0(t-1); layer 1: h0(t) then h1(t-1)
+    float* hs = wl_lds;                             // [WL_SB][KT]
+    float* gs = wl_lds + (size_t)WL_SB * KT;        // [WL_SB][WL_ROWS]
+    const int r = threadIdx.x;
+    const int u0 = blockIdx.x * WL_U, run = blockIdx.y, z = run >> 1, s = run & 1;
+    const int b0 = blockIdx.z * WL_SB;
+    const int G4 = 4 * H;
+    const size_t sz = (size_t)B * H;
+    float* st = state + (size_t)run * 4 * sz;       // [layer][h | c][B][H]
+    const float* h0row = hstep + ((size_t)run * k) * sz;
+    const float* h1row = hstep + ((size_t)(4 + run) * k) * sz;
+    const float* src0 = LAYER == 0 ? (t == 0 ? st : h0row + (size_t)(t - 1) * sz) : h0row + (size_t)t * sz;
+    const float* src1 = t == 0 ? st + 2 * sz : h1row + (size_t)(t - 1) * sz;
+    for (int u = r; u < H; u += WL_ROWS) {          // the loads of the 8 streams are independent: all in flight together
+        float v0[WL_SB], v1[WL_SB];
+#pragma unroll
+        for (int sb = 0; sb < WL_SB; ++sb) {
+            const size_t o = (size_t)min(b0 + sb, B - 1) * H + u;
+            v0[sb] = src0[o];
+            if (LAYER == 1) v1[sb] = src1[o];
+        }
+#pragma unroll
+        for (int sb = 0; sb < WL_SB; ++sb) {
+            hs[sb * KT + u] = v0[sb];
+            if (LAYER == 1) hs[sb * KT + H + u] = v1[sb];
+        }
+    }
+    __syncthreads();
+
+    const int g_r = r / WL_U, row = g_r * H + u0 + (r % WL_U);
+    float acc[WL_SB];
+    if (LAYER == 0) {
+        // column of gate row `row` in the idv_pack_lstm_ih order, set s: ((u/16)*4 + g)*16 + u%16 = 64 * (u0/16) + r
+        const int colp = s * G4 + u0 * 4 + r;
+#pragma unroll
+        for (int sb = 0; sb < WL_SB; ++sb) {
+            const int b = min(b0 + sb, B - 1);
+            acc[sb] = G[((size_t)z * k * B + (size_t)t * B + b) * 2 * G4 + colp];
+        }
+    } else {
+        const float bias1 = b1[s * G4 + row];
+#pragma unroll
+        for (int sb = 0; sb < WL_SB; ++sb) acc[sb] = bias1;
+    }
+    const float* w = wt + (size_t)(s * 3 + (LAYER == 0 ? 0 : 1)) * H * G4 + row;     // W_hh0 | W_ih1 followed by W_hh1, [H][4H] each
+    // blocks of WL_KB k: the weights of the next block are loaded (WL_KB independent loads) while this block's chains run;
+    // KT % WL_KB == 0 as H % 16 == 0, and the last block reloads itself instead of reading past the matrices
+    float wv[WL_KB];
+#pragma unroll
+    for (int j = 0; j < WL_KB; ++j) wv[j] = w[(size_t)j * G4];
+    for (int k0 = 0; k0 < KT; k0 += WL_KB) {
+        const int kn = k0 + WL_KB < KT ? k0 + WL_KB : k0;
+        float wn[WL_KB];
+#pragma unroll
+        for (int j = 0; j < WL_KB; ++j) wn[j] = w[(size_t)(kn + j) * G4];
+#pragma unroll
+        for (int j4 = 0; j4 < WL_KB; j4 += 4) {
+            f32x4 hv[WL_SB];
+#pragma unroll
+            for (int sb = 0; sb < WL_SB; ++sb) hv[sb] = *reinterpret_cast<const f32x4*>(hs + sb * KT + k0 + j4);
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+                for (int sb = 0; sb < WL_SB; ++sb) acc[sb] = fmaf(wv[j4 + jj], hv[sb][jj], acc[sb]);
+        }
+#pragma unroll
+        for (int j = 0; j < WL_KB; ++j) wv[j] = wn[j];
+    }
+#pragma unroll
+    for (int sb = 0; sb < WL_SB; ++sb) gs[sb * WL_ROWS + r] = acc[sb];
+    __syncthreads();
+
+    float* cst = st + (size_t)(2 * LAYER + 1) * sz;
+    float* hout = hstep + ((size_t)(LAYER * 4 + run) * k + t) * sz;
+    for (int e = r; e < WL_SB * WL_U; e += WL_ROWS) {
+        const int sb = e / WL_U, ul = e % WL_U, b = b0 + sb;
+        if (b >= B) continue;
+        const float* gq = gs + sb * WL_ROWS + ul;
+        const float ig = sigmoidf_(gq[0]), fg = sigmoidf_(gq[WL_U]);
+        const float gg = tanhf_(gq[2 * WL_U]), og = sigmoidf_(gq[3 * WL_U]);
+        const size_t o = (size_t)b * H + u0 + ul;
+        const float c = fg * cst[o] + ig * gg;
+        cst[o] = c;
+        hout[o] = og * tanhf_(c);
+    }
+}
+
+// h of both layers after the last step -> state (the c halves are already there)
+__global__ void wide_carry_kernel(const float* __restrict__ hstep, float* __restrict__ state, int H, int B, int k) {
+    const size_t sz = (size_t)B * H;
+    const long long n = 8LL * (long long)sz;
+    for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
+        const int lr = (int)(e / (long long)sz), layer = lr >> 2, run = lr & 3;
+        const size_t o = (size_t)(e % (long long)sz);
+        state[((size_t)run * 4 + 2 * layer) * sz + o] = hstep[((size_t)lr * k + (k - 1)) * sz + o];
+    }
+}
+
 }  // namespace
 
 extern "C" int idv_stream_lstm_supported(int H) { return H == SL_H ? 1 : 0; }
+
+extern "C" int idv_stream_clstm_wide_supported(int H) { return (H >= WL_U && H <= WL_HMAX && H % WL_U == 0) ? 1 : 0; }
+
+extern "C" long long idv_stream_clstm_wide_hstep_floats(int H, int B, int k) {
+    if (!idv_stream_clstm_wide_supported(H) || B <= 0 || k <= 0) return -1;
+    return 8LL * k * B * H;
+}
+
+extern "C" int idv_stream_clstm_wide(const float* G, const float* wt, const float* b1, float* state, float* hstep, float* out, int H,
+                                     int B, int k, int Tp, int Jp, void* stream) {
+    if (!G || !wt || !b1 || !state || !hstep || !out || B <= 0 || k <= 0 || Tp < k + 1 || Jp < B * Tp) return IDV_EINVAL;
+    if (!idv_stream_clstm_wide_supported(H)) return IDV_EINVAL;
+    const long long tiles = ((long long)B + WL_SB - 1) / WL_SB;
+    if (tiles > 65535) return IDV_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)(H / WL_U), 4, (unsigned)tiles);
+    const size_t lds0 = sizeof(float) * WL_SB * ((size_t)H + WL_ROWS), lds1 = sizeof(float) * WL_SB * ((size_t)2 * H + WL_ROWS);
+    for (int t = 0; t < k; ++t) {
+        hipLaunchKernelGGL(wide_step_kernel<0>, grid, dim3(WL_ROWS), lds0, st, G, wt, b1, state, hstep, H, B, k, t);
+        hipLaunchKernelGGL(wide_step_kernel<1>, grid, dim3(WL_ROWS), lds1, st, G, wt, b1, state, hstep, H, B, k, t);
+    }
+    int rc = idv_launch_status();
+    if (rc) return rc;
+    long long g = ((long long)H * B * k + 255) / 256;
+    g = g > 4096 ? 4096 : (g < 1 ? 1 : g);
+    hipLaunchKernelGGL(stream_lstm_combine_kernel, dim3((unsigned)g), dim3(256), 0, st, hstep + (size_t)4 * k * B * H, H, B, k, Tp, Jp,
+                       out);
+    long long gc = (8LL * B * H + 255) / 256;
+    gc = gc > 4096 ? 4096 : gc;
+    hipLaunchKernelGGL(wide_carry_kernel, dim3((unsigned)gc), dim3(256), 0, st, hstep, state, H, B, k);
+    return idv_launch_status();
+}
 
 // rows NULL: the lock-step entry
 static int launch_clstm(const float* G, const float* wt, const float* b1, float* state, float* hout, float* out, int H, int B, int k,

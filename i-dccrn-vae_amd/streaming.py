@@ -8,6 +8,9 @@ Concatenating every ``push`` output and the ``flush`` output gives ``model(x_ful
 model reads one frame of history, the LSTM is unidirectional and eval-mode batch norm is a per-channel affine map, so the only
 look-ahead is the STFT window: frame t reads samples [hop*t - win/2, hop*t + win/2).  :class:`StreamPlan` holds the frame and
 emission bookkeeping from which every kernel launch takes its ranges.
+
+:class:`StreamingSessions` runs one such stream per slot, each starting and ending on its own; :class:`StreamingVAE` streams
+the I-DCCRN-VAE pair (noisy encoder, latent draw, fine-tuned decoder with the noisy skips) under the same contract.
 """
 from __future__ import annotations
 
@@ -308,35 +311,17 @@ class _Launch(NamedTuple):
     rows: object
 
 
-class _Streamer:
-    """What both streamers share: the construction guards, the packed weights, the activation and state buffers, and the network
-    over the frames of one launch group.  A subclass supplies the framing, the conv block and the LSTM of its kind (scalars for
-    lock-step streams, a row table for sessions)."""
+class _StreamBase:
+    """What every streamer shares, whatever network it runs: the conv block packs of either engine (``_conv``, the batch an
+    argument), the lock-step conv call, framing, ring update and overlap-add, and the list of per-stream state buffers."""
 
-    def __init__(self, model, batch: int, frames_per_launch: int = 64, max_columns: int = 4096, conv: str = "valu"):
-        self.conv = check_conv(conv)
-        check_model(model, batch)
-        net = model.std_DCCRN
-        params = list(model.parameters())
-        if len(net.lstms) != 1 or not L.lib().idv_stream_lstm_supported(i(net.lstms[0].hidden_size)) or net.lstms[0].num_layer != 2:
-            raise ValueError("StreamingDCCRN: one two-layer ComplexLSTM with hidden size 128 is supported")
-        for blk in list(net.encoders) + list(net.decoders):
-            (blk.conv if hasattr(blk, "conv") else blk.transconv)._check_supported()
-        self.model, self.B = model, batch
-        self.device = params[0].device
-        st = model.stft
-        self.n_fft, self.hop, self.win = st.n_fft, st.hop_length, st.win_length
-        self.F = self.n_fft // 2 + 1
-        self.cap = max(1, min(frames_per_launch, max_columns // batch))
-        self.plan = StreamPlan(self.n_fft, self.hop, self.win, self.cap)
-        self.skip_to_use = list(net.skip_to_use)
-        with torch.no_grad(), torch.cuda.device(self.device):
-            self._pack(model)
-            self._alloc()
-        self.reset()
+    _name = "StreamingDCCRN"       # in messages
 
-    # ------------------------------------------------------------------ construction
-    def _conv(self, conv, blk, C0, C1, Fin):
+    def reset(self):
+        for t in self.state:
+            t.zero_()
+
+    def _conv(self, conv, blk, C0, C1, Fin, B):
         cp = _ConvPack()
         cp.transposed = conv._transposed
         re, im = conv._re, conv._im
@@ -361,11 +346,102 @@ class _Streamer:
                  p(cp.w), p(cp.bias), stream_ptr())
         cp.fold, cp.slope = _fold_and_slope(blk)
         cp.fold = cp.fold.clone()
-        cp.nsplit = int(L.lib().idv_stream_cconv_splits(i(1 if cp.transposed else 0), i(cin), i(cp.Cout), i(Fin), i(self.B)))
+        cp.nsplit = int(L.lib().idv_stream_cconv_splits(i(1 if cp.transposed else 0), i(cin), i(cp.Cout), i(Fin), i(B)))
         if cp.nsplit <= 0:
-            raise ValueError("StreamingDCCRN: unsupported block shape")
+            raise ValueError(f"{self._name}: unsupported block shape")
         return cp
 
+    def _pack_lstm(self, lstm, K: int):
+        """The two-layer ComplexLSTM as the stream LSTM entries read it: the layer-0 projection for idv_pw_gemm (lstm_ih), the
+        transposed W_hh0 / W_ih1 / W_hh1 of both parts (lstm_wt) and b_ih1 + b_hh1 (lstm_b1)."""
+        self.H = lstm.hidden_size
+        self.K = K
+        sd = {k: v.detach().float().contiguous() for k, v in lstm.named_parameters()}
+        H = self.H
+        wih = torch.empty(ops.mtiles_alloc(8 * H) * ((K + 7) // 8 * 4) * 64, dtype=torch.float32, device=self.device)
+        bih = torch.empty(ops.mtiles_alloc(8 * H) * 32, dtype=torch.float32, device=self.device)
+        call("idv_pack_lstm_ih", p(sd["lstm_re.weight_ih_l0"]), p(sd["lstm_re.bias_ih_l0"]), p(sd["lstm_re.bias_hh_l0"]),
+             p(sd["lstm_im.weight_ih_l0"]), p(sd["lstm_im.bias_ih_l0"]), p(sd["lstm_im.bias_hh_l0"]), i(H), i(K), p(wih), p(bih),
+             stream_ptr())
+        self.lstm_ih = (wih, bih)
+        mats = []
+        for part in ("lstm_re", "lstm_im"):
+            for name in ("weight_hh_l0", "weight_ih_l1", "weight_hh_l1"):
+                mats.append(sd[f"{part}.{name}"].t().contiguous())
+        self.lstm_wt = torch.stack(mats).contiguous()
+        self.lstm_b1 = torch.stack([sd[f"{part}.bias_ih_l1"] + sd[f"{part}.bias_hh_l1"] for part in ("lstm_re", "lstm_im")]).contiguous()
+
+    def _conv_call(self, cp: _ConvPack, x0, h0, x1, h1, out, hist_out, x0hist_out, B, k, Tp, Jp):
+        # one call per engine, each with its entry's name as a literal: the static check of the call sites against the header
+        # (tests/test_host_cpu.py) reads literal names only, and a name picked at run time would go unchecked
+        if cp.engine == "mfma":
+            call("idv_stream_cconv_mfma", x0, p(h0), i(cp.C0), x1 if x1 is not None else p(None), p(h1), i(cp.C1), p(cp.w), p(cp.bias),
+                 p(cp.fold), p(cp.slope), out, p(hist_out), x0hist_out, p(self.work), i(cp.nsplit), i(1 if cp.transposed else 0),
+                 i(cp.Cout), i(cp.Fin), i(B), i(k), i(Tp), i(Jp), stream_ptr())
+            return
+        call("idv_stream_cconv", x0, p(h0), i(cp.C0), x1 if x1 is not None else p(None), p(h1), i(cp.C1), p(cp.w), p(cp.bias),
+             p(cp.fold), p(cp.slope), out, p(hist_out), x0hist_out, p(self.work), i(cp.nsplit), i(1 if cp.transposed else 0),
+             i(cp.Cout), i(cp.Fin), i(B), i(k), i(Tp), i(Jp), stream_ptr())
+
+    # ------------------------------------------------------------------ the lock-step signal ends (scalars, one StreamPlan)
+    @staticmethod
+    def _pitched(x: torch.Tensor, B: int):
+        """push's input as the kernels read it: float32 rows at any pitch (a column slice of a longer signal costs no copy);
+        anything else is made contiguous -> (x, row pitch, samples)."""
+        x = x.float()
+        n_new = int(x.shape[1])
+        if (n_new > 1 and x.stride(1) != 1) or (B > 1 and x.stride(0) < n_new):
+            x = x.contiguous()
+        return x, (x.stride(0) if B > 1 else n_new), n_new
+
+    def _lock_frames(self, c: Chunk, io, frames, Tp: int, Jp: int):
+        x, ldx, n_new, n_prev, L_end = io
+        call("idv_stream_frames", p(self.ring), i(self.plan.ring), p(x) if x is not None else p(None), ll(ldx), i(n_new), ll(n_prev),
+             ll(L_end if L_end is not None else -1), i(self.B), i(self.n_fft), i(self.win), i(self.hop), ll(c.t0), i(c.k), frames,
+             i(Tp), i(Jp), stream_ptr())
+
+    def _lock_ring(self, x, ldx: int, n_new: int, n_prev: int):
+        if n_new:
+            call("idv_stream_ring", p(self.ring), i(self.plan.ring), p(x), ll(ldx), i(n_new), ll(n_prev), i(self.B), stream_ptr())
+
+    def _lock_ola(self, c: Chunk, frames, carry, B: int, T_total: int, y, m: int, y_off: int):
+        """Overlap-add of chunk c's inverse-DFT frames (``frames``: a Planar, None when c.k == 0) for B rows; carry [2][B * cap]."""
+        pin = c.parity
+        Tp = c.k + 1
+        Jp = Planar.jp_for(B, Tp)
+        call("idv_stream_ola", frames.ptr() if frames is not None else p(None), i(Tp), i(Jp), p(carry[pin]), i(c.carry_in),
+             p(carry[1 - pin]), i(self.plan.carry_cap), i(B), i(self.n_fft), i(self.win), i(self.hop), ll(c.t0), i(c.k),
+             ll(T_total), ll(c.e0), ll(c.e1), ll(c.p_end), p(y) if m else p(None), i(max(m, 1)), ll(y_off), stream_ptr())
+
+
+class _Streamer(_StreamBase):
+    """What both DCCRN streamers share: the construction guards, the packed weights, the activation and state buffers, and the
+    network over the frames of one launch group.  A subclass supplies the framing, the conv block and the LSTM of its kind
+    (scalars for lock-step streams, a row table for sessions)."""
+
+    def __init__(self, model, batch: int, frames_per_launch: int = 64, max_columns: int = 4096, conv: str = "valu"):
+        self.conv = check_conv(conv)
+        check_model(model, batch)
+        net = model.std_DCCRN
+        params = list(model.parameters())
+        if len(net.lstms) != 1 or not L.lib().idv_stream_lstm_supported(i(net.lstms[0].hidden_size)) or net.lstms[0].num_layer != 2:
+            raise ValueError("StreamingDCCRN: one two-layer ComplexLSTM with hidden size 128 is supported")
+        for blk in list(net.encoders) + list(net.decoders):
+            (blk.conv if hasattr(blk, "conv") else blk.transconv)._check_supported()
+        self.model, self.B = model, batch
+        self.device = params[0].device
+        st = model.stft
+        self.n_fft, self.hop, self.win = st.n_fft, st.hop_length, st.win_length
+        self.F = self.n_fft // 2 + 1
+        self.cap = max(1, min(frames_per_launch, max_columns // batch))
+        self.plan = StreamPlan(self.n_fft, self.hop, self.win, self.cap)
+        self.skip_to_use = list(net.skip_to_use)
+        with torch.no_grad(), torch.cuda.device(self.device):
+            self._pack(model)
+            self._alloc()
+        self.reset()
+
+    # ------------------------------------------------------------------ construction
     def _pack(self, model):
         net = model.std_DCCRN
         F = self.F
@@ -373,7 +449,7 @@ class _Streamer:
         ch, Fin = 1, F
         self.enc_shapes = []                       # (C, F) of every encoder output
         for blk in net.encoders:
-            cp = self._conv(blk.conv, blk, ch, 0, Fin)
+            cp = self._conv(blk.conv, blk, ch, 0, Fin, self.B)
             self.enc.append(cp)
             ch, Fin = cp.Cout, cp.Fout
             self.enc_shapes.append((ch, Fin))
@@ -388,29 +464,13 @@ class _Streamer:
             c1 = self.enc_shapes[n - 1 - di][0] if di in self.skip_to_use else 0
             if c + c1 != blk.transconv.in_channel:
                 raise ValueError("StreamingDCCRN: decoder input channels do not match")
-            cp = self._conv(blk.transconv, blk, c, c1, f)
+            cp = self._conv(blk.transconv, blk, c, c1, f, self.B)
             self.dec.append(cp)
             c, f = cp.Cout, cp.Fout
         if (c, f) != (1, F):
             raise ValueError("StreamingDCCRN: the last decoder must give one channel of n_fft/2 + 1 bins")
         self.conv_engines = [cp.engine for cp in self.enc + self.dec]      # enc0 .. then dec0 ..: nothing falls back unseen
-        lstm = net.lstms[0]
-        self.H = lstm.hidden_size
-        self.K = ch * Fin
-        sd = {k: v.detach().float().contiguous() for k, v in lstm.named_parameters()}
-        H, K = self.H, self.K
-        wih = torch.empty(ops.mtiles_alloc(8 * H) * ((K + 7) // 8 * 4) * 64, dtype=torch.float32, device=self.device)
-        bih = torch.empty(ops.mtiles_alloc(8 * H) * 32, dtype=torch.float32, device=self.device)
-        call("idv_pack_lstm_ih", p(sd["lstm_re.weight_ih_l0"]), p(sd["lstm_re.bias_ih_l0"]), p(sd["lstm_re.bias_hh_l0"]),
-             p(sd["lstm_im.weight_ih_l0"]), p(sd["lstm_im.bias_ih_l0"]), p(sd["lstm_im.bias_hh_l0"]), i(H), i(K), p(wih), p(bih),
-             stream_ptr())
-        self.lstm_ih = (wih, bih)
-        mats = []
-        for part in ("lstm_re", "lstm_im"):
-            for name in ("weight_hh_l0", "weight_ih_l1", "weight_hh_l1"):
-                mats.append(sd[f"{part}.{name}"].t().contiguous())
-        self.lstm_wt = torch.stack(mats).contiguous()
-        self.lstm_b1 = torch.stack([sd[f"{part}.bias_ih_l1"] + sd[f"{part}.bias_hh_l1"] for part in ("lstm_re", "lstm_im")]).contiguous()
+        self._pack_lstm(net.lstms[0], ch * Fin)
         dn = net.dense
         self.dense = [ops.pack_pw(dn.linear_read.weight.detach().float(), dn.linear_read.bias.detach().float()),
                       ops.pack_pw(dn.linear_imag.weight.detach().float(), dn.linear_imag.bias.detach().float())]
@@ -454,10 +514,6 @@ class _Streamer:
         self.ring = torch.zeros(B * self.plan.ring, dtype=torch.float32, device=dev)
         self.carry = torch.zeros(2, B * self.plan.carry_cap, dtype=torch.float32, device=dev)
         self.state = [self.h_in, self.h_dense, self.lstm_state, self.ring, self.carry] + self.h_enc + self.h_dec
-
-    def reset(self):
-        for t in self.state:
-            t.zero_()
 
     # ------------------------------------------------------------------ the network over one launch group
     def _network(self, c, io):
@@ -539,18 +595,12 @@ class StreamingDCCRN(_Streamer):
     # ------------------------------------------------------------------ push / flush
     def push(self, x: torch.Tensor) -> torch.Tensor:
         check_input(x, self.B, self.device)
-        x = x.float()
-        n_new = int(x.shape[1])
-        # the kernels read rows at any pitch (a column slice of a longer signal costs no copy); anything else is made contiguous
-        if (n_new > 1 and x.stride(1) != 1) or (self.B > 1 and x.stride(0) < n_new):
-            x = x.contiguous()
-        ldx = x.stride(0) if self.B > 1 else n_new
+        x, ldx, n_new = self._pitched(x, self.B)
         n_prev = self.plan.n
         with torch.cuda.device(self.device):
             chunks = self.plan.push(n_new)
             y = self._run(chunks, x, ldx, n_new, n_prev, None)
-            if n_new:
-                call("idv_stream_ring", p(self.ring), i(self.plan.ring), p(x), ll(ldx), i(n_new), ll(n_prev), i(self.B), stream_ptr())
+            self._lock_ring(x, ldx, n_new, n_prev)
         return y
 
     def flush(self) -> torch.Tensor:
@@ -569,22 +619,12 @@ class StreamingDCCRN(_Streamer):
         for c in chunks:
             if c.k > 0:
                 self._network(c, (x, ldx, n_new, n_prev, L_end))
-            pin = c.parity
-            frames = self.ifr if c.k > 0 else None
-            Tp = c.k + 1
-            Jp = Planar.jp_for(self.B, Tp)
-            call("idv_stream_ola", frames.ptr() if frames is not None else p(None), i(Tp), i(Jp), p(self.carry[pin]), i(c.carry_in),
-                 p(self.carry[1 - pin]), i(self.plan.carry_cap), i(self.B), i(self.n_fft), i(self.win), i(self.hop), ll(c.t0), i(c.k),
-                 ll(T_total), ll(c.e0), ll(c.e1), ll(c.p_end), p(y) if m else p(None), i(max(m, 1)), ll(c.e0 - chunks[0].e0),
-                 stream_ptr())
+            self._lock_ola(c, self.ifr if c.k > 0 else None, self.carry, self.B, T_total, y, m, c.e0 - chunks[0].e0)
         return y
 
     # ------------------------------------------------------------------ the lock-step kernels of the network
     def _frames(self, c: Chunk, io, frames, Tp: int, Jp: int):
-        x, ldx, n_new, n_prev, L_end = io
-        call("idv_stream_frames", p(self.ring), i(self.plan.ring), p(x) if x is not None else p(None), ll(ldx), i(n_new), ll(n_prev),
-             ll(L_end if L_end is not None else -1), i(self.B), i(self.n_fft), i(self.win), i(self.hop), ll(c.t0), i(c.k), frames,
-             i(Tp), i(Jp), stream_ptr())
+        self._lock_frames(c, io, frames, Tp, Jp)
 
     def _block(self, cp: _ConvPack, c: Chunk, x0, h0, x1, h1, out, hist, x0hist, Tp: int, Jp: int):
         """One conv block: histories are read from half c.parity of the [2][...] buffers and written to the other half."""
@@ -595,18 +635,6 @@ class StreamingDCCRN(_Streamer):
     def _lstm(self, c: Chunk, out, Tp: int, Jp: int):
         call("idv_stream_clstm", p(self.G), p(self.lstm_wt), p(self.lstm_b1), p(self.lstm_state), p(self.hout), out, i(self.H),
              i(self.B), i(c.k), i(Tp), i(Jp), stream_ptr())
-
-    def _conv_call(self, cp: _ConvPack, x0, h0, x1, h1, out, hist_out, x0hist_out, B, k, Tp, Jp):
-        # one call per engine, each with its entry's name as a literal: the static check of the call sites against the header
-        # (tests/test_host_cpu.py) reads literal names only, and a name picked at run time would go unchecked
-        if cp.engine == "mfma":
-            call("idv_stream_cconv_mfma", x0, p(h0), i(cp.C0), x1 if x1 is not None else p(None), p(h1), i(cp.C1), p(cp.w), p(cp.bias),
-                 p(cp.fold), p(cp.slope), out, p(hist_out), x0hist_out, p(self.work), i(cp.nsplit), i(1 if cp.transposed else 0),
-                 i(cp.Cout), i(cp.Fin), i(B), i(k), i(Tp), i(Jp), stream_ptr())
-            return
-        call("idv_stream_cconv", x0, p(h0), i(cp.C0), x1 if x1 is not None else p(None), p(h1), i(cp.C1), p(cp.w), p(cp.bias),
-             p(cp.fold), p(cp.slope), out, p(hist_out), x0hist_out, p(self.work), i(cp.nsplit), i(1 if cp.transposed else 0),
-             i(cp.Cout), i(cp.Fin), i(B), i(k), i(Tp), i(Jp), stream_ptr())
 
 
 class StreamingSessions(_Streamer):
@@ -747,3 +775,328 @@ class StreamingSessions(_Streamer):
     def _lstm(self, c, out, Tp: int, Jp: int):
         call("idv_stream_clstm_rows", p(self.G), p(self.lstm_wt), p(self.lstm_b1), p(self.lstm_state), p(self.hout), out, i(self.H),
              i(self.B), i(c.k), i(Tp), i(Jp), c.rows, stream_ptr())
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The I-DCCRN-VAE pair: noisy encoder -> latent draw -> fine-tuned decoder with the noisy skips (pad='sig') -> mean over the
+# num_samples waveforms (inference.enhance_vae offline).
+
+LATENTS = ("speech", "noise")
+
+
+def check_vae(noisy_encoder, decoder, batch, latent="speech", seed=0, eps=None) -> None:
+    """The construction guards of StreamingVAE (host only, before any GPU work)."""
+    from .model import pvae_module as pm
+    if not isinstance(noisy_encoder, (pm.nsvae_pvae_dccrn_encoder_twophase, pm.pvae_dccrn_encoder_skip_prepare)):
+        raise ValueError("StreamingVAE takes a model.pvae_module.nsvae_pvae_dccrn_encoder_twophase or pvae_dccrn_encoder_skip_prepare "
+                         "as noisy_encoder")
+    if isinstance(decoder, pm.pvae_dccrn_decoder_skip_prepare):
+        raise ValueError("StreamingVAE: pvae_dccrn_decoder_skip_prepare decodes with pad='zero' (zero skips), which is not streamed; "
+                         "pass the fine-tuned nsvae_pvae_dccrn_decoder_twophase (run with pad='sig')")
+    if not isinstance(decoder, pm.nsvae_pvae_dccrn_decoder_twophase):
+        raise ValueError("StreamingVAE takes a model.pvae_module.nsvae_pvae_dccrn_decoder_twophase as decoder")
+    if not isinstance(latent, str) or latent not in LATENTS:
+        raise ValueError(f"latent must be one of {LATENTS}, got {latent!r}")
+    latent_num = getattr(noisy_encoder, "latent_num", 1)
+    if latent == "noise" and latent_num != 2:
+        raise ValueError("latent='noise' needs an encoder with latent_num 2: this encoder has no noise latent")
+    if not noisy_encoder.causal or not decoder.causal or any(e.conv._cfg[2][1] != 1 for e in noisy_encoder.encoders):
+        raise ValueError("StreamingVAE needs a causal encoder and decoder (encoder time padding 1): with time padding 0 frame t needs "
+                         "x[t+1]")
+    se, sd = noisy_encoder.stft, decoder.istft
+    if (se.n_fft, se.hop_length, se.win_length) != (sd.n_fft, sd.hop_length, sd.win_length):
+        raise ValueError("StreamingVAE: encoder and decoder differ in n_fft / hop / win")
+    if noisy_encoder.zdim != decoder.zdim or noisy_encoder.num_samples != decoder.num_samples:
+        raise ValueError("StreamingVAE: encoder and decoder differ in zdim or num_samples")
+    if decoder.recon_type not in ("mask", "real_imag"):
+        raise ValueError(f"StreamingVAE: unknown recon_type {decoder.recon_type!r} (mask or real_imag)")
+    if isinstance(batch, bool) or not isinstance(batch, int) or batch <= 0:
+        raise ValueError("StreamingVAE: batch must be a positive int")
+    check_seed(seed)
+    if eps is not None and not callable(eps):
+        raise ValueError("eps must be None (the streamer's own draws) or a callable (t0, k) -> (eps_r, eps_i)")
+    lstms = noisy_encoder.lstms
+    if (len(lstms) != 1 or lstms[0].num_layer != 2 or lstms[0].hidden_size != 3 * noisy_encoder.zdim * latent_num
+            or L.lib().idv_stream_clstm_wide_supported(i(lstms[0].hidden_size)) != 1):
+        raise ValueError("StreamingVAE: one two-layer ComplexLSTM with hidden size 3 * zdim * latent_num, a multiple of 16 up to 768, "
+                         "is supported")
+    # the decoder's channel chain against the encoder's skips
+    enc_c = [e.conv.out_channel for e in noisy_encoder.encoders]
+    if len(decoder.decoders) != len(enc_c) or lstms[0].input_size % enc_c[-1]:
+        raise ValueError("StreamingVAE: the decoder does not mirror the encoder")
+    top_f = lstms[0].input_size // enc_c[-1]
+    if decoder.dense.in_channel != decoder.zdim or decoder.dense.out_channel % top_f:
+        raise ValueError("StreamingVAE: the decoder's dense layer does not match zdim and the top encoder shape")
+    c = decoder.dense.out_channel // top_f
+    for di, blk in enumerate(decoder.decoders):
+        c1 = enc_c[len(enc_c) - 1 - di] if (decoder.use_sc and di in decoder.skip_to_use) else 0
+        if c + c1 != blk.transconv.in_channel:
+            raise ValueError(f"StreamingVAE: decoder block {di} takes {blk.transconv.in_channel} channels, the chain and the encoder's "
+                             f"skip give {c} + {c1}")
+        c = blk.transconv.out_channel
+    if c != 1:
+        raise ValueError("StreamingVAE: the last decoder must give one channel")
+    for m in (noisy_encoder, decoder):
+        if any(not q.is_cuda for q in m.parameters()) or any(not b.is_cuda for b in m.buffers()):
+            raise RuntimeError("StreamingVAE runs on the MI355X only: move the models to the GPU first (there is no CPU path)")
+
+
+def check_seed(seed) -> int:
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 63:
+        raise ValueError("seed must be an int in [0, 2**63)")
+    return seed
+
+
+class StreamingVAE(_StreamBase):
+    """Lock-step streaming I-DCCRN-VAE enhancement for ``batch`` signals: the noisy encoder at batch B, one latent draw per
+    sample, the fine-tuned decoder with the noisy skips (``pad='sig'``) at batch B * num_samples (row b * ns + s).
+
+        st = StreamingVAE(noisy_encoder, decoder, batch=B, seed=0, latent="speech", average=True, eps=None)
+        y = st.push(x)          # x [B, n] on the GPU -> [B, m] (average=False: [B * ns, m], row b * ns + s)
+        y = st.flush()
+        er, ei = st.eps(t0, k)  # the draws frames t0 .. t0+k-1 use, each [B, ns, k, zdim]
+
+    Frame and sample bookkeeping is :class:`StreamPlan`, as in :class:`StreamingDCCRN`.  All pushes and the flush together
+    return what ``inference.enhance_vae(noisy_encoder, decoder, x_full, eps=<the same draws>, latent=latent)`` returns, and the
+    same bits however the signal is cut.  The draws come from a counter-based generator (``idv_stream_eps``): a draw is a
+    function of (seed, b, s, t, u) alone, the same seed gives the same draws for every signal, and ``seed`` may be set between
+    signals.  ``eps`` may instead be a callable ``(t0, k) -> (eps_r, eps_i)`` ([B, ns, k, zdim] each, on the GPU) that supplies
+    the chosen latent's draws.  ``conv`` as in :class:`StreamingDCCRN`.  Exact fp32 whatever ``ops.PRECISION`` is; weights are
+    packed at construction.
+    """
+
+    _name = "StreamingVAE"
+
+    def __init__(self, noisy_encoder, decoder, batch: int, seed: int = 0, latent: str = "speech", average: bool = True, eps=None,
+                 frames_per_launch: int = 64, max_columns: int = 4096, conv: str = "valu"):
+        self.conv = check_conv(conv)
+        check_vae(noisy_encoder, decoder, batch, latent, seed, eps)
+        for blk in list(noisy_encoder.encoders) + list(decoder.decoders):
+            (blk.conv if hasattr(blk, "conv") else blk.transconv)._check_supported()
+        self.encoder, self.decoder, self.B = noisy_encoder, decoder, batch
+        self.ns = noisy_encoder.num_samples
+        self.Bn = batch * self.ns
+        self.zdim = noisy_encoder.zdim
+        self.latent, self.average, self._eps_fn = latent, bool(average), eps
+        self._seed = seed
+        self.device = next(noisy_encoder.parameters()).device
+        st = noisy_encoder.stft
+        self.n_fft, self.hop, self.win = st.n_fft, st.hop_length, st.win_length
+        self.F = self.n_fft // 2 + 1
+        self.cap = max(1, min(frames_per_launch, max_columns // self.Bn))
+        self.plan = StreamPlan(self.n_fft, self.hop, self.win, self.cap)
+        self.skip_to_use = list(decoder.skip_to_use) if decoder.use_sc else []
+        self.recon = decoder.recon_type
+        with torch.no_grad(), torch.cuda.device(self.device):
+            self._pack()
+            self._alloc()
+        self.reset()
+
+    @property
+    def seed(self) -> int:
+        return self._seed
+
+    @seed.setter
+    def seed(self, v):
+        self._seed = check_seed(v)
+
+    def reset(self):
+        """Zero every per-stream state buffer and the bookkeeping (done by construction and by flush); the seed stays."""
+        super().reset()
+        self.plan.reset()
+
+    # ------------------------------------------------------------------ construction
+    def _pack(self):
+        enc, dec = self.encoder, self.decoder
+        self.enc, self.enc_shapes = [], []
+        ch, Fin = 1, self.F
+        for blk in enc.encoders:
+            cp = self._conv(blk.conv, blk, ch, 0, Fin, self.B)
+            self.enc.append(cp)
+            ch, Fin = cp.Cout, cp.Fout
+            self.enc_shapes.append((ch, Fin))
+        if ch * Fin != enc.lstms[0].input_size:
+            raise ValueError("StreamingVAE: the LSTM input does not match the top encoder shape")
+        dch = dec.dense.out_channel // Fin
+        self.dense_out = (dch, Fin)
+        self.dec = []
+        n = len(self.enc)
+        c, f = dch, Fin
+        for di, blk in enumerate(dec.decoders):
+            c1 = self.enc_shapes[n - 1 - di][0] if di in self.skip_to_use else 0
+            if c1 and self.enc_shapes[n - 1 - di][1] != f:
+                raise ValueError("StreamingVAE: a skip's bins do not match the decoder block")
+            cp = self._conv(blk.transconv, blk, c, c1, f, self.Bn)
+            self.dec.append(cp)
+            c, f = cp.Cout, cp.Fout
+        if (c, f) != (1, self.F):
+            raise ValueError("StreamingVAE: the last decoder must give one channel of n_fft/2 + 1 bins")
+        self.conv_engines = [cp.engine for cp in self.enc + self.dec]      # enc0 .. then dec0 ..
+        self._pack_lstm(enc.lstms[0], ch * Fin)
+        dn = dec.dense
+        self.dense = [ops.pack_pw(dn.linear_read.weight.detach().float(), dn.linear_read.bias.detach().float()),
+                      ops.pack_pw(dn.linear_imag.weight.detach().float(), dn.linear_imag.bias.detach().float())]
+        dft = ops.DftPlan(self.n_fft, self.win, self.hop, 1, self.device)
+        self.dft_fwd, self.dft_inv = dft.fwd, dft.inv
+        o = 3 * self.zdim * LATENTS.index(self.latent)
+        self.lat_off = (o, o + self.zdim, o + 2 * self.zdim)
+
+    def _alloc(self):
+        B, Bn, dev, cap = self.B, self.Bn, self.device, self.cap
+        Tp = cap + 1
+        mk = lambda C, F, b: Planar.empty(C, F, b, cap, Tp, dev, zero=True)
+        # encoder side, batch B
+        self.fr = mk(1, self.win // 2, B)
+        self.X = mk(1, self.F, B)
+        self.enc_out = [mk(c, f, B) for c, f in self.enc_shapes]
+        self.lat = mk(self.H, 1, B)
+        self.G = torch.empty(2 * B * cap * 8 * self.H, dtype=torch.float32, device=dev)
+        self.hstep = torch.empty(int(L.lib().idv_stream_clstm_wide_hstep_floats(i(self.H), i(B), i(cap))), dtype=torch.float32, device=dev)
+        # decoder side, batch Bn = B * ns, row b * ns + s
+        self.eps_buf = torch.empty(2, Bn * cap * self.zdim, dtype=torch.float32, device=dev)
+        self.z = mk(self.zdim, 1, Bn)
+        self.dense_buf = mk(*self.dense_out, Bn)
+        n = len(self.enc)
+        self.skip_n = {di: mk(*self.enc_shapes[n - 1 - di], Bn) for di in self.skip_to_use if di < n}
+        self.h_skip_n = {di: torch.zeros(2 * self.enc_shapes[n - 1 - di][0] * self.enc_shapes[n - 1 - di][1] * Bn, dtype=torch.float32,
+                                         device=dev) for di in self.skip_n}
+        self.dec_out = [mk(cp.Cout, cp.Fout, Bn) for cp in self.dec]
+        self.pred = mk(1, self.F, Bn)
+        self.ifr = mk(1, self.win // 2, Bn)
+        work = max([cp.nsplit * 2 * cp.Cout * cp.Fout * B * cap for cp in self.enc if cp.nsplit > 1] +
+                   [cp.nsplit * 2 * cp.Cout * cp.Fout * Bn * cap for cp in self.dec if cp.nsplit > 1] + [0])
+        self.work = torch.empty(max(work, 1), dtype=torch.float32, device=dev)
+        # per-stream state
+        hist = lambda C, F, b: torch.zeros(2, 2 * C * F * b, dtype=torch.float32, device=dev)
+        self.h_in = hist(1, self.F, B)
+        self.h_enc = [hist(c, f, B) for c, f in self.enc_shapes]
+        self.lstm_state = torch.zeros(4 * 4 * B * self.H, dtype=torch.float32, device=dev)
+        self.h_dense = hist(*self.dense_out, Bn)
+        self.h_dec = [hist(cp.Cout, cp.Fout, Bn) for cp in self.dec[:-1]]
+        self.ring = torch.zeros(B * self.plan.ring, dtype=torch.float32, device=dev)
+        self.carry = torch.zeros(2, Bn * self.plan.carry_cap, dtype=torch.float32, device=dev)
+        self.state = [self.h_in, self.h_dense, self.lstm_state, self.ring, self.carry] + self.h_enc + self.h_dec
+
+    # ------------------------------------------------------------------ the draws
+    def eps(self, t0: int, k: int):
+        """The draws frames t0 .. t0+k-1 use with the streamer's own generator and its current seed: (eps_r, eps_i), each
+        [B, ns, k, zdim]."""
+        if isinstance(t0, bool) or not isinstance(t0, int) or t0 < 0 or isinstance(k, bool) or not isinstance(k, int) or k <= 0:
+            raise ValueError("eps(t0, k): t0 >= 0 and k > 0 frames")
+        out = torch.empty(2, self.B, self.ns, k, self.zdim, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            call("idv_stream_eps", ll(self._seed), ll(t0), i(k), i(self.B), i(self.ns), i(self.zdim), p(out[0]), p(out[1]), stream_ptr())
+        return out[0], out[1]
+
+    def _draws(self, c: Chunk):
+        """Device pointers of eps_r / eps_i [B][ns][c.k][zdim] of chunk c."""
+        if self._eps_fn is None:
+            call("idv_stream_eps", ll(self._seed), ll(c.t0), i(c.k), i(self.B), i(self.ns), i(self.zdim), p(self.eps_buf[0]),
+                 p(self.eps_buf[1]), stream_ptr())
+            return p(self.eps_buf[0]), p(self.eps_buf[1])
+        pair = self._eps_fn(c.t0, c.k)
+        want = (self.B, self.ns, c.k, self.zdim)
+        if not isinstance(pair, (tuple, list)) or len(pair) != 2:
+            raise ValueError("eps(t0, k) must return (eps_r, eps_i)")
+        out = []
+        for t in pair:
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != want:
+                raise ValueError(f"eps(t0, k) must return two tensors of shape {want}")
+            if t.device != self.device:
+                raise RuntimeError("eps(t0, k) must return tensors on the streamer's GPU")
+            out.append(p(t.float().contiguous()))
+        return out
+
+    # ------------------------------------------------------------------ push / flush
+    def push(self, x: torch.Tensor) -> torch.Tensor:
+        check_input(x, self.B, self.device)
+        x, ldx, n_new = self._pitched(x, self.B)
+        n_prev = self.plan.n
+        with torch.no_grad(), torch.cuda.device(self.device):
+            chunks = self.plan.push(n_new)
+            y = self._run(chunks, x, ldx, n_new, n_prev, None)
+            self._lock_ring(x, ldx, n_new, n_prev)
+        return y
+
+    def flush(self) -> torch.Tensor:
+        L_total = self.plan.n
+        self.plan.check_flush(L_total)
+        with torch.no_grad(), torch.cuda.device(self.device):
+            chunks = self.plan.flush()
+            y = self._run(chunks, None, 0, 0, L_total, L_total)
+            self.reset()
+        return y
+
+    def _run(self, chunks: List[Chunk], x, ldx: int, n_new: int, n_prev: int, L_end: Optional[int]) -> torch.Tensor:
+        m = (chunks[-1].e1 - chunks[0].e0) if chunks else 0
+        y = torch.empty(self.Bn, m, dtype=torch.float32, device=self.device)
+        T_total = self.plan.total_frames(L_end) if L_end is not None else -1
+        for c in chunks:
+            if c.k > 0:
+                self._network(c, (x, ldx, n_new, n_prev, L_end))
+            self._lock_ola(c, self.ifr if c.k > 0 else None, self.carry, self.Bn, T_total, y, m, c.e0 - chunks[0].e0)
+        if not self.average:
+            return y
+        out = torch.empty(self.B, m, dtype=torch.float32, device=self.device)
+        if m:
+            call("idv_mean_over_samples", p(y), i(self.ns), i(self.B), i(m), p(out), stream_ptr())
+        return out
+
+    # ------------------------------------------------------------------ the network over one chunk
+    def _network(self, c: Chunk, io):
+        """Frames -> spectrum -> encoders -> wide LSTM (batch B) -> draws -> reparameterisation -> dense -> decoders with the
+        repeated skips -> mask -> windowed inverse-DFT frames (self.ifr), batch B * ns."""
+        B, Bn, ns, k, P = self.B, self.Bn, self.ns, c.k, c.parity
+        Tp = k + 1
+        Jp, Jpn = Planar.jp_for(B, Tp), Planar.jp_for(Bn, Tp)
+        s = stream_ptr()
+        ptr = lambda pl, plane=0: L._P(pl.buf.data_ptr() + 4 * (ops.SLACK + plane * pl.F * Jp))
+        ptrn = lambda pl, plane=0: L._P(pl.buf.data_ptr() + 4 * (ops.SLACK + plane * pl.F * Jpn))
+        self._lock_frames(c, io, ptr(self.fr), Tp, Jp)
+        ops.pw_gemm(ptr(self.fr), self.win, self.dft_fwd[0], self.dft_fwd[1], 2 * self.F, B, Tp, Jp, k, ptr(self.X))
+        src, hsrc = self.X, self.h_in
+        for e, cp in enumerate(self.enc):
+            out = self.enc_out[e]
+            self._conv_call(cp, ptr(src), hsrc[P], None, None, ptr(out), self.h_enc[e][1 - P],
+                            p(self.h_in[1 - P]) if e == 0 else p(None), B, k, Tp, Jp)
+            src, hsrc = out, self.h_enc[e]
+        # LSTM: layer-0 projection of both input parts (idv_pw_gemm as offline), then one launch per layer per step
+        H, K = self.H, self.K
+        wih, bih = self.lstm_ih
+        top = self.enc_out[-1]
+        for z in range(2):
+            ops.pw_gemm(ptr(top, z * top.C), K, wih, bih, 8 * H, B, Tp, Jp, k,
+                        L._P(self.G.data_ptr() + 4 * z * k * B * 8 * H), swap=True, ldo=8 * H)
+        call("idv_stream_clstm_wide", p(self.G), p(self.lstm_wt), p(self.lstm_b1), p(self.lstm_state), p(self.hstep), ptr(self.lat),
+             i(H), i(B), i(k), i(Tp), i(Jp), s)
+        # latent draw of the chosen latent, batch B -> B * ns
+        er, ei = self._draws(c)
+        zd = self.zdim
+        call("idv_reparam", ptr(self.lat), i(H), i(self.lat_off[0]), i(self.lat_off[1]), i(self.lat_off[2]), i(zd), er, ei, i(ns), i(B),
+             i(k), i(Tp), i(Jp), ptrn(self.z), i(Jpn), s)
+        dc, df = self.dense_out
+        for ri, pk in enumerate(self.dense):
+            ops.pw_gemm(ptrn(self.z, ri * zd), zd, pk[0], pk[1], dc * df, Bn, Tp, Jpn, k, ptrn(self.dense_buf, ri * dc))
+        # decoders: the skips and the history half this chunk reads, repeated to batch B * ns
+        src, hsrc = self.dense_buf, self.h_dense
+        n = len(self.enc)
+        for di, cp in enumerate(self.dec):
+            out = self.dec_out[di]
+            x1 = h1 = None
+            if di in self.skip_n:
+                sk = n - 1 - di
+                sc, sf = self.enc_shapes[sk]
+                call("idv_stream_repeat", ptr(self.enc_out[sk]), p(self.h_enc[sk][P]), i(sc), i(sf), i(B), i(ns), i(k), i(Tp), i(Jp),
+                     ptrn(self.skip_n[di]), p(self.h_skip_n[di]), i(Jpn), s)
+                x1, h1 = ptrn(self.skip_n[di]), self.h_skip_n[di]
+            hout = self.h_dec[di][1 - P] if di < len(self.h_dec) else None      # nothing reads the last block's history
+            self._conv_call(cp, ptrn(src), hsrc[P], x1, h1, ptrn(out), hout, p(self.h_dense[1 - P]) if di == 0 else p(None), Bn, k,
+                            Tp, Jpn)
+            if di < len(self.h_dec):
+                src, hsrc = out, self.h_dec[di]
+        pred = self.dec_out[-1]
+        if self.recon == "mask":
+            call("idv_mask_apply", ptrn(pred), ptr(self.X), i(ns), i(Jp), ptrn(self.pred), p(None), i(self.F), i(Bn), i(k), i(Tp),
+                 i(Jpn), s)
+            pred = self.pred
+        ops.pw_gemm(ptrn(pred), 2 * self.F, self.dft_inv[0], self.dft_inv[1], self.win, Bn, Tp, Jpn, k, ptrn(self.ifr))

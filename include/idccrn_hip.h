@@ -736,6 +736,29 @@ int idv_stream_cconv_mfma_rows(const float* x0, const float* h0, int C0, const f
                                float* work, int nsplit, int transposed, int Cout, int Fin, int B, int k_launch, int Tp, int Jp,
                                const long long* rows, void* stream);
 
+/* ---- streaming I-DCCRN-VAE enhancement (stream_lstm.hip, stream_io.hip; streaming.StreamingVAE; additive entries:
+ * IDV_ABI_VERSION is unchanged).  The noisy encoder runs at batch B, the decoder at batch B * ns with row b * ns + s, the order
+ * of idv_reparam and idv_mask_apply(x_div = ns).  Lock-step only. */
+/* idv_stream_clstm for the hidden sizes of the VAE encoders: H % 16 == 0, 16 <= H <= 768 (idv_stream_clstm_wide_supported).
+ * G, wt, b1, state and out as idv_stream_clstm.  hstep: idv_stream_clstm_wide_hstep_floats(H, B, k) = 8 * k * B * H floats of
+ * scratch, [2 layers][4 runs][k*B][H]: the h of every step (h is never updated in place; the last rows go to state at the end).
+ * One launch per layer per step (2k + 2 launches), no cooperative launch and no wait on another workgroup.  Every
+ * pre-activation is one fmaf chain: G or b1 first, then the products in increasing k (layer 1: W_ih1 h0, then W_hh1 h1). */
+int idv_stream_clstm_wide_supported(int H);
+long long idv_stream_clstm_wide_hstep_floats(int H, int B, int k);
+int idv_stream_clstm_wide(const float* G, const float* wt, const float* b1, float* state, float* hstep, float* out, int H, int B,
+                          int k, int Tp, int Jp, void* stream);
+/* The two Gaussian draws of idv_reparam for frames t0 .. t0+k-1: eps_r, eps_i [B][ns][k][zdim] (idv_reparam's layout with
+ * T = k).  Philox4x32-10, key (seed low 32, seed high 32), counter (t low, t high, b*ns + s, u); words 0 and 1 through
+ * Box-Muller: u1 = ((w0 >> 8) + 1) 2^-24, theta = 2 pi (w1 >> 8) 2^-24, r = sqrtf(-2 logf(u1)), eps_r = r cosf(theta),
+ * eps_i = r sinf(theta).  A draw depends on (seed, b, s, t, u) alone. */
+int idv_stream_eps(long long seed, long long t0, int k, int B, int ns, int zdim, float* eps_r, float* eps_i, void* stream);
+/* A skip at batch B * ns: columns b*Tp + 1 .. b*Tp + k of x (planar [2][C][F][Jp]) go to columns (b*ns + s)*Tp + 1 .. of xn
+ * (planar [2][C][F][Jpn]) for s < ns, and hist [2][C][F][B] (the history half the chunk reads; NULL with histn: none) to
+ * histn [2][C][F][B*ns]. */
+int idv_stream_repeat(const float* x, const float* hist, int C, int F, int B, int ns, int k, int Tp, int Jp, float* xn, float* histn,
+                      int Jpn, void* stream);
+
 /* ---- batches of utterances of different lengths (ragged.hip, reduce.hip; inference.enhance_* / compute_sisdr with `lengths`) ---
  * lens: device int32[], samples per utterance.  Utterance b has T_b = 1 + lens[b] / hop frames and hop * (T_b - 1) output samples;
  * the batch is laid out for Tmax = max_b T_b frames, Tp >= Tmax + 1.  A causal network computes frame t from frames <= t, so only

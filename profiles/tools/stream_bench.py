@@ -1,7 +1,7 @@
 """Streaming enhancement benchmark: one JSON line per batch of lock-step streams, one hop (100 samples) per push.
 
     python profiles/tools/stream_bench.py [--batches 1,16,128,512,1024] [--seconds 2] [--catchup] [--far-seconds 3600] [--sessions]
-                                           [--conv valu|mfma|both]
+                                           [--conv valu|mfma|both] [--vae]
 
 Per line: device time per push (HIP events around >= --seconds of pushes after warm-up), host wall time per push (synchronised),
 the real-time factor (hop / 16 kHz = 6.25 ms over the wall time) and the algorithmic GFLOP per push (4 real products per complex
@@ -13,7 +13,10 @@ that they share the card and its clocks (field "round").  --sessions measures st
 instead (metric "sessions_push"): every slot active, slot b 13 * (b % 7) samples ahead of slot 0, so the slots stand at staggered
 positions and each hop push still completes one frame per slot; counts are passed as a host list on every push.  The
 streams are never flushed; pushes are column slices of a 4 s signal taken round-robin (no copy).  Full-width DCCRN-CL,
-synthetic weights.
+synthetic weights.  --vae measures streaming.StreamingVAE instead (metric "vae_push"): the full-width NSVAE encoder (zdim 128,
+latent_num 2: LSTM hidden 768) and fine-tuned decoder with num_samples 3, default batches 1,16,128; each line adds the device
+time of the wide LSTM entry alone at the push's shape (events around repeated calls of idv_stream_clstm_wide on the streamer's
+own buffers, after the push measurements) and its share of the device time of a push.
 """
 from __future__ import annotations
 
@@ -44,19 +47,54 @@ def gflop_per_frame(st) -> float:
     return 2 * macs / 1e9
 
 
-def build(B, sessions=False, conv="valu"):
+def gflop_per_frame_vae(st) -> float:
+    """Per stream: the encoder blocks, LSTM projection and recurrence once, the dense layer and decoder blocks ns times."""
+    conv = lambda cp: 4 * (cp.C0 + cp.C1) * cp.Cout * 10 * (cp.Fin if cp.transposed else cp.Fout)
+    H, K = st.H, st.K
+    macs = sum(conv(cp) for cp in st.enc) + 2 * 8 * H * K + 4 * 3 * 4 * H * H + 2 * st.F * WIN
+    macs += st.ns * (sum(conv(cp) for cp in st.dec) + 2 * st.zdim * st.dense_out[0] * st.dense_out[1] + 2 * st.F * WIN)
+    return 2 * macs / 1e9
+
+
+def wide_lstm_ms(st, k=1, reps=200) -> float:
+    """Device time of idv_stream_clstm_wide alone for k steps at the streamer's batch (it advances the streamer's LSTM state)."""
+    L = importlib.import_module("i-dccrn-vae_amd._lib")
+    ops = importlib.import_module("i-dccrn-vae_amd.ops")
+    Tp = k + 1
+    Jp = ops.Planar.jp_for(st.B, Tp)
+    args = (L.p(st.G), L.p(st.lstm_wt), L.p(st.lstm_b1), L.p(st.lstm_state), L.p(st.hstep), st.lat.ptr(), L.i(st.H), L.i(st.B), L.i(k),
+            L.i(Tp), L.i(Jp), L.stream_ptr())
+    for _ in range(10):
+        L.call("idv_stream_clstm_wide", *args)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        L.call("idv_stream_clstm_wide", *args)
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def build(B, sessions=False, conv="valu", vae=False):
     pm = importlib.import_module("i-dccrn-vae_amd.model.pvae_module")
     S = importlib.import_module("i-dccrn-vae_amd.streaming")
     from oracle import idccrn_oracle as O
     np_ = O.net_params(True, 32)
+    if vae:
+        load = lambda m, seed: m.load_state_dict(O.synth_state_dict({k: tuple(v.shape) for k, v in m.state_dict().items()}, seed))
+        enc = pm.nsvae_pvae_dccrn_encoder_twophase(np_, True, "cuda", 128, NFFT, HOP, WIN, 3, 2)
+        dec = pm.nsvae_pvae_dccrn_decoder_twophase(np_, True, "cuda", 3, 128, NFFT, HOP, WIN, "mask", True, [0, 1, 2, 3, 4, 5], False)
+        load(enc, 9)
+        load(dec, 10)
+        return S.StreamingVAE(enc.cuda(), dec.cuda(), batch=B, seed=0, conv=conv)
     m = pm.DCCRN_(NFFT, HOP, np_, True, "cuda", WIN, [0, 1, 2, 3, 4, 5], "mask", False, None, None)
     m.load_state_dict(O.synth_state_dict({k: tuple(v.shape) for k, v in m.state_dict().items()}, 7))
     m = m.cuda()
     return S.StreamingSessions(m, slots=B, conv=conv) if sessions else S.StreamingDCCRN(m, batch=B, conv=conv)
 
 
-def run(B, seconds, n=HOP, far_seconds=0, sessions=False, conv="valu"):
-    st = build(B, sessions, conv)
+def run(B, seconds, n=HOP, far_seconds=0, sessions=False, conv="valu", vae=False):
+    st = build(B, sessions, conv, vae)
     x = torch.randn(B, 64000, device="cuda") * 0.1
     pos = 0
     if sessions:                                # stagger the slots: slot b starts 13 * (b % 7) samples ahead
@@ -100,19 +138,38 @@ def run(B, seconds, n=HOP, far_seconds=0, sessions=False, conv="valu"):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--batches", default="1,16,128,512,1024")
+    ap.add_argument("--batches", default=None)
     ap.add_argument("--seconds", type=float, default=2.0)
     ap.add_argument("--catchup", action="store_true")
     ap.add_argument("--far-seconds", type=int, default=0)
     ap.add_argument("--sessions", action="store_true")
     ap.add_argument("--conv", choices=["valu", "mfma", "both"], default="valu")
+    ap.add_argument("--vae", action="store_true")
     a = ap.parse_args()
+    if a.vae and (a.sessions or a.catchup or a.far_seconds):
+        ap.error("--vae measures hop pushes of StreamingVAE only")
+    if a.batches is None:
+        a.batches = "1,16,128" if a.vae else "1,16,128,512,1024"
     torch.set_grad_enabled(False)
     budget = 1e3 * HOP / SR
     turns = [("valu", 0), ("mfma", 0), ("valu", 1), ("mfma", 1)] if a.conv == "both" else [(a.conv, 0)]
     conv1 = "mfma" if a.conv == "both" else a.conv            # the single-engine lines below
     for B in [int(v) for v in a.batches.split(",") if v]:
         for conv, rnd in turns:
+            if a.vae:
+                st, dev_ms, wall_ms, _ = run(B, a.seconds, conv=conv, vae=True)
+                gf = gflop_per_frame_vae(st) * B
+                lstm_ms = wide_lstm_ms(st)
+                print(json.dumps({"metric": "vae_push", "B": B, "ns": st.ns, "H": st.H, "hop": HOP,
+                                  "device_ms_per_push": round(dev_ms, 4), "wall_ms_per_push": round(wall_ms, 4),
+                                  "rtf": round(budget / wall_ms, 3), "device_rtf": round(budget / dev_ms, 3),
+                                  "under_hop_budget": bool(wall_ms < budget), "wide_lstm_device_ms": round(lstm_ms, 4),
+                                  "wide_lstm_share": round(lstm_ms / dev_ms, 3), "gflop_per_push": round(gf, 3),
+                                  "tflops_device": round(gf / dev_ms, 2), "frames_per_launch": st.cap, "conv": conv,
+                                  "conv_engines": st.conv_engines.count("mfma"), "round": rnd}), flush=True)
+                del st
+                torch.cuda.empty_cache()
+                continue
             st, dev_ms, wall_ms, _ = run(B, a.seconds, sessions=a.sessions, conv=conv)
             gf = gflop_per_frame(st) * B
             print(json.dumps({"metric": "sessions_push" if a.sessions else "stream_push", "B": B, "hop": HOP,
