@@ -204,13 +204,25 @@ __device__ __forceinline__ void philox4x32_10(uint32_t k0, uint32_t k1, uint32_t
 
 // eps_r, eps_i [B][ns][k][zdim] for frames t0 .. t0+k-1: counter (t low, t high, b*ns + s, u), key (seed low, seed high); words
 // 0 and 1 through Box-Muller.  A draw depends on (seed, b, s, t, u) only.
+// ROWS (idv_stream_eps_rows): k is k_launch, slot b = bs / ns starts at its own t0_b and draws its first k_b frames; the rest of
+// its entries are zero.
+template <bool ROWS>
 __global__ void stream_eps_kernel(unsigned long long seed, long long t0, int k, int Bn, int zdim, float* __restrict__ eps_r,
-                                  float* __restrict__ eps_i) {
+                                  float* __restrict__ eps_i, int ns, const long long* __restrict__ rows) {
     const long long n = (long long)Bn * k * zdim;
     for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
         const uint32_t u = (uint32_t)(e % zdim);
         const long long tl = (e / zdim) % k;
         const uint32_t bs = (uint32_t)(e / ((long long)zdim * k));
+        if (ROWS) {
+            const long long* row = rows + (size_t)(bs / (uint32_t)ns) * IDV_STREAM_ROW_FIELDS;
+            if (tl >= row[IDV_ROW_K]) {
+                eps_r[e] = 0.f;
+                eps_i[e] = 0.f;
+                continue;
+            }
+            t0 = row[IDV_ROW_T0];
+        }
         const unsigned long long t = (unsigned long long)(t0 + tl);
         uint32_t w0, w1;
         philox4x32_10((uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)t, (uint32_t)(t >> 32), bs, u, w0, w1);
@@ -223,8 +235,12 @@ __global__ void stream_eps_kernel(unsigned long long seed, long long t0, int k, 
 }
 
 // rows of x (pitch Jp, column b*Tp + 1 + tl, tl < k) -> xn (pitch Jpn, column (b*ns + s)*Tp + 1 + tl); hist[rows][B] -> histn[rows][B*ns]
+// ROWS (idv_stream_repeat_rows): k is k_launch, hist / histn hold two parity halves; the columns tl < k_b of slot b and its
+// history of half parity_b (to the same half of histn) are copied, and a slot with k_b = 0 is not touched.
+template <bool ROWS>
 __global__ void stream_repeat_kernel(const float* __restrict__ x, const float* __restrict__ hist, long long rows, int B, int ns, int k,
-                                     int Tp, int Jp, float* __restrict__ xn, float* __restrict__ histn, int Jpn) {
+                                     int Tp, int Jp, float* __restrict__ xn, float* __restrict__ histn, int Jpn,
+                                     const long long* __restrict__ table) {
     const int Bn = B * ns, kc = k + 1;                                        // column kc - 1 of a row's span stands for the history
     const long long n = rows * Bn * kc;
     for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
@@ -232,19 +248,29 @@ __global__ void stream_repeat_kernel(const float* __restrict__ x, const float* _
         const int bn = (int)((e / kc) % Bn);
         const long long row = e / ((long long)kc * Bn);
         const int b = bn / ns;
+        size_t half = 0, halfn = 0;                                           // offsets of the history half read
+        if (ROWS) {
+            const long long kb = table[(size_t)b * IDV_STREAM_ROW_FIELDS + IDV_ROW_K];
+            if (kb == 0 || (tl < k && tl >= kb)) continue;
+            const size_t par = (size_t)table[(size_t)b * IDV_STREAM_ROW_FIELDS + IDV_ROW_PARITY];
+            half = par * (size_t)rows * B;
+            halfn = par * (size_t)rows * Bn;
+        }
         if (tl < k)
             xn[(size_t)row * Jpn + (size_t)bn * Tp + 1 + tl] = x[(size_t)row * Jp + (size_t)b * Tp + 1 + tl];
         else if (hist)
-            histn[(size_t)row * Bn + bn] = hist[(size_t)row * B + b];
+            histn[halfn + (size_t)row * Bn + bn] = hist[half + (size_t)row * B + b];
     }
 }
 
 }  // namespace
 
+static const long long* const no_rows = nullptr;      // the table argument of a lock-step instantiation, which never reads it
+
 extern "C" int idv_stream_eps(long long seed, long long t0, int k, int B, int ns, int zdim, float* eps_r, float* eps_i, void* stream) {
     if (t0 < 0 || k <= 0 || B <= 0 || ns <= 0 || zdim <= 0 || !eps_r || !eps_i || (long long)B * ns > 0x7fffffffLL) return IDV_EINVAL;
-    hipLaunchKernelGGL(stream_eps_kernel, dim3(grid_of((long long)B * ns * k * zdim)), dim3(256), 0, (hipStream_t)stream,
-                       (unsigned long long)seed, t0, k, B * ns, zdim, eps_r, eps_i);
+    hipLaunchKernelGGL(stream_eps_kernel<false>, dim3(grid_of((long long)B * ns * k * zdim)), dim3(256), 0, (hipStream_t)stream,
+                       (unsigned long long)seed, t0, k, B * ns, zdim, eps_r, eps_i, ns, no_rows);
     return idv_launch_status();
 }
 
@@ -254,8 +280,28 @@ extern "C" int idv_stream_repeat(const float* x, const float* hist, int C, int F
         Jp < B * Tp || (long long)B * ns * Tp > Jpn)
         return IDV_EINVAL;
     const long long rows = 2LL * C * F;
-    hipLaunchKernelGGL(stream_repeat_kernel, dim3(grid_of(rows * B * ns * (k + 1))), dim3(256), 0, (hipStream_t)stream, x, hist, rows, B,
-                       ns, k, Tp, Jp, xn, histn, Jpn);
+    hipLaunchKernelGGL(stream_repeat_kernel<false>, dim3(grid_of(rows * B * ns * (k + 1))), dim3(256), 0, (hipStream_t)stream, x, hist, rows,
+                       B, ns, k, Tp, Jp, xn, histn, Jpn, no_rows);
+    return idv_launch_status();
+}
+
+extern "C" int idv_stream_eps_rows(long long seed, const long long* rows, int B, int ns, int zdim, int k_launch, float* eps_r,
+                                   float* eps_i, void* stream) {
+    if (!rows || k_launch <= 0 || B <= 0 || ns <= 0 || zdim <= 0 || !eps_r || !eps_i || (long long)B * ns > 0x7fffffffLL)
+        return IDV_EINVAL;
+    hipLaunchKernelGGL(stream_eps_kernel<true>, dim3(grid_of((long long)B * ns * k_launch * zdim)), dim3(256), 0, (hipStream_t)stream,
+                       (unsigned long long)seed, 0LL, k_launch, B * ns, zdim, eps_r, eps_i, ns, rows);
+    return idv_launch_status();
+}
+
+extern "C" int idv_stream_repeat_rows(const float* x, const float* hist, int C, int F, int B, int ns, int k_launch, int Tp, int Jp,
+                                      const long long* rows, float* xn, float* histn, int Jpn, void* stream) {
+    if (!x || !xn || !rows || (hist != nullptr) != (histn != nullptr) || C <= 0 || F <= 0 || B <= 0 || ns <= 0 || k_launch <= 0 ||
+        Tp < k_launch + 1 || Jp < B * Tp || (long long)B * ns * Tp > Jpn)
+        return IDV_EINVAL;
+    const long long nrow = 2LL * C * F;
+    hipLaunchKernelGGL(stream_repeat_kernel<true>, dim3(grid_of(nrow * B * ns * (k_launch + 1))), dim3(256), 0, (hipStream_t)stream, x,
+                       hist, nrow, B, ns, k_launch, Tp, Jp, xn, histn, Jpn, rows);
     return idv_launch_status();
 }
 

@@ -145,7 +145,11 @@ __global__ __launch_bounds__(4 * SL_H) void stream_lstm_rows_kernel(const float*
 }
 
 // real = rr - ii, imag = ir + ri (runs 0, 3, 2, 1) -> planar [2][H][Jp] at column b*Tp + 1 + t
-__global__ void stream_lstm_combine_kernel(const float* __restrict__ h, int H, int B, int k, int Tp, int Jp, float* __restrict__ out) {
+// ROWS (idv_stream_clstm_wide_rows): k is k_launch; the columns t >= k_b of slot b are zero and their rows of h, which no step
+// wrote, are not read.
+template <bool ROWS>
+__global__ void stream_lstm_combine_kernel(const float* __restrict__ h, int H, int B, int k, int Tp, int Jp, float* __restrict__ out,
+                                           const long long* __restrict__ rows) {
     const long long n = (long long)H * B * k;
     const size_t run = (size_t)k * B * H;
     for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
@@ -154,6 +158,11 @@ __global__ void stream_lstm_combine_kernel(const float* __restrict__ h, int H, i
         const int t = (int)(tb / B), b = (int)(tb % B);
         const size_t o = (size_t)tb * H + u;
         const size_t j = (size_t)u * Jp + (size_t)b * Tp + 1 + t;
+        if (ROWS && t >= rows[(size_t)b * IDV_STREAM_ROW_FIELDS + IDV_ROW_K]) {
+            out[j] = 0.f;
+            out[(size_t)H * Jp + j] = 0.f;
+            continue;
+        }
         out[j] = h[o] - h[3 * run + o];
         out[(size_t)H * Jp + j] = h[2 * run + o] + h[run + o];
     }
@@ -175,10 +184,15 @@ constexpr int WL_HMAX = 768;
 constexpr int WL_KB = 16;                            // k per weight block; divides H
 
 // hstep: [2 layers][4 runs][k][B][H]
-template <int LAYER>
+// ROWS (idv_stream_clstm_wide_rows): k is k_launch and slot b takes part in the steps t < k_b = rows[b][IDV_ROW_K] only.  In a
+// step t >= k_b nothing of the slot is written (c in state, its hstep row), and since no step wrote its hstep rows either, zeros
+// are staged in their place: its chains run on them and their results are dropped.  A chain belongs to one stream, so an active
+// stream's bits do not depend on its tile neighbours.  A workgroup without an active stream returns before its first barrier.
+template <int LAYER, bool ROWS>
 __global__ __launch_bounds__(WL_ROWS) void wide_step_kernel(const float* __restrict__ G, const float* __restrict__ wt,
                                                             const float* __restrict__ b1, float* __restrict__ state,
-                                                            float* __restrict__ hstep, int H, int B, int k, int t) {
+                                                            float* __restrict__ hstep, int H, int B, int k, int t,
+                                                            const long long* __restrict__ rows) {
     extern __shared__ __attribute__((aligned(16))) float wl_lds[];
     const int KT = (LAYER + 1) * H;                 // layer 0: h0(t-1); layer 1: h0(t) then h1(t-1)
     float* hs = wl_lds;                             // [WL_SB][KT]
@@ -186,6 +200,19 @@ __global__ __launch_bounds__(WL_ROWS) void wide_step_kernel(const float* __restr
     const int r = threadIdx.x;
     const int u0 = blockIdx.x * WL_U, run = blockIdx.y, z = run >> 1, s = run & 1;
     const int b0 = blockIdx.z * WL_SB;
+    bool act[WL_SB];                                // stream sb runs step t (lock-step: every stream does)
+    if (ROWS) {
+        bool any = false;
+#pragma unroll
+        for (int sb = 0; sb < WL_SB; ++sb) {
+            act[sb] = b0 + sb < B && t < rows[(size_t)(b0 + sb) * IDV_STREAM_ROW_FIELDS + IDV_ROW_K];
+            any = any || act[sb];
+        }
+        if (!any) return;                           // the same for every thread of the workgroup
+    } else {
+#pragma unroll
+        for (int sb = 0; sb < WL_SB; ++sb) act[sb] = true;
+    }
     const int G4 = 4 * H;
     const size_t sz = (size_t)B * H;
     float* st = state + (size_t)run * 4 * sz;       // [layer][h | c][B][H]
@@ -198,8 +225,8 @@ __global__ __launch_bounds__(WL_ROWS) void wide_step_kernel(const float* __restr
 #pragma unroll
         for (int sb = 0; sb < WL_SB; ++sb) {
             const size_t o = (size_t)min(b0 + sb, B - 1) * H + u;
-            v0[sb] = src0[o];
-            if (LAYER == 1) v1[sb] = src1[o];
+            v0[sb] = (!ROWS || act[sb]) ? src0[o] : 0.f;
+            if (LAYER == 1) v1[sb] = (!ROWS || act[sb]) ? src1[o] : 0.f;
         }
 #pragma unroll
         for (int sb = 0; sb < WL_SB; ++sb) {
@@ -257,6 +284,7 @@ __global__ __launch_bounds__(WL_ROWS) void wide_step_kernel(const float* __restr
     for (int e = r; e < WL_SB * WL_U; e += WL_ROWS) {
         const int sb = e / WL_U, ul = e % WL_U, b = b0 + sb;
         if (b >= B) continue;
+        if (ROWS && t >= rows[(size_t)b * IDV_STREAM_ROW_FIELDS + IDV_ROW_K]) continue;
         const float* gq = gs + sb * WL_ROWS + ul;
         const float ig = sigmoidf_(gq[0]), fg = sigmoidf_(gq[WL_U]);
         const float gg = tanhf_(gq[2 * WL_U]), og = sigmoidf_(gq[3 * WL_U]);
@@ -268,17 +296,27 @@ __global__ __launch_bounds__(WL_ROWS) void wide_step_kernel(const float* __restr
 }
 
 // h of both layers after the last step -> state (the c halves are already there)
-__global__ void wide_carry_kernel(const float* __restrict__ hstep, float* __restrict__ state, int H, int B, int k) {
+// ROWS: the last step of slot b is k_b - 1; a slot with k_b = 0 keeps its state
+template <bool ROWS>
+__global__ void wide_carry_kernel(const float* __restrict__ hstep, float* __restrict__ state, int H, int B, int k,
+                                  const long long* __restrict__ rows) {
     const size_t sz = (size_t)B * H;
     const long long n = 8LL * (long long)sz;
     for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
         const int lr = (int)(e / (long long)sz), layer = lr >> 2, run = lr & 3;
         const size_t o = (size_t)(e % (long long)sz);
-        state[((size_t)run * 4 + 2 * layer) * sz + o] = hstep[((size_t)lr * k + (k - 1)) * sz + o];
+        int last = k - 1;
+        if (ROWS) {
+            last = (int)rows[(o / H) * IDV_STREAM_ROW_FIELDS + IDV_ROW_K] - 1;
+            if (last < 0) continue;
+        }
+        state[((size_t)run * 4 + 2 * layer) * sz + o] = hstep[((size_t)lr * k + last) * sz + o];
     }
 }
 
 }  // namespace
+
+static const long long* const no_rows = nullptr;      // the table argument of a lock-step instantiation, which never reads it
 
 extern "C" int idv_stream_lstm_supported(int H) { return H == SL_H ? 1 : 0; }
 
@@ -299,18 +337,44 @@ extern "C" int idv_stream_clstm_wide(const float* G, const float* wt, const floa
     const dim3 grid((unsigned)(H / WL_U), 4, (unsigned)tiles);
     const size_t lds0 = sizeof(float) * WL_SB * ((size_t)H + WL_ROWS), lds1 = sizeof(float) * WL_SB * ((size_t)2 * H + WL_ROWS);
     for (int t = 0; t < k; ++t) {
-        hipLaunchKernelGGL(wide_step_kernel<0>, grid, dim3(WL_ROWS), lds0, st, G, wt, b1, state, hstep, H, B, k, t);
-        hipLaunchKernelGGL(wide_step_kernel<1>, grid, dim3(WL_ROWS), lds1, st, G, wt, b1, state, hstep, H, B, k, t);
+        hipLaunchKernelGGL((wide_step_kernel<0, false>), grid, dim3(WL_ROWS), lds0, st, G, wt, b1, state, hstep, H, B, k, t, no_rows);
+        hipLaunchKernelGGL((wide_step_kernel<1, false>), grid, dim3(WL_ROWS), lds1, st, G, wt, b1, state, hstep, H, B, k, t, no_rows);
     }
     int rc = idv_launch_status();
     if (rc) return rc;
     long long g = ((long long)H * B * k + 255) / 256;
     g = g > 4096 ? 4096 : (g < 1 ? 1 : g);
-    hipLaunchKernelGGL(stream_lstm_combine_kernel, dim3((unsigned)g), dim3(256), 0, st, hstep + (size_t)4 * k * B * H, H, B, k, Tp, Jp,
-                       out);
+    hipLaunchKernelGGL(stream_lstm_combine_kernel<false>, dim3((unsigned)g), dim3(256), 0, st, hstep + (size_t)4 * k * B * H, H, B, k, Tp,
+                       Jp, out, no_rows);
     long long gc = (8LL * B * H + 255) / 256;
     gc = gc > 4096 ? 4096 : gc;
-    hipLaunchKernelGGL(wide_carry_kernel, dim3((unsigned)gc), dim3(256), 0, st, hstep, state, H, B, k);
+    hipLaunchKernelGGL(wide_carry_kernel<false>, dim3((unsigned)gc), dim3(256), 0, st, hstep, state, H, B, k, no_rows);
+    return idv_launch_status();
+}
+
+extern "C" int idv_stream_clstm_wide_rows(const float* G, const float* wt, const float* b1, float* state, float* hstep, float* out,
+                                          int H, int B, int k_launch, int Tp, int Jp, const long long* rows, void* stream) {
+    const int k = k_launch;
+    if (!G || !wt || !b1 || !state || !hstep || !out || !rows || B <= 0 || k <= 0 || Tp < k + 1 || Jp < B * Tp) return IDV_EINVAL;
+    if (!idv_stream_clstm_wide_supported(H)) return IDV_EINVAL;
+    const long long tiles = ((long long)B + WL_SB - 1) / WL_SB;
+    if (tiles > 65535) return IDV_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)(H / WL_U), 4, (unsigned)tiles);
+    const size_t lds0 = sizeof(float) * WL_SB * ((size_t)H + WL_ROWS), lds1 = sizeof(float) * WL_SB * ((size_t)2 * H + WL_ROWS);
+    for (int t = 0; t < k; ++t) {
+        hipLaunchKernelGGL((wide_step_kernel<0, true>), grid, dim3(WL_ROWS), lds0, st, G, wt, b1, state, hstep, H, B, k, t, rows);
+        hipLaunchKernelGGL((wide_step_kernel<1, true>), grid, dim3(WL_ROWS), lds1, st, G, wt, b1, state, hstep, H, B, k, t, rows);
+    }
+    int rc = idv_launch_status();
+    if (rc) return rc;
+    long long g = ((long long)H * B * k + 255) / 256;
+    g = g > 4096 ? 4096 : (g < 1 ? 1 : g);
+    hipLaunchKernelGGL(stream_lstm_combine_kernel<true>, dim3((unsigned)g), dim3(256), 0, st, hstep + (size_t)4 * k * B * H, H, B, k, Tp,
+                       Jp, out, rows);
+    long long gc = (8LL * B * H + 255) / 256;
+    gc = gc > 4096 ? 4096 : gc;
+    hipLaunchKernelGGL(wide_carry_kernel<true>, dim3((unsigned)gc), dim3(256), 0, st, hstep, state, H, B, k, rows);
     return idv_launch_status();
 }
 
@@ -329,7 +393,7 @@ static int launch_clstm(const float* G, const float* wt, const float* b1, float*
     if (rc) return rc;
     long long g = ((long long)H * B * k + 255) / 256;
     g = g > 4096 ? 4096 : (g < 1 ? 1 : g);
-    hipLaunchKernelGGL(stream_lstm_combine_kernel, dim3((unsigned)g), dim3(256), 0, st, hout, H, B, k, Tp, Jp, out);
+    hipLaunchKernelGGL(stream_lstm_combine_kernel<false>, dim3((unsigned)g), dim3(256), 0, st, hout, H, B, k, Tp, Jp, out, no_rows);
     return idv_launch_status();
 }
 

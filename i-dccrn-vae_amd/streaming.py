@@ -10,7 +10,8 @@ look-ahead is the STFT window: frame t reads samples [hop*t - win/2, hop*t + win
 emission bookkeeping from which every kernel launch takes its ranges.
 
 :class:`StreamingSessions` runs one such stream per slot, each starting and ending on its own; :class:`StreamingVAE` streams
-the I-DCCRN-VAE pair (noisy encoder, latent draw, fine-tuned decoder with the noisy skips) under the same contract.
+the I-DCCRN-VAE pair (noisy encoder, latent draw, fine-tuned decoder with the noisy skips) under the same contract, and
+:class:`StreamingVAESessions` runs that pair one stream per slot.
 """
 from __future__ import annotations
 
@@ -637,7 +638,62 @@ class StreamingDCCRN(_Streamer):
              i(self.B), i(c.k), i(Tp), i(Jp), stream_ptr())
 
 
-class StreamingSessions(_Streamer):
+class _Slots:
+    """What both sessions classes share on top of their streamer (``self.B`` slots): the per-slot host plan, ``positions``,
+    ``drop`` / ``reset``, the one pinned copy that takes a call's tables to the device, and the zeroing of the slots that end.
+    ``self._zero_views`` lists the state buffers as (buffer, outer, inner) of a [outer][slots][inner] view."""
+
+    def _init_slots(self):
+        if int(L.lib().idv_stream_row_fields()) != NF:
+            raise L.IdvError("libidccrn_hip.so and streaming.ROW_FIELDS disagree about the row table")
+        self.sessions = SessionPlan(self.B, self.n_fft, self.hop, self.win, self.cap)
+        self._table = None          # device int64 buffer of the call's tables
+        self._staging = []          # [(pinned int64 buffer, event of the copy that last read it)] * 2
+        self._turn = 0
+
+    @property
+    def positions(self) -> List[int]:
+        return self.sessions.positions
+
+    def reset(self):
+        """Zero every slot's state and bookkeeping."""
+        super().reset()
+        if hasattr(self, "sessions"):
+            self.sessions.drop(range(self.B))
+
+    def drop(self, slots):
+        """Abandon the signals of these slots: nothing is returned for them and their state is zeroed; their next samples begin
+        a new signal."""
+        slots = check_slots(slots, self.B)
+        if not slots:
+            return
+        self.sessions.drop(slots)
+        with torch.cuda.device(self.device):
+            table = self._upload(torch.tensor(slots, dtype=torch.int64))
+            self._zero(L._P(table.data_ptr()), len(slots))
+
+    def _upload(self, host: torch.Tensor) -> torch.Tensor:
+        """One host-to-device copy of a call's tables through a pinned staging buffer."""
+        n = host.numel()
+        if self._table is None or self._table.numel() < n:
+            size = max(1 << (n - 1).bit_length(), 4 * self.B * NF)
+            self._table = torch.empty(size, dtype=torch.int64, device=self.device)
+            self._staging = [(torch.empty(size, dtype=torch.int64).pin_memory(), torch.cuda.Event()) for _ in range(2)]
+        stage, ev = self._staging[self._turn]
+        self._turn ^= 1
+        ev.synchronize()            # the copy that read this buffer two calls ago; an event never recorded does not wait
+        stage[:n].copy_(host)
+        self._table[:n].copy_(stage[:n], non_blocking=True)
+        ev.record()
+        return self._table
+
+    def _zero(self, slots_ptr, n: int):
+        if n:
+            for buf, outer, inner in self._zero_views:
+                call("idv_stream_zero_rows", p(buf), ll(outer), i(self.B), ll(inner), slots_ptr, i(n), stream_ptr())
+
+
+class StreamingSessions(_Slots, _Streamer):
     """Streaming inference of a causal ``DCCRN_`` for ``slots`` independent signals in one batch: every slot starts, receives
     samples and ends on its own.
 
@@ -660,25 +716,10 @@ class StreamingSessions(_Streamer):
 
     def __init__(self, model, slots: int, frames_per_launch: int = 64, max_columns: int = 4096, conv: str = "valu"):
         super().__init__(model, slots, frames_per_launch, max_columns, conv)
-        if int(L.lib().idv_stream_row_fields()) != NF:
-            raise L.IdvError("libidccrn_hip.so and streaming.ROW_FIELDS disagree about the row table")
-        self.sessions = SessionPlan(slots, self.n_fft, self.hop, self.win, self.cap)
+        self._init_slots()
         # state buffers as [outer][slots][inner] for idv_stream_zero_rows
         self._zero_views = [(self.ring, 1, self.plan.ring), (self.carry, 2, self.plan.carry_cap), (self.lstm_state, 16, self.H)]
         self._zero_views += [(h, h.numel() // slots, 1) for h in [self.h_in, self.h_dense] + self.h_enc + self.h_dec]
-        self._table = None          # device int64 buffer of the call's tables
-        self._staging = []          # [(pinned int64 buffer, event of the copy that last read it)] * 2
-        self._turn = 0
-
-    @property
-    def positions(self) -> List[int]:
-        return self.sessions.positions
-
-    def reset(self):
-        """Zero every slot's state and bookkeeping."""
-        super().reset()
-        if hasattr(self, "sessions"):
-            self.sessions.drop(range(self.B))
 
     # ------------------------------------------------------------------ push / drop
     def push(self, x: torch.Tensor, counts=None, end=()):
@@ -724,37 +765,6 @@ class StreamingSessions(_Streamer):
                 call("idv_stream_ring_rows", p(self.ring), i(self.plan.ring), p(x), ll(ldx), i(n), rows_of(0), i(self.B), s)
             self._zero(L._P(table.data_ptr() + 8 * len(plan.groups) * self.B * NF), len(plan.zero))
         return y, plan.m
-
-    def drop(self, slots):
-        """Abandon the signals of these slots: nothing is returned for them and their state is zeroed; their next samples begin
-        a new signal."""
-        slots = check_slots(slots, self.B)
-        if not slots:
-            return
-        self.sessions.drop(slots)
-        with torch.cuda.device(self.device):
-            table = self._upload(torch.tensor(slots, dtype=torch.int64))
-            self._zero(L._P(table.data_ptr()), len(slots))
-
-    def _upload(self, host: torch.Tensor) -> torch.Tensor:
-        """One host-to-device copy of a call's tables through a pinned staging buffer."""
-        n = host.numel()
-        if self._table is None or self._table.numel() < n:
-            size = max(1 << (n - 1).bit_length(), 4 * self.B * NF)
-            self._table = torch.empty(size, dtype=torch.int64, device=self.device)
-            self._staging = [(torch.empty(size, dtype=torch.int64).pin_memory(), torch.cuda.Event()) for _ in range(2)]
-        stage, ev = self._staging[self._turn]
-        self._turn ^= 1
-        ev.synchronize()            # the copy that read this buffer two calls ago; an event never recorded does not wait
-        stage[:n].copy_(host)
-        self._table[:n].copy_(stage[:n], non_blocking=True)
-        ev.record()
-        return self._table
-
-    def _zero(self, slots_ptr, n: int):
-        if n:
-            for buf, outer, inner in self._zero_views:
-                call("idv_stream_zero_rows", p(buf), ll(outer), i(self.B), ll(inner), slots_ptr, i(n), stream_ptr())
 
     # ------------------------------------------------------------------ the per-row kernels of the network
     def _frames(self, c, io, frames, Tp: int, Jp: int):
@@ -847,25 +857,14 @@ def check_seed(seed) -> int:
     return seed
 
 
-class StreamingVAE(_StreamBase):
-    """Lock-step streaming I-DCCRN-VAE enhancement for ``batch`` signals: the noisy encoder at batch B, one latent draw per
-    sample, the fine-tuned decoder with the noisy skips (``pad='sig'``) at batch B * num_samples (row b * ns + s).
-
-        st = StreamingVAE(noisy_encoder, decoder, batch=B, seed=0, latent="speech", average=True, eps=None)
-        y = st.push(x)          # x [B, n] on the GPU -> [B, m] (average=False: [B * ns, m], row b * ns + s)
-        y = st.flush()
-        er, ei = st.eps(t0, k)  # the draws frames t0 .. t0+k-1 use, each [B, ns, k, zdim]
-
-    Frame and sample bookkeeping is :class:`StreamPlan`, as in :class:`StreamingDCCRN`.  All pushes and the flush together
-    return what ``inference.enhance_vae(noisy_encoder, decoder, x_full, eps=<the same draws>, latent=latent)`` returns, and the
-    same bits however the signal is cut.  The draws come from a counter-based generator (``idv_stream_eps``): a draw is a
-    function of (seed, b, s, t, u) alone, the same seed gives the same draws for every signal, and ``seed`` may be set between
-    signals.  ``eps`` may instead be a callable ``(t0, k) -> (eps_r, eps_i)`` ([B, ns, k, zdim] each, on the GPU) that supplies
-    the chosen latent's draws.  ``conv`` as in :class:`StreamingDCCRN`.  Exact fp32 whatever ``ops.PRECISION`` is; weights are
-    packed at construction.
-    """
+class _VAEStreamer(_StreamBase):
+    """What both VAE streamers share: the construction guards, the packed weights of the pair, the activation and state buffers
+    (encoder side at batch B, decoder side at batch B * ns, row b * ns + s), the draws of ``eps`` and the network over the frames
+    of one launch group.  A subclass supplies the framing, the conv block, the LSTM, the draws and the repeated skips of its kind
+    (scalars for lock-step streams, row tables for sessions)."""
 
     _name = "StreamingVAE"
+    _skip_halves = 1               # parity halves of the repeated skip histories (h_skip_n)
 
     def __init__(self, noisy_encoder, decoder, batch: int, seed: int = 0, latent: str = "speech", average: bool = True, eps=None,
                  frames_per_launch: int = 64, max_columns: int = 4096, conv: str = "valu"):
@@ -899,11 +898,6 @@ class StreamingVAE(_StreamBase):
     @seed.setter
     def seed(self, v):
         self._seed = check_seed(v)
-
-    def reset(self):
-        """Zero every per-stream state buffer and the bookkeeping (done by construction and by flush); the seed stays."""
-        super().reset()
-        self.plan.reset()
 
     # ------------------------------------------------------------------ construction
     def _pack(self):
@@ -958,8 +952,9 @@ class StreamingVAE(_StreamBase):
         self.dense_buf = mk(*self.dense_out, Bn)
         n = len(self.enc)
         self.skip_n = {di: mk(*self.enc_shapes[n - 1 - di], Bn) for di in self.skip_to_use if di < n}
-        self.h_skip_n = {di: torch.zeros(2 * self.enc_shapes[n - 1 - di][0] * self.enc_shapes[n - 1 - di][1] * Bn, dtype=torch.float32,
-                                         device=dev) for di in self.skip_n}
+        # scratch, not state: the history half a chunk reads, repeated (sessions: one half per parity, slot b's in half parity_b)
+        self.h_skip_n = {di: torch.zeros(self._skip_halves * 2 * self.enc_shapes[n - 1 - di][0] * self.enc_shapes[n - 1 - di][1] * Bn,
+                                         dtype=torch.float32, device=dev) for di in self.skip_n}
         self.dec_out = [mk(cp.Cout, cp.Fout, Bn) for cp in self.dec]
         self.pred = mk(1, self.F, Bn)
         self.ifr = mk(1, self.win // 2, Bn)
@@ -988,6 +983,86 @@ class StreamingVAE(_StreamBase):
             call("idv_stream_eps", ll(self._seed), ll(t0), i(k), i(self.B), i(self.ns), i(self.zdim), p(out[0]), p(out[1]), stream_ptr())
         return out[0], out[1]
 
+    # ------------------------------------------------------------------ the network over one launch group
+    def _network(self, c, io):
+        """Frames -> spectrum -> encoders -> wide LSTM (batch B) -> draws -> reparameterisation -> dense -> decoders with the
+        repeated skips -> mask -> windowed inverse-DFT frames (self.ifr), batch B * ns, for the c.k columns per stream of launch
+        group c; ``io`` is what the subclass's framing needs."""
+        B, Bn, ns, k = self.B, self.Bn, self.ns, c.k
+        Tp = k + 1
+        Jp, Jpn = Planar.jp_for(B, Tp), Planar.jp_for(Bn, Tp)
+        s = stream_ptr()
+        ptr = lambda pl, plane=0: L._P(pl.buf.data_ptr() + 4 * (ops.SLACK + plane * pl.F * Jp))
+        ptrn = lambda pl, plane=0: L._P(pl.buf.data_ptr() + 4 * (ops.SLACK + plane * pl.F * Jpn))
+        self._frames(c, io, ptr(self.fr), Tp, Jp)
+        ops.pw_gemm(ptr(self.fr), self.win, self.dft_fwd[0], self.dft_fwd[1], 2 * self.F, B, Tp, Jp, k, ptr(self.X))
+        src, hsrc = self.X, self.h_in
+        for e, cp in enumerate(self.enc):
+            out = self.enc_out[e]
+            self._block(cp, c, ptr(src), hsrc, None, None, ptr(out), self.h_enc[e], self.h_in if e == 0 else None, Tp, Jp, False)
+            src, hsrc = out, self.h_enc[e]
+        # LSTM: layer-0 projection of both input parts (idv_pw_gemm as offline), then one launch per layer per step
+        H, K = self.H, self.K
+        wih, bih = self.lstm_ih
+        top = self.enc_out[-1]
+        for z in range(2):
+            ops.pw_gemm(ptr(top, z * top.C), K, wih, bih, 8 * H, B, Tp, Jp, k,
+                        L._P(self.G.data_ptr() + 4 * z * k * B * 8 * H), swap=True, ldo=8 * H)
+        self._lstm(c, ptr(self.lat), Tp, Jp)
+        # latent draw of the chosen latent, batch B -> B * ns
+        er, ei = self._draws(c)
+        zd = self.zdim
+        call("idv_reparam", ptr(self.lat), i(H), i(self.lat_off[0]), i(self.lat_off[1]), i(self.lat_off[2]), i(zd), er, ei, i(ns), i(B),
+             i(k), i(Tp), i(Jp), ptrn(self.z), i(Jpn), s)
+        dc, df = self.dense_out
+        for ri, pk in enumerate(self.dense):
+            ops.pw_gemm(ptrn(self.z, ri * zd), zd, pk[0], pk[1], dc * df, Bn, Tp, Jpn, k, ptrn(self.dense_buf, ri * dc))
+        # decoders: the skips and the history half this group reads, repeated to batch B * ns
+        src, hsrc = self.dense_buf, self.h_dense
+        n = len(self.enc)
+        for di, cp in enumerate(self.dec):
+            out = self.dec_out[di]
+            x1 = h1 = None
+            if di in self.skip_n:
+                sk = n - 1 - di
+                h1 = self._repeat(c, di, sk, ptr(self.enc_out[sk]), ptrn(self.skip_n[di]), Tp, Jp, Jpn)
+                x1 = ptrn(self.skip_n[di])
+            hout = self.h_dec[di] if di < len(self.h_dec) else None      # nothing reads the last block's history
+            self._block(cp, c, ptrn(src), hsrc, x1, h1, ptrn(out), hout, self.h_dense if di == 0 else None, Tp, Jpn, True)
+            if di < len(self.h_dec):
+                src, hsrc = out, self.h_dec[di]
+        pred = self.dec_out[-1]
+        if self.recon == "mask":
+            call("idv_mask_apply", ptrn(pred), ptr(self.X), i(ns), i(Jp), ptrn(self.pred), p(None), i(self.F), i(Bn), i(k), i(Tp),
+                 i(Jpn), s)
+            pred = self.pred
+        ops.pw_gemm(ptrn(pred), 2 * self.F, self.dft_inv[0], self.dft_inv[1], self.win, Bn, Tp, Jpn, k, ptrn(self.ifr))
+
+
+class StreamingVAE(_VAEStreamer):
+    """Lock-step streaming I-DCCRN-VAE enhancement for ``batch`` signals: the noisy encoder at batch B, one latent draw per
+    sample, the fine-tuned decoder with the noisy skips (``pad='sig'``) at batch B * num_samples (row b * ns + s).
+
+        st = StreamingVAE(noisy_encoder, decoder, batch=B, seed=0, latent="speech", average=True, eps=None)
+        y = st.push(x)          # x [B, n] on the GPU -> [B, m] (average=False: [B * ns, m], row b * ns + s)
+        y = st.flush()
+        er, ei = st.eps(t0, k)  # the draws frames t0 .. t0+k-1 use, each [B, ns, k, zdim]
+
+    Frame and sample bookkeeping is :class:`StreamPlan`, as in :class:`StreamingDCCRN`.  All pushes and the flush together
+    return what ``inference.enhance_vae(noisy_encoder, decoder, x_full, eps=<the same draws>, latent=latent)`` returns, and the
+    same bits however the signal is cut.  The draws come from a counter-based generator (``idv_stream_eps``): a draw is a
+    function of (seed, b, s, t, u) alone, the same seed gives the same draws for every signal, and ``seed`` may be set between
+    signals.  ``eps`` may instead be a callable ``(t0, k) -> (eps_r, eps_i)`` ([B, ns, k, zdim] each, on the GPU) that supplies
+    the chosen latent's draws.  ``conv`` as in :class:`StreamingDCCRN`.  Exact fp32 whatever ``ops.PRECISION`` is; weights are
+    packed at construction.
+    """
+
+    def reset(self):
+        """Zero every per-stream state buffer and the bookkeeping (done by construction and by flush); the seed stays."""
+        super().reset()
+        self.plan.reset()
+
+    # ------------------------------------------------------------------ the draws
     def _draws(self, c: Chunk):
         """Device pointers of eps_r / eps_i [B][ns][c.k][zdim] of chunk c."""
         if self._eps_fn is None:
@@ -1042,61 +1117,168 @@ class StreamingVAE(_StreamBase):
             call("idv_mean_over_samples", p(y), i(self.ns), i(self.B), i(m), p(out), stream_ptr())
         return out
 
-    # ------------------------------------------------------------------ the network over one chunk
-    def _network(self, c: Chunk, io):
-        """Frames -> spectrum -> encoders -> wide LSTM (batch B) -> draws -> reparameterisation -> dense -> decoders with the
-        repeated skips -> mask -> windowed inverse-DFT frames (self.ifr), batch B * ns."""
-        B, Bn, ns, k, P = self.B, self.Bn, self.ns, c.k, c.parity
-        Tp = k + 1
-        Jp, Jpn = Planar.jp_for(B, Tp), Planar.jp_for(Bn, Tp)
-        s = stream_ptr()
-        ptr = lambda pl, plane=0: L._P(pl.buf.data_ptr() + 4 * (ops.SLACK + plane * pl.F * Jp))
-        ptrn = lambda pl, plane=0: L._P(pl.buf.data_ptr() + 4 * (ops.SLACK + plane * pl.F * Jpn))
-        self._lock_frames(c, io, ptr(self.fr), Tp, Jp)
-        ops.pw_gemm(ptr(self.fr), self.win, self.dft_fwd[0], self.dft_fwd[1], 2 * self.F, B, Tp, Jp, k, ptr(self.X))
-        src, hsrc = self.X, self.h_in
-        for e, cp in enumerate(self.enc):
-            out = self.enc_out[e]
-            self._conv_call(cp, ptr(src), hsrc[P], None, None, ptr(out), self.h_enc[e][1 - P],
-                            p(self.h_in[1 - P]) if e == 0 else p(None), B, k, Tp, Jp)
-            src, hsrc = out, self.h_enc[e]
-        # LSTM: layer-0 projection of both input parts (idv_pw_gemm as offline), then one launch per layer per step
-        H, K = self.H, self.K
-        wih, bih = self.lstm_ih
-        top = self.enc_out[-1]
-        for z in range(2):
-            ops.pw_gemm(ptr(top, z * top.C), K, wih, bih, 8 * H, B, Tp, Jp, k,
-                        L._P(self.G.data_ptr() + 4 * z * k * B * 8 * H), swap=True, ldo=8 * H)
-        call("idv_stream_clstm_wide", p(self.G), p(self.lstm_wt), p(self.lstm_b1), p(self.lstm_state), p(self.hstep), ptr(self.lat),
-             i(H), i(B), i(k), i(Tp), i(Jp), s)
-        # latent draw of the chosen latent, batch B -> B * ns
-        er, ei = self._draws(c)
-        zd = self.zdim
-        call("idv_reparam", ptr(self.lat), i(H), i(self.lat_off[0]), i(self.lat_off[1]), i(self.lat_off[2]), i(zd), er, ei, i(ns), i(B),
-             i(k), i(Tp), i(Jp), ptrn(self.z), i(Jpn), s)
-        dc, df = self.dense_out
-        for ri, pk in enumerate(self.dense):
-            ops.pw_gemm(ptrn(self.z, ri * zd), zd, pk[0], pk[1], dc * df, Bn, Tp, Jpn, k, ptrn(self.dense_buf, ri * dc))
-        # decoders: the skips and the history half this chunk reads, repeated to batch B * ns
-        src, hsrc = self.dense_buf, self.h_dense
-        n = len(self.enc)
-        for di, cp in enumerate(self.dec):
-            out = self.dec_out[di]
-            x1 = h1 = None
-            if di in self.skip_n:
-                sk = n - 1 - di
-                sc, sf = self.enc_shapes[sk]
-                call("idv_stream_repeat", ptr(self.enc_out[sk]), p(self.h_enc[sk][P]), i(sc), i(sf), i(B), i(ns), i(k), i(Tp), i(Jp),
-                     ptrn(self.skip_n[di]), p(self.h_skip_n[di]), i(Jpn), s)
-                x1, h1 = ptrn(self.skip_n[di]), self.h_skip_n[di]
-            hout = self.h_dec[di][1 - P] if di < len(self.h_dec) else None      # nothing reads the last block's history
-            self._conv_call(cp, ptrn(src), hsrc[P], x1, h1, ptrn(out), hout, p(self.h_dense[1 - P]) if di == 0 else p(None), Bn, k,
-                            Tp, Jpn)
-            if di < len(self.h_dec):
-                src, hsrc = out, self.h_dec[di]
-        pred = self.dec_out[-1]
-        if self.recon == "mask":
-            call("idv_mask_apply", ptrn(pred), ptr(self.X), i(ns), i(Jp), ptrn(self.pred), p(None), i(self.F), i(Bn), i(k), i(Tp),
-                 i(Jpn), s)
-            pred = self.pred
-        ops.pw_gemm(ptrn(pred), 2 * self.F, self.dft_inv[0], self.dft_inv[1], self.win, Bn, Tp, Jpn, k, ptrn(self.ifr))
+    # ------------------------------------------------------------------ the lock-step kernels of the network
+    def _frames(self, c: Chunk, io, frames, Tp: int, Jp: int):
+        self._lock_frames(c, io, frames, Tp, Jp)
+
+    def _block(self, cp: _ConvPack, c: Chunk, x0, h0, x1, h1, out, hist, x0hist, Tp: int, Jp: int, dec: bool):
+        """One conv block of the encoder (batch B) or the decoder (batch B * ns): histories are read from half c.parity of the
+        [2][...] buffers and written to the other half; h1 is what ``_repeat`` returned."""
+        P = c.parity
+        self._conv_call(cp, x0, h0[P], x1, h1, out, hist[1 - P] if hist is not None else None,
+                        p(x0hist[1 - P]) if x0hist is not None else p(None), self.Bn if dec else self.B, c.k, Tp, Jp)
+
+    def _lstm(self, c: Chunk, out, Tp: int, Jp: int):
+        call("idv_stream_clstm_wide", p(self.G), p(self.lstm_wt), p(self.lstm_b1), p(self.lstm_state), p(self.hstep), out,
+             i(self.H), i(self.B), i(c.k), i(Tp), i(Jp), stream_ptr())
+
+    def _repeat(self, c: Chunk, di: int, sk: int, x, xn, Tp: int, Jp: int, Jpn: int):
+        sc, sf = self.enc_shapes[sk]
+        call("idv_stream_repeat", x, p(self.h_enc[sk][c.parity]), i(sc), i(sf), i(self.B), i(self.ns), i(c.k), i(Tp), i(Jp), xn,
+             p(self.h_skip_n[di]), i(Jpn), stream_ptr())
+        return self.h_skip_n[di]
+
+
+def decoder_rows(rows: List[List[int]], ns: int) -> List[List[int]]:
+    """The decoder-side table of a launch group of VAE sessions: [B * ns][NF] with row b * ns + s equal to slot b's row."""
+    return [r for r in rows for _ in range(ns)]
+
+
+def vae_session_tables(plan: SessionCall, ns: int) -> List[int]:
+    """The host side of the one copy a VAE sessions call makes: per launch group the slots' table [B][NF] followed by its
+    decoder-side table [B * ns][NF], then the slots to zero."""
+    return [v for g in plan.groups for r in g.rows + decoder_rows(g.rows, ns) for v in r] + list(plan.zero)
+
+
+class _VAELaunch(NamedTuple):
+    """What the network needs of a VAE sessions launch group: k_launch and the device pointers of its two row tables (encoder
+    side [B][NF], decoder side [B * ns][NF])."""
+    k: int
+    rows: object
+    rows_n: object
+
+
+class StreamingVAESessions(_Slots, _VAEStreamer):
+    """Streaming I-DCCRN-VAE enhancement for ``slots`` independent signals in one batch: :class:`StreamingVAE`'s network with the
+    ``push`` / ``counts`` / ``end`` / ``drop`` / ``positions`` contract of :class:`StreamingSessions`.
+
+        st = StreamingVAESessions(noisy_encoder, decoder, slots, seed=0, latent="speech", average=True)
+        y, m = st.push(x, counts=None, end=())   # x [slots, n] -> y [slots, max(m)] (average=False: [slots * ns, max(m)], row b * ns + s)
+        st.drop(slots); st.positions; st.reset()
+        er, ei = st.eps(t0, k)                   # [slots, ns, k, zdim] each, the generator of StreamingVAE.eps
+
+    Slot b's samples are bit-identical to what ``StreamingVAE(noisy_encoder, decoder, batch=slots, seed=seed, latent=latent,
+    conv=conv)`` returns for the same signal in slot b, whatever the other slots do and for every signal the slot serves one
+    after another: a draw depends on (seed, b, s, the slot's own frame index, u).  ``seed`` can be set only while every position
+    is 0 (a signal's draws must not change midway); a callable ``eps`` is not taken.  Every guard runs on the host before any GPU
+    work and before any bookkeeping changes.  Per launch group the kernels take two tables, the slots' (:class:`SessionPlan`) for
+    the encoder side and :func:`decoder_rows` of it for the decoder side; both tables of every group and the list of slots to
+    zero go to the device in one copy.
+    """
+
+    _name = "StreamingVAESessions"
+    _skip_halves = 2
+
+    def __init__(self, noisy_encoder, decoder, slots: int, seed: int = 0, latent: str = "speech", average: bool = True,
+                 frames_per_launch: int = 64, max_columns: int = 4096, conv: str = "valu"):
+        super().__init__(noisy_encoder, decoder, slots, seed, latent, average, None, frames_per_launch, max_columns, conv)
+        self._init_slots()
+        # state buffers as [outer][slots][inner] for idv_stream_zero_rows; a B * ns-batch buffer has inner = ns * (its inner)
+        ns = self.ns
+        self._zero_views = [(self.ring, 1, self.plan.ring), (self.carry, 2, ns * self.plan.carry_cap), (self.lstm_state, 16, self.H)]
+        self._zero_views += [(h, h.numel() // slots, 1) for h in [self.h_in] + self.h_enc]
+        self._zero_views += [(h, h.numel() // (slots * ns), ns) for h in [self.h_dense] + self.h_dec]
+
+    @property
+    def seed(self) -> int:
+        return self._seed
+
+    @seed.setter
+    def seed(self, v):
+        v = check_seed(v)
+        if any(self.positions):
+            raise ValueError("seed can be set only between signals (every position 0): a signal's draws must not change midway")
+        self._seed = v
+
+    # ------------------------------------------------------------------ push
+    def push(self, x: torch.Tensor, counts=None, end=()):
+        check_input(x, self.B, self.device)
+        n = int(x.shape[1])
+        counts = check_counts(counts, self.B, n)
+        end = check_slots(end, self.B)
+        snap = self.sessions.snapshot()
+        plan = self.sessions.push(counts, end)
+        B, Bn, ns = self.B, self.Bn, self.ns
+        ldy = max(plan.m)
+        x = x.float()
+        if (n > 1 and x.stride(1) != 1) or (B > 1 and x.stride(0) < n):            # the pitch rules of StreamingDCCRN.push
+            x = x.contiguous()
+        ldx = x.stride(0) if B > 1 else n
+        cap = self.plan.carry_cap
+        per = (B + Bn) * NF                          # a group's two tables: [B][NF], then [B * ns][NF]
+        host = torch.tensor(vae_session_tables(plan, ns), dtype=torch.int64)
+        for gi, g in enumerate(plan.groups):         # a bad table never reaches a kernel
+            rc = L.lib().idv_stream_rows_check(L._P(host.data_ptr() + 8 * gi * per), B, self.plan.ring, 0 if g.flush else n,
+                                               self.n_fft, self.win, self.hop, cap, g.k, g.k + 1, ldy, g.span)
+            if rc != 0:
+                self.sessions.restore(snap)
+                raise L.IdvError(f"idv_stream_rows_check refused the table of launch group {gi} (status {rc})")
+        with torch.no_grad(), torch.cuda.device(self.device):
+            s = stream_ptr()
+            y = torch.zeros(Bn, ldy, dtype=torch.float32, device=self.device)
+            if host.numel():
+                table = self._upload(host)
+                rows_of = lambda gi: L._P(table.data_ptr() + 8 * gi * per)
+                ring_due = any(counts)
+                for gi, g in enumerate(plan.groups):
+                    if g.flush and ring_due:         # the flush phase reads this call's samples from the ring
+                        call("idv_stream_ring_rows", p(self.ring), i(self.plan.ring), p(x), ll(ldx), i(n), rows_of(0), i(B), s)
+                        ring_due = False
+                    c = _VAELaunch(g.k, rows_of(gi), L._P(table.data_ptr() + 8 * (gi * per + B * NF)))
+                    if g.k > 0:
+                        self._network(c, (None, 0) if g.flush else (x if n else None, ldx))
+                    Tp = g.k + 1
+                    call("idv_stream_ola_rows", self.ifr.ptr() if g.k > 0 else p(None), i(Tp), i(Planar.jp_for(Bn, Tp)), p(self.carry),
+                         i(cap), c.rows_n, i(Bn), i(self.n_fft), i(self.win), i(self.hop), i(g.k), ll(g.span), p(y) if ldy else p(None),
+                         ll(ldy), s)
+                if ring_due:
+                    call("idv_stream_ring_rows", p(self.ring), i(self.plan.ring), p(x), ll(ldx), i(n), rows_of(0), i(B), s)
+                self._zero(L._P(table.data_ptr() + 8 * len(plan.groups) * per), len(plan.zero))
+            if not self.average:
+                return y, plan.m
+            out = torch.zeros(B, ldy, dtype=torch.float32, device=self.device)
+            if ldy:
+                call("idv_mean_over_samples", p(y), i(ns), i(B), i(ldy), p(out), s)
+        return out, plan.m
+
+    # ------------------------------------------------------------------ the per-row kernels of the network
+    def _frames(self, c, io, frames, Tp: int, Jp: int):
+        x, ldx = io
+        call("idv_stream_frames_rows", p(self.ring), i(self.plan.ring), p(x), ll(ldx), c.rows, i(self.B), i(self.n_fft), i(self.win),
+             i(self.hop), i(c.k), frames, i(Tp), i(Jp), stream_ptr())
+
+    def _block(self, cp: _ConvPack, c, x0, h0, x1, h1, out, hist, x0hist, Tp: int, Jp: int, dec: bool):
+        B, rows = (self.Bn, c.rows_n) if dec else (self.B, c.rows)
+        if cp.engine == "mfma":                  # two literal call sites, as in _StreamBase._conv_call
+            call("idv_stream_cconv_mfma_rows", x0, p(h0), i(cp.C0), x1 if x1 is not None else p(None), p(h1), i(cp.C1), p(cp.w),
+                 p(cp.bias), p(cp.fold), p(cp.slope), out, p(hist), p(x0hist), p(self.work), i(cp.nsplit),
+                 i(1 if cp.transposed else 0), i(cp.Cout), i(cp.Fin), i(B), i(c.k), i(Tp), i(Jp), rows, stream_ptr())
+            return
+        call("idv_stream_cconv_rows", x0, p(h0), i(cp.C0), x1 if x1 is not None else p(None), p(h1), i(cp.C1), p(cp.w), p(cp.bias),
+             p(cp.fold), p(cp.slope), out, p(hist), p(x0hist), p(self.work), i(cp.nsplit), i(1 if cp.transposed else 0), i(cp.Cout),
+             i(cp.Fin), i(B), i(c.k), i(Tp), i(Jp), rows, stream_ptr())
+
+    def _lstm(self, c, out, Tp: int, Jp: int):
+        call("idv_stream_clstm_wide_rows", p(self.G), p(self.lstm_wt), p(self.lstm_b1), p(self.lstm_state), p(self.hstep), out,
+             i(self.H), i(self.B), i(c.k), i(Tp), i(Jp), c.rows, stream_ptr())
+
+    def _draws(self, c):
+        call("idv_stream_eps_rows", ll(self._seed), c.rows, i(self.B), i(self.ns), i(self.zdim), i(c.k), p(self.eps_buf[0]),
+             p(self.eps_buf[1]), stream_ptr())
+        return p(self.eps_buf[0]), p(self.eps_buf[1])
+
+    def _repeat(self, c, di: int, sk: int, x, xn, Tp: int, Jp: int, Jpn: int):
+        sc, sf = self.enc_shapes[sk]
+        call("idv_stream_repeat_rows", x, p(self.h_enc[sk]), i(sc), i(sf), i(self.B), i(self.ns), i(c.k), i(Tp), i(Jp), c.rows, xn,
+             p(self.h_skip_n[di]), i(Jpn), stream_ptr())
+        return self.h_skip_n[di]

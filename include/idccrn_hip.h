@@ -738,7 +738,8 @@ int idv_stream_cconv_mfma_rows(const float* x0, const float* h0, int C0, const f
 
 /* ---- streaming I-DCCRN-VAE enhancement (stream_lstm.hip, stream_io.hip; streaming.StreamingVAE; additive entries:
  * IDV_ABI_VERSION is unchanged).  The noisy encoder runs at batch B, the decoder at batch B * ns with row b * ns + s, the order
- * of idv_reparam and idv_mask_apply(x_div = ns).  Lock-step only. */
+ * of idv_reparam and idv_mask_apply(x_div = ns).  The three entries below are lock-step; each has a _rows twin for sessions
+ * (streaming.StreamingVAESessions) further down. */
 /* idv_stream_clstm for the hidden sizes of the VAE encoders: H % 16 == 0, 16 <= H <= 768 (idv_stream_clstm_wide_supported).
  * G, wt, b1, state and out as idv_stream_clstm.  hstep: idv_stream_clstm_wide_hstep_floats(H, B, k) = 8 * k * B * H floats of
  * scratch, [2 layers][4 runs][k*B][H]: the h of every step (h is never updated in place; the last rows go to state at the end).
@@ -758,6 +759,30 @@ int idv_stream_eps(long long seed, long long t0, int k, int B, int ns, int zdim,
  * histn [2][C][F][B*ns]. */
 int idv_stream_repeat(const float* x, const float* hist, int C, int F, int B, int ns, int k, int Tp, int Jp, float* xn, float* histn,
                       int Jpn, void* stream);
+
+/* ---- VAE sessions: the _rows twins of the three entries above (stream_lstm.hip, stream_io.hip;
+ * streaming.StreamingVAESessions; additive entries: IDV_ABI_VERSION is unchanged).  rows[B][IDV_STREAM_ROW_FIELDS] is the table of
+ * the other _rows entries, one row per slot of the ENCODER batch B; the decoder side takes a second table [B*ns] whose row
+ * b*ns + s equals row b, with the existing idv_stream_cconv_rows / idv_stream_cconv_mfma_rows / idv_stream_ola_rows at B = B*ns.
+ * Each kernel is the lock-step kernel's body compiled a second time: the arithmetic of a column and its order are one source. */
+/* idv_stream_clstm_wide per slot.  G ([2][k_launch*B][8H]) and hstep (idv_stream_clstm_wide_hstep_floats(H, B, k_launch)) have
+ * k_launch as the step stride; 2 * k_launch step launches, then the combine and the state copy.  Slot b takes part in the steps
+ * t < k_b only: in a step t >= k_b nothing of it is written, neither c in state nor its hstep row, and since its hstep rows may
+ * never have been written, zeros are staged in their place and the results dropped.  The fmaf chain of an active stream is the
+ * lock-step one (G or b1 first, then increasing k) whatever its seven tile neighbours do; a workgroup whose 8 streams are all idle
+ * at step t returns before its first barrier.  The state copy takes row k_b - 1 of slot b and nothing when k_b = 0; the combine
+ * writes zeros to the columns t >= k_b of out, as idv_stream_clstm_rows does. */
+int idv_stream_clstm_wide_rows(const float* G, const float* wt, const float* b1, float* state, float* hstep, float* out, int H, int B,
+                               int k_launch, int Tp, int Jp, const long long* rows, void* stream);
+/* idv_stream_eps per slot: eps_r, eps_i [B][ns][k_launch][zdim].  Frame tl < k_b of slot b is drawn with the counter
+ * (t0_b + tl, b*ns + s, u), exactly as idv_stream_eps(seed, t0_b, ...) draws it; the entries with tl >= k_b are zero. */
+int idv_stream_eps_rows(long long seed, const long long* rows, int B, int ns, int zdim, int k_launch, float* eps_r, float* eps_i,
+                        void* stream);
+/* idv_stream_repeat per slot: hist is [2 parities][2][C][F][B] and histn [2 parities][2][C][F][B*ns] (twice the lock-step
+ * scratch: the _rows conv entries read h1 at half parity_b).  The columns tl < k_b of slot b and its history of half parity_b go
+ * to the rows b*ns + s of xn and to half parity_b of histn; a slot with k_b = 0 is not touched, nor are the columns tl >= k_b. */
+int idv_stream_repeat_rows(const float* x, const float* hist, int C, int F, int B, int ns, int k_launch, int Tp, int Jp,
+                           const long long* rows, float* xn, float* histn, int Jpn, void* stream);
 
 /* ---- batches of utterances of different lengths (ragged.hip, reduce.hip; inference.enhance_* / compute_sisdr with `lengths`) ---
  * lens: device int32[], samples per utterance.  Utterance b has T_b = 1 + lens[b] / hop frames and hop * (T_b - 1) output samples;

@@ -1,7 +1,7 @@
 """Streaming enhancement benchmark: one JSON line per batch of lock-step streams, one hop (100 samples) per push.
 
     python profiles/tools/stream_bench.py [--batches 1,16,128,512,1024] [--seconds 2] [--catchup] [--far-seconds 3600] [--sessions]
-                                           [--conv valu|mfma|both] [--vae]
+                                           [--conv valu|mfma|both] [--vae [--sessions]]
 
 Per line: device time per push (HIP events around >= --seconds of pushes after warm-up), host wall time per push (synchronised),
 the real-time factor (hop / 16 kHz = 6.25 ms over the wall time) and the algorithmic GFLOP per push (4 real products per complex
@@ -16,7 +16,10 @@ streams are never flushed; pushes are column slices of a 4 s signal taken round-
 synthetic weights.  --vae measures streaming.StreamingVAE instead (metric "vae_push"): the full-width NSVAE encoder (zdim 128,
 latent_num 2: LSTM hidden 768) and fine-tuned decoder with num_samples 3, default batches 1,16,128; each line adds the device
 time of the wide LSTM entry alone at the push's shape (events around repeated calls of idv_stream_clstm_wide on the streamer's
-own buffers, after the push measurements) and its share of the device time of a push.
+own buffers, after the push measurements) and its share of the device time of a push.  --vae --sessions measures
+streaming.StreamingVAESessions (metric "vae_sessions_push": every slot active at the staggered positions of --sessions, counts as a
+host list on every push) and, right after it in the same process and with the same models, the lock-step StreamingVAE at the same
+B and engine (metric "vae_push"), so that the two lines of a pair share the card and its clocks.
 """
 from __future__ import annotations
 
@@ -75,18 +78,26 @@ def wide_lstm_ms(st, k=1, reps=200) -> float:
     return e0.elapsed_time(e1) / reps
 
 
+_VAE_PAIR = []
+
+
 def build(B, sessions=False, conv="valu", vae=False):
     pm = importlib.import_module("i-dccrn-vae_amd.model.pvae_module")
     S = importlib.import_module("i-dccrn-vae_amd.streaming")
     from oracle import idccrn_oracle as O
     np_ = O.net_params(True, 32)
     if vae:
-        load = lambda m, seed: m.load_state_dict(O.synth_state_dict({k: tuple(v.shape) for k, v in m.state_dict().items()}, seed))
-        enc = pm.nsvae_pvae_dccrn_encoder_twophase(np_, True, "cuda", 128, NFFT, HOP, WIN, 3, 2)
-        dec = pm.nsvae_pvae_dccrn_decoder_twophase(np_, True, "cuda", 3, 128, NFFT, HOP, WIN, "mask", True, [0, 1, 2, 3, 4, 5], False)
-        load(enc, 9)
-        load(dec, 10)
-        return S.StreamingVAE(enc.cuda(), dec.cuda(), batch=B, seed=0, conv=conv)
+        if not _VAE_PAIR:                       # one pair for every streamer of the process
+            load = lambda m, seed: m.load_state_dict(O.synth_state_dict({k: tuple(v.shape) for k, v in m.state_dict().items()}, seed))
+            enc = pm.nsvae_pvae_dccrn_encoder_twophase(np_, True, "cuda", 128, NFFT, HOP, WIN, 3, 2)
+            dec = pm.nsvae_pvae_dccrn_decoder_twophase(np_, True, "cuda", 3, 128, NFFT, HOP, WIN, "mask", True, [0, 1, 2, 3, 4, 5], False)
+            load(enc, 9)
+            load(dec, 10)
+            _VAE_PAIR.extend([enc.cuda(), dec.cuda()])
+        enc, dec = _VAE_PAIR
+        if sessions:
+            return S.StreamingVAESessions(enc, dec, slots=B, seed=0, conv=conv)
+        return S.StreamingVAE(enc, dec, batch=B, seed=0, conv=conv)
     m = pm.DCCRN_(NFFT, HOP, np_, True, "cuda", WIN, [0, 1, 2, 3, 4, 5], "mask", False, None, None)
     m.load_state_dict(O.synth_state_dict({k: tuple(v.shape) for k, v in m.state_dict().items()}, 7))
     m = m.cuda()
@@ -146,8 +157,8 @@ def main():
     ap.add_argument("--conv", choices=["valu", "mfma", "both"], default="valu")
     ap.add_argument("--vae", action="store_true")
     a = ap.parse_args()
-    if a.vae and (a.sessions or a.catchup or a.far_seconds):
-        ap.error("--vae measures hop pushes of StreamingVAE only")
+    if a.vae and (a.catchup or a.far_seconds):
+        ap.error("--vae measures hop pushes of StreamingVAE / StreamingVAESessions only")
     if a.batches is None:
         a.batches = "1,16,128" if a.vae else "1,16,128,512,1024"
     torch.set_grad_enabled(False)
@@ -157,18 +168,21 @@ def main():
     for B in [int(v) for v in a.batches.split(",") if v]:
         for conv, rnd in turns:
             if a.vae:
-                st, dev_ms, wall_ms, _ = run(B, a.seconds, conv=conv, vae=True)
-                gf = gflop_per_frame_vae(st) * B
-                lstm_ms = wide_lstm_ms(st)
-                print(json.dumps({"metric": "vae_push", "B": B, "ns": st.ns, "H": st.H, "hop": HOP,
-                                  "device_ms_per_push": round(dev_ms, 4), "wall_ms_per_push": round(wall_ms, 4),
-                                  "rtf": round(budget / wall_ms, 3), "device_rtf": round(budget / dev_ms, 3),
-                                  "under_hop_budget": bool(wall_ms < budget), "wide_lstm_device_ms": round(lstm_ms, 4),
-                                  "wide_lstm_share": round(lstm_ms / dev_ms, 3), "gflop_per_push": round(gf, 3),
-                                  "tflops_device": round(gf / dev_ms, 2), "frames_per_launch": st.cap, "conv": conv,
-                                  "conv_engines": st.conv_engines.count("mfma"), "round": rnd}), flush=True)
-                del st
-                torch.cuda.empty_cache()
+                for sessions in ([True, False] if a.sessions else [False]):
+                    st, dev_ms, wall_ms, _ = run(B, a.seconds, sessions=sessions, conv=conv, vae=True)
+                    gf = gflop_per_frame_vae(st) * B
+                    line = {"metric": "vae_sessions_push" if sessions else "vae_push", "B": B, "ns": st.ns, "H": st.H, "hop": HOP,
+                            "device_ms_per_push": round(dev_ms, 4), "wall_ms_per_push": round(wall_ms, 4),
+                            "rtf": round(budget / wall_ms, 3), "device_rtf": round(budget / dev_ms, 3),
+                            "under_hop_budget": bool(wall_ms < budget)}
+                    if not sessions:
+                        lstm_ms = wide_lstm_ms(st)
+                        line.update({"wide_lstm_device_ms": round(lstm_ms, 4), "wide_lstm_share": round(lstm_ms / dev_ms, 3)})
+                    line.update({"gflop_per_push": round(gf, 3), "tflops_device": round(gf / dev_ms, 2), "frames_per_launch": st.cap,
+                                 "conv": conv, "conv_engines": st.conv_engines.count("mfma"), "round": rnd})
+                    print(json.dumps(line), flush=True)
+                    del st
+                    torch.cuda.empty_cache()
                 continue
             st, dev_ms, wall_ms, _ = run(B, a.seconds, sessions=a.sessions, conv=conv)
             gf = gflop_per_frame(st) * B
