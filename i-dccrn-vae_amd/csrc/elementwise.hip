@@ -57,6 +57,21 @@ __global__ void istft_ola_kernel(const float* __restrict__ frames, const float* 
 }
 
 // predict = X * M * tanh|M| / |M|   (== |X| tanh|M| exp(j(angle X + angle M)), pvae_module.py:224-234)
+__device__ __forceinline__ void mask_predict(float mr, float mi, float xr, float xi, float& pr, float& pi) {
+    const float mm = sqrtf(mr * mr + mi * mi);
+    const float g = tanhf(mm);
+    // unit phasor of the mask exactly as the reference builds it: (m / (tanh|m| + 1e-8)) normalised
+    float ur, ui;
+    if (mm > 0.f) {
+        const float inv = 1.0f / mm;
+        ur = mr * inv; ui = mi * inv;
+    } else {
+        ur = 1.f; ui = 0.f;     // atan2(0, 0) = 0
+    }
+    pr = g * (xr * ur - xi * ui);
+    pi = g * (xr * ui + xi * ur);
+}
+
 __global__ void mask_apply_kernel(const float* __restrict__ mask, const float* __restrict__ X, int x_div, int JpX,
                                   float* __restrict__ pred, float* __restrict__ pred_c, int F, int B, int T, int Tp, int Jp) {
     const long long n = (long long)B * F * T;
@@ -66,19 +81,8 @@ __global__ void mask_apply_kernel(const float* __restrict__ mask, const float* _
         const int b = (int)(idx / ((long long)T * F));
         const size_t jm = (size_t)f * Jp + (size_t)b * Tp + t + 1;
         const size_t jx = (size_t)f * JpX + (size_t)(b / x_div) * Tp + t + 1;
-        const float mr = mask[jm], mi = mask[(size_t)F * Jp + jm];
-        const float xr = X[jx], xi = X[(size_t)F * JpX + jx];
-        const float mm = sqrtf(mr * mr + mi * mi);
-        const float g = tanhf(mm);
-        // unit phasor of the mask exactly as the reference builds it: (m / (tanh|m| + 1e-8)) normalised
-        float ur, ui;
-        if (mm > 0.f) {
-            const float inv = 1.0f / mm;
-            ur = mr * inv; ui = mi * inv;
-        } else {
-            ur = 1.f; ui = 0.f;     // atan2(0, 0) = 0
-        }
-        const float pr = g * (xr * ur - xi * ui), pi = g * (xr * ui + xi * ur);
+        float pr, pi;
+        mask_predict(mask[jm], mask[(size_t)F * Jp + jm], X[jx], X[(size_t)F * JpX + jx], pr, pi);
         pred[jm] = pr;
         pred[(size_t)F * Jp + jm] = pi;
         if (pred_c) {
@@ -95,11 +99,36 @@ __global__ void mask_apply_kernel(const float* __restrict__ mask, const float* _
 // angle X) * |X| * exp(j angle S) = S * Re(S conj X) / (|S| (|S| + |N| + eps)) (0 where S = 0; where X = 0 both forms are 0).
 // speech / noise: interleaved complex [B*ns][F][T][2]; X: strided [B][F][T][2]; out: planar [2][F][Jp] (guard columns zeroed
 // by the caller), out_c (optional): interleaved complex [B][F][T][2].
+// the estimator of one bin from the two sample means (S, N) and the noisy bin X
+__device__ __forceinline__ void outtype_apply(int mode, float s_r, float s_i, float n_r, float n_i, float xr, float xi, float& er,
+                                              float& ei) {
+    const float eps = 1e-10f;
+    if (mode == 0) {
+        er = s_r * s_r / (s_r * s_r + n_r * n_r + eps) * xr;
+        ei = s_i * s_i / (s_i * s_i + n_i * n_i + eps) * xi;
+    } else if (mode == 1) {
+        const float dr = s_r + n_r + eps, di = s_i + n_i;          // complex + real eps
+        const float dd = dr * dr + di * di;
+        float mr = 0.f, mi = 0.f;
+        if (dd > 0.f) {
+            mr = (s_r * dr + s_i * di) / dd;
+            mi = (s_i * dr - s_r * di) / dd;
+        }
+        er = mr * xr - mi * xi;
+        ei = mr * xi + mi * xr;
+    } else {
+        const float sm = sqrtf(s_r * s_r + s_i * s_i), nm = sqrtf(n_r * n_r + n_i * n_i);
+        float g = 0.f;
+        if (sm > 0.f) g = (s_r * xr + s_i * xi) / (sm * (sm + nm + eps));
+        er = g * s_r;
+        ei = g * s_i;
+    }
+}
+
 __global__ void outtype_kernel(const float* __restrict__ speech, const float* __restrict__ noise, const float* __restrict__ X,
                                long long sb, long long sf, long long st_, long long sr, int mode, int ns, int B, int F, int T,
                                int Tp, int Jp, float* __restrict__ out, float* __restrict__ out_c) {
     const long long n = (long long)B * F * T;
-    const float eps = 1e-10f;
     const float inv = 1.0f / (float)ns;
     for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < n; idx += (long long)gridDim.x * blockDim.x) {
         const int t = (int)(idx % T);
@@ -113,28 +142,8 @@ __global__ void outtype_kernel(const float* __restrict__ speech, const float* __
         }
         s_r *= inv; s_i *= inv; n_r *= inv; n_i *= inv;
         const float* xp = X + b * sb + f * sf + t * st_;
-        const float xr = xp[0], xi = xp[sr];
         float er, ei;
-        if (mode == 0) {
-            er = s_r * s_r / (s_r * s_r + n_r * n_r + eps) * xr;
-            ei = s_i * s_i / (s_i * s_i + n_i * n_i + eps) * xi;
-        } else if (mode == 1) {
-            const float dr = s_r + n_r + eps, di = s_i + n_i;          // complex + real eps
-            const float dd = dr * dr + di * di;
-            float mr = 0.f, mi = 0.f;
-            if (dd > 0.f) {
-                mr = (s_r * dr + s_i * di) / dd;
-                mi = (s_i * dr - s_r * di) / dd;
-            }
-            er = mr * xr - mi * xi;
-            ei = mr * xi + mi * xr;
-        } else {
-            const float sm = sqrtf(s_r * s_r + s_i * s_i), nm = sqrtf(n_r * n_r + n_i * n_i);
-            float g = 0.f;
-            if (sm > 0.f) g = (s_r * xr + s_i * xi) / (sm * (sm + nm + eps));
-            er = g * s_r;
-            ei = g * s_i;
-        }
+        outtype_apply(mode, s_r, s_i, n_r, n_i, xp[0], xp[sr], er, ei);
         const size_t j = (size_t)f * Jp + (size_t)b * Tp + t + 1;
         out[j] = er;
         out[(size_t)F * Jp + j] = ei;
@@ -142,6 +151,42 @@ __global__ void outtype_kernel(const float* __restrict__ speech, const float* __
             out_c[idx * 2] = er;
             out_c[idx * 2 + 1] = ei;
         }
+    }
+}
+
+// streaming.StreamingVAETwoLatents: the two decoders' last-block outputs of the k columns of a launch group -> the estimator's
+// spectrum at batch B.  One thread per (f, b, t); for s = 0 .. ns-1 in this order it reads column (b*ns + s)*Tp + t + 1 of speech /
+// noise (planar [2][F][Jpn]), with MASK turns each into the masked spectrum (mask_predict against X, the arithmetic of
+// mask_apply_kernel with x_div = ns), sums, scales by 1/ns and applies outtype_apply: outtype_kernel's sums in outtype_kernel's
+// order.  An output is a function of its own column alone; the guard columns of out are not written.
+template <bool MASK>
+__global__ void stream_estimate_kernel(const float* __restrict__ speech, const float* __restrict__ noise, const float* __restrict__ X,
+                                       int mode, int ns, int F, int B, int k, int Tp, int Jp, int Jpn, float* __restrict__ out) {
+    const long long n = (long long)F * B * k;
+    const float inv = 1.0f / (float)ns;
+    for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < n; idx += (long long)gridDim.x * blockDim.x) {
+        const int t = (int)(idx % k);
+        const int b = (int)((idx / k) % B);
+        const int f = (int)(idx / ((long long)k * B));
+        const size_t j = (size_t)f * Jp + (size_t)b * Tp + t + 1;
+        const float xr = X[j], xi = X[(size_t)F * Jp + j];
+        float s_r = 0.f, s_i = 0.f, n_r = 0.f, n_i = 0.f;
+        for (int s = 0; s < ns; ++s) {
+            const size_t jn = (size_t)f * Jpn + ((size_t)b * ns + s) * Tp + t + 1;
+            float a_r = speech[jn], a_i = speech[(size_t)F * Jpn + jn];
+            float c_r = noise[jn], c_i = noise[(size_t)F * Jpn + jn];
+            if (MASK) {
+                mask_predict(a_r, a_i, xr, xi, a_r, a_i);
+                mask_predict(c_r, c_i, xr, xi, c_r, c_i);
+            }
+            s_r += a_r; s_i += a_i;
+            n_r += c_r; n_i += c_i;
+        }
+        s_r *= inv; s_i *= inv; n_r *= inv; n_i *= inv;
+        float er, ei;
+        outtype_apply(mode, s_r, s_i, n_r, n_i, xr, xi, er, ei);
+        out[j] = er;
+        out[(size_t)F * Jp + j] = ei;
     }
 }
 
@@ -445,6 +490,23 @@ extern "C" int idv_outtype_estimate(const float* speech_c, const float* noise_c,
     if (hipMemsetAsync(out, 0, sizeof(float) * 2 * (size_t)F * Jp, st) != hipSuccess) return IDV_ELAUNCH;
     hipLaunchKernelGGL(outtype_kernel, dim3(grid_for((long long)B * F * T)), dim3(256), 0, st, speech_c, noise_c, X, sb, sf, st_, sr,
                        mode, ns, B, F, T, Tp, Jp, out, out_c);
+    return idv_launch_status();
+}
+
+// The estimator on the planar streaming layout (streaming.StreamingVAETwoLatents): speech / noise are the two decoders' last-block
+// outputs [2][F][Jpn] at batch B * ns, X the noisy spectrum and out the estimate, both [2][F][Jp] at batch B.
+extern "C" int idv_stream_estimate(const float* speech, const float* noise, const float* X, int recon_mask, int mode, int ns, int F,
+                                   int B, int k, int Tp, int Jp, int Jpn, float* out, void* stream) {
+    if (!speech || !noise || !X || !out || (recon_mask != 0 && recon_mask != 1) || mode < 0 || mode > 2 || ns < 1 || F <= 0 || B <= 0 ||
+        k <= 0 || Tp < k + 1 || (long long)B * Tp > Jp || (long long)B * ns * Tp > Jpn)
+        return IDV_EINVAL;
+    const dim3 grid(grid_for((long long)F * B * k)), block(256);
+    if (recon_mask)
+        hipLaunchKernelGGL(stream_estimate_kernel<true>, grid, block, 0, (hipStream_t)stream, speech, noise, X, mode, ns, F, B, k, Tp, Jp,
+                           Jpn, out);
+    else
+        hipLaunchKernelGGL(stream_estimate_kernel<false>, grid, block, 0, (hipStream_t)stream, speech, noise, X, mode, ns, F, B, k, Tp,
+                           Jp, Jpn, out);
     return idv_launch_status();
 }
 

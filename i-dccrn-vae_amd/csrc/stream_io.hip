@@ -186,7 +186,7 @@ __global__ void stream_zero_rows_kernel(float* __restrict__ buf, long long outer
 
 // Philox4x32-10 (Salmon et al., SC'11): ten rounds of two 32x32 -> 64 multiplies, the key bumped by the Weyl constants
 __device__ __forceinline__ void philox4x32_10(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                                              uint32_t& w0, uint32_t& w1) {
+                                              uint32_t& w0, uint32_t& w1, uint32_t& w2, uint32_t& w3) {
 #pragma unroll
     for (int round = 0; round < 10; ++round) {
         const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
@@ -200,15 +200,29 @@ __device__ __forceinline__ void philox4x32_10(uint32_t k0, uint32_t k1, uint32_t
     }
     w0 = c0;
     w1 = c1;
+    w2 = c2;
+    w3 = c3;
+}
+
+// two words of a Philox block -> one complex Gaussian draw (Box-Muller in fp32)
+__device__ __forceinline__ void box_muller(uint32_t wa, uint32_t wb, float& re, float& im) {
+    const float u1 = (float)((wa >> 8) + 1u) * 0x1p-24f;                  // (0, 1]
+    const float th = 6.283185307179586476925286766559f * ((float)(wb >> 8) * 0x1p-24f);
+    const float rad = sqrtf(-2.0f * logf(u1));
+    re = rad * cosf(th);
+    im = rad * sinf(th);
 }
 
 // eps_r, eps_i [B][ns][k][zdim] for frames t0 .. t0+k-1: counter (t low, t high, b*ns + s, u), key (seed low, seed high); words
 // 0 and 1 through Box-Muller.  A draw depends on (seed, b, s, t, u) only.
 // ROWS (idv_stream_eps_rows): k is k_launch, slot b = bs / ns starts at its own t0_b and draws its first k_b frames; the rest of
 // its entries are zero.
-template <bool ROWS>
+// PAIR (idv_stream_eps_pair): words 2 and 3 of the same block through the same Box-Muller give a second, independent pair
+// (eps2_r, eps2_i), the noise latent's draws; words 0 and 1 are what the kernel without PAIR writes.
+template <bool ROWS, bool PAIR>
 __global__ void stream_eps_kernel(unsigned long long seed, long long t0, int k, int Bn, int zdim, float* __restrict__ eps_r,
-                                  float* __restrict__ eps_i, int ns, const long long* __restrict__ rows) {
+                                  float* __restrict__ eps_i, float* __restrict__ eps2_r, float* __restrict__ eps2_i, int ns,
+                                  const long long* __restrict__ rows) {
     const long long n = (long long)Bn * k * zdim;
     for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
         const uint32_t u = (uint32_t)(e % zdim);
@@ -224,13 +238,10 @@ __global__ void stream_eps_kernel(unsigned long long seed, long long t0, int k, 
             t0 = row[IDV_ROW_T0];
         }
         const unsigned long long t = (unsigned long long)(t0 + tl);
-        uint32_t w0, w1;
-        philox4x32_10((uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)t, (uint32_t)(t >> 32), bs, u, w0, w1);
-        const float u1 = (float)((w0 >> 8) + 1u) * 0x1p-24f;                  // (0, 1]
-        const float th = 6.283185307179586476925286766559f * ((float)(w1 >> 8) * 0x1p-24f);
-        const float rad = sqrtf(-2.0f * logf(u1));
-        eps_r[e] = rad * cosf(th);
-        eps_i[e] = rad * sinf(th);
+        uint32_t w0, w1, w2, w3;
+        philox4x32_10((uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)t, (uint32_t)(t >> 32), bs, u, w0, w1, w2, w3);
+        box_muller(w0, w1, eps_r[e], eps_i[e]);
+        if (PAIR) box_muller(w2, w3, eps2_r[e], eps2_i[e]);
     }
 }
 
@@ -266,11 +277,22 @@ __global__ void stream_repeat_kernel(const float* __restrict__ x, const float* _
 }  // namespace
 
 static const long long* const no_rows = nullptr;      // the table argument of a lock-step instantiation, which never reads it
+static float* const no_eps = nullptr;                 // the second pair of an instantiation without PAIR, which never writes it
 
 extern "C" int idv_stream_eps(long long seed, long long t0, int k, int B, int ns, int zdim, float* eps_r, float* eps_i, void* stream) {
     if (t0 < 0 || k <= 0 || B <= 0 || ns <= 0 || zdim <= 0 || !eps_r || !eps_i || (long long)B * ns > 0x7fffffffLL) return IDV_EINVAL;
-    hipLaunchKernelGGL(stream_eps_kernel<false>, dim3(grid_of((long long)B * ns * k * zdim)), dim3(256), 0, (hipStream_t)stream,
-                       (unsigned long long)seed, t0, k, B * ns, zdim, eps_r, eps_i, ns, no_rows);
+    hipLaunchKernelGGL((stream_eps_kernel<false, false>), dim3(grid_of((long long)B * ns * k * zdim)), dim3(256), 0, (hipStream_t)stream,
+                       (unsigned long long)seed, t0, k, B * ns, zdim, eps_r, eps_i, no_eps, no_eps, ns, no_rows);
+    return idv_launch_status();
+}
+
+extern "C" int idv_stream_eps_pair(long long seed, long long t0, int k, int B, int ns, int zdim, float* eps_sr, float* eps_si,
+                                   float* eps_nr, float* eps_ni, void* stream) {
+    if (t0 < 0 || k <= 0 || B <= 0 || ns <= 0 || zdim <= 0 || !eps_sr || !eps_si || !eps_nr || !eps_ni ||
+        (long long)B * ns > 0x7fffffffLL)
+        return IDV_EINVAL;
+    hipLaunchKernelGGL((stream_eps_kernel<false, true>), dim3(grid_of((long long)B * ns * k * zdim)), dim3(256), 0, (hipStream_t)stream,
+                       (unsigned long long)seed, t0, k, B * ns, zdim, eps_sr, eps_si, eps_nr, eps_ni, ns, no_rows);
     return idv_launch_status();
 }
 
@@ -289,8 +311,8 @@ extern "C" int idv_stream_eps_rows(long long seed, const long long* rows, int B,
                                    float* eps_i, void* stream) {
     if (!rows || k_launch <= 0 || B <= 0 || ns <= 0 || zdim <= 0 || !eps_r || !eps_i || (long long)B * ns > 0x7fffffffLL)
         return IDV_EINVAL;
-    hipLaunchKernelGGL(stream_eps_kernel<true>, dim3(grid_of((long long)B * ns * k_launch * zdim)), dim3(256), 0, (hipStream_t)stream,
-                       (unsigned long long)seed, 0LL, k_launch, B * ns, zdim, eps_r, eps_i, ns, rows);
+    hipLaunchKernelGGL((stream_eps_kernel<true, false>), dim3(grid_of((long long)B * ns * k_launch * zdim)), dim3(256), 0,
+                       (hipStream_t)stream, (unsigned long long)seed, 0LL, k_launch, B * ns, zdim, eps_r, eps_i, no_eps, no_eps, ns, rows);
     return idv_launch_status();
 }
 

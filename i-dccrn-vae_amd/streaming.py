@@ -10,8 +10,9 @@ look-ahead is the STFT window: frame t reads samples [hop*t - win/2, hop*t + win
 emission bookkeeping from which every kernel launch takes its ranges.
 
 :class:`StreamingSessions` runs one such stream per slot, each starting and ending on its own; :class:`StreamingVAE` streams
-the I-DCCRN-VAE pair (noisy encoder, latent draw, fine-tuned decoder with the noisy skips) under the same contract, and
-:class:`StreamingVAESessions` runs that pair one stream per slot.
+the I-DCCRN-VAE pair (noisy encoder, latent draw, fine-tuned decoder with the noisy skips) under the same contract,
+:class:`StreamingVAESessions` runs that pair one stream per slot, and :class:`StreamingVAETwoLatents` streams the two-latent
+evaluation: speech and noise decoder on one encoder pass, then a mask estimator.
 """
 from __future__ import annotations
 
@@ -23,6 +24,7 @@ import torch
 from . import _lib as L
 from . import ops
 from ._lib import call, i, ll, p, stream_ptr
+from .inference import OUTTYPES
 from .ops import Planar
 
 
@@ -322,11 +324,15 @@ class _StreamBase:
         for t in self.state:
             t.zero_()
 
-    def _conv(self, conv, blk, C0, C1, Fin, B):
+    def _conv(self, conv, blk, C0, C1, Fin, B, zero_skip=False):
+        """``zero_skip``: a transposed block whose skip input is all zeros is packed with the first C0 input channels of its
+        weights only (C1 = 0): the other channels would multiply zeros, and no zero buffer is ever read."""
         cp = _ConvPack()
         cp.transposed = conv._transposed
         re, im = conv._re, conv._im
-        cin = conv.in_channel if C1 == 0 else C0 + C1
+        if zero_skip and (C1 != 0 or not cp.transposed or C0 > conv.in_channel):
+            raise ValueError(f"{self._name}: a zero skip belongs to a transposed block called with C1 = 0")
+        cin = C0 if zero_skip else (conv.in_channel if C1 == 0 else C0 + C1)
         cp.Cout = conv.out_channel
         cp.C0, cp.C1, cp.Fin = C0, C1, Fin
         cp.Fout = 2 * Fin - 1 if cp.transposed else (Fin - 1) // 2 + 1
@@ -334,7 +340,9 @@ class _StreamBase:
         mfma = self.conv == "mfma" and L.lib().idv_stream_cconv_mfma_supported(i(1 if cp.transposed else 0), i(cin), i(cp.Cout)) == 1
         cp.engine = "mfma" if mfma else "valu"
         cp.bias = torch.empty(2 * cp.Cout, dtype=torch.float32, device=self.device)
-        wsrc = (p(re.weight.detach().float().contiguous()), p(im.weight.detach().float().contiguous()),
+        # transposed-conv weights are [Cin][Cout][5][2]: the first cin input channels are a prefix
+        wsrc = (p(re.weight.detach().float()[:cin if zero_skip else None].contiguous()),
+                p(im.weight.detach().float()[:cin if zero_skip else None].contiguous()),
                 p(re.bias.detach().float().contiguous()), p(im.bias.detach().float().contiguous()))
         if mfma:
             cp.w = torch.empty(int(L.lib().idv_stream_cconv_mfma_wfloats(i(cin), i(cp.Cout))), dtype=torch.float32, device=self.device)
@@ -810,51 +818,133 @@ def check_vae(noisy_encoder, decoder, batch, latent="speech", seed=0, eps=None) 
     latent_num = getattr(noisy_encoder, "latent_num", 1)
     if latent == "noise" and latent_num != 2:
         raise ValueError("latent='noise' needs an encoder with latent_num 2: this encoder has no noise latent")
+    _check_pair("StreamingVAE", noisy_encoder, decoder)
+    _check_batch_seed("StreamingVAE", batch, seed)
+    if eps is not None and not callable(eps):
+        raise ValueError("eps must be None (the streamer's own draws) or a callable (t0, k) -> (eps_r, eps_i)")
+    _check_lstm("StreamingVAE", noisy_encoder)
+    _check_chain("StreamingVAE", noisy_encoder, decoder)
+    _check_on_gpu("StreamingVAE", (noisy_encoder, decoder))
+
+
+def _check_pair(name, noisy_encoder, decoder, what="decoder") -> None:
+    """An encoder and one decoder agree: causal, n_fft / hop / win, zdim, num_samples, a known recon_type."""
     if not noisy_encoder.causal or not decoder.causal or any(e.conv._cfg[2][1] != 1 for e in noisy_encoder.encoders):
-        raise ValueError("StreamingVAE needs a causal encoder and decoder (encoder time padding 1): with time padding 0 frame t needs "
+        raise ValueError(f"{name} needs a causal encoder and {what} (encoder time padding 1): with time padding 0 frame t needs "
                          "x[t+1]")
     se, sd = noisy_encoder.stft, decoder.istft
     if (se.n_fft, se.hop_length, se.win_length) != (sd.n_fft, sd.hop_length, sd.win_length):
-        raise ValueError("StreamingVAE: encoder and decoder differ in n_fft / hop / win")
+        raise ValueError(f"{name}: encoder and {what} differ in n_fft / hop / win")
     if noisy_encoder.zdim != decoder.zdim or noisy_encoder.num_samples != decoder.num_samples:
-        raise ValueError("StreamingVAE: encoder and decoder differ in zdim or num_samples")
+        raise ValueError(f"{name}: encoder and {what} differ in zdim or num_samples")
     if decoder.recon_type not in ("mask", "real_imag"):
-        raise ValueError(f"StreamingVAE: unknown recon_type {decoder.recon_type!r} (mask or real_imag)")
+        raise ValueError(f"{name}: unknown recon_type {decoder.recon_type!r} (mask or real_imag)")
+
+
+def _check_batch_seed(name, batch, seed) -> None:
     if isinstance(batch, bool) or not isinstance(batch, int) or batch <= 0:
-        raise ValueError("StreamingVAE: batch must be a positive int")
+        raise ValueError(f"{name}: batch must be a positive int")
     check_seed(seed)
-    if eps is not None and not callable(eps):
-        raise ValueError("eps must be None (the streamer's own draws) or a callable (t0, k) -> (eps_r, eps_i)")
+
+
+def _check_lstm(name, noisy_encoder) -> None:
+    latent_num = getattr(noisy_encoder, "latent_num", 1)
     lstms = noisy_encoder.lstms
     if (len(lstms) != 1 or lstms[0].num_layer != 2 or lstms[0].hidden_size != 3 * noisy_encoder.zdim * latent_num
             or L.lib().idv_stream_clstm_wide_supported(i(lstms[0].hidden_size)) != 1):
-        raise ValueError("StreamingVAE: one two-layer ComplexLSTM with hidden size 3 * zdim * latent_num, a multiple of 16 up to 768, "
+        raise ValueError(f"{name}: one two-layer ComplexLSTM with hidden size 3 * zdim * latent_num, a multiple of 16 up to 768, "
                          "is supported")
-    # the decoder's channel chain against the encoder's skips
+
+
+def _check_chain(name, noisy_encoder, decoder, what="decoder") -> None:
+    """The decoder's channel chain against the encoder's skips (a zero skip takes the same channels of the weights)."""
+    lstms = noisy_encoder.lstms
     enc_c = [e.conv.out_channel for e in noisy_encoder.encoders]
     if len(decoder.decoders) != len(enc_c) or lstms[0].input_size % enc_c[-1]:
-        raise ValueError("StreamingVAE: the decoder does not mirror the encoder")
+        raise ValueError(f"{name}: the {what} does not mirror the encoder")
     top_f = lstms[0].input_size // enc_c[-1]
     if decoder.dense.in_channel != decoder.zdim or decoder.dense.out_channel % top_f:
-        raise ValueError("StreamingVAE: the decoder's dense layer does not match zdim and the top encoder shape")
+        raise ValueError(f"{name}: the {what}'s dense layer does not match zdim and the top encoder shape")
     c = decoder.dense.out_channel // top_f
     for di, blk in enumerate(decoder.decoders):
         c1 = enc_c[len(enc_c) - 1 - di] if (decoder.use_sc and di in decoder.skip_to_use) else 0
         if c + c1 != blk.transconv.in_channel:
-            raise ValueError(f"StreamingVAE: decoder block {di} takes {blk.transconv.in_channel} channels, the chain and the encoder's "
+            raise ValueError(f"{name}: {what} block {di} takes {blk.transconv.in_channel} channels, the chain and the encoder's "
                              f"skip give {c} + {c1}")
         c = blk.transconv.out_channel
     if c != 1:
-        raise ValueError("StreamingVAE: the last decoder must give one channel")
-    for m in (noisy_encoder, decoder):
+        raise ValueError(f"{name}: the last {what} must give one channel")
+
+
+def _check_on_gpu(name, modules) -> None:
+    for m in modules:
         if any(not q.is_cuda for q in m.parameters()) or any(not b.is_cuda for b in m.buffers()):
-            raise RuntimeError("StreamingVAE runs on the MI355X only: move the models to the GPU first (there is no CPU path)")
+            raise RuntimeError(f"{name} runs on the MI355X only: move the models to the GPU first (there is no CPU path)")
+
+
+ESTIMATES = ("clean_direct",) + tuple(OUTTYPES)       # outtype: the speech decoder alone, or a mask estimator of inference.py
+
+
+def check_vae_two_latents(noisy_encoder, speech_decoder, noise_decoder, batch, outtype="phase_mask", phase=2, seed=0,
+                          eps=None) -> None:
+    """The construction guards of StreamingVAETwoLatents (host only, before any GPU work)."""
+    from .model import pvae_module as pm
+    name = "StreamingVAETwoLatents"
+    if not isinstance(noisy_encoder, (pm.nsvae_pvae_dccrn_encoder_twophase, pm.pvae_dccrn_encoder_skip_prepare)):
+        raise ValueError(f"{name} takes a model.pvae_module.nsvae_pvae_dccrn_encoder_twophase as noisy_encoder")
+    if getattr(noisy_encoder, "latent_num", 1) != 2:
+        raise ValueError(f"{name} needs an encoder with latent_num 2: this encoder has no noise latent")
+    if not isinstance(outtype, str) or outtype not in ESTIMATES:
+        raise ValueError(f"outtype must be one of {ESTIMATES}, got {outtype!r}")
+    if isinstance(phase, bool) or phase not in (1, 2):
+        raise ValueError(f"phase must be 1 (zero skips) or 2 (the noisy skips, pad='sig'), got {phase!r}")
+    if outtype == "clean_direct":
+        noise_decoder = None            # not run
+    elif noise_decoder is None:
+        raise ValueError(f"outtype {outtype!r} needs a noise_decoder: only 'clean_direct' runs the speech decoder alone")
+    decs = [("speech_decoder", speech_decoder)] + ([("noise_decoder", noise_decoder)] if noise_decoder is not None else [])
+    for what, dec in decs:
+        if isinstance(dec, pm.pvae_dccrn_decoder_skip_prepare):
+            if phase == 2:
+                raise ValueError(f"{name}: phase=2 decodes with the noisy skips (pad='sig'), which the {what}, a "
+                                 "pvae_dccrn_decoder_skip_prepare, does not take; pass phase=1 or the fine-tuned "
+                                 "nsvae_pvae_dccrn_decoder_twophase")
+            if dec.recon_type != "real_imag":
+                raise ValueError(f"{name}: the {what}, a pvae_dccrn_decoder_skip_prepare, implements recon_type 'real_imag' only")
+        elif not isinstance(dec, pm.nsvae_pvae_dccrn_decoder_twophase):
+            raise ValueError(f"{name} takes a model.pvae_module.nsvae_pvae_dccrn_decoder_twophase or "
+                             f"pvae_dccrn_decoder_skip_prepare as {what}")
+        _check_pair(name, noisy_encoder, dec, what)
+        if outtype != "clean_direct" and getattr(dec, "resynthesis", False):
+            raise ValueError(f"{name}: the {what} has resynthesis=True: its predict is a re-analysis of the decoded waveform, which "
+                             f"cannot be formed per column, so outtype {outtype!r} is not streamed with it")
+    if noise_decoder is not None:
+        a, b = speech_decoder, noise_decoder
+        if a.recon_type != b.recon_type:
+            raise ValueError(f"{name}: speech_decoder and noise_decoder differ in recon_type")
+        skips = lambda d: sorted(set(d.skip_to_use)) if d.use_sc else []
+        if skips(a) != skips(b):
+            raise ValueError(f"{name}: speech_decoder and noise_decoder differ in their skip set (use_sc / skip_to_use)")
+    _check_batch_seed(name, batch, seed)
+    if eps is not None and not callable(eps):
+        raise ValueError("eps must be None (the streamer's own draws) or a callable (t0, k) -> (eps_sr, eps_si, eps_nr, eps_ni)")
+    _check_lstm(name, noisy_encoder)
+    for what, dec in decs:
+        _check_chain(name, noisy_encoder, dec, what)
+    _check_on_gpu(name, [noisy_encoder] + [d for _, d in decs])
 
 
 def check_seed(seed) -> int:
     if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 63:
         raise ValueError("seed must be an int in [0, 2**63)")
     return seed
+
+
+class _DecChain:
+    """One decoder of a VAE streamer: the packs of its dense layer and blocks (``dense``, ``dec``), the rows of the LSTM output
+    its latent takes (``lat_off``), whether its blocks read the repeated noisy skips (``skips``; else they are packed as zero
+    skips), and what it owns on the device: the histories ``h_dense`` / ``h_dec`` and the raw last-block output ``raw``."""
+    __slots__ = ("dec", "dense", "lat_off", "skips", "h_dense", "h_dec", "raw")
 
 
 class _VAEStreamer(_StreamBase):
@@ -901,7 +991,13 @@ class _VAEStreamer(_StreamBase):
 
     # ------------------------------------------------------------------ construction
     def _pack(self):
-        enc, dec = self.encoder, self.decoder
+        self._pack_encoder()
+        self.chain = self._pack_chain(self.decoder, LATENTS.index(self.latent), False)
+        self.dec, self.dense, self.lat_off = self.chain.dec, self.chain.dense, self.chain.lat_off
+        self.conv_engines = [cp.engine for cp in self.enc + self.dec]      # enc0 .. then dec0 ..
+
+    def _pack_encoder(self):
+        enc = self.encoder
         self.enc, self.enc_shapes = [], []
         ch, Fin = 1, self.F
         for blk in enc.encoders:
@@ -910,67 +1006,95 @@ class _VAEStreamer(_StreamBase):
             ch, Fin = cp.Cout, cp.Fout
             self.enc_shapes.append((ch, Fin))
         if ch * Fin != enc.lstms[0].input_size:
-            raise ValueError("StreamingVAE: the LSTM input does not match the top encoder shape")
+            raise ValueError(f"{self._name}: the LSTM input does not match the top encoder shape")
+        self._pack_lstm(enc.lstms[0], ch * Fin)
+        dft = ops.DftPlan(self.n_fft, self.win, self.hop, 1, self.device)
+        self.dft_fwd, self.dft_inv = dft.fwd, dft.inv
+
+    def _pack_chain(self, dec, latent: int, zero_skip: bool) -> "_DecChain":
+        """The packs of one decoder on latent number ``latent``: dense and blocks, with the noisy skips of ``self.skip_to_use``
+        or, ``zero_skip``, with zero skips (packed away, see ``_conv``)."""
+        ch = _DecChain()
+        Fin = self.enc_shapes[-1][1]
         dch = dec.dense.out_channel // Fin
+        if getattr(self, "dense_out", (dch, Fin)) != (dch, Fin):
+            raise ValueError(f"{self._name}: the decoders' dense layers differ in shape")
         self.dense_out = (dch, Fin)
-        self.dec = []
+        ch.dec = []
         n = len(self.enc)
         c, f = dch, Fin
         for di, blk in enumerate(dec.decoders):
             c1 = self.enc_shapes[n - 1 - di][0] if di in self.skip_to_use else 0
             if c1 and self.enc_shapes[n - 1 - di][1] != f:
-                raise ValueError("StreamingVAE: a skip's bins do not match the decoder block")
-            cp = self._conv(blk.transconv, blk, c, c1, f, self.Bn)
-            self.dec.append(cp)
+                raise ValueError(f"{self._name}: a skip's bins do not match the decoder block")
+            cp = self._conv(blk.transconv, blk, c, 0 if zero_skip else c1, f, self.Bn, zero_skip=bool(zero_skip and c1))
+            ch.dec.append(cp)
             c, f = cp.Cout, cp.Fout
         if (c, f) != (1, self.F):
-            raise ValueError("StreamingVAE: the last decoder must give one channel of n_fft/2 + 1 bins")
-        self.conv_engines = [cp.engine for cp in self.enc + self.dec]      # enc0 .. then dec0 ..
-        self._pack_lstm(enc.lstms[0], ch * Fin)
+            raise ValueError(f"{self._name}: the last decoder must give one channel of n_fft/2 + 1 bins")
         dn = dec.dense
-        self.dense = [ops.pack_pw(dn.linear_read.weight.detach().float(), dn.linear_read.bias.detach().float()),
-                      ops.pack_pw(dn.linear_imag.weight.detach().float(), dn.linear_imag.bias.detach().float())]
-        dft = ops.DftPlan(self.n_fft, self.win, self.hop, 1, self.device)
-        self.dft_fwd, self.dft_inv = dft.fwd, dft.inv
-        o = 3 * self.zdim * LATENTS.index(self.latent)
-        self.lat_off = (o, o + self.zdim, o + 2 * self.zdim)
+        ch.dense = [ops.pack_pw(dn.linear_read.weight.detach().float(), dn.linear_read.bias.detach().float()),
+                    ops.pack_pw(dn.linear_imag.weight.detach().float(), dn.linear_imag.bias.detach().float())]
+        o = 3 * self.zdim * latent
+        ch.lat_off = (o, o + self.zdim, o + 2 * self.zdim)
+        ch.skips = not zero_skip
+        return ch
 
     def _alloc(self):
-        B, Bn, dev, cap = self.B, self.Bn, self.device, self.cap
+        self._alloc_encoder()
+        self._alloc_decoder([self.chain], self.Bn)
+        self.dec_out.append(self.chain.raw)
+        self.h_dense, self.h_dec = self.chain.h_dense, self.chain.h_dec
+        self.state = [self.h_in, self.h_dense, self.lstm_state, self.ring, self.carry] + self.h_enc + self.h_dec
+
+    def _alloc_encoder(self):
+        """The encoder side, batch B: activations, LSTM scratch and the per-stream state of the encoder and the input ring."""
+        B, dev, cap = self.B, self.device, self.cap
         Tp = cap + 1
         mk = lambda C, F, b: Planar.empty(C, F, b, cap, Tp, dev, zero=True)
-        # encoder side, batch B
         self.fr = mk(1, self.win // 2, B)
         self.X = mk(1, self.F, B)
         self.enc_out = [mk(c, f, B) for c, f in self.enc_shapes]
         self.lat = mk(self.H, 1, B)
         self.G = torch.empty(2 * B * cap * 8 * self.H, dtype=torch.float32, device=dev)
         self.hstep = torch.empty(int(L.lib().idv_stream_clstm_wide_hstep_floats(i(self.H), i(B), i(cap))), dtype=torch.float32, device=dev)
-        # decoder side, batch Bn = B * ns, row b * ns + s
-        self.eps_buf = torch.empty(2, Bn * cap * self.zdim, dtype=torch.float32, device=dev)
-        self.z = mk(self.zdim, 1, Bn)
-        self.dense_buf = mk(*self.dense_out, Bn)
-        n = len(self.enc)
-        self.skip_n = {di: mk(*self.enc_shapes[n - 1 - di], Bn) for di in self.skip_to_use if di < n}
-        # scratch, not state: the history half a chunk reads, repeated (sessions: one half per parity, slot b's in half parity_b)
-        self.h_skip_n = {di: torch.zeros(self._skip_halves * 2 * self.enc_shapes[n - 1 - di][0] * self.enc_shapes[n - 1 - di][1] * Bn,
-                                         dtype=torch.float32, device=dev) for di in self.skip_n}
-        self.dec_out = [mk(cp.Cout, cp.Fout, Bn) for cp in self.dec]
-        self.pred = mk(1, self.F, Bn)
-        self.ifr = mk(1, self.win // 2, Bn)
-        work = max([cp.nsplit * 2 * cp.Cout * cp.Fout * B * cap for cp in self.enc if cp.nsplit > 1] +
-                   [cp.nsplit * 2 * cp.Cout * cp.Fout * Bn * cap for cp in self.dec if cp.nsplit > 1] + [0])
-        self.work = torch.empty(max(work, 1), dtype=torch.float32, device=dev)
-        # per-stream state
         hist = lambda C, F, b: torch.zeros(2, 2 * C * F * b, dtype=torch.float32, device=dev)
         self.h_in = hist(1, self.F, B)
         self.h_enc = [hist(c, f, B) for c, f in self.enc_shapes]
         self.lstm_state = torch.zeros(4 * 4 * B * self.H, dtype=torch.float32, device=dev)
-        self.h_dense = hist(*self.dense_out, Bn)
-        self.h_dec = [hist(cp.Cout, cp.Fout, Bn) for cp in self.dec[:-1]]
         self.ring = torch.zeros(B * self.plan.ring, dtype=torch.float32, device=dev)
-        self.carry = torch.zeros(2, Bn * self.plan.carry_cap, dtype=torch.float32, device=dev)
-        self.state = [self.h_in, self.h_dense, self.lstm_state, self.ring, self.carry] + self.h_enc + self.h_dec
+
+    def _alloc_decoder(self, chains, carry_rows: int):
+        """The decoder side, batch Bn = B * ns, row b * ns + s: the activation scratch the chains share (``z``, ``dense_buf``,
+        ``dec_out`` of every block but the last, the repeated skips), each chain's own state (``h_dense``, ``h_dec``) and raw
+        last-block output, and the overlap-add carry of ``carry_rows`` rows."""
+        B, Bn, dev, cap = self.B, self.Bn, self.device, self.cap
+        Tp = cap + 1
+        mk = lambda C, F, b: Planar.empty(C, F, b, cap, Tp, dev, zero=True)
+        hist = lambda C, F, b: torch.zeros(2, 2 * C * F * b, dtype=torch.float32, device=dev)
+        self.z = mk(self.zdim, 1, Bn)
+        self.dense_buf = mk(*self.dense_out, Bn)
+        n = len(self.enc)
+        skips = self.skip_to_use if any(ch.skips for ch in chains) else []
+        self.skip_n = {di: mk(*self.enc_shapes[n - 1 - di], Bn) for di in skips if di < n}
+        # scratch, not state: the history half a chunk reads, repeated (sessions: one half per parity, slot b's in half parity_b)
+        self.h_skip_n = {di: torch.zeros(self._skip_halves * 2 * self.enc_shapes[n - 1 - di][0] * self.enc_shapes[n - 1 - di][1] * Bn,
+                                         dtype=torch.float32, device=dev) for di in self.skip_n}
+        first = chains[0].dec
+        self.dec_out = [mk(cp.Cout, cp.Fout, Bn) for cp in first[:-1]]
+        for ch in chains:
+            if [(cp.Cout, cp.Fout) for cp in ch.dec] != [(cp.Cout, cp.Fout) for cp in first]:
+                raise ValueError(f"{self._name}: the decoders differ in their block shapes")
+            ch.raw = mk(first[-1].Cout, first[-1].Fout, Bn)
+            ch.h_dense = hist(*self.dense_out, Bn)
+            ch.h_dec = [hist(cp.Cout, cp.Fout, Bn) for cp in ch.dec[:-1]]
+        self.eps_buf = torch.empty(2 * len(chains), Bn * cap * self.zdim, dtype=torch.float32, device=dev)
+        self.pred = mk(1, self.F, Bn)
+        self.ifr = mk(1, self.win // 2, Bn)
+        work = max([cp.nsplit * 2 * cp.Cout * cp.Fout * B * cap for cp in self.enc if cp.nsplit > 1] +
+                   [cp.nsplit * 2 * cp.Cout * cp.Fout * Bn * cap for ch in chains for cp in ch.dec if cp.nsplit > 1] + [0])
+        self.work = torch.empty(max(work, 1), dtype=torch.float32, device=dev)
+        self.carry = torch.zeros(2, carry_rows * self.plan.carry_cap, dtype=torch.float32, device=dev)
 
     # ------------------------------------------------------------------ the draws
     def eps(self, t0: int, k: int):
@@ -984,16 +1108,25 @@ class _VAEStreamer(_StreamBase):
         return out[0], out[1]
 
     # ------------------------------------------------------------------ the network over one launch group
+    @staticmethod
+    def _at(pl, Jp: int, plane: int = 0):
+        """Device pointer of plane ``plane`` of a Planar used at row pitch ``Jp``."""
+        return L._P(pl.buf.data_ptr() + 4 * (ops.SLACK + plane * pl.F * Jp))
+
     def _network(self, c, io):
         """Frames -> spectrum -> encoders -> wide LSTM (batch B) -> draws -> reparameterisation -> dense -> decoders with the
         repeated skips -> mask -> windowed inverse-DFT frames (self.ifr), batch B * ns, for the c.k columns per stream of launch
         group c; ``io`` is what the subclass's framing needs."""
-        B, Bn, ns, k = self.B, self.Bn, self.ns, c.k
+        self._encode(c, io)
+        self._decode(c, self.chain, self._draws(c), self._skips(c))
+        self._tail(c, self.chain)
+
+    def _encode(self, c, io):
+        """Frames -> spectrum (self.X) -> encoders (self.enc_out) -> wide LSTM (self.lat), batch B."""
+        B, k = self.B, c.k
         Tp = k + 1
-        Jp, Jpn = Planar.jp_for(B, Tp), Planar.jp_for(Bn, Tp)
-        s = stream_ptr()
-        ptr = lambda pl, plane=0: L._P(pl.buf.data_ptr() + 4 * (ops.SLACK + plane * pl.F * Jp))
-        ptrn = lambda pl, plane=0: L._P(pl.buf.data_ptr() + 4 * (ops.SLACK + plane * pl.F * Jpn))
+        Jp = Planar.jp_for(B, Tp)
+        ptr = lambda pl, plane=0: self._at(pl, Jp, plane)
         self._frames(c, io, ptr(self.fr), Tp, Jp)
         ops.pw_gemm(ptr(self.fr), self.win, self.dft_fwd[0], self.dft_fwd[1], 2 * self.F, B, Tp, Jp, k, ptr(self.X))
         src, hsrc = self.X, self.h_in
@@ -1009,32 +1142,56 @@ class _VAEStreamer(_StreamBase):
             ops.pw_gemm(ptr(top, z * top.C), K, wih, bih, 8 * H, B, Tp, Jp, k,
                         L._P(self.G.data_ptr() + 4 * z * k * B * 8 * H), swap=True, ldo=8 * H)
         self._lstm(c, ptr(self.lat), Tp, Jp)
-        # latent draw of the chosen latent, batch B -> B * ns
-        er, ei = self._draws(c)
-        zd = self.zdim
-        call("idv_reparam", ptr(self.lat), i(H), i(self.lat_off[0]), i(self.lat_off[1]), i(self.lat_off[2]), i(zd), er, ei, i(ns), i(B),
-             i(k), i(Tp), i(Jp), ptrn(self.z), i(Jpn), s)
-        dc, df = self.dense_out
-        for ri, pk in enumerate(self.dense):
-            ops.pw_gemm(ptrn(self.z, ri * zd), zd, pk[0], pk[1], dc * df, Bn, Tp, Jpn, k, ptrn(self.dense_buf, ri * dc))
-        # decoders: the skips and the history half this group reads, repeated to batch B * ns
-        src, hsrc = self.dense_buf, self.h_dense
+
+    def _skips(self, c):
+        """The skips and the history half this group reads, repeated to batch B * ns, once for every chain that reads them:
+        block number -> (x1, h1) of its ``_block`` call."""
+        B, Bn, k = self.B, self.Bn, c.k
+        Tp = k + 1
+        Jp, Jpn = Planar.jp_for(B, Tp), Planar.jp_for(Bn, Tp)
         n = len(self.enc)
-        for di, cp in enumerate(self.dec):
-            out = self.dec_out[di]
-            x1 = h1 = None
-            if di in self.skip_n:
-                sk = n - 1 - di
-                h1 = self._repeat(c, di, sk, ptr(self.enc_out[sk]), ptrn(self.skip_n[di]), Tp, Jp, Jpn)
-                x1 = ptrn(self.skip_n[di])
-            hout = self.h_dec[di] if di < len(self.h_dec) else None      # nothing reads the last block's history
-            self._block(cp, c, ptrn(src), hsrc, x1, h1, ptrn(out), hout, self.h_dense if di == 0 else None, Tp, Jpn, True)
-            if di < len(self.h_dec):
-                src, hsrc = out, self.h_dec[di]
-        pred = self.dec_out[-1]
+        out = {}
+        for di in self.skip_n:
+            sk = n - 1 - di
+            xn = self._at(self.skip_n[di], Jpn)
+            out[di] = (xn, self._repeat(c, di, sk, self._at(self.enc_out[sk], Jp), xn, Tp, Jp, Jpn))
+        return out
+
+    def _decode(self, c, ch: "_DecChain", draws, skips):
+        """One decoder chain at batch B * ns: reparameterisation of the chain's latent with ``draws`` (eps_r, eps_i) -> dense ->
+        decoder blocks (``skips`` from ``_skips``; none for a zero-skip chain) -> the raw last-block output ``ch.raw``."""
+        B, Bn, ns, k = self.B, self.Bn, self.ns, c.k
+        Tp = k + 1
+        Jp, Jpn = Planar.jp_for(B, Tp), Planar.jp_for(Bn, Tp)
+        s = stream_ptr()
+        ptrn = lambda pl, plane=0: self._at(pl, Jpn, plane)
+        er, ei = draws
+        zd = self.zdim
+        call("idv_reparam", self._at(self.lat, Jp), i(self.H), i(ch.lat_off[0]), i(ch.lat_off[1]), i(ch.lat_off[2]), i(zd), er, ei,
+             i(ns), i(B), i(k), i(Tp), i(Jp), ptrn(self.z), i(Jpn), s)
+        dc, df = self.dense_out
+        for ri, pk in enumerate(ch.dense):
+            ops.pw_gemm(ptrn(self.z, ri * zd), zd, pk[0], pk[1], dc * df, Bn, Tp, Jpn, k, ptrn(self.dense_buf, ri * dc))
+        src, hsrc = self.dense_buf, ch.h_dense
+        last = len(ch.dec) - 1
+        for di, cp in enumerate(ch.dec):
+            out = ch.raw if di == last else self.dec_out[di]
+            x1, h1 = skips[di] if (ch.skips and di in skips) else (None, None)
+            hout = ch.h_dec[di] if di < last else None                   # nothing reads the last block's history
+            self._block(cp, c, ptrn(src), hsrc, x1, h1, ptrn(out), hout, ch.h_dense if di == 0 else None, Tp, Jpn, True)
+            if di < last:
+                src, hsrc = out, ch.h_dec[di]
+
+    def _tail(self, c, ch: "_DecChain"):
+        """``ch.raw`` -> mask -> windowed inverse-DFT frames (self.ifr), batch B * ns."""
+        B, Bn, k = self.B, self.Bn, c.k
+        Tp = k + 1
+        Jp, Jpn = Planar.jp_for(B, Tp), Planar.jp_for(Bn, Tp)
+        ptrn = lambda pl, plane=0: self._at(pl, Jpn, plane)
+        pred = ch.raw
         if self.recon == "mask":
-            call("idv_mask_apply", ptrn(pred), ptr(self.X), i(ns), i(Jp), ptrn(self.pred), p(None), i(self.F), i(Bn), i(k), i(Tp),
-                 i(Jpn), s)
+            call("idv_mask_apply", ptrn(pred), self._at(self.X, Jp), i(self.ns), i(Jp), ptrn(self.pred), p(None), i(self.F), i(Bn), i(k),
+                 i(Tp), i(Jpn), stream_ptr())
             pred = self.pred
         ops.pw_gemm(ptrn(pred), 2 * self.F, self.dft_inv[0], self.dft_inv[1], self.win, Bn, Tp, Jpn, k, ptrn(self.ifr))
 
@@ -1080,7 +1237,7 @@ class StreamingVAE(_VAEStreamer):
             if t.device != self.device:
                 raise RuntimeError("eps(t0, k) must return tensors on the streamer's GPU")
             out.append(p(t.float().contiguous()))
-        return out
+        return tuple(out)
 
     # ------------------------------------------------------------------ push / flush
     def push(self, x: torch.Tensor) -> torch.Tensor:
@@ -1137,6 +1294,153 @@ class StreamingVAE(_VAEStreamer):
         call("idv_stream_repeat", x, p(self.h_enc[sk][c.parity]), i(sc), i(sf), i(self.B), i(self.ns), i(c.k), i(Tp), i(Jp), xn,
              p(self.h_skip_n[di]), i(Jpn), stream_ptr())
         return self.h_skip_n[di]
+
+
+class StreamingVAETwoLatents(StreamingVAE):
+    """Lock-step streaming of the two-latent evaluation (``inference.enhance_vae_two_latents``, the reference's
+    ``latent_to_use == 2``) for ``batch`` signals: one pass of the noisy encoder at batch B, the speech decoder on the speech
+    latent and the noise decoder on the noise latent at batch B * num_samples (row b * ns + s), then the ``outtype`` estimator.
+
+        st = StreamingVAETwoLatents(noisy_encoder, speech_decoder, noise_decoder, batch=B, outtype="phase_mask", phase=2, seed=0)
+        y = st.push(x)                   # x [B, n] on the GPU -> [B, m], the samples that became final
+        y = st.flush()
+        sr, si, nr, ni = st.eps(t0, k)   # the draws frames t0 .. t0+k-1 use, each [B, ns, k, zdim]
+
+    :class:`StreamingVAE`'s contract: :class:`StreamPlan` bookkeeping, the same sample counts per ``push`` / ``flush`` and the
+    same bits however the signal is cut; all pushes and the flush together return what ``inference.enhance_vae_two_latents(
+    noisy_encoder, speech_decoder, noise_decoder, x_full, outtype, phase, eps=<the same four draws>)`` returns.
+
+    ``phase=2``: both decoders are ``nsvae_pvae_dccrn_decoder_twophase`` and read the noisy skips (``pad='sig'``); the repeated
+    skips and their history halves are formed once per launch group for both.  ``phase=1``: zero skips, as ``pad='zero'``
+    offline, with either decoder class; a zero skip is packed away (the block keeps the first C0 input channels of its
+    weights), so no zeros are read.  ``outtype="clean_direct"`` runs the speech decoder alone (``noise_decoder`` may be None)
+    and, at ``phase=2``, returns the bits of ``StreamingVAE(noisy_encoder, speech_decoder, batch=B, seed=seed)``.  The mask
+    estimators (``real_imag_mask``, ``complex_mask``, ``phase_mask``) form the two sample means and the estimate per column
+    (``idv_stream_estimate``) in front of the inverse DFT, which with the overlap-add then runs at batch B.
+
+    The draws of both latents come from one counter-based block per (seed, b, s, t, u) (``idv_stream_eps_pair``; the speech
+    pair is ``StreamingVAE``'s); ``eps`` may instead be a callable ``(t0, k) -> (eps_sr, eps_si, eps_nr, eps_ni)``, each
+    [B, ns, k, zdim] on the GPU.  ``conv`` as in :class:`StreamingDCCRN`; ``conv_engines`` lists enc0 .. 5, speech dec0 .. 5,
+    then noise dec0 .. 5.  Exact fp32; weights are packed at construction.
+    """
+
+    _name = "StreamingVAETwoLatents"
+
+    def __init__(self, noisy_encoder, speech_decoder, noise_decoder, batch: int, outtype: str = "phase_mask", phase: int = 2,
+                 seed: int = 0, eps=None, frames_per_launch: int = 64, max_columns: int = 4096, conv: str = "valu"):
+        self.conv = check_conv(conv)
+        check_vae_two_latents(noisy_encoder, speech_decoder, noise_decoder, batch, outtype, phase, seed, eps)
+        if outtype == "clean_direct":
+            noise_decoder = None
+        decoders = [speech_decoder] + ([noise_decoder] if noise_decoder is not None else [])
+        for blk in list(noisy_encoder.encoders) + [b for d in decoders for b in d.decoders]:
+            (blk.conv if hasattr(blk, "conv") else blk.transconv)._check_supported()
+        self.encoder, self.decoder, self.noise_decoder, self.B = noisy_encoder, speech_decoder, noise_decoder, batch
+        self.outtype, self.phase = outtype, phase
+        self.ns = noisy_encoder.num_samples
+        self.Bn = batch * self.ns
+        self.zdim = noisy_encoder.zdim
+        self.latent, self.average, self._eps_fn = "speech", True, eps
+        self._seed = seed
+        self.device = next(noisy_encoder.parameters()).device
+        st = noisy_encoder.stft
+        self.n_fft, self.hop, self.win = st.n_fft, st.hop_length, st.win_length
+        self.F = self.n_fft // 2 + 1
+        self.cap = max(1, min(frames_per_launch, max_columns // self.Bn))
+        self.plan = StreamPlan(self.n_fft, self.hop, self.win, self.cap)
+        self.skip_to_use = list(speech_decoder.skip_to_use) if speech_decoder.use_sc else []
+        self.recon = speech_decoder.recon_type
+        with torch.no_grad(), torch.cuda.device(self.device):
+            self._pack()
+            self._alloc()
+        self.reset()
+
+    # ------------------------------------------------------------------ construction
+    def _pack(self):
+        self._pack_encoder()
+        zero = self.phase == 1
+        self.chain = self.speech = self._pack_chain(self.decoder, 0, zero)
+        self.noise = self._pack_chain(self.noise_decoder, 1, zero) if self.noise_decoder is not None else None
+        self.chains = [self.speech] + ([self.noise] if self.noise is not None else [])
+        self.conv_engines = [cp.engine for cp in self.enc] + [cp.engine for ch in self.chains for cp in ch.dec]
+
+    def _alloc(self):
+        B, dev, cap = self.B, self.device, self.cap
+        self._alloc_encoder()
+        # clean_direct keeps StreamingVAE's tail: one overlap-add row per sample; the estimators leave one row per stream
+        self._alloc_decoder(self.chains, self.Bn if self.noise is None else B)
+        if self.noise is not None:
+            self.spec = Planar.empty(1, self.F, B, cap, cap + 1, dev, zero=True)
+            self.ifr_b = Planar.empty(1, self.win // 2, B, cap, cap + 1, dev, zero=True)
+        self.state = [self.h_in, self.lstm_state, self.ring, self.carry] + self.h_enc
+        for ch in self.chains:
+            self.state += [ch.h_dense] + ch.h_dec
+
+    # ------------------------------------------------------------------ the draws
+    def eps(self, t0: int, k: int):
+        """The draws frames t0 .. t0+k-1 use with the streamer's own generator and its current seed: (eps_sr, eps_si, eps_nr,
+        eps_ni), each [B, ns, k, zdim]; the first two are ``StreamingVAE.eps``'s."""
+        if isinstance(t0, bool) or not isinstance(t0, int) or t0 < 0 or isinstance(k, bool) or not isinstance(k, int) or k <= 0:
+            raise ValueError("eps(t0, k): t0 >= 0 and k > 0 frames")
+        out = torch.empty(4, self.B, self.ns, k, self.zdim, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            call("idv_stream_eps_pair", ll(self._seed), ll(t0), i(k), i(self.B), i(self.ns), i(self.zdim), p(out[0]), p(out[1]),
+                 p(out[2]), p(out[3]), stream_ptr())
+        return out[0], out[1], out[2], out[3]
+
+    def _draws(self, c: Chunk):
+        """Device pointers of eps_sr / eps_si / eps_nr / eps_ni [B][ns][c.k][zdim] of chunk c."""
+        if self._eps_fn is None:
+            if self.noise is None:
+                return super()._draws(c) + (p(None), p(None))
+            e = self.eps_buf
+            call("idv_stream_eps_pair", ll(self._seed), ll(c.t0), i(c.k), i(self.B), i(self.ns), i(self.zdim), p(e[0]), p(e[1]), p(e[2]),
+                 p(e[3]), stream_ptr())
+            return p(e[0]), p(e[1]), p(e[2]), p(e[3])
+        four = self._eps_fn(c.t0, c.k)
+        want = (self.B, self.ns, c.k, self.zdim)
+        if not isinstance(four, (tuple, list)) or len(four) != 4:
+            raise ValueError("eps(t0, k) must return (eps_sr, eps_si, eps_nr, eps_ni)")
+        out = []
+        for t in four:
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != want:
+                raise ValueError(f"eps(t0, k) must return four tensors of shape {want}")
+            if t.device != self.device:
+                raise RuntimeError("eps(t0, k) must return tensors on the streamer's GPU")
+            out.append(p(t.float().contiguous()))
+        return tuple(out)
+
+    # ------------------------------------------------------------------ the network over one launch group
+    def _network(self, c, io):
+        """Encoder and LSTM once; both decoder chains on their latents; then either StreamingVAE's tail on the speech chain
+        (clean_direct: self.ifr, batch B * ns) or the estimator and the inverse DFT at batch B (self.ifr_b)."""
+        self._encode(c, io)
+        d = self._draws(c)
+        skips = self._skips(c)
+        self._decode(c, self.speech, d[:2], skips)
+        if self.noise is None:
+            self._tail(c, self.speech)
+            return
+        self._decode(c, self.noise, d[2:], skips)
+        B, k = self.B, c.k
+        Tp = k + 1
+        Jp, Jpn = Planar.jp_for(B, Tp), Planar.jp_for(self.Bn, Tp)
+        call("idv_stream_estimate", self._at(self.speech.raw, Jpn), self._at(self.noise.raw, Jpn), self._at(self.X, Jp),
+             i(1 if self.recon == "mask" else 0), i(OUTTYPES[self.outtype]), i(self.ns), i(self.F), i(B), i(k), i(Tp), i(Jp), i(Jpn),
+             self._at(self.spec, Jp), stream_ptr())
+        ops.pw_gemm(self._at(self.spec, Jp), 2 * self.F, self.dft_inv[0], self.dft_inv[1], self.win, B, Tp, Jp, k, self._at(self.ifr_b, Jp))
+
+    def _run(self, chunks: List[Chunk], x, ldx: int, n_new: int, n_prev: int, L_end: Optional[int]) -> torch.Tensor:
+        if self.noise is None:
+            return super()._run(chunks, x, ldx, n_new, n_prev, L_end)
+        m = (chunks[-1].e1 - chunks[0].e0) if chunks else 0
+        y = torch.empty(self.B, m, dtype=torch.float32, device=self.device)
+        T_total = self.plan.total_frames(L_end) if L_end is not None else -1
+        for c in chunks:
+            if c.k > 0:
+                self._network(c, (x, ldx, n_new, n_prev, L_end))
+            self._lock_ola(c, self.ifr_b if c.k > 0 else None, self.carry, self.B, T_total, y, m, c.e0 - chunks[0].e0)
+        return y
 
 
 def decoder_rows(rows: List[List[int]], ns: int) -> List[List[int]]:

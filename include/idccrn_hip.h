@@ -784,6 +784,23 @@ int idv_stream_eps_rows(long long seed, const long long* rows, int B, int ns, in
 int idv_stream_repeat_rows(const float* x, const float* hist, int C, int F, int B, int ns, int k_launch, int Tp, int Jp,
                            const long long* rows, float* xn, float* histn, int Jpn, void* stream);
 
+/* ---- streaming two-latent enhancement (stream_io.hip, elementwise.hip; streaming.StreamingVAETwoLatents; additive entries:
+ * IDV_ABI_VERSION is unchanged).  The speech and the noise decoder both run at batch B * ns on one encoder pass; the estimator
+ * takes the mean over the samples in front of the inverse DFT, which then runs at batch B. */
+/* idv_stream_eps with the second pair of the same Philox block: words 0 and 1 give eps_sr, eps_si, bit for bit what
+ * idv_stream_eps(seed, t0, k, B, ns, zdim, ...) writes; words 2 and 3 go through the same Box-Muller and give eps_nr, eps_ni, the
+ * noise latent's draws.  All four are [B][ns][k][zdim]; a draw depends on (seed, b, s, t, u) alone. */
+int idv_stream_eps_pair(long long seed, long long t0, int k, int B, int ns, int zdim, float* eps_sr, float* eps_si, float* eps_nr,
+                        float* eps_ni, void* stream);
+/* The estimators of idv_outtype_estimate (mode 0 real_imag_mask, 1 complex_mask, 2 phase_mask) on the planar streaming layout,
+ * for the k columns of a launch group.  speech, noise: the last-block outputs of the two decoders, planar [2][F][Jpn], sample s of
+ * stream b in column (b*ns + s)*Tp + t + 1; X: the noisy spectrum, planar [2][F][Jp], column b*Tp + t + 1.  recon_mask 1: each
+ * sample is first turned into the masked spectrum with the arithmetic of idv_mask_apply (x_div = ns); 0 (real_imag): taken as it
+ * is.  S and N are the means over s = 0 .. ns-1 summed in this order, as idv_outtype_estimate sums them.  out: planar [2][F][Jp],
+ * column b*Tp + t + 1 for t < k; the guard columns are not written.  An output depends on its own column alone. */
+int idv_stream_estimate(const float* speech, const float* noise, const float* X, int recon_mask, int mode, int ns, int F, int B,
+                        int k, int Tp, int Jp, int Jpn, float* out, void* stream);
+
 /* ---- batches of utterances of different lengths (ragged.hip, reduce.hip; inference.enhance_* / compute_sisdr with `lengths`) ---
  * lens: device int32[], samples per utterance.  Utterance b has T_b = 1 + lens[b] / hop frames and hop * (T_b - 1) output samples;
  * the batch is laid out for Tmax = max_b T_b frames, Tp >= Tmax + 1.  A causal network computes frame t from frames <= t, so only

@@ -1,7 +1,7 @@
 """Streaming enhancement benchmark: one JSON line per batch of lock-step streams, one hop (100 samples) per push.
 
     python profiles/tools/stream_bench.py [--batches 1,16,128,512,1024] [--seconds 2] [--catchup] [--far-seconds 3600] [--sessions]
-                                           [--conv valu|mfma|both] [--vae [--sessions]]
+                                           [--conv valu|mfma|both] [--vae [--sessions]] [--two-latents [--outtype O] [--phase P]]
 
 Per line: device time per push (HIP events around >= --seconds of pushes after warm-up), host wall time per push (synchronised),
 the real-time factor (hop / 16 kHz = 6.25 ms over the wall time) and the algorithmic GFLOP per push (4 real products per complex
@@ -19,7 +19,10 @@ time of the wide LSTM entry alone at the push's shape (events around repeated ca
 own buffers, after the push measurements) and its share of the device time of a push.  --vae --sessions measures
 streaming.StreamingVAESessions (metric "vae_sessions_push": every slot active at the staggered positions of --sessions, counts as a
 host list on every push) and, right after it in the same process and with the same models, the lock-step StreamingVAE at the same
-B and engine (metric "vae_push"), so that the two lines of a pair share the card and its clocks.
+B and engine (metric "vae_push"), so that the two lines of a pair share the card and its clocks.  --two-latents measures
+streaming.StreamingVAETwoLatents (metric "two_latents_push"; --outtype, default phase_mask, and --phase, default 2; the encoder of
+--vae, a speech and a noise decoder, num_samples 3, default batches 1,16) and, right after it in the same process with the same
+encoder and speech decoder, StreamingVAE at the same B, ns and engine (metric "vae_push").
 """
 from __future__ import annotations
 
@@ -59,6 +62,16 @@ def gflop_per_frame_vae(st) -> float:
     return 2 * macs / 1e9
 
 
+def gflop_per_frame_two(st) -> float:
+    """gflop_per_frame_vae with every decoder chain ns times and, for the mask estimators, one inverse DFT per stream."""
+    conv = lambda cp: 4 * (cp.C0 + cp.C1) * cp.Cout * 10 * (cp.Fin if cp.transposed else cp.Fout)
+    H, K = st.H, st.K
+    macs = sum(conv(cp) for cp in st.enc) + 2 * 8 * H * K + 4 * 3 * 4 * H * H + 2 * st.F * WIN
+    macs += st.ns * sum(sum(conv(cp) for cp in ch.dec) + 2 * st.zdim * st.dense_out[0] * st.dense_out[1] for ch in st.chains)
+    macs += (st.ns if st.noise is None else 1) * 2 * st.F * WIN
+    return 2 * macs / 1e9
+
+
 def wide_lstm_ms(st, k=1, reps=200) -> float:
     """Device time of idv_stream_clstm_wide alone for k steps at the streamer's batch (it advances the streamer's LSTM state)."""
     L = importlib.import_module("i-dccrn-vae_amd._lib")
@@ -81,7 +94,7 @@ def wide_lstm_ms(st, k=1, reps=200) -> float:
 _VAE_PAIR = []
 
 
-def build(B, sessions=False, conv="valu", vae=False):
+def build(B, sessions=False, conv="valu", vae=False, two=None):
     pm = importlib.import_module("i-dccrn-vae_amd.model.pvae_module")
     S = importlib.import_module("i-dccrn-vae_amd.streaming")
     from oracle import idccrn_oracle as O
@@ -91,10 +104,14 @@ def build(B, sessions=False, conv="valu", vae=False):
             load = lambda m, seed: m.load_state_dict(O.synth_state_dict({k: tuple(v.shape) for k, v in m.state_dict().items()}, seed))
             enc = pm.nsvae_pvae_dccrn_encoder_twophase(np_, True, "cuda", 128, NFFT, HOP, WIN, 3, 2)
             dec = pm.nsvae_pvae_dccrn_decoder_twophase(np_, True, "cuda", 3, 128, NFFT, HOP, WIN, "mask", True, [0, 1, 2, 3, 4, 5], False)
+            noise = pm.nsvae_pvae_dccrn_decoder_twophase(np_, True, "cuda", 3, 128, NFFT, HOP, WIN, "mask", True, [0, 1, 2, 3, 4, 5], False)
             load(enc, 9)
             load(dec, 10)
-            _VAE_PAIR.extend([enc.cuda(), dec.cuda()])
-        enc, dec = _VAE_PAIR
+            load(noise, 11)
+            _VAE_PAIR.extend([enc.cuda(), dec.cuda(), noise.cuda()])
+        enc, dec, noise = _VAE_PAIR
+        if two is not None:
+            return S.StreamingVAETwoLatents(enc, dec, noise, batch=B, outtype=two[0], phase=two[1], seed=0, conv=conv)
         if sessions:
             return S.StreamingVAESessions(enc, dec, slots=B, seed=0, conv=conv)
         return S.StreamingVAE(enc, dec, batch=B, seed=0, conv=conv)
@@ -104,8 +121,8 @@ def build(B, sessions=False, conv="valu", vae=False):
     return S.StreamingSessions(m, slots=B, conv=conv) if sessions else S.StreamingDCCRN(m, batch=B, conv=conv)
 
 
-def run(B, seconds, n=HOP, far_seconds=0, sessions=False, conv="valu", vae=False):
-    st = build(B, sessions, conv, vae)
+def run(B, seconds, n=HOP, far_seconds=0, sessions=False, conv="valu", vae=False, two=None):
+    st = build(B, sessions, conv, vae, two)
     x = torch.randn(B, 64000, device="cuda") * 0.1
     pos = 0
     if sessions:                                # stagger the slots: slot b starts 13 * (b % 7) samples ahead
@@ -156,17 +173,39 @@ def main():
     ap.add_argument("--sessions", action="store_true")
     ap.add_argument("--conv", choices=["valu", "mfma", "both"], default="valu")
     ap.add_argument("--vae", action="store_true")
+    ap.add_argument("--two-latents", action="store_true")
+    ap.add_argument("--outtype", default="phase_mask")
+    ap.add_argument("--phase", type=int, default=2)
     a = ap.parse_args()
+    if a.two_latents and (a.sessions or a.catchup or a.far_seconds):
+        ap.error("--two-latents measures hop pushes of StreamingVAETwoLatents and StreamingVAE only")
+    a.vae = a.vae or a.two_latents
     if a.vae and (a.catchup or a.far_seconds):
         ap.error("--vae measures hop pushes of StreamingVAE / StreamingVAESessions only")
     if a.batches is None:
-        a.batches = "1,16,128" if a.vae else "1,16,128,512,1024"
+        a.batches = "1,16" if a.two_latents else "1,16,128" if a.vae else "1,16,128,512,1024"
     torch.set_grad_enabled(False)
     budget = 1e3 * HOP / SR
     turns = [("valu", 0), ("mfma", 0), ("valu", 1), ("mfma", 1)] if a.conv == "both" else [(a.conv, 0)]
     conv1 = "mfma" if a.conv == "both" else a.conv            # the single-engine lines below
     for B in [int(v) for v in a.batches.split(",") if v]:
         for conv, rnd in turns:
+            if a.two_latents:
+                for two in ((a.outtype, a.phase), None):
+                    st, dev_ms, wall_ms, _ = run(B, a.seconds, conv=conv, vae=True, two=two)
+                    gf = (gflop_per_frame_two(st) if two else gflop_per_frame_vae(st)) * B
+                    line = {"metric": "two_latents_push" if two else "vae_push", "B": B, "ns": st.ns, "H": st.H, "hop": HOP}
+                    if two:
+                        line.update({"outtype": st.outtype, "phase": st.phase})
+                    line.update({"device_ms_per_push": round(dev_ms, 4), "wall_ms_per_push": round(wall_ms, 4),
+                                 "rtf": round(budget / wall_ms, 3), "device_rtf": round(budget / dev_ms, 3),
+                                 "under_hop_budget": bool(wall_ms < budget), "gflop_per_push": round(gf, 3),
+                                 "tflops_device": round(gf / dev_ms, 2), "frames_per_launch": st.cap, "conv": conv,
+                                 "conv_engines": st.conv_engines.count("mfma"), "round": rnd})
+                    print(json.dumps(line), flush=True)
+                    del st
+                    torch.cuda.empty_cache()
+                continue
             if a.vae:
                 for sessions in ([True, False] if a.sessions else [False]):
                     st, dev_ms, wall_ms, _ = run(B, a.seconds, sessions=sessions, conv=conv, vae=True)
