@@ -219,23 +219,32 @@ __device__ __forceinline__ void box_muller(uint32_t wa, uint32_t wb, float& re, 
 // its entries are zero.
 // PAIR (idv_stream_eps_pair): words 2 and 3 of the same block through the same Box-Muller give a second, independent pair
 // (eps2_r, eps2_i), the noise latent's draws; words 0 and 1 are what the kernel without PAIR writes.
-template <bool ROWS, bool PAIR>
+// SEEDS (idv_stream_eps_pair_rows, with ROWS): the key of slot b is seeds[b] in place of seed.  seeds is the last parameter, so
+// the kernel arguments of the forms without SEEDS sit where they sat.
+template <bool ROWS, bool PAIR, bool SEEDS>
 __global__ void stream_eps_kernel(unsigned long long seed, long long t0, int k, int Bn, int zdim, float* __restrict__ eps_r,
                                   float* __restrict__ eps_i, float* __restrict__ eps2_r, float* __restrict__ eps2_i, int ns,
-                                  const long long* __restrict__ rows) {
+                                  const long long* __restrict__ rows, const long long* __restrict__ seeds) {
+    static_assert(ROWS || !SEEDS, "per-slot seeds come with the row table");
     const long long n = (long long)Bn * k * zdim;
     for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
         const uint32_t u = (uint32_t)(e % zdim);
         const long long tl = (e / zdim) % k;
         const uint32_t bs = (uint32_t)(e / ((long long)zdim * k));
         if (ROWS) {
-            const long long* row = rows + (size_t)(bs / (uint32_t)ns) * IDV_STREAM_ROW_FIELDS;
+            const uint32_t b = bs / (uint32_t)ns;
+            const long long* row = rows + (size_t)b * IDV_STREAM_ROW_FIELDS;
             if (tl >= row[IDV_ROW_K]) {
                 eps_r[e] = 0.f;
                 eps_i[e] = 0.f;
+                if (PAIR) {
+                    eps2_r[e] = 0.f;
+                    eps2_i[e] = 0.f;
+                }
                 continue;
             }
             t0 = row[IDV_ROW_T0];
+            if (SEEDS) seed = (unsigned long long)seeds[b];
         }
         const unsigned long long t = (unsigned long long)(t0 + tl);
         uint32_t w0, w1, w2, w3;
@@ -278,11 +287,12 @@ __global__ void stream_repeat_kernel(const float* __restrict__ x, const float* _
 
 static const long long* const no_rows = nullptr;      // the table argument of a lock-step instantiation, which never reads it
 static float* const no_eps = nullptr;                 // the second pair of an instantiation without PAIR, which never writes it
+static const long long* const no_seeds = nullptr;     // the seed array of an instantiation without SEEDS, which never reads it
 
 extern "C" int idv_stream_eps(long long seed, long long t0, int k, int B, int ns, int zdim, float* eps_r, float* eps_i, void* stream) {
     if (t0 < 0 || k <= 0 || B <= 0 || ns <= 0 || zdim <= 0 || !eps_r || !eps_i || (long long)B * ns > 0x7fffffffLL) return IDV_EINVAL;
-    hipLaunchKernelGGL((stream_eps_kernel<false, false>), dim3(grid_of((long long)B * ns * k * zdim)), dim3(256), 0, (hipStream_t)stream,
-                       (unsigned long long)seed, t0, k, B * ns, zdim, eps_r, eps_i, no_eps, no_eps, ns, no_rows);
+    hipLaunchKernelGGL((stream_eps_kernel<false, false, false>), dim3(grid_of((long long)B * ns * k * zdim)), dim3(256), 0, (hipStream_t)stream,
+                       (unsigned long long)seed, t0, k, B * ns, zdim, eps_r, eps_i, no_eps, no_eps, ns, no_rows, no_seeds);
     return idv_launch_status();
 }
 
@@ -291,8 +301,8 @@ extern "C" int idv_stream_eps_pair(long long seed, long long t0, int k, int B, i
     if (t0 < 0 || k <= 0 || B <= 0 || ns <= 0 || zdim <= 0 || !eps_sr || !eps_si || !eps_nr || !eps_ni ||
         (long long)B * ns > 0x7fffffffLL)
         return IDV_EINVAL;
-    hipLaunchKernelGGL((stream_eps_kernel<false, true>), dim3(grid_of((long long)B * ns * k * zdim)), dim3(256), 0, (hipStream_t)stream,
-                       (unsigned long long)seed, t0, k, B * ns, zdim, eps_sr, eps_si, eps_nr, eps_ni, ns, no_rows);
+    hipLaunchKernelGGL((stream_eps_kernel<false, true, false>), dim3(grid_of((long long)B * ns * k * zdim)), dim3(256), 0, (hipStream_t)stream,
+                       (unsigned long long)seed, t0, k, B * ns, zdim, eps_sr, eps_si, eps_nr, eps_ni, ns, no_rows, no_seeds);
     return idv_launch_status();
 }
 
@@ -311,8 +321,24 @@ extern "C" int idv_stream_eps_rows(long long seed, const long long* rows, int B,
                                    float* eps_i, void* stream) {
     if (!rows || k_launch <= 0 || B <= 0 || ns <= 0 || zdim <= 0 || !eps_r || !eps_i || (long long)B * ns > 0x7fffffffLL)
         return IDV_EINVAL;
-    hipLaunchKernelGGL((stream_eps_kernel<true, false>), dim3(grid_of((long long)B * ns * k_launch * zdim)), dim3(256), 0,
-                       (hipStream_t)stream, (unsigned long long)seed, 0LL, k_launch, B * ns, zdim, eps_r, eps_i, no_eps, no_eps, ns, rows);
+    hipLaunchKernelGGL((stream_eps_kernel<true, false, false>), dim3(grid_of((long long)B * ns * k_launch * zdim)), dim3(256), 0,
+                       (hipStream_t)stream, (unsigned long long)seed, 0LL, k_launch, B * ns, zdim, eps_r, eps_i, no_eps, no_eps, ns, rows,
+                       no_seeds);
+    return idv_launch_status();
+}
+
+extern "C" int idv_stream_eps_pair_rows(const long long* seeds, const long long* rows, int B, int ns, int zdim, int k_launch,
+                                        float* eps_sr, float* eps_si, float* eps_nr, float* eps_ni, void* stream) {
+    if (!seeds || !rows || k_launch <= 0 || B <= 0 || ns <= 0 || zdim <= 0 || !eps_sr || !eps_si ||
+        (eps_nr != nullptr) != (eps_ni != nullptr) || (long long)B * ns > 0x7fffffffLL)
+        return IDV_EINVAL;
+    const dim3 grid(grid_of((long long)B * ns * k_launch * zdim));
+    if (eps_nr)
+        hipLaunchKernelGGL((stream_eps_kernel<true, true, true>), grid, dim3(256), 0, (hipStream_t)stream, 0ULL, 0LL, k_launch,
+                           B * ns, zdim, eps_sr, eps_si, eps_nr, eps_ni, ns, rows, seeds);
+    else      // the single-pair form: the speech draws alone
+        hipLaunchKernelGGL((stream_eps_kernel<true, false, true>), grid, dim3(256), 0, (hipStream_t)stream, 0ULL, 0LL, k_launch,
+                           B * ns, zdim, eps_sr, eps_si, no_eps, no_eps, ns, rows, seeds);
     return idv_launch_status();
 }
 

@@ -1296,38 +1296,16 @@ class StreamingVAE(_VAEStreamer):
         return self.h_skip_n[di]
 
 
-class StreamingVAETwoLatents(StreamingVAE):
-    """Lock-step streaming of the two-latent evaluation (``inference.enhance_vae_two_latents``, the reference's
-    ``latent_to_use == 2``) for ``batch`` signals: one pass of the noisy encoder at batch B, the speech decoder on the speech
-    latent and the noise decoder on the noise latent at batch B * num_samples (row b * ns + s), then the ``outtype`` estimator.
-
-        st = StreamingVAETwoLatents(noisy_encoder, speech_decoder, noise_decoder, batch=B, outtype="phase_mask", phase=2, seed=0)
-        y = st.push(x)                   # x [B, n] on the GPU -> [B, m], the samples that became final
-        y = st.flush()
-        sr, si, nr, ni = st.eps(t0, k)   # the draws frames t0 .. t0+k-1 use, each [B, ns, k, zdim]
-
-    :class:`StreamingVAE`'s contract: :class:`StreamPlan` bookkeeping, the same sample counts per ``push`` / ``flush`` and the
-    same bits however the signal is cut; all pushes and the flush together return what ``inference.enhance_vae_two_latents(
-    noisy_encoder, speech_decoder, noise_decoder, x_full, outtype, phase, eps=<the same four draws>)`` returns.
-
-    ``phase=2``: both decoders are ``nsvae_pvae_dccrn_decoder_twophase`` and read the noisy skips (``pad='sig'``); the repeated
-    skips and their history halves are formed once per launch group for both.  ``phase=1``: zero skips, as ``pad='zero'``
-    offline, with either decoder class; a zero skip is packed away (the block keeps the first C0 input channels of its
-    weights), so no zeros are read.  ``outtype="clean_direct"`` runs the speech decoder alone (``noise_decoder`` may be None)
-    and, at ``phase=2``, returns the bits of ``StreamingVAE(noisy_encoder, speech_decoder, batch=B, seed=seed)``.  The mask
-    estimators (``real_imag_mask``, ``complex_mask``, ``phase_mask``) form the two sample means and the estimate per column
-    (``idv_stream_estimate``) in front of the inverse DFT, which with the overlap-add then runs at batch B.
-
-    The draws of both latents come from one counter-based block per (seed, b, s, t, u) (``idv_stream_eps_pair``; the speech
-    pair is ``StreamingVAE``'s); ``eps`` may instead be a callable ``(t0, k) -> (eps_sr, eps_si, eps_nr, eps_ni)``, each
-    [B, ns, k, zdim] on the GPU.  ``conv`` as in :class:`StreamingDCCRN`; ``conv_engines`` lists enc0 .. 5, speech dec0 .. 5,
-    then noise dec0 .. 5.  Exact fp32; weights are packed at construction.
-    """
+class _TwoLatents:
+    """What both two-latent streamers share, mixed in in front of their single-decoder base: the construction (guards, the two
+    decoder chains on their latents), the buffers, and the network over one launch group.  The base supplies the framing, the
+    conv block, the LSTM, the repeated skips and the draws of its kind; ``self._draws(c)`` returns the pointers of the speech
+    pair followed, when the noise decoder runs, by those of the noise pair."""
 
     _name = "StreamingVAETwoLatents"
 
-    def __init__(self, noisy_encoder, speech_decoder, noise_decoder, batch: int, outtype: str = "phase_mask", phase: int = 2,
-                 seed: int = 0, eps=None, frames_per_launch: int = 64, max_columns: int = 4096, conv: str = "valu"):
+    def _init_two_latents(self, noisy_encoder, speech_decoder, noise_decoder, batch, outtype, phase, seed, eps, frames_per_launch,
+                          max_columns, conv):
         self.conv = check_conv(conv)
         check_vae_two_latents(noisy_encoder, speech_decoder, noise_decoder, batch, outtype, phase, seed, eps)
         if outtype == "clean_direct":
@@ -1376,6 +1354,60 @@ class StreamingVAETwoLatents(StreamingVAE):
         for ch in self.chains:
             self.state += [ch.h_dense] + ch.h_dec
 
+    # ------------------------------------------------------------------ the network over one launch group
+    def _network(self, c, io):
+        """Encoder and LSTM once; both decoder chains on their latents; then either StreamingVAE's tail on the speech chain
+        (clean_direct: self.ifr, batch B * ns) or the estimator and the inverse DFT at batch B (self.ifr_b)."""
+        self._encode(c, io)
+        d = self._draws(c)
+        skips = self._skips(c)
+        self._decode(c, self.speech, d[:2], skips)
+        if self.noise is None:
+            self._tail(c, self.speech)
+            return
+        self._decode(c, self.noise, d[2:], skips)
+        B, k = self.B, c.k
+        Tp = k + 1
+        Jp, Jpn = Planar.jp_for(B, Tp), Planar.jp_for(self.Bn, Tp)
+        call("idv_stream_estimate", self._at(self.speech.raw, Jpn), self._at(self.noise.raw, Jpn), self._at(self.X, Jp),
+             i(1 if self.recon == "mask" else 0), i(OUTTYPES[self.outtype]), i(self.ns), i(self.F), i(B), i(k), i(Tp), i(Jp), i(Jpn),
+             self._at(self.spec, Jp), stream_ptr())
+        ops.pw_gemm(self._at(self.spec, Jp), 2 * self.F, self.dft_inv[0], self.dft_inv[1], self.win, B, Tp, Jp, k, self._at(self.ifr_b, Jp))
+
+
+class StreamingVAETwoLatents(_TwoLatents, StreamingVAE):
+    """Lock-step streaming of the two-latent evaluation (``inference.enhance_vae_two_latents``, the reference's
+    ``latent_to_use == 2``) for ``batch`` signals: one pass of the noisy encoder at batch B, the speech decoder on the speech
+    latent and the noise decoder on the noise latent at batch B * num_samples (row b * ns + s), then the ``outtype`` estimator.
+
+        st = StreamingVAETwoLatents(noisy_encoder, speech_decoder, noise_decoder, batch=B, outtype="phase_mask", phase=2, seed=0)
+        y = st.push(x)                   # x [B, n] on the GPU -> [B, m], the samples that became final
+        y = st.flush()
+        sr, si, nr, ni = st.eps(t0, k)   # the draws frames t0 .. t0+k-1 use, each [B, ns, k, zdim]
+
+    :class:`StreamingVAE`'s contract: :class:`StreamPlan` bookkeeping, the same sample counts per ``push`` / ``flush`` and the
+    same bits however the signal is cut; all pushes and the flush together return what ``inference.enhance_vae_two_latents(
+    noisy_encoder, speech_decoder, noise_decoder, x_full, outtype, phase, eps=<the same four draws>)`` returns.
+
+    ``phase=2``: both decoders are ``nsvae_pvae_dccrn_decoder_twophase`` and read the noisy skips (``pad='sig'``); the repeated
+    skips and their history halves are formed once per launch group for both.  ``phase=1``: zero skips, as ``pad='zero'``
+    offline, with either decoder class; a zero skip is packed away (the block keeps the first C0 input channels of its
+    weights), so no zeros are read.  ``outtype="clean_direct"`` runs the speech decoder alone (``noise_decoder`` may be None)
+    and, at ``phase=2``, returns the bits of ``StreamingVAE(noisy_encoder, speech_decoder, batch=B, seed=seed)``.  The mask
+    estimators (``real_imag_mask``, ``complex_mask``, ``phase_mask``) form the two sample means and the estimate per column
+    (``idv_stream_estimate``) in front of the inverse DFT, which with the overlap-add then runs at batch B.
+
+    The draws of both latents come from one counter-based block per (seed, b, s, t, u) (``idv_stream_eps_pair``; the speech
+    pair is ``StreamingVAE``'s); ``eps`` may instead be a callable ``(t0, k) -> (eps_sr, eps_si, eps_nr, eps_ni)``, each
+    [B, ns, k, zdim] on the GPU.  ``conv`` as in :class:`StreamingDCCRN`; ``conv_engines`` lists enc0 .. 5, speech dec0 .. 5,
+    then noise dec0 .. 5.  Exact fp32; weights are packed at construction.
+    """
+
+    def __init__(self, noisy_encoder, speech_decoder, noise_decoder, batch: int, outtype: str = "phase_mask", phase: int = 2,
+                 seed: int = 0, eps=None, frames_per_launch: int = 64, max_columns: int = 4096, conv: str = "valu"):
+        self._init_two_latents(noisy_encoder, speech_decoder, noise_decoder, batch, outtype, phase, seed, eps, frames_per_launch,
+                               max_columns, conv)
+
     # ------------------------------------------------------------------ the draws
     def eps(self, t0: int, k: int):
         """The draws frames t0 .. t0+k-1 use with the streamer's own generator and its current seed: (eps_sr, eps_si, eps_nr,
@@ -1410,26 +1442,6 @@ class StreamingVAETwoLatents(StreamingVAE):
             out.append(p(t.float().contiguous()))
         return tuple(out)
 
-    # ------------------------------------------------------------------ the network over one launch group
-    def _network(self, c, io):
-        """Encoder and LSTM once; both decoder chains on their latents; then either StreamingVAE's tail on the speech chain
-        (clean_direct: self.ifr, batch B * ns) or the estimator and the inverse DFT at batch B (self.ifr_b)."""
-        self._encode(c, io)
-        d = self._draws(c)
-        skips = self._skips(c)
-        self._decode(c, self.speech, d[:2], skips)
-        if self.noise is None:
-            self._tail(c, self.speech)
-            return
-        self._decode(c, self.noise, d[2:], skips)
-        B, k = self.B, c.k
-        Tp = k + 1
-        Jp, Jpn = Planar.jp_for(B, Tp), Planar.jp_for(self.Bn, Tp)
-        call("idv_stream_estimate", self._at(self.speech.raw, Jpn), self._at(self.noise.raw, Jpn), self._at(self.X, Jp),
-             i(1 if self.recon == "mask" else 0), i(OUTTYPES[self.outtype]), i(self.ns), i(self.F), i(B), i(k), i(Tp), i(Jp), i(Jpn),
-             self._at(self.spec, Jp), stream_ptr())
-        ops.pw_gemm(self._at(self.spec, Jp), 2 * self.F, self.dft_inv[0], self.dft_inv[1], self.win, B, Tp, Jp, k, self._at(self.ifr_b, Jp))
-
     def _run(self, chunks: List[Chunk], x, ldx: int, n_new: int, n_prev: int, L_end: Optional[int]) -> torch.Tensor:
         if self.noise is None:
             return super()._run(chunks, x, ldx, n_new, n_prev, L_end)
@@ -1448,18 +1460,19 @@ def decoder_rows(rows: List[List[int]], ns: int) -> List[List[int]]:
     return [r for r in rows for _ in range(ns)]
 
 
-def vae_session_tables(plan: SessionCall, ns: int) -> List[int]:
+def vae_session_tables(plan: SessionCall, ns: int, seeds: Sequence[int] = ()) -> List[int]:
     """The host side of the one copy a VAE sessions call makes: per launch group the slots' table [B][NF] followed by its
-    decoder-side table [B * ns][NF], then the slots to zero."""
-    return [v for g in plan.groups for r in g.rows + decoder_rows(g.rows, ns) for v in r] + list(plan.zero)
+    decoder-side table [B * ns][NF], then the slots to zero, then ``seeds`` (one per slot, as they stand when the call is made)."""
+    return [v for g in plan.groups for r in g.rows + decoder_rows(g.rows, ns) for v in r] + list(plan.zero) + list(seeds)
 
 
 class _VAELaunch(NamedTuple):
     """What the network needs of a VAE sessions launch group: k_launch and the device pointers of its two row tables (encoder
-    side [B][NF], decoder side [B * ns][NF])."""
+    side [B][NF], decoder side [B * ns][NF]) and of the slots' seeds [B]."""
     k: int
     rows: object
     rows_n: object
+    seeds: object
 
 
 class StreamingVAESessions(_Slots, _VAEStreamer):
@@ -1469,19 +1482,24 @@ class StreamingVAESessions(_Slots, _VAEStreamer):
         st = StreamingVAESessions(noisy_encoder, decoder, slots, seed=0, latent="speech", average=True)
         y, m = st.push(x, counts=None, end=())   # x [slots, n] -> y [slots, max(m)] (average=False: [slots * ns, max(m)], row b * ns + s)
         st.drop(slots); st.positions; st.reset()
-        er, ei = st.eps(t0, k)                   # [slots, ns, k, zdim] each, the generator of StreamingVAE.eps
+        st.seed; st.seeds; st.set_seed(slots, seed)
+        er, ei = st.eps(t0, k)                   # [slots, ns, k, zdim] each, the generator of StreamingVAE.eps, every slot's own seed
 
-    Slot b's samples are bit-identical to what ``StreamingVAE(noisy_encoder, decoder, batch=slots, seed=seed, latent=latent,
-    conv=conv)`` returns for the same signal in slot b, whatever the other slots do and for every signal the slot serves one
-    after another: a draw depends on (seed, b, s, the slot's own frame index, u).  ``seed`` can be set only while every position
-    is 0 (a signal's draws must not change midway); a callable ``eps`` is not taken.  Every guard runs on the host before any GPU
-    work and before any bookkeeping changes.  Per launch group the kernels take two tables, the slots' (:class:`SessionPlan`) for
-    the encoder side and :func:`decoder_rows` of it for the decoder side; both tables of every group and the list of slots to
-    zero go to the device in one copy.
+    Slot b's samples are bit-identical to what ``StreamingVAE(noisy_encoder, decoder, batch=slots, seed=st.seeds[b],
+    latent=latent, conv=conv)`` returns for the same signal in slot b, whatever the other slots do and for every signal the slot
+    serves one after another: a draw depends on (the slot's seed, b, s, the slot's own frame index, u).  ``seed`` is the default
+    every slot draws with; ``set_seed(slots, seed)`` gives the named slots a seed of their own, which they keep over ``end`` and
+    ``drop`` until it is set again or ``seed`` is assigned.  A slot's seed can change only while its position is 0, ``seed`` only
+    while every position is 0 (a signal's draws must not change midway); a callable ``eps`` is not taken.  Every guard runs on
+    the host before any GPU work and before any bookkeeping changes.  Per launch group the kernels take two tables, the slots'
+    (:class:`SessionPlan`) for the encoder side and :func:`decoder_rows` of it for the decoder side; both tables of every group,
+    the list of slots to zero and the slots' seeds go to the device in one copy (:func:`vae_session_tables`).
     """
 
     _name = "StreamingVAESessions"
     _skip_halves = 2
+    _eps_outputs = 2               # tensors ``eps`` returns: one pair, or the speech and the noise pair
+    _per_sample = True             # overlap-add at batch B * ns (self.ifr, then the mean over the samples) or at batch B (self.ifr_b)
 
     def __init__(self, noisy_encoder, decoder, slots: int, seed: int = 0, latent: str = "speech", average: bool = True,
                  frames_per_launch: int = 64, max_columns: int = 4096, conv: str = "valu"):
@@ -1493,6 +1511,11 @@ class StreamingVAESessions(_Slots, _VAEStreamer):
         self._zero_views += [(h, h.numel() // slots, 1) for h in [self.h_in] + self.h_enc]
         self._zero_views += [(h, h.numel() // (slots * ns), ns) for h in [self.h_dense] + self.h_dec]
 
+    def _init_slots(self):
+        super()._init_slots()
+        self._own_seeds = {}        # slot -> the seed set_seed gave it
+
+    # ------------------------------------------------------------------ seeds
     @property
     def seed(self) -> int:
         return self._seed
@@ -1503,6 +1526,40 @@ class StreamingVAESessions(_Slots, _VAEStreamer):
         if any(self.positions):
             raise ValueError("seed can be set only between signals (every position 0): a signal's draws must not change midway")
         self._seed = v
+        self._own_seeds.clear()
+
+    @property
+    def seeds(self) -> List[int]:
+        """The seed every slot draws with: its own where ``set_seed`` gave it one, else ``seed``."""
+        return [self._own_seeds.get(b, self._seed) for b in range(self.B)]
+
+    def set_seed(self, slots, seed):
+        """Give these slots a seed of their own; each must be between signals (position 0)."""
+        slots = check_slots(slots, self.B)
+        seed = check_seed(seed)
+        pos = self.positions
+        for b in slots:
+            if pos[b]:
+                raise ValueError(f"set_seed: slot {b} is {pos[b]} samples into its signal; a slot's seed can be set only between "
+                                 "signals (position 0): a signal's draws must not change midway")
+        for b in slots:
+            self._own_seeds[b] = seed
+
+    def eps(self, t0: int, k: int):
+        """The draws frames t0 .. t0+k-1 use, every slot's with its own seed (``seeds``): (eps_r, eps_i), each [slots, ns, k,
+        zdim]; a two-latent streamer returns (eps_sr, eps_si, eps_nr, eps_ni)."""
+        if isinstance(t0, bool) or not isinstance(t0, int) or t0 < 0 or isinstance(k, bool) or not isinstance(k, int) or k <= 0:
+            raise ValueError("eps(t0, k): t0 >= 0 and k > 0 frames")
+        B = self.B
+        row = [0] * NF
+        row[ROW_FIELDS.index("t0")], row[ROW_FIELDS.index("k")] = t0, k
+        out = torch.empty(self._eps_outputs, B, self.ns, k, self.zdim, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            table = self._upload(torch.tensor(row * B + self.seeds, dtype=torch.int64))
+            nr, ni = (p(out[2]), p(out[3])) if self._eps_outputs == 4 else (p(None), p(None))
+            call("idv_stream_eps_pair_rows", L._P(table.data_ptr() + 8 * B * NF), L._P(table.data_ptr()), i(B), i(self.ns),
+                 i(self.zdim), i(k), p(out[0]), p(out[1]), nr, ni, stream_ptr())
+        return tuple(out)
 
     # ------------------------------------------------------------------ push
     def push(self, x: torch.Tensor, counts=None, end=()):
@@ -1520,7 +1577,7 @@ class StreamingVAESessions(_Slots, _VAEStreamer):
         ldx = x.stride(0) if B > 1 else n
         cap = self.plan.carry_cap
         per = (B + Bn) * NF                          # a group's two tables: [B][NF], then [B * ns][NF]
-        host = torch.tensor(vae_session_tables(plan, ns), dtype=torch.int64)
+        host = torch.tensor(vae_session_tables(plan, ns, self.seeds), dtype=torch.int64)
         for gi, g in enumerate(plan.groups):         # a bad table never reaches a kernel
             rc = L.lib().idv_stream_rows_check(L._P(host.data_ptr() + 8 * gi * per), B, self.plan.ring, 0 if g.flush else n,
                                                self.n_fft, self.win, self.hop, cap, g.k, g.k + 1, ldy, g.span)
@@ -1529,26 +1586,29 @@ class StreamingVAESessions(_Slots, _VAEStreamer):
                 raise L.IdvError(f"idv_stream_rows_check refused the table of launch group {gi} (status {rc})")
         with torch.no_grad(), torch.cuda.device(self.device):
             s = stream_ptr()
-            y = torch.zeros(Bn, ldy, dtype=torch.float32, device=self.device)
-            if host.numel():
+            # the overlap-add runs on the decoder side's rows (one per sample) or, behind an estimator, on the slots' rows
+            rows_y, frames = (Bn, self.ifr) if self._per_sample else (B, self.ifr_b)
+            y = torch.zeros(rows_y, ldy, dtype=torch.float32, device=self.device)
+            if plan.groups or plan.zero:
                 table = self._upload(host)
                 rows_of = lambda gi: L._P(table.data_ptr() + 8 * gi * per)
+                seeds = L._P(table.data_ptr() + 8 * (len(plan.groups) * per + len(plan.zero)))
                 ring_due = any(counts)
                 for gi, g in enumerate(plan.groups):
                     if g.flush and ring_due:         # the flush phase reads this call's samples from the ring
                         call("idv_stream_ring_rows", p(self.ring), i(self.plan.ring), p(x), ll(ldx), i(n), rows_of(0), i(B), s)
                         ring_due = False
-                    c = _VAELaunch(g.k, rows_of(gi), L._P(table.data_ptr() + 8 * (gi * per + B * NF)))
+                    c = _VAELaunch(g.k, rows_of(gi), L._P(table.data_ptr() + 8 * (gi * per + B * NF)), seeds)
                     if g.k > 0:
                         self._network(c, (None, 0) if g.flush else (x if n else None, ldx))
                     Tp = g.k + 1
-                    call("idv_stream_ola_rows", self.ifr.ptr() if g.k > 0 else p(None), i(Tp), i(Planar.jp_for(Bn, Tp)), p(self.carry),
-                         i(cap), c.rows_n, i(Bn), i(self.n_fft), i(self.win), i(self.hop), i(g.k), ll(g.span), p(y) if ldy else p(None),
-                         ll(ldy), s)
+                    call("idv_stream_ola_rows", frames.ptr() if g.k > 0 else p(None), i(Tp), i(Planar.jp_for(rows_y, Tp)),
+                         p(self.carry), i(cap), c.rows_n if self._per_sample else c.rows, i(rows_y), i(self.n_fft), i(self.win),
+                         i(self.hop), i(g.k), ll(g.span), p(y) if ldy else p(None), ll(ldy), s)
                 if ring_due:
                     call("idv_stream_ring_rows", p(self.ring), i(self.plan.ring), p(x), ll(ldx), i(n), rows_of(0), i(B), s)
                 self._zero(L._P(table.data_ptr() + 8 * len(plan.groups) * per), len(plan.zero))
-            if not self.average:
+            if not (self._per_sample and self.average):
                 return y, plan.m
             out = torch.zeros(B, ldy, dtype=torch.float32, device=self.device)
             if ldy:
@@ -1577,12 +1637,53 @@ class StreamingVAESessions(_Slots, _VAEStreamer):
              i(self.H), i(self.B), i(c.k), i(Tp), i(Jp), c.rows, stream_ptr())
 
     def _draws(self, c):
-        call("idv_stream_eps_rows", ll(self._seed), c.rows, i(self.B), i(self.ns), i(self.zdim), i(c.k), p(self.eps_buf[0]),
-             p(self.eps_buf[1]), stream_ptr())
-        return p(self.eps_buf[0]), p(self.eps_buf[1])
+        """Device pointers of the draws of launch group c, every slot's with its own seed: eps_r / eps_i [B][ns][c.k][zdim], and
+        the noise pair behind them where ``eps_buf`` holds one (two decoder chains)."""
+        e = [p(t) for t in self.eps_buf]
+        nr, ni = e[2:] if len(e) == 4 else (p(None), p(None))
+        call("idv_stream_eps_pair_rows", c.seeds, c.rows, i(self.B), i(self.ns), i(self.zdim), i(c.k), e[0], e[1], nr, ni, stream_ptr())
+        return tuple(e)
 
     def _repeat(self, c, di: int, sk: int, x, xn, Tp: int, Jp: int, Jpn: int):
         sc, sf = self.enc_shapes[sk]
         call("idv_stream_repeat_rows", x, p(self.h_enc[sk]), i(sc), i(sf), i(self.B), i(self.ns), i(c.k), i(Tp), i(Jp), c.rows, xn,
              p(self.h_skip_n[di]), i(Jpn), stream_ptr())
         return self.h_skip_n[di]
+
+
+class StreamingVAETwoLatentsSessions(_TwoLatents, StreamingVAESessions):
+    """The two-latent evaluation of :class:`StreamingVAETwoLatents` for ``slots`` independent signals in one batch, with the
+    ``push`` / ``counts`` / ``end`` / ``drop`` / ``positions`` / seeds contract of :class:`StreamingVAESessions`.
+
+        st = StreamingVAETwoLatentsSessions(noisy_encoder, speech_decoder, noise_decoder, slots, outtype="phase_mask", phase=2, seed=0)
+        y, m = st.push(x, counts=None, end=())   # x [slots, n] -> y [slots, max(m)], m[b] valid samples of slot b, zeros behind
+        st.drop(slots); st.positions; st.reset(); st.seed; st.seeds; st.set_seed(slots, seed)
+        sr, si, nr, ni = st.eps(t0, k)           # [slots, ns, k, zdim] each, with every slot's own seed
+
+    Slot b's samples are bit-identical to what ``StreamingVAETwoLatents(noisy_encoder, speech_decoder, noise_decoder, batch=slots,
+    outtype=outtype, phase=phase, seed=st.seeds[b], conv=conv)`` returns for the same signal in slot b, whatever the other slots
+    do and for every signal the slot serves one after another.  A callable ``eps`` is not taken.
+
+    The network is the lock-step class's on the per-slot kernels of :class:`StreamingVAESessions`, with both tables of a launch
+    group; the draws of both latents come from ``idv_stream_eps_pair_rows``.  The estimator (``idv_stream_estimate``) takes no
+    table: it runs on all k_launch columns of every slot, each output column from its own input column alone, and the
+    overlap-add, on the slots' table at batch B, reads the columns tl < k_b only.  ``clean_direct`` keeps
+    :class:`StreamingVAESessions`'s tail at batch B * ns and, at ``phase=2``, returns its bits for the same seeds.
+    ``conv_engines`` as in :class:`StreamingVAETwoLatents`.
+    """
+
+    _name = "StreamingVAETwoLatentsSessions"
+    _eps_outputs = 4
+
+    def __init__(self, noisy_encoder, speech_decoder, noise_decoder, slots: int, outtype: str = "phase_mask", phase: int = 2,
+                 seed: int = 0, frames_per_launch: int = 64, max_columns: int = 4096, conv: str = "valu"):
+        self._init_two_latents(noisy_encoder, speech_decoder, noise_decoder, slots, outtype, phase, seed, None, frames_per_launch,
+                               max_columns, conv)
+        self._init_slots()
+        self._per_sample = self.noise is None
+        # state buffers as [outer][slots][inner]; the estimators leave one overlap-add row per slot, clean_direct one per sample
+        ns = self.ns
+        self._zero_views = [(self.ring, 1, self.plan.ring), (self.carry, 2, (ns if self._per_sample else 1) * self.plan.carry_cap),
+                            (self.lstm_state, 16, self.H)]
+        self._zero_views += [(h, h.numel() // slots, 1) for h in [self.h_in] + self.h_enc]
+        self._zero_views += [(h, h.numel() // (slots * ns), ns) for ch in self.chains for h in [ch.h_dense] + ch.h_dec]

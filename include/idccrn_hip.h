@@ -801,6 +801,18 @@ int idv_stream_eps_pair(long long seed, long long t0, int k, int B, int ns, int 
 int idv_stream_estimate(const float* speech, const float* noise, const float* X, int recon_mask, int mode, int ns, int F, int B,
                         int k, int Tp, int Jp, int Jpn, float* out, void* stream);
 
+/* ---- two-latent sessions and per-slot seeds (stream_io.hip; streaming.StreamingVAETwoLatentsSessions and
+ * streaming.StreamingVAESessions; an additive entry: IDV_ABI_VERSION is unchanged). */
+/* idv_stream_eps_pair per slot, each slot with a seed of its own: seeds is a device array [B], rows the slots' table
+ * [B][IDV_STREAM_ROW_FIELDS]; all four outputs are [B][ns][k_launch][zdim].  Frame tl < k_b of slot b is drawn with the key
+ * seeds[b] and the counter (t0_b + tl, b*ns + s, u): words 0 and 1 through Box-Muller give eps_sr, eps_si, words 2 and 3 eps_nr,
+ * eps_ni, bit for bit what idv_stream_eps_pair(seeds[b], t0_b, k_b, B, ns, zdim, ...) writes for slot b.  The entries with
+ * tl >= k_b are zero in every output.  eps_nr == eps_ni == NULL selects the single-pair form, which writes the speech draws
+ * alone (with equal seeds: what idv_stream_eps_rows writes); exactly one of the two NULL is IDV_EINVAL.  The same kernel source
+ * as the three entries above it, compiled with the seed read from seeds[b]. */
+int idv_stream_eps_pair_rows(const long long* seeds, const long long* rows, int B, int ns, int zdim, int k_launch, float* eps_sr,
+                             float* eps_si, float* eps_nr, float* eps_ni, void* stream);
+
 /* ---- batches of utterances of different lengths (ragged.hip, reduce.hip; inference.enhance_* / compute_sisdr with `lengths`) ---
  * lens: device int32[], samples per utterance.  Utterance b has T_b = 1 + lens[b] / hop frames and hop * (T_b - 1) output samples;
  * the batch is laid out for Tmax = max_b T_b frames, Tp >= Tmax + 1.  A causal network computes frame t from frames <= t, so only

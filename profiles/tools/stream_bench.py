@@ -1,7 +1,8 @@
 """Streaming enhancement benchmark: one JSON line per batch of lock-step streams, one hop (100 samples) per push.
 
     python profiles/tools/stream_bench.py [--batches 1,16,128,512,1024] [--seconds 2] [--catchup] [--far-seconds 3600] [--sessions]
-                                           [--conv valu|mfma|both] [--vae [--sessions]] [--two-latents [--outtype O] [--phase P]]
+                                           [--conv valu|mfma|both] [--vae [--sessions]]
+                                           [--two-latents [--sessions] [--outtype O] [--phase P]]
 
 Per line: device time per push (HIP events around >= --seconds of pushes after warm-up), host wall time per push (synchronised),
 the real-time factor (hop / 16 kHz = 6.25 ms over the wall time) and the algorithmic GFLOP per push (4 real products per complex
@@ -22,7 +23,10 @@ host list on every push) and, right after it in the same process and with the sa
 B and engine (metric "vae_push"), so that the two lines of a pair share the card and its clocks.  --two-latents measures
 streaming.StreamingVAETwoLatents (metric "two_latents_push"; --outtype, default phase_mask, and --phase, default 2; the encoder of
 --vae, a speech and a noise decoder, num_samples 3, default batches 1,16) and, right after it in the same process with the same
-encoder and speech decoder, StreamingVAE at the same B, ns and engine (metric "vae_push").
+encoder and speech decoder, StreamingVAE at the same B, ns and engine (metric "vae_push").  --two-latents --sessions measures
+streaming.StreamingVAETwoLatentsSessions (metric "two_latents_sessions_push": every slot active at the staggered positions of
+--sessions, counts as a host list on every push) and, right after it in the same process with the same three models, the lock-step
+StreamingVAETwoLatents at the same B and engine (metric "two_latents_push").
 """
 from __future__ import annotations
 
@@ -110,6 +114,8 @@ def build(B, sessions=False, conv="valu", vae=False, two=None):
             load(noise, 11)
             _VAE_PAIR.extend([enc.cuda(), dec.cuda(), noise.cuda()])
         enc, dec, noise = _VAE_PAIR
+        if two is not None and sessions:
+            return S.StreamingVAETwoLatentsSessions(enc, dec, noise, slots=B, outtype=two[0], phase=two[1], seed=0, conv=conv)
         if two is not None:
             return S.StreamingVAETwoLatents(enc, dec, noise, batch=B, outtype=two[0], phase=two[1], seed=0, conv=conv)
         if sessions:
@@ -177,8 +183,8 @@ def main():
     ap.add_argument("--outtype", default="phase_mask")
     ap.add_argument("--phase", type=int, default=2)
     a = ap.parse_args()
-    if a.two_latents and (a.sessions or a.catchup or a.far_seconds):
-        ap.error("--two-latents measures hop pushes of StreamingVAETwoLatents and StreamingVAE only")
+    if a.two_latents and (a.catchup or a.far_seconds):
+        ap.error("--two-latents measures hop pushes of StreamingVAETwoLatents / StreamingVAETwoLatentsSessions and StreamingVAE only")
     a.vae = a.vae or a.two_latents
     if a.vae and (a.catchup or a.far_seconds):
         ap.error("--vae measures hop pushes of StreamingVAE / StreamingVAESessions only")
@@ -191,10 +197,13 @@ def main():
     for B in [int(v) for v in a.batches.split(",") if v]:
         for conv, rnd in turns:
             if a.two_latents:
-                for two in ((a.outtype, a.phase), None):
-                    st, dev_ms, wall_ms, _ = run(B, a.seconds, conv=conv, vae=True, two=two)
+                two_ = (a.outtype, a.phase)
+                # (estimator or None: StreamingVAE, sessions form): the sessions form first, then its lock-step form
+                for two, sessions in (((two_, True), (two_, False)) if a.sessions else ((two_, False), (None, False))):
+                    st, dev_ms, wall_ms, _ = run(B, a.seconds, sessions=sessions, conv=conv, vae=True, two=two)
                     gf = (gflop_per_frame_two(st) if two else gflop_per_frame_vae(st)) * B
-                    line = {"metric": "two_latents_push" if two else "vae_push", "B": B, "ns": st.ns, "H": st.H, "hop": HOP}
+                    metric = "two_latents_sessions_push" if sessions else "two_latents_push" if two else "vae_push"
+                    line = {"metric": metric, "B": B, "ns": st.ns, "H": st.H, "hop": HOP}
                     if two:
                         line.update({"outtype": st.outtype, "phase": st.phase})
                     line.update({"device_ms_per_push": round(dev_ms, 4), "wall_ms_per_push": round(wall_ms, 4),
