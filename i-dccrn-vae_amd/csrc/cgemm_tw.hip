@@ -20,11 +20,17 @@
 // 2 p + 1) interleaved per pair (one 8-byte read fetches the operands of two tiles); the FREQUENCY transform A + cb B of cgemm_wino
 // happens at the operand read (two reads + one add).  Weights: cgemm_wino's fragments re-ordered by idv_pack_cconv_tw (lane =
 // channel parity x 32 + co), per (channel pair, wave).  Design notes and measurements: DESIGN.md 3.1e.
+//
+// Odd row counts (every decoder layer of the model): the last even output row, out[2 (Fin - 1)] = W4 x[Fin - 2] + W2 x[Fin - 1], has no
+// partner row.  It is not a row tile of its own: the even-row launch holds EDGE workgroups (cgemm_tw_map.hpp) that compute that row
+// for TWO adjacent column blocks, wave w the raw-tap product (column block w >> 1, tap W4 | W2 = w & 1) on raw row Fin - 2 + (w & 1)
+// -- the same K loop on other offsets and a third weight region, and out = P[2 c] + P[2 c + 1] in the epilogue.
 #include <atomic>
 #include <cstdint>
 #include <cstdlib>
 #include <type_traits>
 #include "cgemm.hpp"
+#include "cgemm_tw_map.hpp"
 #include "../../include/idccrn_hip.h"
 
 namespace {
@@ -35,7 +41,8 @@ struct TwArgs {
     int C0, C1;
     int Fin, Fout;
     int J, Jp, Tp;
-    const float* wfrag;   // [phase 0: cotiles][UP][4 waves x 9 slots][64] then [phase 1: cotiles][UP][4 x 8][64] (idv_pack_cconv_tw)
+    const float* wfrag;   // [phase 0: cotiles][UP][4 waves x 9 slots][64], [phase 1: cotiles][UP][4 x 8][64], then the raw taps of the
+                          // edge workgroups [cotiles][UP][4 waves x 9 slots][64] (waves 0, 2: W4; 1, 3: W2) (idv_pack_cconv_tw)
     int UP;               // channel pairs per co tile as packed (Cin rounded up to the pack granularity, / 2)
     const float* epi;     // as cgemm_gauss: [cotiles * 32][8]
     int has_fold;
@@ -47,9 +54,7 @@ struct TwArgs {
     int stats_rep;        // > 1: that many replicas [rep][Cout][5] (power of two), one chosen per workgroup
     const float* add;     // optional addend (see cgemm_gauss.hip)
     int add_div, add_Jp;
-    int jtiles, ftiles;
-    int xcd_split;        // block order: the co tiles of a column block on different XCDs (see the kernel)
-    int cgroups;          // cotiles / NCT: workgroups per (column block, row pair); the block order runs over these
+    TwGrid grid;          // block order (cgemm_tw_map.hpp); cgroups = cotiles / NCT workgroups per (column block, row pair)
     int stagger;          // NCT = 2, odd-row phase: waves 4 .. 7 stage one k-step later than their SIMD partners, waves 0 .. 3
 };
 
@@ -122,26 +127,13 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw_kernel(c
     const int w4 = NCT == 1 ? wave : wave & 3, cth = NCT == 1 ? 0 : wave >> 2;
     const int half = lane >> 5, l31 = lane & 31;
 
-    // block order: all (frequency tile, co tile) workgroups of a 64-column block on ONE XCD (block ids equal mod 8 share an XCD):
-    // they read the same raw input rows
-    const int bid = blockIdx.x;
-    const int xcd = bid & 7, slot = bid >> 3;
-    int jt, ft, ct;
-    if (a.xcd_split) {
-        // 2 / 4 / 8 co tiles: co tile ct always on the XCDs = ct (mod cotiles), so that an XCD streams 1 / cotiles of the layer's taps
-        // (2 - 5 MB: its L2 holds them) and the raw rows of a column block are read by cotiles XCDs instead of one
-        const int G = 8 / a.cgroups;
-        ct = xcd % a.cgroups;
-        jt = (slot / a.ftiles) * G + xcd / a.cgroups;
-        ft = slot - (slot / a.ftiles) * a.ftiles;
-    } else {
-        const int per = a.cgroups * a.ftiles;
-        jt = (slot / per) * 8 + xcd;
-        const int rem = slot - (slot / per) * per;
-        ft = rem / a.cgroups;
-        ct = rem - ft * a.cgroups;
-    }
-    if (jt >= a.jtiles) return;
+    // block order: cgemm_tw_map.hpp.  An EDGE workgroup (even-row phase, odd row count; block-uniform) computes the last even output
+    // row of the column blocks jt, jt + 1
+    TwTile tile;
+    if (!tw_block_tile(a.grid, blockIdx.x, tile)) return;
+    const bool edge = PH == 0 && tile.edge;
+    const int jt = tile.jt, ft = tile.ft;
+    int ct = tile.ct;
     ct = NCT * ct + cth;                          // (ct was the workgroup's group of NCT co tiles)
     const int j0 = jt * 64;
     const int m0 = 2 * ft;
@@ -156,16 +148,16 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw_kernel(c
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[k][r] = 0.f;
     // this wave's tiles (tw_tile): NPAIR pairs of planes + one single; slot j of the wave reads raw rows ra(r_j), rb(r_j) at plane pair
-    // pj_j -- the frequency transform  A + cb B  happens at the operand read.  In a half tile the products r = 3 do work nobody reads
-    // (they only feed the missing output row), branch-free.
+    // pj_j -- the frequency transform  A + cb B  happens at the operand read.  An edge workgroup's wave reads ONE raw slot, its own
+    // (A = B, cb = 0).
     constexpr int NPAIR = (NTW - 1) / 2;
     constexpr bool UNI = PH == 0;             // every slot of the wave belongs to ONE frequency product: one row offset, constant plane offsets
     int offA[UNI ? 1 : NPAIR + 1], offB[UNI ? 1 : NPAIR + 1];
     float cbj[UNI ? 1 : NPAIR + 1];
     if (UNI) {
-        cbj[0] = tw_cb<PH>(w4);
-        offA[0] = (tw_ra<PH>(w4) - ROW0) * 288;
-        offB[0] = (tw_rb<PH>(w4) - ROW0) * 288;             // (cb is never 0 in this phase)
+        cbj[0] = edge ? 0.f : tw_cb<PH>(w4);
+        offA[0] = (edge ? w4 : tw_ra<PH>(w4) - ROW0) * 288;
+        offB[0] = (edge ? w4 : tw_rb<PH>(w4) - ROW0) * 288; // (cb is never 0 in a full tile of this phase)
     } else {
 #pragma unroll
         for (int j = 0; j <= NPAIR; ++j) {
@@ -180,7 +172,9 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw_kernel(c
     }
 
     // ---- staging: one item = channel cl, raw row, column pairs 2 c8, 2 c8 + 1 (output columns j0 + 4 c8 .. + 3): window columns
-    // w0..w4 = input columns jc + tshift .. jc + 4 + tshift, real and imaginary -> the 9 planes (s = r + i | r | i) x (a - b | b | b - d)
+    // w0..w4 = input columns jc + tshift .. jc + 4 + tshift, real and imaginary -> the 9 planes (s = r + i | r | i) x (a - b | b | b - d).
+    // Edge workgroup: raw slot rl holds (column block jt + (rl >> 1), row Fin - 2 + (rl & 1)); a second column block past J is masked
+    // like any column out of range.
     f32x4 v_r[NLD], v_i[NLD];
     float e_r[NLD], e_i[NLD];
     unsigned off_v[NLD], off_e[NLD], ldsoff[NLD];
@@ -193,8 +187,8 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw_kernel(c
         const int c8 = e & 15;
         const int rl = (e >> 4) % NRAW, cl = e / (16 * NRAW);
         item_cl[i] = cl;
-        const int f = rbase + rl;
-        const int jc = j0 + 4 * c8;
+        const int f = edge ? a.Fin - 2 + (rl & 1) : rbase + rl;
+        const int jc = j0 + (edge ? 64 * (rl >> 1) : 0) + 4 * c8;
         const int je = LEFT ? jc - 1 : jc + 4;
         const bool exists = e < NITEM;
         const bool okr = exists && f >= 0 && f < a.Fin;
@@ -290,8 +284,8 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw_kernel(c
     // channel parity x 32 + co; idv_pack_cconv_tw): even-row phase two 16-byte loads + one 4-byte load ([64 lanes]) per k-step,
     // odd-row phase two 16-byte loads
     constexpr int WS = tw_wslots<PH>();
-    const float* wbase = a.wfrag + ((size_t)(PH == 1 ? (size_t)a.cotiles * a.UP * tw_ntp<0>() : 0) + (size_t)ct * a.UP * NTP) * 64 +
-                         (size_t)w4 * WS * 64;
+    const size_t wregion = PH == 1 ? (size_t)a.cotiles * a.UP * tw_ntp<0>() : (edge ? (size_t)a.cotiles * a.UP * (tw_ntp<0>() + tw_ntp<1>()) : 0);
+    const float* wbase = a.wfrag + (wregion + (size_t)ct * a.UP * NTP) * 64 + (size_t)w4 * WS * 64;
     const int total_ks = nchunk * KS;
     float a_w[RDW][NTW];
     auto load_w = [&](int g, float (&dst)[NTW]) {
@@ -396,17 +390,21 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw_kernel(c
     const float slope = a.slope ? *a.slope : 1.0f;
     const bool has_act = a.slope != nullptr;
     float* E = smem + cth * (NT * 4 * 64);                    // one exchange area per co tile
-    const int jA = j0 + 2 * l31;                              // the pair's two output columns jA, jA + 1
-    bool keep[2], inb[2];
-    int ja[2];                                                // the addend's column: utterance b / add_div of its own buffer
+    // the pair's two output columns jA, jA + 1 of the thread's two outputs rt: the two rows of a full tile, or (edge workgroup) the
+    // one row of the column blocks jt, jt + 1
+    const int jAc[2] = {j0 + 2 * l31, j0 + 2 * l31 + (edge ? 64 : 0)};
+    bool keep[2][2], inb[2][2];
+    int ja[2][2];                                             // the addend's column: utterance b / add_div of its own buffer
 #pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const int j = jA + q;
-        const int bj = j / a.Tp, tp = j - bj * a.Tp;
-        inb[q] = j < a.J;
-        keep[q] = inb[q] && tp >= 1 && tp <= a.t_valid;
-        ja[q] = j - (bj - bj / a.add_div) * a.Tp;
-    }
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int j = jAc[c] + q;
+            const int bj = j / a.Tp, tp = j - bj * a.Tp;
+            inb[c][q] = j < a.J;
+            keep[c][q] = inb[c][q] && tp >= 1 && tp <= a.t_valid;
+            ja[c][q] = j - (bj - bj / a.add_div) * a.Tp;
+        }
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
         if (s > 0) __syncthreads();
@@ -447,7 +445,8 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw_kernel(c
         float st[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int rt = 0; rt < 2; ++rt) {
-            const int fo = 2 * m0 + PH + 2 * rt;
+            const int fo = edge ? a.Fout - 1 : 2 * m0 + PH + 2 * rt;
+            const int jA = jAc[rt];
             if (fo >= a.Fout) continue;
             float yr[2], yi[2];
 #pragma unroll
@@ -456,13 +455,17 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw_kernel(c
                 if (PH == 0) {
                     re = rt == 0 ? pr[0][q] + pr[1][q] + pr[2][q] : pr[1][q] - pr[2][q] - pr[NR - 1][q];
                     im = rt == 0 ? pi[0][q] + pi[1][q] + pi[2][q] : pi[1][q] - pi[2][q] - pi[NR - 1][q];
+                    if (edge) {                               // the two raw-tap products of column block rt
+                        re = pr[2 * rt][q] + pr[(2 * rt + 1) % NR][q];
+                        im = pi[2 * rt][q] + pi[(2 * rt + 1) % NR][q];
+                    }
                 } else {
                     re = rt == 0 ? pr[0][q] + pr[1][q] : pr[1][q] - pr[2][q];
                     im = rt == 0 ? pi[0][q] + pi[1][q] : pi[1][q] - pi[2][q];
                 }
-                if (a.add && cok && inb[q]) {
-                    re += a.add[((size_t)co * a.Fout + fo) * a.add_Jp + ja[q]];
-                    im += a.add[((size_t)(a.Cout + co) * a.Fout + fo) * a.add_Jp + ja[q]];
+                if (a.add && cok && inb[rt][q]) {
+                    re += a.add[((size_t)co * a.Fout + fo) * a.add_Jp + ja[rt][q]];
+                    im += a.add[((size_t)(a.Cout + co) * a.Fout + fo) * a.add_Jp + ja[rt][q]];
                 }
                 float r_, i_;
                 if (a.has_fold) {
@@ -476,9 +479,9 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw_kernel(c
                     r_ = r_ >= 0.f ? r_ : slope * r_;
                     i_ = i_ >= 0.f ? i_ : slope * i_;
                 }
-                yr[q] = keep[q] ? r_ : 0.f;
-                yi[q] = keep[q] ? i_ : 0.f;
-                if (STATS && keep[q]) {
+                yr[q] = keep[rt][q] ? r_ : 0.f;
+                yi[q] = keep[rt][q] ? i_ : 0.f;
+                if (STATS && keep[rt][q]) {
                     st[0] += yr[q];
                     st[1] += yi[q];
                     st[2] += yr[q] * yr[q];
@@ -489,10 +492,10 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw_kernel(c
             if (cok) {
                 float* o_r = a.out + ((size_t)co * a.Fout + fo) * a.Jp + jA;
                 float* o_i = a.out + ((size_t)(a.Cout + co) * a.Fout + fo) * a.Jp + jA;
-                if (inb[1]) {
+                if (inb[rt][1]) {
                     *(float2*)o_r = make_float2(yr[0], yr[1]);
                     *(float2*)o_i = make_float2(yi[0], yi[1]);
-                } else if (inb[0]) {
+                } else if (inb[rt][0]) {
                     o_r[0] = yr[0];
                     o_i[0] = yi[0];
                 }
@@ -514,12 +517,15 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw_kernel(c
 
 // cgemm_wino's fragments [phase][ct][unit = ci * 3 + g][slot r (4)][lane = h * 32 + co] (h: the two time taps as the MFMA's two k,
 // h = 0 multiplies column j + tshift) -> [phase][ct][pair u][tile t = r * 9 + g * 3 + tau (36 | 28 slots)][lane = parity * 32 + co]
-// with the time-transformed taps  tau 0: W_h0,  tau 1: W_h0 + W_h1,  tau 2: W_h1.
+// with the time-transformed taps  tau 0: W_h0,  tau 1: W_h0 + W_h1,  tau 2: W_h1.  A third region in the even-row phase's layout holds
+// the RAW frequency taps of the edge workgroups in place of the frequency products r: waves 0, 2 the tap W4 (the even-row phase's
+// slot r = 0), waves 1, 3 the tap W2 = slot r = 1 minus slot r = 2 ((W4 + W2 + W0) / 2 - (W4 - W2 + W0) / 2).
 __global__ void pack_cconv_tw_kernel(const float* __restrict__ wino, int cotiles, int UN, int UP, int vec, float* __restrict__ out) {
     const long long n0 = (long long)cotiles * UP * tw_ntp<0>() * 64, n1 = (long long)cotiles * UP * tw_ntp<1>() * 64;
-    for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < n0 + n1; idx += (long long)gridDim.x * blockDim.x) {
-        const int ph = idx >= n0;
-        const long long i = ph ? idx - n0 : idx;
+    for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < n0 + n1 + n0; idx += (long long)gridDim.x * blockDim.x) {
+        const bool raw = idx >= n0 + n1;
+        const int ph = idx >= n0 && !raw;
+        const long long i = raw ? idx - n0 - n1 : (ph ? idx - n0 : idx);
         const int ntp = ph ? tw_ntp<1>() : tw_ntp<0>(), nt = ph ? tw_nt<1>() : tw_nt<0>();
         const int lane = (int)(i & 63);
         long long t_ = i >> 6;
@@ -537,8 +543,12 @@ __global__ void pack_cconv_tw_kernel(const float* __restrict__ wino, int cotiles
         const int ci = 2 * u + (ln >> 5), co = ln & 31;
         if (tt >= 0 && ci * 3 < UN) {
             const int r = tt / 9, g = (tt % 9) / 3, tau = tt % 3;
-            const float* src = wino + ((((size_t)ph * cotiles + ct) * UN + (size_t)ci * 3 + g) * 4 + r) * 64;
-            const float w0 = src[co], w1 = src[32 + co];
+            const float* src = wino + ((((size_t)ph * cotiles + ct) * UN + (size_t)ci * 3 + g) * 4 + (raw ? 0 : r)) * 64;
+            float w0 = src[co], w1 = src[32 + co];
+            if (raw && (r & 1)) {
+                w0 = src[64 + co] - src[128 + co];
+                w1 = src[64 + 32 + co] - src[128 + 32 + co];
+            }
             val = tau == 0 ? w0 : (tau == 1 ? w0 + w1 : w1);
         }
         out[idx] = val;
@@ -551,18 +561,11 @@ int launch_tw_ph_l(const TwArgs& a, hipStream_t st) {
     constexpr size_t smem = 2 * NE * sizeof(float);
     static_assert(smem * (NCT == 1 ? 2 : 1) <= 160 * 1024, "the patch buffers of two workgroups (NCT = 2: of one) must fit the 160 KB of LDS");
     TwArgs b = a;
-    b.jtiles = (a.J + 63) / 64;
-    b.ftiles = PH == 1 ? a.Fin / 2 : (a.Fin + 1) / 2;
-    if (b.ftiles == 0) return IDV_OK;
-    b.cgroups = b.cotiles / NCT;                              // (NCT = 2: the caller checked that the co-tile count is even)
-    if (b.cgroups * NCT != b.cotiles) return IDV_EINVAL;
+    if (b.cotiles % NCT) return IDV_EINVAL;                   // (NCT = 2: the caller checked that the co-tile count is even)
+    b.grid = tw_grid(PH, a.Fin, a.J, b.cotiles / NCT, TW_XCD_SPLIT);
     b.stagger = TW_PAIR_STAGGER;
-    b.xcd_split = (TW_XCD_SPLIT && (b.cgroups == 2 || b.cgroups == 4 || b.cgroups == 8)) ? 1 : 0;
-    long long nblk = (long long)((b.jtiles + 7) / 8) * 8 * b.ftiles * b.cgroups;
-    if (b.xcd_split) {
-        const int G = 8 / b.cgroups;
-        nblk = (long long)((b.jtiles + G - 1) / G) * b.ftiles * 8;
-    }
+    const long long nblk = tw_grid_blocks(b.grid);
+    if (nblk == 0) return IDV_OK;
     if (nblk > 0x7fffffffLL) return IDV_EINVAL;
     auto k = cconv_tw_kernel<PH, CIK, LEFT, STATS, NCT>;
     // (once per instantiation and device: setting it on every launch is host time, a lot of it under a profiler.  Two threads that
@@ -629,7 +632,7 @@ extern "C" int idv_cconv_tw_supported(int C0, int C1, int Cout, int Fin) {
 
 extern "C" long long idv_cconv_tw_wfrag_floats(int Cout, int cin_used) {
     const long long cotiles = (Cout + 31) / 32, cpad = (cin_used + TW_PACK_CI - 1) / TW_PACK_CI * TW_PACK_CI;
-    return cotiles * (cpad / 2) * (36 + 32) * 64;
+    return cotiles * (cpad / 2) * (36 + 32 + 36) * 64;        // even-row phase, odd-row phase, raw taps of the edge workgroups
 }
 
 // wino_frag: idv_pack_cconv_wino(transposed = 1) of the same weights; tw_frag: idv_cconv_tw_wfrag_floats floats
