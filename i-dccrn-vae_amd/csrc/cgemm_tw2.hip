@@ -14,11 +14,20 @@
 //     wave 3        = A0, A1, A3 on planes 7, 8 (12 MFMAs) + A2 on planes 6, 7, 8 (3)                     (15 per k-step)
 // Staging, LDS layout (raw rows, planes paired per column pair), weight ring and the epilogue exchange are cgemm_tw.hip's; the
 // frequency transform A + cb B happens at the operand read.  Weights: cgemm_wino's conv fragments re-ordered by idv_pack_cconv_tw2.
+//
+// Odd row counts with Fin = 2 Fout - 1 (every encoder layer of the model): the last output row has no partner, and rows Fin, Fin + 1
+// are padding, so  out[Fout - 1] = W0 x[Fin - 3] + W1 x[Fin - 2] + W2 x[Fin - 1].  It is not a row tile of its own: the launch holds
+// EDGE workgroups (cgemm_tw_map.hpp) that compute that row for TWO adjacent column blocks with the raw taps.  Raw slot 3 c + t of the
+// patch buffer holds row Fin - 3 + t of column block c; wave w works on column block w >> 1, an even wave on planes 0 .. 4 (15 MFMAs
+// per k-step), an odd wave on planes 5 .. 8 (12), the three taps of a plane into ONE accumulator (at most five per wave).  Staging,
+// barriers, weight ring and epilogue exchange are those of a full tile; the K loop is a further copy with other operand reads and a
+// second weight region (the raw taps, time-transformed).
 #include <atomic>
 #include <cstdint>
 #include <cstdlib>
 #include <type_traits>
 #include "cgemm.hpp"
+#include "cgemm_tw_map.hpp"
 #include "../../include/idccrn_hip.h"
 
 namespace {
@@ -28,7 +37,8 @@ struct Tw2Args {
     int Cin;
     int Fin, Fout;
     int J, Jp, Tp;
-    const float* wfrag;   // [cotiles][UP][4 waves][4 groups][64 lanes][4 slots] (idv_pack_cconv_tw2)
+    const float* wfrag;   // [cotiles][UP][4 waves][4 groups][64 lanes][4 slots], then the raw taps of the edge workgroups in the same
+                          // layout (idv_pack_cconv_tw2)
     int UP;               // channel pairs per co tile as packed
     const float* epi;     // as cgemm_gauss: [cotiles * 32][8]
     int has_fold;
@@ -38,9 +48,7 @@ struct Tw2Args {
     int tshift, t_valid;
     double* stats;
     int stats_rep;
-    int jtiles, ftiles;
-    int xcd_split;
-    int cgroups;          // cotiles / NCT: workgroups per (column block, row pair); the block order runs over these
+    TwGrid grid;          // block order (cgemm_tw_map.hpp); cgroups = cotiles / NCT workgroups per (column block, row pair)
     int stagger;          // NCT = 2: waves 4 .. 7 stage eight MFMA slots later than their SIMD partners, waves 0 .. 3
 };
 
@@ -73,6 +81,28 @@ __host__ __device__ inline void tw2_slot(int w, int k, int& q, int& plane) {
 __host__ __device__ inline int tw2_acc_tile(int w, int i) {
     if (w < 3) return i < 7 ? tw2_main_acc(w) * 9 + i : 2 * 9 + 2 * w + (i - 7);
     return i < 6 ? tw2_main_acc(i >> 1) * 9 + 7 + (i & 1) : 2 * 9 + 6 + (i - 6);
+}
+
+// edge workgroup, wave w (odd = w & 1): MFMA slot k (0 .. 15) -> raw tap t and plane, false: no product in the slot.  Even waves:
+// planes 0 .. 4, slot = tap * 5 + plane (slot 15 empty); odd waves: planes 5 .. 8, three products in each group of four slots.  The
+// accumulator of a slot is its plane less the wave's first; its three taps follow one another in k.
+__host__ __device__ inline bool tw2_eslot(bool odd, int k, int& t, int& plane) {
+    if (odd) {
+        const int m = (k >> 2) * 3 + (k & 3);
+        t = m >> 2;
+        plane = 5 + (m & 3);
+        return (k & 3) != 3;
+    }
+    t = k / 5;
+    plane = k % 5;
+    return k < 15;
+}
+// accumulator i (0 .. 8) of edge wave w -> tile of the epilogue exchange: column block c = w >> 1's sums at c * 9 + plane, the
+// accumulators without a product (zero) on the 18 tiles behind, so that every tile the epilogue reads is written
+__host__ __device__ inline int tw2_edge_tile(int w, int i) {
+    const int c = w >> 1;
+    if (w & 1) return i < 4 ? c * 9 + 5 + i : 18 + c * 9 + i;
+    return i < 5 ? c * 9 + i : 18 + c * 9 + (i - 5);
 }
 
 // offset of plane p inside a raw row of the patch buffer (planes (2 j, 2 j + 1) interleaved per column pair, plane 8 apart), lane part
@@ -109,23 +139,12 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw2_kernel(
     const int w4 = NCT == 1 ? wave : wave & 3, cth = NCT == 1 ? 0 : wave >> 2;
     const int half = lane >> 5, l31 = lane & 31;
 
-    const int bid = blockIdx.x;
-    const int xcd = bid & 7, slot = bid >> 3;
-    int jt, ft, ct;
-    if (a.xcd_split) {                            // co tile ct always on the XCDs = ct (mod cotiles): see cgemm_tw.hip
-        const int G = 8 / a.cgroups;
-        ct = xcd % a.cgroups;
-        jt = (slot / a.ftiles) * G + xcd / a.cgroups;
-        ft = slot - (slot / a.ftiles) * a.ftiles;
-    } else {
-        const int per = a.cgroups * a.ftiles;
-        jt = (slot / per) * 8 + xcd;
-        const int rem = slot - (slot / per) * per;
-        ft = rem / a.cgroups;
-        ct = rem - ft * a.cgroups;
-    }
-    if (jt >= a.jtiles) return;
-    ct = NCT * ct + cth;                          // (ct was the workgroup's group of NCT co tiles)
+    // block order: cgemm_tw_map.hpp.  An EDGE workgroup (block-uniform) computes the last output row of the column blocks jt, jt + 1
+    TwTile tile;
+    if (!tw_block_tile(a.grid, blockIdx.x, tile)) return;
+    const bool edge = tile.edge;
+    const int jt = tile.jt, ft = tile.ft;
+    const int ct = NCT * tile.ct + cth;           // (tile.ct is the workgroup's group of NCT co tiles)
     const int j0 = jt * 64;
     const int m0 = 2 * ft;                        // first OUTPUT row of the pair
     const int rbase = 2 * m0 - 2;                 // raw row r0
@@ -139,7 +158,9 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw2_kernel(
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[k][r] = 0.f;
 
-    // ---- staging (cgemm_tw.hip): item = channel cl, raw row, column pairs 2 c8, 2 c8 + 1
+    // ---- staging (cgemm_tw.hip): item = channel cl, raw row, column pairs 2 c8, 2 c8 + 1.  Edge workgroup: raw slot rl < 6 holds
+    // (column block jt + rl / 3, row Fin - 3 + rl % 3), slot 6 nothing; a second column block past J is masked like any column out of
+    // range
     f32x4 v_r[NLD], v_i[NLD];
     float e_r[NLD], e_i[NLD];
     unsigned off_v[NLD], ldsoff[NLD];
@@ -152,8 +173,8 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw2_kernel(
         const int c8 = e & 15;
         // (NCT = 2, no item: channel CIK is dead in every chunk, and its row 0 is the dump row behind the buffer)
         const int cl = e / (16 * NRAW), rl = (NCT == 2 && e >= NITEM) ? 0 : (e >> 4) % NRAW;
-        const int f = rbase + rl;
-        const int jc = j0 + 4 * c8;
+        const int f = edge ? (rl < 6 ? a.Fin - 3 + rl % 3 : -1) : rbase + rl;
+        const int jc = j0 + (edge && rl >= 3 ? 64 : 0) + 4 * c8;
         const int je = LEFT ? jc - 1 : jc + 4;
         const bool exists = e < NITEM;
         const bool okr = exists && f >= 0 && f < a.Fin;
@@ -238,7 +259,7 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw2_kernel(
     // ---- weights: 16 slots per k-step as four 16-byte loads ([group][64 lanes][4 slots]).  ONE set of registers: group g of the next
     // k-step is fetched right after the four MFMAs that use group g of this one (two sets do not fit beside 144 accumulator, 32
     // operand and 20 staging registers)
-    const float* wbase = a.wfrag + (((size_t)ct * a.UP) * 4 + w4) * 1024 + lane * 4;
+    const float* wbase = a.wfrag + (((size_t)(edge ? a.cotiles : 0) + ct) * a.UP * 4 + w4) * 1024 + lane * 4;
     const int total_ks = nchunk * KS;
     float a_w[NSLOT];
     auto load_wg = [&](int g, int grp) {
@@ -283,24 +304,44 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw2_kernel(
             ob[s4] = base[tw2_rb(q) * 288 + tw2_poff(plane, l31)];
         }
     };
+    // Edge workgroup: the products of tw2_eslot, one 4-byte read each from raw slot 3 c + tap of the wave's column block c
+    const int eoff = (w4 >> 1) * 3 * 288;
+    auto load_grp_e = [&](auto odd_, const float* base, int g, float (&oa)[4]) {
+#pragma unroll
+        for (int s4 = 0; s4 < 4; ++s4) {
+            int t, plane;
+            if (!tw2_eslot(decltype(odd_)::value, 4 * g + s4, t, plane)) continue;
+            oa[s4] = base[eoff + t * 288 + tw2_poff(plane, l31)];
+        }
+    };
 
+    // chunk 0 into the first buffer, chunk 1 on its way, the first k-step's weights.  Every copy of the loop below begins with its own
+    // copy of this: what a loop overwrites (staging registers, weights, operands) would otherwise have to survive, in the state this
+    // prologue left, through every copy placed before the one that runs -- the register allocator sees the copies in a row -- and
+    // with the edge copies that was 72 - 156 bytes of scratch per lane for NCT = 1; like this no instantiation spills
+    auto prologue = [&]() {
 #pragma unroll
-    for (int i = 0; i < NLD; ++i) stage_load(0, i);
+        for (int i = 0; i < NLD; ++i) stage_load(0, i);
 #pragma unroll
-    for (int grp = 0; grp < 4; ++grp) load_wg(0, grp);
+        for (int grp = 0; grp < 4; ++grp) load_wg(0, grp);
 #pragma unroll
-    for (int i = 0; i < NLD; ++i) stage_store(smem, 0, i);
+        for (int i = 0; i < NLD; ++i) stage_store(smem, 0, i);
 #pragma unroll
-    for (int i = 0; i < NLD; ++i) stage_load(nchunk > 1 ? 1 : 0, i);
-    __syncthreads();
-    if (w4 < 3)
-        load_grp_a(smem + (size_t)half * RT, 0, xa[0], xb[0]);
-    else
-        load_grp_b(smem + (size_t)half * RT, 0, xa[0], xb[0]);
+        for (int i = 0; i < NLD; ++i) stage_load(nchunk > 1 ? 1 : 0, i);
+        __syncthreads();
+    };
 
-    // the main loop, once per wave role (the branch is outside the loop: two straight-line loops, each with the workgroup's barriers)
+    // the main loop, once per wave role (the branch is outside the loop: straight-line loops, each with the workgroup's barriers).
+    // Roles 0, 1: waves 0 .. 2 and wave 3 of a full tile; 2, 3: even and odd waves of an edge workgroup (all 16 slots are walked, for
+    // the weight ring and the staging that ride on them; a slot without a product issues no MFMA)
     auto run = [&](auto role, auto late_) {
-        constexpr bool ROLE_B = decltype(role)::value;
+        constexpr int ROLE = decltype(role)::value;
+        constexpr bool ROLE_B = ROLE == 1, EDGE = ROLE >= 2;
+        using EdgeOdd = std::integral_constant<bool, ROLE == 3>;
+        prologue();
+        if constexpr (EDGE) load_grp_e(EdgeOdd{}, smem + (size_t)half * RT, 0, xa[0]);
+        else if (ROLE_B) load_grp_b(smem + (size_t)half * RT, 0, xa[0], xb[0]);
+        else load_grp_a(smem + (size_t)half * RT, 0, xa[0], xb[0]);
         for (int chunk = 0; chunk < nchunk; ++chunk) {
             const float* P = smem + (chunk & 1) * NEB;
             float* Pn = smem + ((chunk + 1) & 1) * NEB;
@@ -314,7 +355,13 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw2_kernel(
                     const int g = k >> 2, s4 = k & 3;
                     float cb;
                     int ai;
-                    if (ROLE_B) {
+                    bool product = true;
+                    if (EDGE) {
+                        int t, plane;
+                        product = tw2_eslot(EdgeOdd::value, k, t, plane);
+                        cb = 0.f;
+                        ai = plane - (EdgeOdd::value ? 5 : 0);
+                    } else if (ROLE_B) {
                         int q, plane;
                         tw2_slot(3, k, q, plane);
                         cb = tw2_cb(q);
@@ -327,19 +374,25 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw2_kernel(
                         // the next group's operands (of this k-step, or group 0 of the next one: after the barrier in the last k-step)
                         const float* src = g < 3 ? P + (size_t)(2 * ul + half) * RT : bnext;
                         if (!(ul == KS - 1 && g == 3)) {
-                            if (ROLE_B) load_grp_b(src, (g + 1) & 3, xa[(g + 1) & 1], xb[(g + 1) & 1]);
+                            if constexpr (EDGE) load_grp_e(EdgeOdd{}, src, (g + 1) & 3, xa[(g + 1) & 1]);
+                            else if (ROLE_B) load_grp_b(src, (g + 1) & 3, xa[(g + 1) & 1], xb[(g + 1) & 1]);
                             else load_grp_a(src, (g + 1) & 3, xa[(g + 1) & 1], xb[(g + 1) & 1]);
                         }
                     }
-                    const float b = xa[g & 1][s4] + cb * xb[g & 1][s4];
-                    acc[ai] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_w[k], b, acc[ai], 0, 0, 0);
+                    if constexpr (EDGE) {
+                        if (product) acc[ai] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_w[k], xa[g & 1][s4], acc[ai], 0, 0, 0);
+                    } else {
+                        const float b = xa[g & 1][s4] + cb * xb[g & 1][s4];
+                        acc[ai] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_w[k], b, acc[ai], 0, 0, 0);
+                    }
                     if (ul == KS - 1 && k == 0) {
                         __builtin_amdgcn_sched_barrier(0);
                         __syncthreads();
                     }
                     if (ul == KS - 1 && k == 12) {
                         // (last k-step: group 0 of the next chunk comes from the other buffer, complete since the barrier above)
-                        if (ROLE_B) load_grp_b(bnext, 0, xa[0], xb[0]);
+                        if constexpr (EDGE) load_grp_e(EdgeOdd{}, bnext, 0, xa[0]);
+                        else if (ROLE_B) load_grp_b(bnext, 0, xa[0], xb[0]);
                         else load_grp_a(bnext, 0, xa[0], xb[0]);
                     }
                     // weights of the next k-step, group by group
@@ -376,36 +429,59 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw2_kernel(
     };
     // (NCT = 2 with a.stagger: waves 4 .. 7 run the copies of the loops that stage eight slots later -- a copy, because a branch on the
     // wave inside the loop costs the register allocator 80 - 90 bytes of scratch per lane)
-    if (NCT == 2 && a.stagger && cth) {
-        if (w4 < 3)
-            run(std::false_type{}, std::integral_constant<bool, NCT == 2>{});
+    using Late = std::integral_constant<bool, NCT == 2>;
+    const bool late = NCT == 2 && a.stagger && cth;
+    if (edge) {
+        if (late) {
+            if (w4 & 1)
+                run(std::integral_constant<int, 3>{}, Late{});
+            else
+                run(std::integral_constant<int, 2>{}, Late{});
+        } else if (w4 & 1)
+            run(std::integral_constant<int, 3>{}, std::false_type{});
         else
-            run(std::true_type{}, std::integral_constant<bool, NCT == 2>{});
+            run(std::integral_constant<int, 2>{}, std::false_type{});
+    } else if (late) {
+        if (w4 < 3)
+            run(std::integral_constant<int, 0>{}, Late{});
+        else
+            run(std::integral_constant<int, 1>{}, Late{});
     } else if (w4 < 3)
-        run(std::false_type{}, std::false_type{});
+        run(std::integral_constant<int, 0>{}, std::false_type{});
     else
-        run(std::true_type{}, std::false_type{});
+        run(std::integral_constant<int, 1>{}, std::false_type{});
     __syncthreads();                                          // all patch reads done: the buffers become the exchange area
 
     // ------------------------------------------------------------------ epilogue (cgemm_tw.hip's, 36 tiles)
     const float slope = a.slope ? *a.slope : 1.0f;
     const bool has_act = a.slope != nullptr;
     float* E = smem + cth * (NT * 4 * 64);                    // one exchange area per co tile
-    const int jA = j0 + 2 * l31;
-    bool keep[2], inb[2];
+    // the pair's two output columns jA, jA + 1 of the thread's two outputs rt: the two rows of a full tile, or (edge workgroup) the
+    // one row of the column blocks jt, jt + 1
+    const int jAc[2] = {j0 + 2 * l31, j0 + 2 * l31 + (edge ? 64 : 0)};
+    bool keep[2][2], inb[2][2];
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
-        const int j = jA + q;
+        const int j = jAc[0] + q;
         const int tp = j % a.Tp;
-        inb[q] = j < a.J;
-        keep[q] = inb[q] && tp >= 1 && tp <= a.t_valid;
+        inb[0][q] = inb[1][q] = j < a.J;
+        keep[0][q] = keep[1][q] = inb[0][q] && tp >= 1 && tp <= a.t_valid;
+    }
+    if (edge) {
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int j = jAc[1] + q;
+            const int tp = j % a.Tp;
+            inb[1][q] = j < a.J;
+            keep[1][q] = inb[1][q] && tp >= 1 && tp <= a.t_valid;
+        }
     }
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
         if (s > 0) __syncthreads();
 #pragma unroll
         for (int k = 0; k < NACC; ++k) {
-            const int t = tw2_acc_tile(w4, k);
+            const int t = edge ? tw2_edge_tile(w4, k) : tw2_acc_tile(w4, k);
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) E[(t * 4 + rr) * 64 + lane] = acc[k][4 * s + rr];
         }
@@ -437,13 +513,18 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw2_kernel(
         float st[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int rt = 0; rt < 2; ++rt) {
-            const int fo = m0 + rt;
+            const int fo = edge ? a.Fout - 1 : m0 + rt;
+            const int jA = jAc[rt];
             if (fo >= a.Fout) continue;
             float yr[2], yi[2];
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
-                const float re = rt == 0 ? pr[0][q] + pr[1][q] + pr[2][q] : pr[1][q] - pr[2][q] - pr[3][q];
-                const float im = rt == 0 ? pi[0][q] + pi[1][q] + pi[2][q] : pi[1][q] - pi[2][q] - pi[3][q];
+                float re = rt == 0 ? pr[0][q] + pr[1][q] + pr[2][q] : pr[1][q] - pr[2][q] - pr[3][q];
+                float im = rt == 0 ? pi[0][q] + pi[1][q] + pi[2][q] : pi[1][q] - pi[2][q] - pi[3][q];
+                if (edge) {                                   // the taps are summed in the accumulators of column block rt
+                    re = pr[rt][q];
+                    im = pi[rt][q];
+                }
                 float r_, i_;
                 if (a.has_fold) {
                     r_ = e0[0] * re + e0[1] * im + e4;
@@ -456,9 +537,9 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw2_kernel(
                     r_ = r_ >= 0.f ? r_ : slope * r_;
                     i_ = i_ >= 0.f ? i_ : slope * i_;
                 }
-                yr[q] = keep[q] ? r_ : 0.f;
-                yi[q] = keep[q] ? i_ : 0.f;
-                if (STATS && keep[q]) {
+                yr[q] = keep[rt][q] ? r_ : 0.f;
+                yi[q] = keep[rt][q] ? i_ : 0.f;
+                if (STATS && keep[rt][q]) {
                     st[0] += yr[q];
                     st[1] += yi[q];
                     st[2] += yr[q] * yr[q];
@@ -469,10 +550,10 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw2_kernel(
             if (cok) {
                 float* o_r = a.out + ((size_t)co * a.Fout + fo) * a.Jp + jA;
                 float* o_i = a.out + ((size_t)(a.Cout + co) * a.Fout + fo) * a.Jp + jA;
-                if (inb[1]) {
+                if (inb[rt][1]) {
                     *(float2*)o_r = make_float2(yr[0], yr[1]);
                     *(float2*)o_i = make_float2(yi[0], yi[1]);
-                } else if (inb[0]) {
+                } else if (inb[rt][0]) {
                     o_r[0] = yr[0];
                     o_i[0] = yi[0];
                 }
@@ -492,21 +573,34 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw2_kernel(
 }
 
 // cgemm_wino's conv fragments [ct][unit = ci * 3 + g][8 slots q][lane = h * 32 + co] -> [ct][pair u][wave][group][lane = parity * 32 +
-// co][4 slots] with the time-transformed taps (tau 0: W_h0, tau 1: W_h0 + W_h1, tau 2: W_h1) of the slot's (product, plane)
+// co][4 slots] with the time-transformed taps (tau 0: W_h0, tau 1: W_h0 + W_h1, tau 2: W_h1) of the slot's (product, plane).  A second
+// region in the same layout holds the RAW frequency taps of the edge workgroups (tw2_eslot): tap 0 = W0 (slot q = 0), tap 1 = W1 (slot
+// q = 4), tap 2 = W2 = slot 1 minus slot 2 ((W0 + W2 + W4) / 2 - (W0 - W2 + W4) / 2).
 __global__ void pack_cconv_tw2_kernel(const float* __restrict__ wino, int cotiles, int UN, int UP, float* __restrict__ out) {
     const long long n = (long long)cotiles * UP * 4096;
-    for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < n; idx += (long long)gridDim.x * blockDim.x) {
-        const int kk = (int)(idx & 3), ln = (int)((idx >> 2) & 63), grp = (int)((idx >> 8) & 3), w = (int)((idx >> 10) & 3);
-        const long long t_ = idx >> 12;
+    for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < 2 * n; idx += (long long)gridDim.x * blockDim.x) {
+        const bool raw = idx >= n;
+        const long long i = raw ? idx - n : idx;
+        const int kk = (int)(i & 3), ln = (int)((i >> 2) & 63), grp = (int)((i >> 8) & 3), w = (int)((i >> 10) & 3);
+        const long long t_ = i >> 12;
         const int u = (int)(t_ % UP), ct = (int)(t_ / UP);
         int q, plane;
-        tw2_slot(w, grp * 4 + kk, q, plane);
+        if (raw) {
+            int t;
+            q = tw2_eslot(w & 1, grp * 4 + kk, t, plane) ? (t == 0 ? 0 : (t == 1 ? 4 : 1)) : -1;
+        } else {
+            tw2_slot(w, grp * 4 + kk, q, plane);
+        }
         float val = 0.f;
         const int ci = 2 * u + (ln >> 5), co = ln & 31;
         if (q >= 0 && ci * 3 < UN) {
             const int g = plane / 3, tau = plane % 3;
             const float* src = wino + ((((size_t)ct * UN + (size_t)ci * 3 + g) * 8 + q)) * 64;
-            const float w0 = src[co], w1 = src[32 + co];
+            float w0 = src[co], w1 = src[32 + co];
+            if (raw && q == 1) {
+                w0 -= src[64 + co];
+                w1 -= src[64 + 32 + co];
+            }
             val = tau == 0 ? w0 : (tau == 1 ? w0 + w1 : w1);
         }
         out[idx] = val;
@@ -518,17 +612,10 @@ int launch_tw2(const Tw2Args& a, hipStream_t st) {
     constexpr size_t smem = tw2_smem_floats(NCT) * sizeof(float);
     static_assert(smem * (NCT == 1 ? 2 : 1) <= 160 * 1024, "the patch buffers of two workgroups (NCT = 2: of one) must fit the 160 KB of LDS");
     Tw2Args b = a;
-    b.jtiles = (a.J + 63) / 64;
-    b.ftiles = (a.Fout + 1) / 2;
-    b.cgroups = b.cotiles / NCT;                              // (NCT = 2: the caller checked that the co-tile count is even)
-    if (b.cgroups * NCT != b.cotiles) return IDV_EINVAL;
+    if (b.cotiles % NCT) return IDV_EINVAL;                   // (NCT = 2: the caller checked that the co-tile count is even)
+    b.grid = tw2_grid(a.Fin, a.Fout, a.J, b.cotiles / NCT, TW2_XCD_SPLIT);
     b.stagger = TW2_PAIR_STAGGER;
-    b.xcd_split = (TW2_XCD_SPLIT && (b.cgroups == 2 || b.cgroups == 4 || b.cgroups == 8)) ? 1 : 0;
-    long long nblk = (long long)((b.jtiles + 7) / 8) * 8 * b.ftiles * b.cgroups;
-    if (b.xcd_split) {
-        const int G = 8 / b.cgroups;
-        nblk = (long long)((b.jtiles + G - 1) / G) * b.ftiles * 8;
-    }
+    const long long nblk = tw_grid_blocks(b.grid);
     if (nblk > 0x7fffffffLL) return IDV_EINVAL;
     auto k = cconv_tw2_kernel<LEFT, STATS, NCT>;
     // (once per instantiation and device: setting it on every launch is host time, a lot of it under a profiler.  Two threads that
@@ -559,7 +646,7 @@ extern "C" int idv_cconv_tw2_supported(int Cin, int Cout, int Fin) {
 
 extern "C" long long idv_cconv_tw2_wfrag_floats(int Cout, int cin_used) {
     const long long cotiles = (Cout + 31) / 32, cpad = (cin_used + TW2_PACK_CI - 1) / TW2_PACK_CI * TW2_PACK_CI;
-    return cotiles * (cpad / 2) * 4096;
+    return cotiles * (cpad / 2) * 2 * 4096;                   // the Winograd products, the raw taps of the edge workgroups
 }
 
 // wino_frag: idv_pack_cconv_wino(transposed = 0) of the same weights; tw_frag: idv_cconv_tw2_wfrag_floats floats

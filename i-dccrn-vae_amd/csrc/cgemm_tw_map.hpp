@@ -7,6 +7,10 @@
 // (2 e, 2 e + 1) and co-tile group, one EDGE workgroup for that row.  Edge workgroups last as long as full ones, so they come FIRST
 // in the grid, never in its last round.  Both regions are whole rounds of eight blocks: block ids equal mod 8 share an XCD, and with
 // xcd_split the co-tile group ct stays on the XCDs = ct (mod cgroups) in either region.
+//
+// The conv form (cgemm_tw2.hip) has the same geometry over OUTPUT rows: a full row tile is a pair of output rows, and with an odd
+// number of output rows whose last row has three real taps (Fin = 2 Fout - 1) that row, out[Fout - 1], goes to edge workgroups
+// (tw2_grid).
 #pragma once
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
@@ -34,6 +38,19 @@ TW_HD inline TwGrid tw_grid(int ph, int Fin, int J, int cgroups, int want_split)
     g.jtiles = (J + 63) / 64;
     g.ftiles = Fin / 2;
     g.etiles = (ph == 0 && (Fin & 1)) ? (g.jtiles + 1) / 2 : 0;
+    g.cgroups = cgroups;
+    g.xcd_split = (want_split && (cgroups == 2 || cgroups == 4 || cgroups == 8)) ? 1 : 0;
+    return g;
+}
+
+// the conv form: Fout / 2 full row tiles and edge workgroups where Fout is odd and Fin = 2 Fout - 1.  An odd Fout with an even Fin
+// keeps its half tile (ftiles = (Fout + 1) / 2): its last row has four real taps, more than an edge workgroup holds for two blocks.
+TW_HD inline TwGrid tw2_grid(int Fin, int Fout, int J, int cgroups, int want_split) {
+    TwGrid g;
+    const bool edge = (Fout & 1) && Fin == 2 * Fout - 1;
+    g.jtiles = (J + 63) / 64;
+    g.ftiles = edge ? Fout / 2 : (Fout + 1) / 2;
+    g.etiles = edge ? (g.jtiles + 1) / 2 : 0;
     g.cgroups = cgroups;
     g.xcd_split = (want_split && (cgroups == 2 || cgroups == 4 || cgroups == 8)) ? 1 : 0;
     return g;
