@@ -733,6 +733,9 @@ extern "C" int idv_cconv2d_bwd_weight(const float* x, int Cx, int ci_off, const 
     if ((tshift != 0 && tshift != -1) || (Jp_x % 4) || (Jp_dy % 4) || !aligned16(x) || !aligned16(dy) || Jp_x < B * Tp ||
         Jp_dy < B * Tp)
         return IDV_EINVAL;
+    // the documented size, not only what this Fin happens to need: the sizer cannot see Fin and bounds every row count, and a
+    // caller that passes less has sized for some other layer
+    if (idv_cconv_wgrad_work_floats(transposed ? Cx : Cout, transposed ? Cout : Cx, B, Tp) > work_floats) return IDV_EINVAL;
     const int Fout = transposed ? 2 * Fin - 1 : (Fin - 1) / 2 + 1;
     WgradArgs a{};
     if (!transposed) {      // S = dy [2Cout][Fout], L = x [2Cx][Fin]
@@ -893,6 +896,7 @@ extern "C" int idv_pw_bwd_weight(const float* dout, int M, int Jp_d, const float
     if (!dout || !x || !work || !dw || M <= 0 || K <= 0 || J <= 0 || ldw < K || (shift != 0 && shift != -1)) return IDV_EINVAL;
     if ((Jp_d % 4) || (Jp_x % 4) || !aligned16(dout) || !aligned16(x) || Jp_d < J || Jp_x < J) return IDV_EINVAL;
     if (rowmap == 1 && (H <= 0 || (H % 16) || M % (4 * H))) return IDV_EINVAL;
+    if (idv_pw_wgrad_work_floats(M, K, J) > work_floats) return IDV_EINVAL;      // the documented size (it also covers the bf16x3 entry)
     WgradArgs a{};
     a.S = dout; a.Sp = M; a.Fs = 1; a.JpS = Jp_d;
     a.L = x;    a.Lp = K; a.Fl = 1; a.JpL = Jp_x;

@@ -362,6 +362,8 @@ extern "C" int idv_cconv2d_bwd_weight_bf16x3(const float* x, int Cx, int ci_off,
     if ((tshift != 0 && tshift != -1) || (Jp_x % 4) || (Jp_dy % 4) || !aligned16(x) || !aligned16(dy) || Jp_x < B * Tp ||
         Jp_dy < B * Tp)
         return IDV_EINVAL;
+    // the documented size: it covers this kernel's plan and the exact-fp32 fallback
+    if (idv_cconv_wgrad_bf16_work_floats(transposed ? Cx : Cout, transposed ? Cout : Cx, B, Tp) > work_floats) return IDV_EINVAL;
     const int Fout = transposed ? 2 * Fin - 1 : (Fin - 1) / 2 + 1;
     WgradArgs a{};
     if (!transposed) {      // S = dy [2Cout][Fout], L = x [2Cx][Fin]
@@ -400,6 +402,7 @@ extern "C" int idv_pw_bwd_weight_bf16x3(const float* dout, int M, int Jp_d, cons
     if (!dout || !x || !work || !dw || M <= 0 || K <= 0 || J <= 0 || ldw < K || (shift != 0 && shift != -1)) return IDV_EINVAL;
     if ((Jp_d % 4) || (Jp_x % 4) || !aligned16(dout) || !aligned16(x) || Jp_d < J || Jp_x < J) return IDV_EINVAL;
     if (rowmap == 1 && (H <= 0 || (H % 16) || M % (4 * H))) return IDV_EINVAL;
+    if (idv_pw_wgrad_work_floats(M, K, J) > work_floats) return IDV_EINVAL;      // the documented size
     if ((size_t)M * Jp_d * 4 >= 0xfffffe00ull || (size_t)K * Jp_x * 4 >= 0xfffffe00ull)
         return idv_pw_bwd_weight(dout, M, Jp_d, x, K, Jp_x, J, shift, work, work_floats, dw, ldw, rowmap, H, accumulate, stream);
     WgradArgs a{};

@@ -424,7 +424,8 @@ int idv_pack_cconv_bf16_adjoint(const float* w_re, const float* w_im, int Cout, 
  * idv_cbn_bwd_apply in a train-mode block).  Writes dw_re / dw_im entries [*, ci_off:ci_off+Cx] (conv [Cout][Cin_total][5][2])
  * or [ci_off:ci_off+Cx, *] (transposed [Cin_total][Cout][5][2]).  Split-K over the B*Tp columns with deterministic
  * two-stage summation; work: idv_cconv_wgrad_work_floats(Cs, Cl, B, Tp) floats with (Cs, Cl) = (Cout, Cx) for a conv and
- * (Cx, Cout) for a transposed conv.  tshift as in idv_cconv2d_fwd. */
+ * (Cx, Cout) for a transposed conv.  tshift as in idv_cconv2d_fwd.  Every weight-gradient entry below returns IDV_EINVAL,
+ * and launches nothing, when work_floats is less than its sizer returns for the same arguments. */
 long long idv_cconv_wgrad_work_floats(int Cs, int Cl, int B, int Tp);
 int idv_cconv2d_bwd_weight(const float* x, int Cx, int ci_off, const float* dy, int Cout, int Cin_total, int transposed,
                            int tshift, int Fin, int B, int Tp, int Jp_x, int Jp_dy, float* work, long long work_floats,
