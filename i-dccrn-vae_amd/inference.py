@@ -9,8 +9,11 @@
     latents, then one of the ``outtype`` estimators -- ``clean_direct`` (mean of the sampled speech waveforms),
     ``real_imag_mask`` (:85-101), ``complex_mask`` (:104-116), ``phase_mask`` (:119-135) -- as one HIP kernel
     (``idv_outtype_estimate``) + the ISTFT (``torch.istft`` with the analysis window, :288 etc.);
-  * ``compute_sisdr`` (utils/eval_metrics.py:49-64) on the device.  PESQ / ESTOI / DNSMOS are third-party CPU metrics and
-    stay out of scope.
+  * the metrics of ``EvalMetrics.eval`` (utils/eval_metrics.py:67-122) that are closed-form signal pipelines, on the device:
+    ``compute_sisdr`` (:49-64), ``compute_rmse`` (:33-41) and ``compute_stoi`` / ``compute_estoi`` (the ``pystoi`` call of :92-95
+    and :119; csrc/stoi.hip, DESIGN 3.8 -- the package's definition restated, parity with the package itself pinned only where it
+    is installed); :func:`score_list` scores a list of recordings of any lengths in padded batches.  PESQ (an ITU program) and
+    DNSMOS (an ONNX model) are third-party CPU metrics and stay out of scope.
 
 Utterances of different lengths (causal models, the ones every shipped recipe builds): every entry point takes ``lengths``
 (a python sequence or a CPU integer tensor, one sample count per row of the zero- or anything-padded ``[B, Lmax]`` batch).  Row
@@ -157,6 +160,131 @@ def compute_sisdr(x_est: torch.Tensor, x_ref: torch.Tensor, lengths=None) -> tor
     out = torch.empty(B, dtype=torch.float32, device=e.device)
     call("idv_sisdr", p(r), i(r.stride(0)), p(e), i(e.stride(0)), i(B), i(L), p(work), p(out), stream_ptr())
     return out[0] if single else out
+
+
+def _score_args(x_est, x_ref, lengths):
+    """The guards the per-utterance metrics share (all on the host, before any GPU work) -> (est rows, ref rows, Lengths or None,
+    samples per row, single).  The value guards come first and the device check last, so each can be met with CPU tensors."""
+    if not isinstance(x_est, torch.Tensor) or not isinstance(x_ref, torch.Tensor):
+        raise ValueError("x_est and x_ref must be tensors")
+    single = x_est.dim() == 1
+    e = x_est.reshape(1, -1) if single else x_est
+    r = x_ref.reshape(1, -1) if single else x_ref
+    if e.dim() != 2 or r.dim() != 2:
+        raise ValueError(f"estimate {tuple(x_est.shape)} / reference {tuple(x_ref.shape)}: [L] or [B, L] expected")
+    if e.shape[0] != r.shape[0]:
+        raise ValueError(f"estimate {tuple(e.shape)} and reference {tuple(r.shape)} differ in batch size")
+    if lengths is None:
+        if e.shape != r.shape:
+            raise ValueError(f"estimate {tuple(e.shape)} and reference {tuple(r.shape)} differ")
+        if e.shape[1] < 1:
+            raise ValueError("empty signals")
+        host, n = None, e.shape[1]
+    else:
+        host = ops.check_lengths(lengths, e.shape[0], min(e.shape[1], r.shape[1]), None)
+        n = max(host)
+    ops.check_dev_f32(x_est, "x_est")
+    ops.check_dev_f32(x_ref, "x_ref", x_est.device)
+    lens = None if host is None else ops.Lengths(host, e.device)
+    return e.float().contiguous(), r.float().contiguous(), lens, n, single
+
+
+def compute_stoi(x_est: torch.Tensor, x_ref: torch.Tensor, fs: int = 16000, extended: bool = False, lengths=None, counts: bool = False):
+    """STOI (Taal et al. 2011) or, with ``extended``, ESTOI (Jensen & Taal 2016) per utterance on the device: inputs [L] or [B, L] on
+    the GPU -> float32 tensor [B] (or a scalar).  The definition is the ``pystoi`` package's (10 kHz, 256-sample frames at hop 128,
+    40 dB silent-frame removal on the reference, 15 third-octave bands, 30-frame segments; exactly 1e-5 when fewer than 30 frames
+    remain); parity with the package itself is pinned only where it is installed.
+
+    The argument order is :func:`compute_sisdr`'s and ``EvalMetrics.eval``'s, ESTIMATE FIRST; the package's own call is
+    ``stoi(clean, processed, fs, extended)``.  ``fs``: 16000 (resampled on the device) or 10000.  ``lengths``: row b is scored
+    over its first lengths[b] samples only; nothing behind them is read and a row's value does not depend on the rest of the batch.
+    ``counts=True`` also returns the int32 tensor [B, 3] (or [3]) of (frames, frames kept, segments)."""
+    if isinstance(fs, bool) or fs not in (10000, 16000):
+        raise ValueError(f"fs = {fs!r}: STOI is defined here for 10000 and 16000 Hz input")
+    e, r, lens, n, single = _score_args(x_est, x_ref, lengths)
+    B = e.shape[0]
+    nbytes = int(ops._ll_fn("idv_stoi_work_bytes")(i(B), i(n), i(fs)))
+    if nbytes < 0:
+        raise ValueError(f"compute_stoi: a batch of {B} rows of {n} samples is not supported")
+    work = torch.empty(nbytes, dtype=torch.uint8, device=e.device)
+    out = torch.empty(B, dtype=torch.float32, device=e.device)
+    cnt = torch.empty(B, 3, dtype=torch.int32, device=e.device)
+    call("idv_stoi", p(r), ll(r.stride(0)), p(e), ll(e.stride(0)), p(None if lens is None else lens.dev), i(B), i(n), i(fs),
+         i(1 if extended else 0), p(work), ll(nbytes), p(out), p(cnt), stream_ptr())
+    if single:
+        out, cnt = out[0], cnt[0]
+    return (out, cnt) if counts else out
+
+
+def compute_estoi(x_est: torch.Tensor, x_ref: torch.Tensor, fs: int = 16000, lengths=None, counts: bool = False):
+    """:func:`compute_stoi` with ``extended=True`` (what ``EvalMetrics.eval(..., metric='all')`` reports)."""
+    return compute_stoi(x_est, x_ref, fs=fs, extended=True, lengths=lengths, counts=counts)
+
+
+def compute_rmse(x_est: torch.Tensor, x_ref: torch.Tensor, lengths=None) -> torch.Tensor:
+    """The scaled RMSE of utils/eval_metrics.py:33-41 per utterance on the device: alpha = <est, ref> / <est, est>,
+    sqrt(mean((alpha est - ref)^2)); inputs and ``lengths`` as :func:`compute_sisdr`."""
+    e, r, lens, n, single = _score_args(x_est, x_ref, lengths)
+    B = e.shape[0]
+    if lens is None:
+        lens = ops.Lengths([n] * B, e.device)
+    work = torch.empty(3 * B, dtype=torch.float64, device=e.device)
+    out = torch.empty(B, dtype=torch.float32, device=e.device)
+    call("idv_rmse_ragged", p(r), ll(r.stride(0)), p(e), ll(e.stride(0)), p(lens.dev), i(B), p(work), p(out), stream_ptr())
+    return out[0] if single else out
+
+
+# metric name of score_list -> f(padded estimates, padded references, fs, lengths)
+METRICS = {"sisdr": lambda e, r, fs, lengths: compute_sisdr(e, r, lengths=lengths),
+           "rmse": lambda e, r, fs, lengths: compute_rmse(e, r, lengths=lengths),
+           "stoi": lambda e, r, fs, lengths: compute_stoi(e, r, fs=fs, lengths=lengths),
+           "estoi": lambda e, r, fs, lengths: compute_estoi(e, r, fs=fs, lengths=lengths)}
+
+
+def score_list(estimates: Sequence[torch.Tensor], references: Sequence[torch.Tensor], metrics: Sequence[str] = ("sisdr", "estoi"),
+               fs: int = 16000, max_batch: int = 64) -> dict:
+    """Score a folder of recordings at batch throughput.  ``estimates`` / ``references``: lists of 1-D float32 GPU tensors of any
+    lengths; pair k is scored over the first ``min(len(estimates[k]), len(references[k]))`` samples of both, as ``EvalMetrics.eval``
+    aligns them.  ``metrics``: names out of "sisdr", "rmse", "stoi", "estoi".  The pairs are sorted by length, padded into batches
+    of at most ``max_batch`` and scored with ``lengths=``; every value equals the per-utterance call's.  Returns
+    ``{metric: CPU float32 tensor [N]}`` in the caller's order, with one copy to the host per metric at the end."""
+    metrics = list(metrics)
+    for m in metrics:
+        if m not in METRICS:
+            raise ValueError(f"metric {m!r}: expected one of {sorted(METRICS)}")
+    if isinstance(fs, bool) or fs not in (10000, 16000):
+        raise ValueError(f"fs = {fs!r}: STOI is defined here for 10000 and 16000 Hz input")
+    if len(estimates) != len(references):
+        raise ValueError(f"{len(estimates)} estimates for {len(references)} references")
+    if isinstance(max_batch, bool) or not isinstance(max_batch, int) or max_batch < 1:
+        raise ValueError("score_list: max_batch must be a positive integer")
+    for name, seq in (("estimates", estimates), ("references", references)):
+        for k, sgn in enumerate(seq):
+            if not isinstance(sgn, torch.Tensor) or sgn.dim() != 1 or sgn.shape[0] < 1:
+                raise ValueError(f"{name}[{k}] must be a non-empty 1-D tensor")
+            ops.check_dev_f32(sgn, f"{name}[{k}]")
+    N = len(estimates)
+    lens = [min(int(a.shape[0]), int(b.shape[0])) for a, b in zip(estimates, references)]
+    order = sorted(range(N), key=lambda k: (-lens[k], k))
+    parts = {m: [] for m in metrics}
+    for b0 in range(0, N, max_batch):
+        batch = order[b0:b0 + max_batch]
+        blens = [lens[k] for k in batch]
+        dev = estimates[batch[0]].device
+        pe = torch.zeros(len(batch), blens[0], dtype=torch.float32, device=dev)
+        pr = torch.zeros(len(batch), blens[0], dtype=torch.float32, device=dev)
+        for row, k in enumerate(batch):
+            pe[row, :lens[k]] = estimates[k][:lens[k]]
+            pr[row, :lens[k]] = references[k][:lens[k]]
+        for m in metrics:
+            parts[m].append(METRICS[m](pe, pr, fs, blens))
+    inv = torch.empty(N, dtype=torch.long)
+    inv[torch.tensor(order, dtype=torch.long)] = torch.arange(N)
+    out = {}
+    for m in metrics:
+        vals = torch.cat(parts[m]).cpu() if parts[m] else torch.empty(0, dtype=torch.float32)
+        out[m] = vals[inv]
+    return out
 
 
 def plan_ragged_batches(lengths: Sequence[int], hop: int, max_batch: int = 64, max_columns: int = 64 * 642,

@@ -835,6 +835,24 @@ int idv_istft_ola_ragged(const float* frames, const int* lens, int len_div, int 
 int idv_sisdr_ragged(const float* ref, int ref_ld, const float* est, int est_ld, const int* lens, int B, double* work, float* out,
                      void* stream);
 
+/* ---- STOI / ESTOI and RMSE scoring of a padded batch (stoi.hip; inference.compute_stoi / compute_estoi / compute_rmse / score_list;
+ * additive entries: IDV_ABI_VERSION is unchanged).  idv_stoi: the short-time objective intelligibility of Taal et al. 2011
+ * (extended = 0) or its extended form of Jensen & Taal 2016 (extended = 1) with the constants and the framing of the pystoi package,
+ * resampling of fs = 16000 input to 10 kHz (fs = 10000 skips it; nothing else is accepted), removal of the frames
+ * more than 40 dB under the clean signal's loudest, 512-point DFT, 15 third-octave bands, 30-frame segments.  ref: the clean
+ * signals, est: the processed ones, rows at pitch ref_ld / est_ld >= Lmax; lens: device int32[B], samples per row (clamped to
+ * Lmax), or NULL: every row has Lmax (<= 2^27) samples.  Nothing at or past lens[b] is read and row b's result does not depend on
+ * B, on the other rows or on the padding.  out[b]: the score, exactly 1e-5 when fewer than 30 frames remain; counts (may be
+ * NULL): [B][3] = (frames, kept frames, segments).  work: idv_stoi_work_bytes(B, Lmax, fs) bytes (-1 for arguments idv_stoi
+ * refuses), 16-byte aligned.  The tables are formed on the device once per device, on the stream of the first call.
+ * idv_rmse_ragged: utils/eval_metrics.py:33-41 over the first lens[b] (required; clamped to the shorter pitch) samples of each
+ * row, alpha = <est, ref> / <est, est>, out[b] = sqrt(mean((alpha est - ref)^2)), sums in double; work: 3*B doubles. */
+long long idv_stoi_work_bytes(int B, int Lmax, int fs);
+int idv_stoi(const float* ref, long long ref_ld, const float* est, long long est_ld, const int* lens, int B, int Lmax, int fs,
+             int extended, void* work, long long work_bytes, float* out, int* counts, void* stream);
+int idv_rmse_ragged(const float* ref, long long ref_ld, const float* est, long long est_ld, const int* lens, int B, double* work,
+                    float* out, void* stream);
+
 /* ---- time-Winograd convs with two co tiles per workgroup (cgemm_tw.hip, cgemm_tw2.hip; additive entries: IDV_ABI_VERSION is
  * unchanged).  A layer with an even number of 32-channel co tiles runs workgroups of eight waves that stage the raw input rows once
  * for two co tiles; the outputs are bit-identical to the one-co-tile kernels (the train-mode moment sums within the rounding of a
