@@ -261,7 +261,8 @@ def test_clstm_grads_bf16x3(ops, cp, H, I, T, B):
         ops.set_precision(keep)
 
 
-def _clstm_grads(ops, cp, H, I, T, B, ftol, gtol):
+def _clstm_setup(cp, H, I, T, B):
+    """The module with seeded parameters (scaled 1 / sqrt(H)), the input x [T, B, I, 2] and the output gradient R [T, B, H, 2]."""
     g = torch.Generator().manual_seed(11)
     dev = "cuda"
     m = cp.ComplexLSTM(I, H, dev, num_layers=2)
@@ -271,21 +272,42 @@ def _clstm_grads(ops, cp, H, I, T, B, ftol, gtol):
     m = m.to(dev)
     x = rnd(g, T, B, I, 2)
     R = rnd(g, T, B, H, 2)
+    return m, x, R
+
+
+def _clstm_step(ops, m, x, R):
+    """One forward + backward of sum(y * R) on the GPU -> (y [T, B, H, 2], the planar input, its gradient buffer); the
+    parameter gradients are in m (cleared first)."""
+    dev = "cuda"
+    for p_ in m.parameters():
+        p_.grad = None
     xp = ops.Planar.from_tensor5(x.permute(1, 2, 0, 3).unsqueeze(2).to(dev))
     xp.buf.requires_grad_(True)
     with torch.enable_grad():
         out = m.forward_planar(xp)
-        y = out.channel_slice(0, H).permute(1, 0, 2, 3)                 # [T, B, H, 2]
+        y = out.channel_slice(0, m.hidden_size).permute(1, 0, 2, 3)     # [T, B, H, 2]
         (y * R.to(dev)).sum().backward()
+    return y, xp, xp.buf.grad
+
+
+def _clstm_oracle(m, x, R):
+    """float64 autograd through the oracle -> (forward, dx, {name: parameter gradient})."""
     sd = {k: leaf64(v.cpu()) for k, v in m.state_dict().items()}
     x64 = leaf64(x)
     want = O.complex_lstm(x64, sd, "", 2)
-    check("forward", y, want, ftol)
     (want * R.double()).sum().backward()
-    gx = ops.rewrap(xp.buf.grad, xp).tensor5()                          # [B, I, 1, T, 2]
-    check("dx", gx[:, :, 0].permute(2, 0, 1, 3), x64.grad, gtol)
+    return want.detach(), x64.grad, {k: v.grad for k, v in sd.items()}
+
+
+def _clstm_grads(ops, cp, H, I, T, B, ftol, gtol):
+    m, x, R = _clstm_setup(cp, H, I, T, B)
+    y, xp, gbuf = _clstm_step(ops, m, x, R)
+    want, dx, grads = _clstm_oracle(m, x, R)
+    check("forward", y, want, ftol)
+    gx = ops.rewrap(gbuf, xp).tensor5()                                 # [B, I, 1, T, 2]
+    check("dx", gx[:, :, 0].permute(2, 0, 1, 3), dx, gtol)
     for k, p_ in m.named_parameters():
-        check(k, p_.grad, sd[k].grad, gtol)
+        check(k, p_.grad, grads[k], gtol)
 
 
 def test_cooperative_bptt_times_out_instead_of_hanging(ops, cp):

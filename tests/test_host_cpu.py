@@ -32,20 +32,44 @@ def test_lstm_scratch_covers_the_cooperative_exchange_buffers(amd):
     cooperative recurrences, whose size does not shrink with T or Jp (a short input used to overflow it)."""
     lib = amd._lib.lib()
     I, LL = ctypes.c_int, ctypes.c_longlong
-    for fn in (lib.idv_clstm_work_floats, lib.idv_clstm_train_work_floats, lib.idv_lstm_pers_work_bytes, lib.idv_lstm_coop_f32_work_bytes):
+    for fn in (lib.idv_clstm_work_floats, lib.idv_clstm_train_work_floats, lib.idv_lstm_pers_work_bytes, lib.idv_lstm_coop_f32_work_bytes,
+               lib.idv_lstm_stack2_f32_work_bytes, lib.idv_lstm_bptt_work_floats, lib.idv_lstm_bptt_coop_work_bytes,
+               lib.idv_lstm_bptt_stack2_work_bytes):
         fn.restype = LL
-    for H, B, T, Jp in ((128, 1, 3, 8), (128, 64, 17, 64 * 18), (384, 3, 5, 20), (768, 32, 2, 96), (768, 20, 7, 160), (384, 64, 641, 64 * 642)):
+    # H = 128 at the batches where the kernel changes (240 cooperative workgroups, the figure without a device): 7 / 8 and
+    # 15 / 16 sequence tiles, one frame, a Jp far below the exchange buffers' size
+    edges = ((128, 112, 1, 228), (128, 113, 1, 228), (128, 240, 1, 484), (128, 241, 1, 484))
+    for H, B, T, Jp in ((128, 1, 3, 8), (128, 64, 17, 64 * 18), (384, 3, 5, 20), (768, 32, 2, 96), (768, 20, 7, 160),
+                        (384, 64, 641, 64 * 642)) + edges:
         need = 0
         if lib.idv_lstm_pers_supported(I(H), I(B)):
             need = max(need, lib.idv_lstm_pers_work_bytes(I(H), I(B)))
         if lib.idv_lstm_coop_f32_supported(I(H), I(B)):
             need = max(need, lib.idv_lstm_coop_f32_work_bytes(I(H), I(B)))
-        assert need > 0
+        if lib.idv_lstm_stack2_f32_supported(I(H), I(B)):
+            need = max(need, lib.idv_lstm_stack2_f32_work_bytes(I(H), I(B)))
+        assert need > 0 or (H, B) == (128, 241)                 # no cooperative form at 16 tiles
         TBH = T * B * H
         scratch_eval = lib.idv_clstm_work_floats(I(H), I(B), I(T), I(Jp)) - (24 * TBH + 4 * B * H + 4 * H * Jp)
         scratch_train = lib.idv_clstm_train_work_floats(I(H), I(B), I(T), I(Jp)) - (48 * TBH + 4 * B * H + 4 * H * Jp)
         assert 4 * scratch_eval >= need and 4 * scratch_train >= need, (H, B, T, Jp, scratch_eval, scratch_train, need)
         assert scratch_eval >= 4 * H * Jp and scratch_train >= 4 * H * Jp
+        # the BPTT scratch hosts the per-step kernels' buffers and, where supported, the cooperative form's
+        per_step = 4 * B * H + 2 * 4 * ((B + 15) // 16) * 4 * H * 16
+        assert lib.idv_lstm_bptt_work_floats(I(H), I(B)) >= per_step
+        if lib.idv_lstm_bptt_coop_supported(I(H), I(B)):
+            assert 4 * lib.idv_lstm_bptt_work_floats(I(H), I(B)) >= lib.idv_lstm_bptt_coop_work_bytes(I(H), I(B)) > 0
+        if lib.idv_lstm_bptt_stack2_supported(I(H), I(B)):
+            assert lib.idv_lstm_bptt_stack2_work_bytes(I(H), I(B)) > 0
+    assert lib.idv_coop_max_workgroups() == 240                 # no device here
+    want = {112: (1, 1), 113: (0, 1), 240: (0, 1), 241: (0, 0)}
+    for H, B, _, _ in edges:
+        fwd = (lib.idv_lstm_stack2_f32_supported(I(H), I(B)), lib.idv_lstm_coop_f32_supported(I(H), I(B)))
+        bwd = (lib.idv_lstm_bptt_stack2_supported(I(H), I(B)), lib.idv_lstm_bptt_coop_supported(I(H), I(B)))
+        assert fwd == want[B] and bwd == want[B], (B, fwd, bwd)
+    for B in (1, 17, 112, 113, 230, 240):                       # wherever the coop form is supported
+        assert lib.idv_lstm_bptt_coop_supported(I(128), I(B))
+        assert 4 * lib.idv_lstm_bptt_work_floats(I(128), I(B)) >= lib.idv_lstm_bptt_coop_work_bytes(I(128), I(B))
 
 
 def test_missing_library_fails_loudly(amd, monkeypatch):
