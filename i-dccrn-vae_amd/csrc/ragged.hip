@@ -17,8 +17,9 @@ constexpr int RG_TT = 32;         // frames per block (as stft_frames_kernel)
 // One block per (b, 32 frames): the signal segment of the block's valid frames is staged in LDS with both mirrors applied (the
 // end mirror at L = lens[b]; no sample at or past L is read), then written out coalesced along j.  KIMG = false: planar
 // frames[win][Jp] (idv_stft_frames); KIMG = true: the split-bf16 K-major image (idv_stft_frames_kimage).  Frames t >= T_b and
-// the guard column are zeros.
-template <bool KIMG>
+// the guard column are zeros.  ZPAD (idv_stft_frames_ragged_pad, pad_mode 1): the samples before 0 and at or past L are zeros instead
+// of the mirror images (librosa.stft's pad_mode="constant"); any L >= 0 is then valid.
+template <bool KIMG, bool ZPAD = false>
 __global__ __launch_bounds__(256) void stft_frames_ragged_kernel(const float* __restrict__ x, long long ldx, const int* __restrict__ lens,
                                                                  int n_fft, int win, int hop, int Tmax, float* __restrict__ frames,
                                                                  unsigned short* __restrict__ img, long long lo_off, int KO, int Tp,
@@ -36,8 +37,10 @@ __global__ __launch_bounds__(256) void stft_frames_ragged_kernel(const float* __
     const long long s0 = (long long)hop * t0 + left - half;       // original-signal index of seg[0]
     for (int e = threadIdx.x; e < seglen; e += blockDim.x) {
         long long s = s0 + e;
-        if (s < 0) s = -s;
-        if (s >= L) s = 2LL * (L - 1) - s;
+        if constexpr (!ZPAD) {
+            if (s < 0) s = -s;
+            if (s >= L) s = 2LL * (L - 1) - s;
+        }
         seg[e] = (s >= 0 && s < L) ? x[(size_t)b * ldx + s] : 0.f;
     }
     __syncthreads();
@@ -127,9 +130,10 @@ inline int grid_for(long long n) {
     return (int)(g > 8192 ? 8192 : (g < 1 ? 1 : g));
 }
 
-inline bool frames_args_ok(const float* x, long long ldx, const int* lens, int B, int n_fft, int win, int hop, int Tmax, int Tp, int Jp) {
-    return x && lens && B > 0 && B <= 65535 && n_fft > 0 && win > 0 && win <= n_fft && hop > 0 && Tmax >= 1 && ldx > n_fft / 2 &&
-           Tp >= Tmax + 1 && (long long)Jp >= (long long)B * Tp;
+inline bool frames_args_ok(const float* x, long long ldx, const int* lens, int B, int n_fft, int win, int hop, int Tmax, int Tp, int Jp,
+                           bool zpad = false) {
+    return x && lens && B > 0 && B <= 65535 && n_fft > 0 && win > 0 && win <= n_fft && hop > 0 && Tmax >= 1 &&
+           ldx > (zpad ? 0 : n_fft / 2) && Tp >= Tmax + 1 && (long long)Jp >= (long long)B * Tp;
 }
 
 }  // namespace
@@ -140,6 +144,16 @@ extern "C" int idv_stft_frames_ragged(const float* x, long long ldx, const int* 
     const size_t smem = (size_t)(hop * (RG_TT - 1) + win) * sizeof(float);
     hipLaunchKernelGGL(stft_frames_ragged_kernel<false>, dim3((Tmax + RG_TT - 1) / RG_TT, B), dim3(256), smem, (hipStream_t)stream, x,
                        ldx, lens, n_fft, win, hop, Tmax, frames, (unsigned short*)nullptr, 0LL, 0, Tp, Jp);
+    return idv_launch_status();
+}
+
+extern "C" int idv_stft_frames_ragged_pad(const float* x, long long ldx, const int* lens, int B, int n_fft, int win, int hop, int Tmax,
+                                          int pad_mode, float* frames, int Tp, int Jp, void* stream) {
+    if (pad_mode == IDV_PAD_REFLECT) return idv_stft_frames_ragged(x, ldx, lens, B, n_fft, win, hop, Tmax, frames, Tp, Jp, stream);
+    if (pad_mode != IDV_PAD_CONSTANT || !frames || !frames_args_ok(x, ldx, lens, B, n_fft, win, hop, Tmax, Tp, Jp, true)) return IDV_EINVAL;
+    const size_t smem = (size_t)(hop * (RG_TT - 1) + win) * sizeof(float);
+    hipLaunchKernelGGL((stft_frames_ragged_kernel<false, true>), dim3((Tmax + RG_TT - 1) / RG_TT, B), dim3(256), smem, (hipStream_t)stream,
+                       x, ldx, lens, n_fft, win, hop, Tmax, frames, (unsigned short*)nullptr, 0LL, 0, Tp, Jp);
     return idv_launch_status();
 }
 

@@ -13,7 +13,11 @@
     ``compute_sisdr`` (:49-64), ``compute_rmse`` (:33-41) and ``compute_stoi`` / ``compute_estoi`` (the ``pystoi`` call of :92-95
     and :119; csrc/stoi.hip, DESIGN 3.8 -- the package's definition restated, parity with the package itself pinned only where it
     is installed); :func:`score_list` scores a list of recordings of any lengths in padded batches.  PESQ (an ITU program) and
-    DNSMOS (an ONNX model) are third-party CPU metrics and stay out of scope.
+    DNSMOS (an ONNX model) are third-party CPU metrics and stay out of scope (SURVEY 2, rows 12 and 14);
+  * the resampling the evaluation scripts do with librosa in front of these (test_se_cvaefinetune.py:236-239, the 48 kHz
+    VoiceBank-DEMAND references): :func:`resample` / :func:`resample_list`, a rational polyphase resampler with
+    ``scipy.signal.resample_poly``'s definition (csrc/resample.hip; librosa's own soxr filter is another one and is
+    not pinned).  ``enhance_list`` and ``score_list`` take 16 kHz signals as before: the calls compose.
 
 Utterances of different lengths (causal models, the ones every shipped recipe builds): every entry point takes ``lengths``
 (a python sequence or a CPU integer tensor, one sample count per row of the zero- or anything-padded ``[B, Lmax]`` batch).  Row
@@ -284,6 +288,72 @@ def score_list(estimates: Sequence[torch.Tensor], references: Sequence[torch.Ten
     for m in metrics:
         vals = torch.cat(parts[m]).cpu() if parts[m] else torch.empty(0, dtype=torch.float32)
         out[m] = vals[inv]
+    return out
+
+
+def resample(x: torch.Tensor, fs_in: int, fs_out: int = 16000, lengths=None):
+    """Rational polyphase resampling on the device: x [B, L] (or [L]) at ``fs_in`` Hz -> ``(y [B, ceil(L * up / down)], out_lengths)``
+    at ``fs_out`` Hz, up / down = fs_out / fs_in reduced.  The definition is ``scipy.signal.resample_poly(x, up, down)`` with its
+    default filter (kaiser(5.0)-windowed sinc of 20 * max(up, down) + 1 taps; fp32 samples and taps, a double accumulator; DESIGN
+    3.9) -- NOT ``librosa.resample``, whose default is soxr: parity with librosa itself is unpinned.  ``lengths`` (a python
+    sequence or a CPU integer tensor): row b holds lengths[b] samples; nothing behind them is read, its result does not depend on the
+    rest of the batch, and its ``out_lengths[b] = ceil(lengths[b] * up / down)`` samples are followed by zeros.  ``out_lengths`` is a
+    list of ints.  ``fs_in == fs_out`` returns ``x`` itself.  Raises on the host, before any GPU work, for non-positive rates,
+    max(up, down) > 640 after reduction and rows longer than 2^27 samples."""
+    up, down = ops.resample_ratio(fs_in, fs_out)
+    if not isinstance(x, torch.Tensor) or x.dim() not in (1, 2):
+        raise ValueError("resample: x must be a tensor [L] or [B, L]")
+    single = x.dim() == 1
+    xr = x.reshape(1, -1) if single else x
+    B, L = xr.shape
+    if L < 1 or L > ops.RESAMPLE_MAX_LEN:
+        raise ValueError(f"resample: rows of {L} samples; 1 .. 2^27 are supported")
+    host = [L] * B if lengths is None else ops.check_lengths(lengths, B, L, None)
+    out_lens = [ops.resample_len(v, up, down) for v in host]
+    ops.check_dev_f32(x, "x")
+    if up == down:
+        return x, out_lens
+    lens = None if lengths is None else (lengths if isinstance(lengths, ops.Lengths) else ops.Lengths(host, x.device))
+    y = ops.resample(xr, up, down, lens)
+    return (y[0] if single else y), out_lens
+
+
+def resample_list(signals: Sequence[torch.Tensor], fs_in, fs_out: int = 16000, max_batch: int = 64) -> List[torch.Tensor]:
+    """Resample recordings of any lengths (and rates) at batch throughput.  ``signals``: 1-D float32 GPU tensors; ``fs_in``: an int
+    or one int per signal.  The signals of one rate are sorted by length and padded into batches of at most ``max_batch``, the way
+    :func:`score_list` batches; every result equals the per-signal :func:`resample` call bit for bit and comes back in the caller's
+    order.  A signal already at ``fs_out`` is returned as it is (the same tensor)."""
+    if isinstance(max_batch, bool) or not isinstance(max_batch, int) or max_batch < 1:
+        raise ValueError("resample_list: max_batch must be a positive integer")
+    N = len(signals)
+    rates = list(fs_in) if isinstance(fs_in, (list, tuple)) else [fs_in] * N
+    if len(rates) != N:
+        raise ValueError(f"{len(rates)} sampling rates for {N} signals")
+    ratios = {fs: ops.resample_ratio(fs, fs_out) for fs in dict.fromkeys(rates)}
+    for k, sgn in enumerate(signals):
+        if not isinstance(sgn, torch.Tensor) or sgn.dim() != 1 or sgn.shape[0] < 1:
+            raise ValueError(f"signals[{k}] must be a non-empty 1-D tensor")
+        if sgn.shape[0] > ops.RESAMPLE_MAX_LEN:
+            raise ValueError(f"signals[{k}]: {sgn.shape[0]} samples; at most 2^27 are supported")
+    for k, sgn in enumerate(signals):
+        ops.check_dev_f32(sgn, f"signals[{k}]")
+    out: List[Optional[torch.Tensor]] = [None] * N
+    for fs, (up, down) in ratios.items():
+        idx = [k for k in range(N) if rates[k] == fs]
+        if up == down:
+            for k in idx:
+                out[k] = signals[k]
+            continue
+        idx.sort(key=lambda k: (-int(signals[k].shape[0]), k))
+        for b0 in range(0, len(idx), max_batch):
+            batch = idx[b0:b0 + max_batch]
+            blens = [int(signals[k].shape[0]) for k in batch]
+            padded = torch.zeros(len(batch), blens[0], dtype=torch.float32, device=signals[batch[0]].device)
+            for row, k in enumerate(batch):
+                padded[row, :blens[row]] = signals[k]
+            y = ops.resample(padded, up, down, ops.Lengths(blens, padded.device))
+            for row, k in enumerate(batch):
+                out[k] = y[row, :ops.resample_len(blens[row], up, down)].clone()
     return out
 
 

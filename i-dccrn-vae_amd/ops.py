@@ -964,6 +964,81 @@ def istft(spec: Planar, plan: DftPlan, lengths=None) -> torch.Tensor:
     return y
 
 
+# ----------------------------------------------------------------------------- corpus preparation
+RESAMPLE_MAX_M = 640           # max(up, down) after reduction: 8 / 11.025 / 22.05 / 24 / 32 / 44.1 / 48 / 96 kHz <-> 16 kHz all fit
+RESAMPLE_MAX_LEN = 1 << 27     # samples per row
+PAD_MODES = {"reflect": 0, "constant": 1}      # IDV_PAD_REFLECT / IDV_PAD_CONSTANT
+_RESAMPLE_TAPS = {}            # (up, down, device) -> fp32 taps on the device
+
+
+def resample_ratio(fs_in, fs_out):
+    """(up, down) = (fs_out, fs_in) reduced by their gcd; the guards on the rates (host only, no device use)."""
+    for name, v in (("fs_in", fs_in), ("fs_out", fs_out)):
+        if isinstance(v, bool) or not isinstance(v, int) or v <= 0:
+            raise ValueError(f"{name} = {v!r}: a sampling rate must be a positive integer")
+    import math
+    g = math.gcd(fs_in, fs_out)
+    up, down = fs_out // g, fs_in // g
+    if max(up, down) > RESAMPLE_MAX_M:
+        raise ValueError(f"{fs_in} -> {fs_out} Hz reduces to {up}/{down}: max(up, down) may not exceed {RESAMPLE_MAX_M}")
+    return up, down
+
+
+def resample_len(L: int, up: int, down: int) -> int:
+    """ceil(L * up / down): the number of output samples of L input samples."""
+    return -((-L * up) // down)
+
+
+def resample_taps_host(up: int, down: int):
+    """scipy.signal.resample_poly's default filter for the reduced ratio, in float64: 2 * half + 1 taps, half = 10 * max(up, down),
+    kaiser(5.0) * sinc(t / m) / m normalised to sum 1."""
+    import numpy as np
+    m = max(up, down)
+    half = 10 * m
+    t = np.arange(-half, half + 1, dtype=np.float64)
+    h = np.kaiser(2 * half + 1, 5.0) * np.sinc(t / m) / m
+    return h / h.sum()
+
+
+def resample_taps(up: int, down: int, device) -> torch.Tensor:
+    """The taps as the kernel reads them, formed once per (up, down, device) and cached."""
+    device = torch.device(device)
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (up, down, device)
+    if key not in _RESAMPLE_TAPS:
+        _RESAMPLE_TAPS[key] = torch.from_numpy(resample_taps_host(up, down).astype("float32")).to(device)
+    return _RESAMPLE_TAPS[key]
+
+
+def resample(x: torch.Tensor, up: int, down: int, lengths: Optional[Lengths] = None) -> torch.Tensor:
+    """idv_resample: x [B, L] -> y [B, ceil(L * up / down)] for a reduced (up, down) of :func:`resample_ratio`; with ``lengths`` row b
+    holds ceil(lengths[b] * up / down) samples followed by zeros, and nothing at or past lengths[b] is read."""
+    B, Lx = x.shape
+    if Lx < 1 or Lx > RESAMPLE_MAX_LEN:
+        raise ValueError(f"resample: rows of {Lx} samples; 1 .. 2^27 are supported")
+    if B < 1 or B > 65535:
+        raise ValueError(f"resample: a batch of {B} rows; 1 .. 65535 are supported")
+    n = resample_len(Lx, up, down)
+    if n > 2 ** 31 - 1 - 256:
+        raise ValueError(f"resample: {n} output samples per row are not supported")
+    check_dev_f32(x, "x")
+    x = _ragged_rows(x)
+    taps = resample_taps(up, down, x.device)
+    y = torch.empty(B, n, dtype=torch.float32, device=x.device)
+    call("idv_resample", p(x), ll(x.stride(0)), p(None if lengths is None else lengths.dev), i(B), i(Lx), i(up), i(down), p(taps), p(y),
+         ll(y.stride(0)), stream_ptr())
+    return y
+
+
+def stft_frames_pad(x: torch.Tensor, lengths: Lengths, n_fft: int, win: int, hop: int, T: int, pad_mode: str) -> Planar:
+    """idv_stft_frames_ragged_pad: the frames [win][Jp] (a Planar of win // 2 "channels") of a padded batch, T columns per row."""
+    fr = Planar.empty(1, win // 2, x.shape[0], T, T + 1, x.device)
+    call("idv_stft_frames_ragged_pad", p(x), ll(x.stride(0)), p(lengths.dev), i(x.shape[0]), i(n_fft), i(win), i(hop), i(T),
+         i(PAD_MODES[pad_mode]), fr.ptr(), i(T + 1), i(fr.Jp), stream_ptr())
+    return fr
+
+
 def mask_apply(mask: Planar, X: Planar, x_div: int = 1):
     """-> (pred planar, pred complex64 [B, F, T])."""
     B, F, T = mask.B, mask.F, mask.T

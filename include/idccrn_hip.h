@@ -853,6 +853,44 @@ int idv_stoi(const float* ref, long long ref_ld, const float* est, long long est
 int idv_rmse_ragged(const float* ref, long long ref_ld, const float* est, long long est_ld, const int* lens, int B, double* work,
                     float* out, void* stream);
 
+/* ---- corpus preparation (resample.hip, moments.hip, ragged.hip; inference.resample / resample_list, dataset/stats.py; additive
+ * entries: IDV_ABI_VERSION is unchanged).
+ *
+ * idv_resample: scipy.signal.resample_poly(x, up, down) with its default filter for a padded batch x[B][ldx] -> y[B][ldy].  up / down
+ * are reduced by their gcd inside; with m = max(up, down) and half = 10 m,
+ *     y[b][n] = up * sum_j x[b][j] taps[half + n down - j up],  0 <= j < lens[b],  tap index in [0, 2 half],  n < ceil(lens[b] up / down).
+ * taps: device fp32[idv_resample_ntaps(up, down) = 20 m + 1], formed by the caller in double: kaiser(2 half + 1, 5.0) * sinc(t / m) / m
+ * for t = -half .. half, normalised to sum 1.  lens: device int32[B] (clamped to [0, L]) or NULL: every row has L samples.  Row b
+ * reads nothing at or past lens[b] and nothing of another row; columns ceil(lens[b] up / down) .. ceil(L up / down) - 1 are written as
+ * zeros; fp32 samples and taps, a double accumulator per output in increasing j, no atomics: a row's result does not depend on B, on
+ * the other rows or on the padding.  IDV_EINVAL (before any GPU work) for up <= 0, down <= 0, m > 640 (8 / 11.025 / 22.05 / 24 / 32 /
+ * 44.1 / 48 / 96 kHz to and from 16 kHz all fit), L <= 0, L > 2^27, ldx < L, ldy < ceil(L up / down) and an output row of 2^31 - 256
+ * columns or more.  idv_resample_ntaps / idv_resample_len: host only; the tap count and ceil(L up / down), -1 for refused arguments. */
+int idv_resample_ntaps(int up, int down);
+long long idv_resample_len(long long L, int up, int down);
+int idv_resample(const float* x, long long ldx, const int* lens, int B, int L, int up, int down, const float* taps, float* y,
+                 long long ldy, void* stream);
+/* idv_stft_frames_ragged with the padding of the signal ends as an argument.  IDV_PAD_REFLECT: that entry itself (torch.stft's
+ * mirror; ldx > n_fft/2 and every lens[b] > n_fft/2).  IDV_PAD_CONSTANT: zeros before sample 0 and from lens[b] on, as
+ * librosa.stft(center=True) of librosa >= 0.10 pads (pad_mode="constant"); any lens[b] >= 1 is valid.  In both modes row b has
+ * T_b = 1 + lens[b] / hop frames, and the DFT is idv_pw_gemm with the idv_make_dft matrix (periodic hann(win) centred in n_fft). */
+#define IDV_PAD_REFLECT 0
+#define IDV_PAD_CONSTANT 1
+int idv_stft_frames_ragged_pad(const float* x, long long ldx, const int* lens, int B, int n_fft, int win, int hop, int Tmax, int pad_mode,
+                               float* frames, int Tp, int Jp, void* stream);
+/* Running mean and sum of squared deviations (M2) of every row of planar spectra spec[rows = 2F][Jp] over their valid columns: frame
+ * t < min(Tmax, 1 + lens[b] / hop) of utterance b sits in column b Tp + t + 1 (lens NULL: Tmax frames each); guard columns and frames
+ * past a row's end are skipped, not counted as zeros.  state: device double[1 + 2 rows] = (n, mean[rows], M2[rows]), zeroed by the
+ * caller before the first update; var = M2 / (n - 1).  Each workgroup forms (n, mean, M2) of its 2048-column tile about the tile's own
+ * mean (two passes over registers), and one workgroup folds the tiles and then the state by Chan's formula in a fixed order: no
+ * atomics, the same sequence of calls gives the same bits.  work: idv_spec_moments_work_bytes(rows, B, Tp) bytes (-1 for refused
+ * arguments), 8-byte aligned.  idv_spec_moments_merge: state <- Chan merge of state and other (another state of the same rows, e.g.
+ * of another rank or loader shard). */
+long long idv_spec_moments_work_bytes(int rows, int B, int Tp);
+int idv_spec_moments_update(const float* spec, const int* lens, int B, int hop, int Tmax, int Tp, int Jp, int rows, double* state,
+                            void* work, long long work_bytes, void* stream);
+int idv_spec_moments_merge(double* state, const double* other, int rows, void* stream);
+
 /* ---- time-Winograd convs with two co tiles per workgroup (cgemm_tw.hip, cgemm_tw2.hip; additive entries: IDV_ABI_VERSION is
  * unchanged).  A layer with an even number of 32-channel co tiles runs workgroups of eight waves that stage the raw input rows once
  * for two co tiles; the outputs are bit-identical to the one-co-tile kernels (the train-mode moment sums within the rounding of a
