@@ -9,7 +9,12 @@ Reference behaviour kept (dataset/dataload_supervised_dccrn.py:98-219, dataset/d
   * the index ``[(wavfile, start, end), ...]`` is pickled to ``<dataset_name>_train.pkl`` / ``_val.pkl`` in the working
     directory on first use and re-read afterwards (:130-143, :177-183); optional shuffle of the index;
   * clean / noise companions are found from the file id after the last ``_``: ``clean_fileid_<id>.wav``,
-    ``noise_fileid_<id>.wav`` (:201-204, dataload_nsvae.py:178-181); a sampling-rate mismatch raises ValueError (:152).
+    ``noise_fileid_<id>.wav`` (:201-204, dataload_nsvae.py:178-181); a sampling-rate mismatch raises ValueError (:152);
+  * ``[STFT] trim = True`` (every VAE recipe): the NSVAE and the pretrained-VAE loader cut the leading and trailing silence of a file
+    with ``librosa.effects.trim(x, top_db=30)`` before they count its segments, and every segment starts ``ind_beg`` later
+    (dataload_nsvae.py:131-148, dataload_pretrained_vaes.py:133-150).  Here the bounds come from the GPU (csrc/trim.hip, DESIGN 3.10:
+    librosa 0.10's definition restated, parity with the package itself unpinned); the supervised loader stays untrimmed as in the
+    reference, where the call is commented out (:155-156).
 librosa / soundfile are not needed: 16-bit / 32-bit / float PCM wav files are decoded with ``scipy.io.wavfile`` to float32
 in [-1, 1), which is what ``librosa.load(sr=None)`` returns for them.  The hot path itself never touches the disk.
 """
@@ -49,17 +54,52 @@ def wav_length(path: str) -> Tuple[int, int]:
     return int(x.shape[0]), int(fs)
 
 
-def segment_index(files: Iterable[str], hop: int, sequence_len: int, fs: int) -> List[Tuple[str, int, int]]:
-    """The reference's ``compute_len`` (dataload_supervised_dccrn.py:143-175)."""
-    out = []
+def segments_from_bounds(wav: str, beg: int, end: int, hop: int, sequence_len: int) -> List[Tuple[str, int, int]]:
+    """The segments of one file whose non-silent span is ``[beg, end)`` (dataload_nsvae.py:131-160; ``(0, len)`` untrimmed):
+    ``n_seq = (1 + int((end - beg) / hop)) // sequence_len`` segments of ``(sequence_len - 1) * hop`` samples, the first at ``beg``."""
     seq_length = (sequence_len - 1) * hop
-    for wav in files:
-        n, fs_x = wav_length(wav)
-        if fs != fs_x:
-            raise ValueError('Unexpected sampling rate')
-        n_seq = (1 + int(n / hop)) // sequence_len
-        for i in range(n_seq):
-            out.append((wav, i * seq_length, (i + 1) * seq_length))
+    n_seq = (1 + int((end - beg) / hop)) // sequence_len
+    return [(wav, i * seq_length + beg, (i + 1) * seq_length + beg) for i in range(n_seq)]
+
+
+def segment_index(files: Iterable[str], hop: int, sequence_len: int, fs: int, trim: bool = False, top_db: float = 30.0, device=None,
+                  max_batch: int = 64) -> List[Tuple[str, int, int]]:
+    """The reference's ``compute_len`` (dataload_supervised_dccrn.py:143-175).  ``trim`` (``[STFT] trim = True``, dataload_nsvae.py:
+    131-148, dataload_pretrained_vaes.py:133-150): the leading and trailing silence of every file, ``librosa.effects.trim(x,
+    top_db=30)`` there, is bounded on the GPU (inference.trim_bounds_list on ``max_batch`` files at a time) and the
+    segments are counted and placed inside those bounds; the index keeps the order of ``files``.  ``device``: the GPU to use (it is
+    made the current device for the launches), default the current one.  Without a GPU ``trim=True`` raises before any file is
+    opened: there is no host fallback."""
+    if not trim:
+        out = []
+        for wav in files:
+            n, fs_x = wav_length(wav)
+            if fs != fs_x:
+                raise ValueError('Unexpected sampling rate')
+            out += segments_from_bounds(wav, 0, n, hop, sequence_len)
+        return out
+    if not torch.cuda.is_available():
+        raise RuntimeError("segment_index(trim=True) bounds the silence on the GPU and none is available; there is no host fallback")
+    from .. import inference
+    device = torch.device("cuda" if device is None else device)
+    if device.type != "cuda":
+        raise ValueError(f"segment_index: device {device} is not a GPU")
+    files, out = list(files), []
+    with torch.cuda.device(device):                         # the kernels are queued on the current device's stream
+        for g0 in range(0, len(files), max_batch):
+            group = files[g0:g0 + max_batch]
+            bounds, sigs, rows = [(0, 0)] * len(group), [], []
+            for k, wav in enumerate(group):
+                x, fs_x = read_wav(wav)
+                if fs != fs_x:
+                    raise ValueError('Unexpected sampling rate')
+                if x.shape[0]:                              # an empty file has the empty span
+                    sigs.append(torch.from_numpy(np.ascontiguousarray(x)).to(device))
+                    rows.append(k)
+            for k, be in zip(rows, inference.trim_bounds_list(sigs, top_db, max_batch)):
+                bounds[k] = be
+            for wav, (beg, end) in zip(group, bounds):
+                out += segments_from_bounds(wav, beg, end, hop, sequence_len)
     return out
 
 
@@ -71,12 +111,14 @@ def companion(wavfile: str, directory: str, kind: str) -> str:
 
 class SpeechSequencesFull(data.Dataset):
     """Same constructor keywords and item layout as the reference class: items are ``(noisy, clean)`` float32 segments,
-    or ``(noisy, clean, noise)`` when ``noise_file_dir`` is given (the NSVAE loader)."""
+    or ``(noisy, clean, noise)`` when ``noise_file_dir`` is given (the NSVAE loader); with ``clean_file_dir=None`` an item is the
+    segment of the listed file alone (the pretrained-VAE loader, dataload_pretrained_vaes.py:172-189).  ``trim`` / ``top_db``: see
+    :func:`segment_index`."""
 
-    def __init__(self, noisy_file_list: Sequence[str], clean_file_dir: str, shuffle: bool = False, sample_mean=None,
+    def __init__(self, noisy_file_list: Sequence[str], clean_file_dir: Optional[str], shuffle: bool = False, sample_mean=None,
                  sample_std=None, name: str = 'WSJ0', sr: int = 16000, hop: int = 100, sequence_len: int = 100,
                  first_use: bool = True, dataset_to: str = 'train', noise_file_dir: Optional[str] = None,
-                 cache_dir: str = "."):
+                 cache_dir: str = ".", trim: bool = False, top_db: float = 30.0):
         super().__init__()
         self.noisy_file_list = list(noisy_file_list)
         self.clean_file_dir, self.noise_file_dir = clean_file_dir, noise_file_dir
@@ -87,7 +129,7 @@ class SpeechSequencesFull(data.Dataset):
             raise ValueError("dataset_to must be 'train' or 'val'")
         cache = os.path.join(cache_dir, f"{self.name}_{dataset_to}.pkl")
         if first_use:
-            self.valid_seq_list = segment_index(self.noisy_file_list, hop, sequence_len, sr)
+            self.valid_seq_list = segment_index(self.noisy_file_list, hop, sequence_len, sr, trim=trim, top_db=top_db)
             if shuffle:
                 random.shuffle(self.valid_seq_list)
             with open(cache, "wb") as f:
@@ -102,6 +144,8 @@ class SpeechSequencesFull(data.Dataset):
     def __getitem__(self, index):
         wavfile, s0, s1 = self.valid_seq_list[index]
         x, _ = read_wav(wavfile, s0, s1)
+        if self.clean_file_dir is None:
+            return x
         c, _ = read_wav(companion(wavfile, self.clean_file_dir, 'clean'), s0, s1)
         if self.noise_file_dir is None:
             return x, c
@@ -168,8 +212,13 @@ class SyntheticMixtures:
             k += 1
 
 
-def build_dataloader(cfg, first_use_dataset: bool = True, nsvae: bool = False, cache_dir: str = "."):
-    """``build_dataloader`` of the reference (dataload_supervised_dccrn.py:15-95) on a parsed .ini (utils.read_config.myconf)."""
+def build_dataloader(cfg, first_use_dataset: bool = True, nsvae: bool = False, cache_dir: str = ".", pretrained: bool = False):
+    """``build_dataloader`` of the reference (dataload_supervised_dccrn.py:15-95) on a parsed .ini (utils.read_config.myconf).
+    ``nsvae``: the three-signal loader of dataload_nsvae.py; ``pretrained``: the one-signal loader of dataload_pretrained_vaes.py,
+    which lists ``[User] train_data_dir`` / ``val_data_dir``.  Both honour ``[STFT] trim`` (False where the key is missing); the
+    supervised loader has its trim commented out in the reference (dataload_supervised_dccrn.py:155-156) and stays untrimmed."""
+    if nsvae and pretrained:
+        raise ValueError("build_dataloader: nsvae and pretrained are two different loaders")
     def listing(path, suffix):
         if path.endswith('.txt'):
             with open(path) as f:
@@ -184,13 +233,17 @@ def build_dataloader(cfg, first_use_dataset: bool = True, nsvae: bool = False, c
     workers, suffix = cfg.getint('DataFrame', 'num_workers'), cfg.get('DataFrame', 'suffix')
     seq = cfg.getint('DataFrame', 'sequence_len')
     hop, fs = cfg.getint('STFT', 'hopfrac'), cfg.getint('STFT', 'fs')
+    trim = cfg.getboolean('STFT', 'trim') if cfg.has_option('STFT', 'trim') else False
     sets = []
     for split in ("train", "val"):
-        kw = dict(noisy_file_list=listing(u(f'noisy_{split}_data_dir'), suffix), clean_file_dir=u(f'clean_{split}_data_dir'),
-                  shuffle=shuffle, name=name, sr=fs, hop=hop, sequence_len=seq, first_use=first_use_dataset,
-                  dataset_to=split, cache_dir=cache_dir)
+        kw = dict(shuffle=shuffle, name=name, sr=fs, hop=hop, sequence_len=seq, first_use=first_use_dataset, dataset_to=split,
+                  cache_dir=cache_dir)
+        if pretrained:
+            kw.update(noisy_file_list=listing(u(f'{split}_data_dir'), suffix), clean_file_dir=None, trim=trim)
+        else:
+            kw.update(noisy_file_list=listing(u(f'noisy_{split}_data_dir'), suffix), clean_file_dir=u(f'clean_{split}_data_dir'))
         if nsvae:
-            kw["noise_file_dir"] = u(f'noise_{split}_data_dir')
+            kw.update(noise_file_dir=u(f'noise_{split}_data_dir'), trim=trim)
         sets.append(SpeechSequencesFull(**kw))
     mk = lambda ds: data.DataLoader(ds, batch_size=bs, shuffle=shuffle, num_workers=workers)
     return mk(sets[0]), mk(sets[1]), len(sets[0]), len(sets[1])

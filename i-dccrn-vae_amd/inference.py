@@ -17,7 +17,10 @@
   * the resampling the evaluation scripts do with librosa in front of these (test_se_cvaefinetune.py:236-239, the 48 kHz
     VoiceBank-DEMAND references): :func:`resample` / :func:`resample_list`, a rational polyphase resampler with
     ``scipy.signal.resample_poly``'s definition (csrc/resample.hip; librosa's own soxr filter is another one and is
-    not pinned).  ``enhance_list`` and ``score_list`` take 16 kHz signals as before: the calls compose.
+    not pinned).  ``enhance_list`` and ``score_list`` take 16 kHz signals as before: the calls compose;
+  * the silence trimming in front of the scoring (i_dccrn_vae/pretrained_vaes/test_prevae.py:154-155, ``librosa.effects.trim(x,
+    top_db=30)``) and of the loaders' segment index: :func:`trim` / :func:`trim_list` (csrc/trim.hip; librosa 0.10's
+    definition restated, parity with the package itself unpinned).
 
 Utterances of different lengths (causal models, the ones every shipped recipe builds): every entry point takes ``lengths``
 (a python sequence or a CPU integer tensor, one sample count per row of the zero- or anything-padded ``[B, Lmax]`` batch).  Row
@@ -355,6 +358,106 @@ def resample_list(signals: Sequence[torch.Tensor], fs_in, fs_out: int = 16000, m
             for row, k in enumerate(batch):
                 out[k] = y[row, :ops.resample_len(blens[row], up, down)].clone()
     return out
+
+
+def trim(x: torch.Tensor, top_db: float = 30.0, lengths=None, frame_length: int = 2048, hop_length: int = 512, power: bool = False):
+    """Cut the leading and trailing silence of every row on the device: x [B, L] (or [L]) -> ``(y, out_lengths, bounds)``.  The
+    definition is ``librosa.effects.trim(x, top_db=top_db, frame_length=frame_length, hop_length=hop_length)`` of librosa 0.10 with
+    ``ref=np.max`` restated (csrc/trim.hip; parity with the package itself is unpinned): the mean square of every centred,
+    zero-padded frame in double, frames more than ``top_db`` dB below the loudest are silent, ``start = t0 * hop_length`` and ``end =
+    min(n, (t1 + 1) * hop_length)`` from the first / last non-silent frame.  ``bounds`` is the list of ``(start, end)``,
+    ``out_lengths`` the list of ``end - start`` and ``y [B, max(out_lengths)]`` (or ``[out_lengths[0]]``) holds ``x[b, start:end]``
+    followed by zeros; ``[B, 0]`` if every row is trimmed to nothing.  A row of zeros comes back untrimmed.  ``lengths`` (a python
+    sequence or a CPU integer tensor): row b holds lengths[b] samples; nothing behind them is read and its result does not depend on
+    the rest of the batch.  ``power=True`` also returns the float64 frame powers ``[B, 1 + L // hop_length]`` (zeros behind a row's
+    own ``1 + lengths[b] // hop_length``).  The bounds come to the host with one synchronisation.  Raises on the host, before any GPU
+    work, for a bad ``top_db``, frame sizes other than ``hop_length % 4 == 0``, ``frame_length % (2 * hop_length) == 0`` and
+    ``frame_length <= 64 * hop_length``, and rows longer than 2^27 samples."""
+    top_db = ops.check_trim_args(top_db, frame_length, hop_length)
+    if not isinstance(x, torch.Tensor) or x.dim() not in (1, 2):
+        raise ValueError("trim: x must be a tensor [L] or [B, L]")
+    single = x.dim() == 1
+    xr = x.reshape(1, -1) if single else x
+    B, L = xr.shape
+    if L < 1 or L > ops.TRIM_MAX_LEN:
+        raise ValueError(f"trim: rows of {L} samples; 1 .. 2^27 are supported")
+    if B < 1 or B > 65535:
+        raise ValueError(f"trim: a batch of {B} rows; 1 .. 65535 are supported")
+    host = None if lengths is None else ops.check_lengths(lengths, B, L, None)
+    ops.check_dev_f32(x, "x")
+    lens = None if host is None else (lengths if isinstance(lengths, ops.Lengths) else ops.Lengths(host, x.device))
+    xr = ops._ragged_rows(xr)
+    got = ops.trim_bounds(xr, top_db, frame_length, hop_length, lens, power)
+    bounds_dev, P = got if power else (got, None)
+    bounds = [(int(s), int(e)) for s, e in bounds_dev.tolist()]
+    out_lens = [e - s for s, e in bounds]
+    y = ops.trim_gather(xr, bounds_dev, max(out_lens))
+    if single:
+        y, P = y[0], (None if P is None else P[0])
+    return (y, out_lens, bounds, P) if power else (y, out_lens, bounds)
+
+
+def _trim_batches(lengths: Sequence[int], max_batch: int) -> List[List[int]]:
+    """The batches of :func:`trim_list` (host only): indices sorted by length (descending, ties by index) in groups of ``max_batch``."""
+    order = sorted(range(len(lengths)), key=lambda k: (-lengths[k], k))
+    return [order[b0:b0 + max_batch] for b0 in range(0, len(order), max_batch)]
+
+
+def _trim_pad(signals: Sequence[torch.Tensor], device) -> torch.Tensor:
+    """The signals (1-D float32, host or device) as rows of one zero-padded device batch [B, len(signals[0])], the first one the
+    longest.  The row pitch is a multiple of 4 samples, so every row starts on a 16-byte boundary."""
+    n0 = int(signals[0].shape[0])
+    padded = torch.zeros(len(signals), (n0 + 3) // 4 * 4, dtype=torch.float32, device=device)[:, :n0]
+    for row, sgn in enumerate(signals):
+        padded[row, :sgn.shape[0]].copy_(sgn, non_blocking=True)
+    return padded
+
+
+def _trim_list_run(signals, top_db, max_batch, frame_length, hop_length, gather: bool, who: str):
+    """The guards and the batches :func:`trim_list` and :func:`trim_bounds_list` share -> [(indices, device bounds, gathered rows or
+    None)], every launch queued and nothing fetched yet."""
+    top_db = ops.check_trim_args(top_db, frame_length, hop_length)
+    if isinstance(max_batch, bool) or not isinstance(max_batch, int) or max_batch < 1:
+        raise ValueError(f"{who}: max_batch must be a positive integer")
+    for k, sgn in enumerate(signals):
+        if not isinstance(sgn, torch.Tensor) or sgn.dim() != 1 or sgn.shape[0] < 1:
+            raise ValueError(f"signals[{k}] must be a non-empty 1-D tensor")
+        if sgn.shape[0] > ops.TRIM_MAX_LEN:
+            raise ValueError(f"signals[{k}]: {sgn.shape[0]} samples; at most 2^27 are supported")
+    for k, sgn in enumerate(signals):
+        ops.check_dev_f32(sgn, f"signals[{k}]")
+    pending = []
+    for batch in _trim_batches([int(s.shape[0]) for s in signals], max_batch):
+        blens = [int(signals[k].shape[0]) for k in batch]
+        padded = _trim_pad([signals[k] for k in batch], signals[batch[0]].device)
+        bdev = ops.trim_bounds(padded, top_db, frame_length, hop_length, ops.Lengths(blens, padded.device))
+        # as wide as the longest input: the bounds need not come to the host in between
+        pending.append((batch, bdev, ops.trim_gather(padded, bdev, blens[0]) if gather else None))
+    return pending
+
+
+def trim_list(signals: Sequence[torch.Tensor], top_db: float = 30.0, max_batch: int = 64, frame_length: int = 2048,
+              hop_length: int = 512):
+    """Trim recordings of any lengths at batch throughput.  ``signals``: 1-D float32 GPU tensors.  They are sorted by length and padded
+    into batches of at most ``max_batch``, the way :func:`resample_list` batches -> ``(trimmed signals, bounds)`` in the caller's
+    order, ``bounds`` a list of ``(start, end)``.  Every result equals the per-signal :func:`trim` call bit for bit."""
+    out: List[Optional[torch.Tensor]] = [None] * len(signals)
+    bounds: List[Optional[tuple]] = [None] * len(signals)
+    for batch, bdev, y in _trim_list_run(signals, top_db, max_batch, frame_length, hop_length, True, "trim_list"):
+        for row, (k, (s, e)) in enumerate(zip(batch, bdev.tolist())):
+            bounds[k] = (int(s), int(e))
+            out[k] = y[row, :e - s].clone()
+    return out, bounds
+
+
+def trim_bounds_list(signals: Sequence[torch.Tensor], top_db: float = 30.0, max_batch: int = 64, frame_length: int = 2048,
+                     hop_length: int = 512) -> List[tuple]:
+    """The ``bounds`` of :func:`trim_list` alone, with its batches and without the gather: what an index of segments needs."""
+    bounds: List[Optional[tuple]] = [None] * len(signals)
+    for batch, bdev, _ in _trim_list_run(signals, top_db, max_batch, frame_length, hop_length, False, "trim_bounds_list"):
+        for k, (s, e) in zip(batch, bdev.tolist()):
+            bounds[k] = (int(s), int(e))
+    return bounds
 
 
 def plan_ragged_batches(lengths: Sequence[int], hop: int, max_batch: int = 64, max_columns: int = 64 * 642,

@@ -1039,6 +1039,72 @@ def stft_frames_pad(x: torch.Tensor, lengths: Lengths, n_fft: int, win: int, hop
     return fr
 
 
+# ----------------------------------------------------------------------------- silence trimming
+TRIM_MAX_LEN = 1 << 27         # samples per row
+TRIM_MAX_BLOCKS = 64           # frame_length / hop_length
+_TRIM_WORK = {}                # (device, stream) -> uint8 work buffer, grow-only
+
+
+def check_trim_args(top_db, frame_length, hop_length) -> float:
+    """The guards on the trimming parameters (host only, no device use) -> top_db as a float."""
+    import math
+    if isinstance(top_db, bool) or not isinstance(top_db, (int, float)) or not math.isfinite(top_db) or top_db <= 0:
+        raise ValueError(f"trim: top_db = {top_db!r}: a positive finite number of decibels is expected")
+    for name, v in (("frame_length", frame_length), ("hop_length", hop_length)):
+        if isinstance(v, bool) or not isinstance(v, int) or v <= 0:
+            raise ValueError(f"trim: {name} = {v!r}: a positive integer is expected")
+    if hop_length > TRIM_MAX_LEN or hop_length % 4 or frame_length % (2 * hop_length) or frame_length // hop_length > TRIM_MAX_BLOCKS:
+        raise ValueError(f"trim: frame_length = {frame_length}, hop_length = {hop_length}: hop_length must be a multiple of 4 and "
+                         f"frame_length a multiple of 2 * hop_length, at most {TRIM_MAX_BLOCKS} * hop_length")
+    return float(top_db)
+
+
+def _trim_work(nbytes: int, device) -> torch.Tensor:
+    """Grow-only work buffer per (device, stream), as :func:`_scratch`: a corpus of many batch sizes keeps the largest one only."""
+    device = torch.device(device)
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (device, torch.cuda.current_stream(device).cuda_stream)
+    t = _TRIM_WORK.get(key)
+    if t is None or t.numel() < nbytes:
+        t = torch.empty(bucket(nbytes), dtype=torch.uint8, device=device)
+        _TRIM_WORK[key] = t
+    return t
+
+
+def trim_bounds(x: torch.Tensor, top_db: float, frame_length: int, hop_length: int, lengths: Optional[Lengths] = None, power: bool = False):
+    """idv_trim_bounds: x [B, L] -> int32 bounds [B, 2] on the device (start, end of the non-silent span of every row); with ``power``
+    also the float64 frame powers [B, 1 + L // hop_length].  Nothing at or past lengths[b] is read."""
+    B, Lx = x.shape
+    if Lx < 1 or Lx > TRIM_MAX_LEN:
+        raise ValueError(f"trim: rows of {Lx} samples; 1 .. 2^27 are supported")
+    if B < 1 or B > 65535:
+        raise ValueError(f"trim: a batch of {B} rows; 1 .. 65535 are supported")
+    check_dev_f32(x, "x")
+    x = _ragged_rows(x)
+    nbytes = int(_ll_fn("idv_trim_work_bytes")(i(B), i(Lx), i(hop_length)))
+    if nbytes < 0:
+        raise ValueError(f"trim: a batch of {B} rows of {Lx} samples at hop {hop_length} is not supported")
+    work = _trim_work(nbytes, x.device)
+    bounds = torch.empty(B, 2, dtype=torch.int32, device=x.device)
+    P = torch.empty(B, 1 + Lx // hop_length, dtype=torch.float64, device=x.device) if power else None
+    call("idv_trim_bounds", p(x), ll(x.stride(0)), p(None if lengths is None else lengths.dev), i(B), i(Lx), i(frame_length),
+         i(hop_length), d(top_db), p(work), ll(work.numel()), p(bounds), p(P), ll(0 if P is None else P.stride(0)), stream_ptr())
+    return (bounds, P) if power else bounds
+
+
+def trim_gather(x: torch.Tensor, bounds: torch.Tensor, Lout: int) -> torch.Tensor:
+    """idv_trim_gather: y [B, Lout] with y[b, :end_b - start_b] = x[b, start_b:end_b] and zeros behind; ``bounds`` int32 [B, 2] on the
+    device, as :func:`trim_bounds` returns them."""
+    B = x.shape[0]
+    check_dev_f32(x, "x")
+    x = _ragged_rows(x)
+    y = torch.empty(B, Lout, dtype=torch.float32, device=x.device)
+    if Lout > 0:
+        call("idv_trim_gather", p(x), ll(x.stride(0)), p(bounds), i(B), i(Lout), p(y), ll(y.stride(0)), stream_ptr())
+    return y
+
+
 def mask_apply(mask: Planar, X: Planar, x_div: int = 1):
     """-> (pred planar, pred complex64 [B, F, T])."""
     B, F, T = mask.B, mask.F, mask.T

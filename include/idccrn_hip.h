@@ -891,6 +891,30 @@ int idv_spec_moments_update(const float* spec, const int* lens, int B, int hop, 
                             void* work, long long work_bytes, void* stream);
 int idv_spec_moments_merge(double* state, const double* other, int rows, void* stream);
 
+/* ---- silence trimming (trim.hip; inference.trim / trim_list, the trimmed segment index of dataset/dataload.py; additive entries:
+ * IDV_ABI_VERSION is unchanged).  The definition is librosa.effects.trim(y, top_db, ref=np.max, frame_length=frame,
+ * hop_length=hop) of librosa 0.10 restated (tests/trim_ref.py; parity with the package itself is unpinned).  For row b of n = lens[b]
+ * samples (lens: device int32[B], clamped to [0, L], or NULL: every row has L samples) of the padded batch x[B][ldx]:
+ *     T = 1 + n / hop frames; frame t covers samples [t hop - frame/2, t hop + frame/2), zeros outside [0, n);
+ *     P[t] = mean of the squares over the frame;  db[t] = 10 log10(max(1e-10, P[t])) - 10 log10(max(1e-10, max_t P[t]));
+ *     t0 / t1 the first / last frame with db[t] > -top_db:  bounds[b] = {t0 hop, min(n, (t1 + 1) hop)};  no such frame: {0, 0}.
+ * So a row of zeros (or wholly below 1e-10 in power) comes back untrimmed as {0, n}, and n = 0 gives {0, 0}.
+ * idv_trim_bounds: one wave sums the squares of one hop-sample block in double (fp32 squares are exact in double; 16-byte loads at
+ * any row pitch; the order of the sum depends on the sample's index in its block alone), one workgroup per row adds the frame / hop
+ * blocks of each frame in increasing order, divides by frame and compares in double.  Nothing at or past lens[b] and nothing of
+ * another row is read, no atomics: a row's result does not depend on B, the other rows, the padding or ldx.  work:
+ * idv_trim_work_bytes(B, L, hop) = 8 B ceil(L / hop) bytes, 8-byte aligned (host only; -1 for refused arguments).  bounds: device
+ * int32[B][2].  power: NULL, or device double[B][ldp] that receives P[b][0 .. T_b - 1] and zeros up to column L / hop.
+ * idv_trim_gather: y[b][i] = x[b][bounds[b][0] + i] for i < bounds[b][1] - bounds[b][0], zeros from there to Lout - 1; bounds are read
+ * on the device and must lie inside the row.
+ * IDV_EINVAL (before any GPU work) for a NULL pointer (lens and power may be NULL), B <= 0 or B > 65535, L <= 0 or L > 2^27, ldx < L,
+ * hop <= 0, hop > 2^27 or hop % 4 != 0, frame % (2 hop) != 0 or frame / hop > 64, top_db <= 0 or not finite, work_bytes too small,
+ * ldp < 1 + L / hop when power is given; for the gather Lout <= 0 or Lout > 2^27 and ldy < Lout. */
+long long idv_trim_work_bytes(int B, int L, int hop);
+int idv_trim_bounds(const float* x, long long ldx, const int* lens, int B, int L, int frame, int hop, double top_db, void* work,
+                    long long work_bytes, int* bounds, double* power, long long ldp, void* stream);
+int idv_trim_gather(const float* x, long long ldx, const int* bounds, int B, int Lout, float* y, long long ldy, void* stream);
+
 /* ---- time-Winograd convs with two co tiles per workgroup (cgemm_tw.hip, cgemm_tw2.hip; additive entries: IDV_ABI_VERSION is
  * unchanged).  A layer with an even number of 32-channel co tiles runs workgroups of eight waves that stage the raw input rows once
  * for two co tiles; the outputs are bit-identical to the one-co-tile kernels (the train-mode moment sums within the rounding of a
