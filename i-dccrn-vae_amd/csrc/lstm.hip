@@ -656,7 +656,8 @@ static long long hp_floats(int H, int B, int Jp) {
         if (m > n) n = m;
     }
     if (idv_lstm_stack2_f32_supported(H, B)) {
-        const long long m = (idv_lstm_stack2_f32_work_bytes(H, B) + 3) / 4;
+        // with the layer-0 projection inside the launch: one more arrive counter per time chunk, T <= Jp / B
+        const long long m = (idv_lstm_stack2_f32_proj_work_bytes(H, B, Jp / B) + 3) / 4;
         if (m > n) n = m;
     }
     return (n + 63) / 64 * 64;
@@ -673,7 +674,7 @@ extern "C" long long idv_clstm_train_work_floats(int H, int B, int T, int Jp) {
 
 static int clstm_fwd_impl(const float* x, int K, const float* wih0, const float* bih0, const float* whh0,
                           const float* wih1, const float* bih1, const float* whh1, int H, int B, int T, int Tp, int Jp,
-                          float* work, float* out, int flags, const void* wih1_bf16, const float* wih1_hh, void* stream) {
+                          float* work, float* out, int flags, const void* wih1_bf16, const float* wih1_hh, int proj_c0, void* stream) {
     if (!x || !wih0 || !bih0 || !whh0 || !wih1 || !bih1 || !whh1 || !work || !out) return IDV_EINVAL;
     if (H <= 0 || (H % 16) || K <= 0 || (K & 1) || B <= 0 || T <= 0 || Tp < T + 1 || Jp < B * Tp) return IDV_EINVAL;
     if ((size_t)3 * H * 16 * sizeof(float) > 160 * 1024) return IDV_EINVAL;
@@ -691,9 +692,14 @@ static int clstm_fwd_impl(const float* x, int K, const float* wih0, const float*
     float* c1 = save ? c0 + 4 * TB * H : nullptr;
     float* cstate = (save ? c1 : h1) + 4 * TB * H;       // [4][B][H], used by the per-step kernel only
     int rc;
+    // exact fp32 at H = 128 with W_ih of layer 1 in the recurrence's fragment order: both layers in one cooperative launch
+    // (below); unless flags bit 4 (16) keeps it hoisted, the layer-0 projection runs inside that launch where there is room for
+    // producer workgroups and T is longer than the opening phase (idv_lstm_stack2_f32_proj_split)
+    const bool stack2 = wih1_hh && !(flags & 1) && !(flags & 8) && idv_lstm_stack2_f32_supported(H, B) && 16LL * TB * H < 0xfffffe00LL;
+    const bool fused = stack2 && !(flags & 2) && !(flags & 16) && idv_lstm_stack2_f32_proj_split(H, B, T, K, proj_c0, nullptr, nullptr);
     // layer 0 input projection: both weight sets at once (M = 8H), one call per input part z
     // (flags bit 1: the caller already filled G through idv_lstm_proj_bf16x3)
-    for (int z = 0; z < 2 && !(flags & 2); ++z) {
+    for (int z = 0; z < 2 && !(flags & 2) && !fused; ++z) {
         rc = idv_pw_gemm(x + (size_t)z * K * Jp, K, wih0, bih0, nullptr, G + (size_t)z * TB * 8 * H, 8 * H, B, Tp, Jp, T, 1,
                          8 * H, stream);
         if (rc) return rc;
@@ -708,10 +714,14 @@ static int clstm_fwd_impl(const float* x, int K, const float* wih0, const float*
     // exact fp32 at H = 128 with W_ih of layer 1 in the recurrence's fragment order: both layers in one cooperative launch,
     // layer 1 one step behind layer 0, no hoisted layer-1 projection (lstm_stack2_f32.hip); the training forward keeps the
     // same buffers as the per-layer path (activated gates over G / in G1, cell states)
-    if (wih1_hh && !(flags & 1) && !(flags & 8) && idv_lstm_stack2_f32_supported(H, B) && 16LL * TB * H < 0xfffffe00LL) {
-        if ((rc = idv_lstm_stack2_f32(G, TB * 8 * H, 4LL * H, 8 * H, whh0, wih1_hh, whh1, bih1, h0, h1, H, B, T,
-                                      (void*)(cstate + 4LL * B * H), save ? G1 : nullptr, c0, c1, stream)))
-            return rc;
+    if (stack2) {
+        if (fused)
+            rc = idv_lstm_stack2_f32_proj(x, K, Tp, Jp, wih0, bih0, G, whh0, wih1_hh, whh1, bih1, h0, h1, H, B, T,
+                                          (void*)(cstate + 4LL * B * H), save ? G1 : nullptr, c0, c1, proj_c0, stream);
+        else
+            rc = idv_lstm_stack2_f32(G, TB * 8 * H, 4LL * H, 8 * H, whh0, wih1_hh, whh1, bih1, h0, h1, H, B, T,
+                                     (void*)(cstate + 4LL * B * H), save ? G1 : nullptr, c0, c1, stream);
+        if (rc) return rc;
         hipLaunchKernelGGL(lstm_combine_kernel, dim3((T + 31) / 32, (H + 31) / 32, B), dim3(256), 0, st, h1, H, B, T, Tp, Jp, out);
         const long long ntail2 = 2LL * H * B * (Tp - 1 - T);
         if (ntail2 > 0)
@@ -760,7 +770,7 @@ static int clstm_fwd_impl(const float* x, int K, const float* wih0, const float*
 extern "C" int idv_clstm_fwd(const float* x, int K, const float* wih0, const float* bih0, const float* whh0,
                              const float* wih1, const float* bih1, const float* whh1, int H, int B, int T, int Tp, int Jp,
                              float* work, float* out, int flags, const void* wih1_bf16, void* stream) {
-    return clstm_fwd_impl(x, K, wih0, bih0, whh0, wih1, bih1, whh1, H, B, T, Tp, Jp, work, out, flags, wih1_bf16, nullptr, stream);
+    return clstm_fwd_impl(x, K, wih0, bih0, whh0, wih1, bih1, whh1, H, B, T, Tp, Jp, work, out, flags, wih1_bf16, nullptr, -1, stream);
 }
 
 // idv_clstm_fwd with W_ih of layer 1 ALSO in the recurrence's fragment order (idv_pack_lstm_hh on weight_ih_l1; [4H][H] like
@@ -769,5 +779,13 @@ extern "C" int idv_clstm_fwd(const float* x, int K, const float* wih0, const flo
 extern "C" int idv_clstm_fwd2(const float* x, int K, const float* wih0, const float* bih0, const float* whh0,
                               const float* wih1, const float* bih1, const float* whh1, const float* wih1_hh, int H, int B, int T,
                               int Tp, int Jp, float* work, float* out, int flags, const void* wih1_bf16, void* stream) {
-    return clstm_fwd_impl(x, K, wih0, bih0, whh0, wih1, bih1, whh1, H, B, T, Tp, Jp, work, out, flags, wih1_bf16, wih1_hh, stream);
+    return clstm_fwd_impl(x, K, wih0, bih0, whh0, wih1, bih1, whh1, H, B, T, Tp, Jp, work, out, flags, wih1_bf16, wih1_hh, -1, stream);
+}
+
+// idv_clstm_fwd2 with the opening phase of the fused layer-0 projection chosen by the caller (tests and probes): proj_c0 = -1
+// automatic (idv_clstm_fwd2), else that many time chunks (lstm_proj_split.hpp); flags bit 4 (16) keeps the projection hoisted.
+extern "C" int idv_clstm_fwd3(const float* x, int K, const float* wih0, const float* bih0, const float* whh0,
+                              const float* wih1, const float* bih1, const float* whh1, const float* wih1_hh, int H, int B, int T,
+                              int Tp, int Jp, float* work, float* out, int flags, const void* wih1_bf16, int proj_c0, void* stream) {
+    return clstm_fwd_impl(x, K, wih0, bih0, whh0, wih1, bih1, whh1, H, B, T, Tp, Jp, work, out, flags, wih1_bf16, wih1_hh, proj_c0, stream);
 }

@@ -15,9 +15,24 @@
 // sc1 loads behind poll + barrier); all 8 x 4 x tiles workgroups must be resident (one per CU: 84 KB of LDS requested,
 // idv_lstm_stack2_f32_supported checks the count against idv_coop_max_workgroups()); bounded spins, NaN poison and the sticky
 // status word on time-out (coop.hpp).
+//
+// PROJ (idv_lstm_stack2_f32_proj): the layer-0 input projection G = W_ih0 x + b runs INSIDE the launch, on the CUs the
+// recurrence leaves empty, instead of as two hoisted idv_pw_gemm calls in front of it.  W_ih0 ([8H][K]) does not fit in
+// registers, so other workgroups contract it: the grid (one-dimensional then) is the 32 x tiles recurrence workgroups followed
+// by P PRODUCER workgroups.  G is cut into time chunks of PROJ_CH steps and those into the workgroup tiles of idv_pw_gemm
+// (cgemm_tile, the same K loop, hence the same bits); lstm_proj_split.hpp numbers the tiles and says who computes which:
+//   * opening phase: every workgroup of the launch takes tiles of the first C0 chunks, grid-strided;
+//   * then the recurrence workgroups load their weights and run as above, and the producers go on with the later chunks, in
+//     order, never waiting for anybody (on an abort they simply finish);
+//   * hand-off, the protocol above: a tile's rows of G are stored write-through (sc1), every wave drains its stores, the
+//     workgroup meets and adds one arrival to the CHUNK's counter (counters 2 x groups + c behind the recurrence's); a layer-0
+//     workgroup that enters a chunk polls that counter (bounded, abort flag) for the chunk's tile count and reads its rows of G
+//     with sc1 loads, issued at the top of the step and used after the reduce.  Layer 1 is untouched.
+// The training forward overwrites consumed rows of G with the activated gates: those rows are behind every producer.
 #include <cstdlib>
-#include "common.hpp"
+#include "cgemm.hpp"
 #include "coop.hpp"
+#include "lstm_proj_split.hpp"
 #include "../../include/idccrn_hip.h"
 
 namespace idv_stack2 {
@@ -25,6 +40,13 @@ namespace idv_stack2 {
 typedef int v4i __attribute__((ext_vector_type(4)));
 
 struct Args {
+    // PROJ: the projection's operands (idv_pw_gemm's: x planar [2 parts][K][Jp], fragments of W_ih0, bias) and its split
+    const float* x;
+    const float* wih0;
+    const float* bih0;
+    int K, Tp, Jp;
+    unsigned g_bytes;
+    ProjSplit ps;
     const float* g;           // layer-0 gate pre-activations (hoisted input projection), addressing as lstm.hip RecArgs
     long long g_run_z, g_run_s;
     int ldg;
@@ -47,7 +69,12 @@ struct Args {
 constexpr int H = 128, NSL = 4, UPW = 32;          // hidden size, workgroups per (layer, group), units per workgroup
 constexpr int MAX_GROUPS = 64, MAX_REP = 8;
 constexpr int SYNC_BYTES = idv_coop_sync_bytes(2 * MAX_GROUPS, MAX_REP);
+constexpr int PROJ_CCK = 32;                                                   // planes per K chunk of the projection tile
+constexpr int RED_FLOATS = 4 * 8 * 4 * 64;                                     // red[]; PROJ: the tile's two patch buffers behind it
+constexpr int proj_sync_bytes(int T) { return idv_coop_sync_bytes(2 * MAX_GROUPS + (T + PROJ_CH - 1) / PROJ_CH, MAX_REP); }
 
+// PROJ false: grid (2 NSL, 4 runs, tiles); true: (32 tiles + P), the recurrence workgroups first and in the same linear order
+template <bool PROJ>
 __global__ __launch_bounds__(256, 1) void lstm_stack2_f32_kernel(const Args a) {
     extern __shared__ __attribute__((aligned(16))) float red[];                // [4 waves][8 tiles][4 r][64 lanes]
     __shared__ int abort_sh;
@@ -57,7 +84,11 @@ __global__ __launch_bounds__(256, 1) void lstm_stack2_f32_kernel(const Args a) {
     const __amdgpu_buffer_rsrc_t h0r = __builtin_amdgcn_make_buffer_rsrc((void*)a.h0, 0, a.h0_bytes, 0x00020000);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int layer = blockIdx.x >> 2, sl = blockIdx.x & 3, run = blockIdx.y, tile = blockIdx.z;
+    const int nrec = 2 * NSL * 4 * a.tiles;
+    const bool producer = PROJ && (int)blockIdx.x >= nrec;
+    const int rid = producer ? 0 : (int)blockIdx.x;                            // PROJ: x + 8 (y + 4 z) of the three-dimensional grid
+    const int layer = PROJ ? (rid >> 2) & 1 : blockIdx.x >> 2, sl = blockIdx.x & 3;
+    const int run = PROJ ? (rid >> 3) & 3 : blockIdx.y, tile = PROJ ? rid >> 5 : blockIdx.z;
     const int z = run >> 1, s = run & 1;
     const int col = lane & 15, rq = lane >> 4;
     const int b0 = tile * 16;
@@ -70,6 +101,34 @@ __global__ __launch_bounds__(256, 1) void lstm_stack2_f32_kernel(const Args a) {
     // exchange regions: [layer][parity][run][Bpad][H]
     const unsigned hx_layer = (unsigned)layer * 2u * 4u * (unsigned)a.Bpad * (unsigned)H * 4u;
     const unsigned hx_par = 4u * (unsigned)a.Bpad * (unsigned)H * 4u;
+
+    // PROJ: the tiles of G this workgroup computes -- opening phase (every workgroup), then, producers only, the later chunks
+    const __amdgpu_buffer_rsrc_t gr = __builtin_amdgcn_make_buffer_rsrc((void*)a.g, 0, PROJ ? a.g_bytes : 0u, 0x00020000);
+    if constexpr (PROJ) {
+        if (idv_coop_withheld(a.cs)) return;
+        for (ProjWalk w = proj_walk(a.ps, (int)blockIdx.x, (int)gridDim.x);
+             proj_walk_tile(a.ps, w, producer ? (int)blockIdx.x - nrec : -1); w.i += w.stride) {
+            const ProjTile pt = proj_tile(a.ps, a.T, w.i);
+            CgemmArgs ca{};
+            ca.x0 = a.x + (size_t)pt.z * a.K * a.Jp;
+            ca.C0 = a.K / 2;
+            ca.Fin = 1; ca.Fout = 1;
+            ca.J = pt.steps * a.B; ca.Jp = a.Jp; ca.Tp = a.Tp;
+            ca.wfrag = a.wih0; ca.bias = a.bih0;
+            ca.out = const_cast<float*>(a.g) + (size_t)pt.z * a.g_run_z;
+            ca.M = 8 * H; ca.Mtiles = 8 * H / 32; ca.Cout = 8 * H;
+            ca.t_valid = a.T; ca.ldo = a.ldg; ca.nB = a.B;
+            // idv_pw_gemm's 4 x 1 form with 32 planes per K chunk instead of 8 (the same k order, hence the same bits): this
+            // workgroup has the CU to itself, and a chunk of 8 planes (0.43 us of MFMA) is shorter than the latency of its
+            // staging loads, which no second workgroup hides here: 133 us per tile against 102 us per tile and CU hoisted
+            cgemm_tile<IDV_PW, 4, 1, 2, 1, 2, PROJ_CCK, true, false, false>(ca, red + RED_FLOATS, pt.grp, 0, pt.mb,
+                                                                            CgemmTimeChunkCols{pt.t0, pt.steps});
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+            idv_coop_arrive(a.cs, idv_coop_counter(a.cs, 2 * groups + pt.chunk), tid);
+        }
+        if (producer) return;
+    }
 
     // W_hh slice (and, layer 1, the W_ih slice): this workgroup's 8 column tiles (unit blocks 2 sl, 2 sl + 1 x 4 gates), this
     // wave's 32 k, 8 consecutive k per lane (MFMA k-step j of lane (row, kq) is k = 32 w + 8 kq + j) -- as lstm_coop_f32.hip
@@ -135,11 +194,30 @@ __global__ __launch_bounds__(256, 1) void lstm_stack2_f32_kernel(const Args a) {
     for (int t = 0; t < a.T && !aborted; ++t) {
         float gpre[2][4];
         if (layer == 0) {
-            const float* gp = g + ((size_t)t * a.B + bclamp) * a.ldg + (2 * sl) * 64 + col;
+            if constexpr (PROJ) {
+                // a new chunk: all of its tiles must have arrived; then sc1 loads (the rows were stored inside this launch)
+                if (t % PROJ_CH == 0) {
+                    const int c = t / PROJ_CH;
+                    if (tid == 0)
+                        idv_coop_wait(idv_coop_replica(a.cs, idv_coop_counter(a.cs, 2 * groups + c), sl),
+                                      (unsigned)proj_chunk_tiles(a.B, a.T, c), abortf, &abort_sh);
+                    __syncthreads();
+                    if (abort_sh) { aborted = true; break; }
+                }
+                const unsigned off = (unsigned)(((size_t)z * a.g_run_z + (size_t)s * a.g_run_s + ((size_t)t * a.B + bclamp) * a.ldg +
+                                                 (2 * sl) * 64 + col) * 4u);
 #pragma unroll
-            for (int ub = 0; ub < 2; ++ub)
+                for (int ub = 0; ub < 2; ++ub)
 #pragma unroll
-                for (int gg = 0; gg < 4; ++gg) gpre[ub][gg] = gp[ub * 64 + 16 * gg];
+                    for (int gg = 0; gg < 4; ++gg)
+                        gpre[ub][gg] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(gr, off + (ub * 64 + 16 * gg) * 4u, 0, 16));
+            } else {
+                const float* gp = g + ((size_t)t * a.B + bclamp) * a.ldg + (2 * sl) * 64 + col;
+#pragma unroll
+                for (int ub = 0; ub < 2; ++ub)
+#pragma unroll
+                    for (int gg = 0; gg < 4; ++gg) gpre[ub][gg] = gp[ub * 64 + 16 * gg];
+            }
         } else {
 #pragma unroll
             for (int ub = 0; ub < 2; ++ub)
@@ -300,5 +378,65 @@ extern "C" int idv_lstm_stack2_f32(const float* g, long long g_run_z, long long 
     a.cs.nrep = 4;
     a.B = B; a.T = T; a.Bpad = (int)Bpad; a.tiles = tiles;
     const size_t smem = 84 * 1024;                   // > half a CU's LDS: one workgroup per CU (red[] needs 32 KB)
-    return idv_coop_launch(lstm_stack2_f32_kernel, dim3(2 * NSL, 4, tiles), smem, st, work, SYNC_BYTES, a);
+    return idv_coop_launch(lstm_stack2_f32_kernel<false>, dim3(2 * NSL, 4, tiles), smem, st, work, SYNC_BYTES, a);
+}
+
+// ---- the layer-0 projection inside the launch ----------------------------------------------------------------------------------
+// 1: idv_lstm_stack2_f32_proj takes (H, B, T, K); *c0 / *P (may be NULL): chunks of the opening phase and producer workgroups.
+// 0: no room for producers beside the recurrence (large B), every chunk in the opening phase (short T), a G beyond 32-bit
+// buffer offsets, or IDV_LSTM_PROJ_OVERLAP=0 -- the projection stays hoisted (idv_pw_gemm in front of idv_lstm_stack2_f32).
+// force_c0: -1 automatic; tests: 0 .. chunks (clamped), the opening phase (the chunk count: all of G in it, one idle producer).
+extern "C" int idv_lstm_stack2_f32_proj_split(int H, int B, int T, int K, int force_c0, int* c0, int* P) {
+    static const bool on = [] { const char* e = getenv("IDV_LSTM_PROJ_OVERLAP"); return !e || e[0] != '0'; }();
+    if (c0) *c0 = 0;
+    if (P) *P = 0;
+    if (!on || T <= 0 || K <= 0 || (K & 1) || !idv_lstm_stack2_f32_supported(H, B)) return 0;
+    if (64LL * T * B * H >= 0xfffffe00LL) return 0;
+    const ProjSplit ps = proj_split(B, T, K, 2 * 4 * 4 * ((B + 15) / 16), idv_coop_max_workgroups(), force_c0);
+    if (c0) *c0 = ps.c0;
+    if (P) *P = ps.P;
+    return ps.P > 0;
+}
+
+// sync words (with one counter per chunk of Tmax steps) + the exchange buffers
+extern "C" long long idv_lstm_stack2_f32_proj_work_bytes(int H, int B, int Tmax) {
+    const long long Bpad = (B + 15) / 16 * 16;
+    return idv_stack2::proj_sync_bytes(Tmax < 1 ? 1 : Tmax) + 2LL * 2 * 4 * Bpad * H * 4;
+}
+
+// idv_lstm_stack2_f32 that computes G itself: x planar [2 parts][K planes][Jp] (column b Tp + 1 + t), wih0 / bih0: idv_pack_lstm_ih
+// of layer 0 (both weight sets, M = 8H); g: [2 parts][T*B][8H], written and (training forward) overwritten with the activated
+// gates exactly as by idv_pw_gemm + idv_lstm_stack2_f32; work: idv_lstm_stack2_f32_proj_work_bytes(H, B, Tmax >= T) bytes.
+// IDV_EINVAL where idv_lstm_stack2_f32_proj_split says 0.
+extern "C" int idv_lstm_stack2_f32_proj(const float* x, int K, int Tp, int Jp, const float* wih0, const float* bih0, float* g,
+                                        const float* whh0, const float* wih1_hh, const float* whh1, const float* bias1, float* h0,
+                                        float* hout, int H, int B, int T, void* work, float* gsave1, float* csave0, float* csave1,
+                                        int force_c0, void* stream) {
+    using namespace idv_stack2;
+    if (!x || !wih0 || !bih0 || !g || !whh0 || !wih1_hh || !whh1 || !bias1 || !h0 || !hout || !work || T <= 0 || Tp < T + 1 ||
+        (long long)Jp < (long long)B * Tp || !idv_lstm_stack2_f32_proj_split(H, B, T, K, force_c0, nullptr, nullptr))
+        return IDV_EINVAL;
+    if ((gsave1 != nullptr) != (csave0 != nullptr) || (csave0 != nullptr) != (csave1 != nullptr)) return IDV_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(work) & 15) || (reinterpret_cast<uintptr_t>(h0) & 15) || (reinterpret_cast<uintptr_t>(hout) & 15) ||
+        (reinterpret_cast<uintptr_t>(g) & 3))
+        return IDV_EINVAL;
+    const long long TB = (long long)T * B;
+    const int tiles = (B + 15) / 16;
+    const long long Bpad = 16LL * tiles;
+    const int sync_bytes = proj_sync_bytes(T);
+    Args a{};
+    a.x = x; a.wih0 = wih0; a.bih0 = bih0; a.K = K; a.Tp = Tp; a.Jp = Jp;
+    a.g_bytes = (unsigned)(64LL * TB * H);
+    a.ps = proj_split(B, T, K, 2 * NSL * 4 * tiles, idv_coop_max_workgroups(), force_c0);
+    a.g = g; a.g_run_z = TB * 8 * H; a.g_run_s = 4LL * H; a.ldg = 8 * H;
+    a.whh0 = whh0; a.wih1 = wih1_hh; a.whh1 = whh1; a.bias1 = bias1;
+    a.h0 = h0; a.h0_bytes = (unsigned)(16LL * TB * H); a.hout = hout;
+    a.gsave1 = gsave1; a.csave0 = csave0; a.csave1 = csave1;
+    a.hx = (float*)((char*)work + sync_bytes);
+    a.hx_bytes = (unsigned)(2LL * 2 * 4 * Bpad * H * 4);
+    a.cs.nrep = 4;
+    a.B = B; a.T = T; a.Bpad = (int)Bpad; a.tiles = tiles;
+    const size_t smem = 84 * 1024;                   // one workgroup per CU: red[] 32 KB, the tile's patch buffers 4.2 KB behind it
+    return idv_coop_launch(lstm_stack2_f32_kernel<true>, dim3(2 * NSL * 4 * tiles + a.ps.P), smem, (hipStream_t)stream, work,
+                           sync_bytes, a);
 }

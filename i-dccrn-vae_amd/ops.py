@@ -482,6 +482,12 @@ def side_streams(n: int, device):
     return pool[:n]
 
 
+def on_side_stream(device) -> bool:
+    """True while the current stream of `device` is one of side_streams(): inside a part of a split batch."""
+    pool = _SIDE_STREAMS.get(torch.device(device).index or 0)
+    return bool(pool) and any(torch.cuda.current_stream(device) == s for s in pool)
+
+
 def repeat_batch(x: Planar, n: int) -> Planar:
     """Each utterance n times in a row (`skip.repeat_interleave(n, 0)`, reference pvae_module.py:2563-2567) as a new
     planar buffer, so the repeated-skip decoder can use the kernels that take x1_div == 1 sources (bf16x3 / images)."""
@@ -765,6 +771,10 @@ def clstm(x: Planar, packed0: LstmPack, packed1: LstmPack, H: int) -> Planar:
     flags = 1 if PRECISION == "bf16x3" else 0
     if not LSTM_PERSISTENT:
         flags |= 8
+    if on_side_stream(x.buf.device):
+        # sub-batch pipelining: the other part's encoder runs on the CUs this part's recurrence leaves empty, so the layer-0
+        # projection stays hoisted instead of taking them for its producer workgroups (csrc/lstm_stack2_f32.hip)
+        flags |= 16
     if (flags & 1) and packed0.wih16 is not None:
         # layer-0 input projection on the bf16 MFMA: K-major split image of the 2K input planes, then G into `work`
         kimg = KImage.from_planes(x.ptr(), 2 * K, x.B * x.Tp, x.Jp, x.buf.device)

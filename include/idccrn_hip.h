@@ -322,6 +322,25 @@ int idv_clstm_fwd2(const float* x, int K, const float* wih0, const float* bih0, 
                    const float* bih1, const float* whh1, const float* wih1_hh, int H, int B, int T, int Tp, int Jp, float* work,
                    float* out, int flags, const void* wih1_bf16, void* stream);
 
+/* The layer-0 input projection INSIDE that cooperative launch (lstm_stack2_f32.hip, lstm_proj_split.hpp): producer workgroups
+ * on the CUs the recurrence leaves empty compute G = W_ih0 x + b in time chunks of 16 steps, after an opening phase in which
+ * every workgroup of the launch computes the first c0 chunks; G, the saved buffers and the output have the bits of idv_pw_gemm +
+ * idv_lstm_stack2_f32.  idv_lstm_stack2_f32_proj_split: 1 where this form is taken (there is room for producers and T is longer
+ * than the opening phase; IDV_LSTM_PROJ_OVERLAP=0 turns it off), *c0 / *P (may be NULL): the opening chunks and the producer
+ * count; force_c0: -1 automatic, tests: the opening phase, clamped to the chunk count.  x, wih0, bih0: as idv_clstm_fwd;
+ * g: [2 parts][T*B][8H]; work: idv_lstm_stack2_f32_proj_work_bytes(H, B, Tmax >= T) bytes; the rest as idv_lstm_stack2_f32.
+ * idv_clstm_fwd2 takes this form where the split says 1 unless flags bit 4 (value 16) keeps the projection hoisted;
+ * idv_clstm_fwd3 = idv_clstm_fwd2 + proj_c0 (= force_c0). */
+int idv_lstm_stack2_f32_proj_split(int H, int B, int T, int K, int force_c0, int* c0, int* P);
+long long idv_lstm_stack2_f32_proj_work_bytes(int H, int B, int Tmax);
+int idv_lstm_stack2_f32_proj(const float* x, int K, int Tp, int Jp, const float* wih0, const float* bih0, float* g,
+                             const float* whh0, const float* wih1_hh, const float* whh1, const float* bias1, float* h0,
+                             float* hout, int H, int B, int T, void* work, float* gsave1, float* csave0, float* csave1,
+                             int force_c0, void* stream);
+int idv_clstm_fwd3(const float* x, int K, const float* wih0, const float* bih0, const float* whh0, const float* wih1,
+                   const float* bih1, const float* whh1, const float* wih1_hh, int H, int B, int T, int Tp, int Jp, float* work,
+                   float* out, int flags, const void* wih1_bf16, int proj_c0, void* stream);
+
 /* Split-precision (bf16x3) form of the layer-0 input projection inside idv_clstm_fwd (nn.LSTM weight_ih_l0 of
  * lstm_re / lstm_im applied to the real / imaginary input, complex_progress.py:50-74): ximg = K-major split image of
  * the 2*K input planes (idv_planar_to_kimage: octet o = planes 8o..8o+7, layout as "split image" with F = 1),
