@@ -501,6 +501,7 @@ class _VAEEncoderBase(nn.Module):
             lat = lstm.forward_planar(lat)
         stft_x = X.tensor4()
         stft_x._idv = X
+        stft_x._idv_hop = self.stft.hop_length                       # latent.frames_of: frames per row from X.lengths
         return lat, [tag5(s) for s in skips], top.C, top.F, stft_x
 
 

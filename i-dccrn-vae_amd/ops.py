@@ -1245,6 +1245,57 @@ def miu_dist(q1: Planar, off1: int, q2: Planar, off2: int, zdim: int) -> torch.T
     return out[0]
 
 
+# latent-space report (csrc/latent.hip; latent.py): q, q1, q2 are F == 1 planar latents, off the channel offsets (miu, log_sigma, delta),
+# frames an int32 device tensor [B] or None, T the frames per row of the reference-shaped tensor.
+def latent_row_stats(q: Planar, off, zdim: int, frames, B: int, T: int) -> torch.Tensor:
+    out = torch.empty(B, 13, dtype=torch.float64, device=q.buf.device)
+    work = torch.empty(B * zdim * 10, dtype=torch.float64, device=q.buf.device)
+    call("idv_latent_row_stats", q.ptr(), i(q.C), i(q.Jp), i(q.Tp), i(off[0]), i(off[1]), i(off[2]), i(zdim), p(frames), i(B), i(T),
+         p(work), p(out), stream_ptr())
+    return out
+
+
+def latent_pair_dist(q1: Planar, off1, q2: Planar, off2, zdim: int, frames, B: int, T: int) -> torch.Tensor:
+    out = torch.empty(B, 3, dtype=torch.float64, device=q1.buf.device)
+    work = torch.empty(B * zdim * 3, dtype=torch.float64, device=q1.buf.device)
+    call("idv_latent_pair_dist", q1.ptr(), i(q1.C), i(q1.Jp), i(q1.Tp), i(off1[0]), i(off1[1]), i(off1[2]), q2.ptr(), i(q2.C), i(q2.Jp),
+         i(q2.Tp), i(off2[0]), i(off2[1]), i(off2[2]), i(zdim), p(frames), i(B), i(T), p(work), p(out), stream_ptr())
+    return out
+
+
+def miu_moments_chunk() -> int:
+    return int(L.lib().idv_miu_moments_chunk())
+
+
+def miu_moments_update(q: Planar, off: int, zdim: int, frames, B: int, T: int, state: torch.Tensor):
+    nbytes = int(_ll_fn("idv_miu_moments_work_bytes")(i(zdim), i(B), i(T)))
+    if nbytes < 0:
+        raise ValueError(f"miu moments: a batch of {B} rows of {T} frames at zdim = {zdim} is not supported")
+    work = torch.empty(nbytes // 8, dtype=torch.float64, device=state.device)
+    call("idv_miu_moments_update", q.ptr(), i(q.C), i(q.Jp), i(q.Tp), i(off), i(zdim), p(frames), i(B), i(T), p(state), p(work),
+         ll(nbytes), stream_ptr())
+
+
+def miu_moments_merge(state: torch.Tensor, other: torch.Tensor, zdim: int):
+    call("idv_miu_moments_merge", p(state), p(other), i(zdim), stream_ptr())
+
+
+def latent_set_moments(x: torch.Tensor) -> torch.Tensor:
+    """x [N, zdim, 2] contiguous fp32 -> double [2, 2 zdim]: the mean and the population variance of every column."""
+    N, D = x.shape[0], x.shape[1] * 2
+    mom = torch.empty(2, D, dtype=torch.float64, device=x.device)
+    call("idv_latent_set_moments", p(x), i(N), i(D), p(mom), stream_ptr())
+    return mom
+
+
+def latent_silhouette(x1: torch.Tensor, x2: torch.Tensor, mom1: torch.Tensor, mom2: torch.Tensor) -> torch.Tensor:
+    N1, N2, D = x1.shape[0], x2.shape[0], x1.shape[1] * 2
+    work = torch.empty(N1 + N2, dtype=torch.float64, device=x1.device)
+    out = torch.empty(6, dtype=torch.float64, device=x1.device)
+    call("idv_latent_silhouette", p(x1), i(N1), p(x2), i(N2), i(D), p(mom1), p(mom2), p(work), p(out), stream_ptr())
+    return out
+
+
 def cbn_stats(act: Planar) -> torch.Tensor:
     """Moment sums [C][5] (double) of a planar activation, for a stand-alone train-mode batch norm."""
     stats = torch.zeros(act.C, 5, dtype=torch.float64, device=act.buf.device)

@@ -934,6 +934,41 @@ int idv_trim_bounds(const float* x, long long ldx, const int* lens, int B, int L
                     long long work_bytes, int* bounds, double* power, long long ldp, void* stream);
 int idv_trim_gather(const float* x, long long ldx, const int* bounds, int B, int Lout, float* y, long long ldy, void* stream);
 
+/* ---- latent-space report (latent.hip; latent.py; additive entries: IDV_ABI_VERSION is unchanged).  A latent is read
+ * in place from a planar buffer q[2][H][Jp] with F = 1: channel off + h of frame t of row b is q[(ri H + off + h) Jp + b Tp + t + 1].
+ * frames: device int32[B], the valid frames of each row, clamped to [1, T] (NULL: T each); nothing at or past frame frames[b] and no
+ * guard column is read.  Elementwise arithmetic is fp32 as the reference's, every sum is double in a fixed order, no atomics.
+ *
+ * idv_latent_row_stats: out[b][13] = kl, then (min, max, mean, norm) of vrr, of vri and of vii (pretrained_vaes/test_prevae.py:25-74,
+ * 171-197 per row).  idv_latent_pair_dist: out[b][3] = dis_mean, dis_sigma, dis_delta between two posteriors
+ * (nsvae_dccrn/test_nsvae_se.py:27-35).  One wave per (row, channel), its lanes the frames t = lane, lane + 64, ..., then the xor
+ * butterfly; a second kernel, one wave per row, adds the channels h = lane, lane + 64 and runs the butterfly again.  A row's value
+ * depends on frames[b] and zdim alone, bit for bit.  work: device double[B zdim 10] (row_stats) / [B zdim 3] (pair_dist).
+ * zdim % 16 == 0, 16 <= zdim <= 128, B <= 65535. */
+int idv_latent_row_stats(const float* q, int H, int Jp, int Tp, int off_miu, int off_ls, int off_dl, int zdim, const int* frames, int B,
+                         int T, double* work, double* out, void* stream);
+int idv_latent_pair_dist(const float* qa, int Ha, int Jpa, int Tpa, int oa_miu, int oa_ls, int oa_dl, const float* qb, int Hb, int Jpb,
+                         int Tpb, int ob_miu, int ob_ls, int ob_dl, int zdim, const int* frames, int B, int T, double* work, double* out,
+                         void* stream);
+/* Running mean and co-moments of the 2 zdim rows (real channels, then imaginary channels) of miu over the valid frames.
+ * state: device double[1 + 2 zdim + (2 zdim)^2] = (n, mean[2 zdim], C[2 zdim][2 zdim]), zeroed by the caller; cov = C / n.  Only the
+ * 32 x 32 blocks on and above the block diagonal of C are written (the rest stays as the caller left it).  The frames are numbered
+ * b T + t and cut into chunks of idv_miu_moments_chunk() numbers, whatever Tp and Jp are.  Per chunk: the count and mean of the valid
+ * frames, then X X^T of the values centred on that mean (invalid columns zero) on v_mfma_f64_16x16x4_f64 through LDS; the chunks and then
+ * the state are folded in increasing order by Chan's formula C = Ca + Cb + (na nb / n) d d^T.  work: idv_miu_moments_work_bytes bytes
+ * (-1 for refused arguments), 8-byte aligned.  idv_miu_moments_merge: state <- Chan merge of state and another state. */
+int idv_miu_moments_chunk(void);
+long long idv_miu_moments_work_bytes(int zdim, int B, int T);
+int idv_miu_moments_update(const float* q, int H, int Jp, int Tp, int off_miu, int zdim, const int* frames, int B, int T, double* state,
+                           void* work, long long work_bytes, void* stream);
+int idv_miu_moments_merge(double* state, const double* other, int zdim, void* stream);
+/* Sets of latent vectors x[N][D] (D = 2 zdim floats each, contiguous).  idv_latent_set_moments: mom[2 D] = the mean and the population
+ * variance of every column.  idv_latent_silhouette (test_nsvae_se.py:39-50, 482-500): out[6] = sc, mean_dis, then the variance averaged
+ * over the even (real) and the odd (imaginary) columns of set 1 and of set 2; work: double[N1 + N2], the score of every vector. */
+int idv_latent_set_moments(const float* x, int N, int D, double* mom, void* stream);
+int idv_latent_silhouette(const float* x1, int N1, const float* x2, int N2, int D, const double* mom1, const double* mom2, double* work,
+                          double* out, void* stream);
+
 /* ---- time-Winograd convs with two co tiles per workgroup (cgemm_tw.hip, cgemm_tw2.hip; additive entries: IDV_ABI_VERSION is
  * unchanged).  A layer with an even number of 32-channel co tiles runs workgroups of eight waves that stage the raw input rows once
  * for two co tiles; the outputs are bit-identical to the one-co-tile kernels (the train-mode moment sums within the rounding of a
