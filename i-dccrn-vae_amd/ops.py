@@ -1115,6 +1115,71 @@ def trim_gather(x: torch.Tensor, bounds: torch.Tensor, Lout: int) -> torch.Tenso
     return y
 
 
+# ----------------------------------------------------------------------------- mixture synthesis
+MIX_MAX_LEN = 1 << 27          # samples per row
+MIX_WIN_FIELDS = 6             # IDV_MIX_WIN_FIELDS: max|c|, sum c^2, max|v|, sum v^2, max|y0|, sum y0^2 per window
+MIX_ROW_FIELDS = 16            # IDV_MIX_ROW_FIELDS, the IDV_MIX_* indices of include/idccrn_hip.h:
+MIX_FIELD = {"max_c": 0, "sum_c2": 1, "max_v": 2, "sum_v2": 3, "act_c2": 4, "act_v2": 5, "active": 6, "a": 7, "b": 8, "sum_y2": 9,
+             "max_y": 10, "g_clean": 11, "g_noise": 12, "level_db": 13, "clipped": 14, "len": 15}
+_MIX_WORK = {}                 # (device, stream) -> uint8 work buffer, grow-only
+
+
+class MixRows(NamedTuple):
+    """Where the kernels of csrc/mix.hip find their B rows: ``clean`` / ``noise`` are fp32 device tensors, either a padded batch
+    ([B, L] / [B, Ln], ``*_off`` None) or a flat pool with ``*_off`` the int64 device table of every row's first sample; ``table`` is
+    the int32 device tensor [3, B] of (lens, noise_lens, phase)."""
+    clean: torch.Tensor
+    clean_off: Optional[torch.Tensor]
+    noise: torch.Tensor
+    noise_off: Optional[torch.Tensor]
+    table: torch.Tensor
+    B: int
+    L: int
+    Ln: int
+
+    def args(self):
+        ldc = 0 if self.clean_off is not None else self.clean.stride(0)
+        ldn = 0 if self.noise_off is not None else self.noise.stride(0)
+        return (p(self.clean), p(self.clean_off), ll(ldc), p(self.noise), p(self.noise_off), ll(ldn), p(self.table[0]), p(self.table[1]),
+                p(self.table[2]), i(self.B), i(self.L), i(self.Ln))
+
+
+def _mix_work(nbytes: int, device) -> torch.Tensor:
+    """Grow-only work buffer per (device, stream), as :func:`_trim_work`."""
+    device = torch.device(device)
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (device, torch.cuda.current_stream(device).cuda_stream)
+    t = _MIX_WORK.get(key)
+    if t is None or t.numel() < nbytes:
+        t = torch.empty(bucket(nbytes), dtype=torch.uint8, device=device)
+        _MIX_WORK[key] = t
+    return t
+
+
+def mix_gains(rows: MixRows, par: torch.Tensor, segmental: bool, target_db: float, clip: float, win: int, thresh_db: float):
+    """idv_mix_gains: ``par`` float64 [B, 2] = (snr_db, level_db) on the device -> (the float64 row records [B, MIX_ROW_FIELDS],
+    the float64 window sums [B, ceil(L / win), MIX_WIN_FIELDS]).  The window sums are a view of the work buffer of this device and
+    stream: the next call overwrites them."""
+    check_dev_f32(rows.clean, "clean")
+    check_dev_f32(rows.noise, "noise", rows.clean.device)
+    nbytes = int(_ll_fn("idv_mix_work_bytes")(i(rows.B), i(rows.L), i(win)))
+    if nbytes < 0:
+        raise ValueError(f"mix: a batch of {rows.B} rows of {rows.L} samples in windows of {win} is not supported")
+    work = _mix_work(nbytes, rows.clean.device)
+    rec = torch.empty(rows.B, MIX_ROW_FIELDS, dtype=torch.float64, device=rows.clean.device)
+    call("idv_mix_gains", *rows.args(), p(par), i(1 if segmental else 0), d(target_db), d(clip), i(win), d(thresh_db), p(work),
+         ll(work.numel()), p(rec), stream_ptr())
+    return rec, work[:nbytes].view(torch.float64).view(rows.B, -1, MIX_WIN_FIELDS)
+
+
+def mix_write(rows: MixRows, rec: torch.Tensor):
+    """idv_mix_write: -> (noisy, clean_out, noise_out), each fp32 [B, L] with zeros from a row's length on."""
+    out = torch.empty(3, rows.B, rows.L, dtype=torch.float32, device=rows.clean.device)
+    call("idv_mix_write", *rows.args(), p(rec), p(out[0]), p(out[1]), p(out[2]), ll(rows.L), stream_ptr())
+    return out[0], out[1], out[2]
+
+
 def mask_apply(mask: Planar, X: Planar, x_div: int = 1):
     """-> (pred planar, pred complex64 [B, F, T])."""
     B, F, T = mask.B, mask.F, mask.T

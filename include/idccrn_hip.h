@@ -969,6 +969,57 @@ int idv_latent_set_moments(const float* x, int N, int D, double* mom, void* stre
 int idv_latent_silhouette(const float* x1, int N1, const float* x2, int N2, int D, const double* mom1, const double* mom2, double* work,
                           double* out, void* stream);
 
+/* ---- mixture synthesis (mix.hip; dataset/mix.py snr_mix / DynamicMixtures; additive entries: IDV_ABI_VERSION is unchanged; DESIGN.md
+ * 3.12).  The definition is normalize / snr_mixer / segmental_snr_mixer of the DNS-Challenge synthesizer restated (tests/mix_ref.py;
+ * parity with the package itself is unpinned), except that a window's level is the true dB of its mean square.  EPS = 2^-52.  Row b:
+ * n = lens[b] clean samples c (lens: device int32[B], clamped to [0, L], or NULL: L each) at clean + clean_off[b] (device int64[B]
+ * sample offsets: rows in place in a packed pool) or, clean_off == NULL, at clean + b ldc; the noise row likewise with m = noise_lens[b]
+ * samples (clamped to [1, Ln]; NULL: Ln each), read cyclically from phase[b] (taken mod m; NULL: 0): v[i] = noise_b[(phase + i) mod m].
+ *     c1 = c / (max|c| + EPS), c2 = c1 10^(target_db / 20) / (rms(c1) + EPS), the same for v1, v2 (rms over the n samples);
+ *     rc, rv = rms(c2), rms(v2); segmental: over the samples of the windows [k win, min(n, (k + 1) win)) with
+ *     10 log10(mean(v2^2) + EPS) > thresh_db (both EPS if there is none);
+ *     v3 = v2 rc / 10^(snr_db / 20) / (rv + EPS), y = c2 + v3;  y, c2, v3 are scaled by 10^(level_db / 20) / (rms(y) + EPS) and, where
+ *     max|y| > clip then, divided by max|y| / (clip - EPS).
+ * par: device double[B][2] = (snr_db, level_db) of every row.  Everything being linear, idv_mix_gains reduces each row to
+ * rows[b][IDV_MIX_ROW_FIELDS] (device doubles, the indices below): one wave per window writes max|c|, sum c^2, max|v|, sum v^2 in double
+ * (fp32 squares are exact in double; 16-byte loads at any base alignment and row pitch), one workgroup per row combines them and decides
+ * the active windows, a second window pass forms sum y0^2 and max|y0| of y0 = a c + b v from the samples themselves, a second row
+ * kernel applies level and clip rule.  work: idv_mix_work_bytes(B, L, win) = 8 IDV_MIX_WIN_FIELDS B ceil(L / win) bytes, 8-byte aligned
+ * (host only; -1 for refused arguments); afterwards it holds per row and window max|c|, sum c^2, max|v|, sum v^2, max|y0|, sum y0^2 (zeros
+ * for the windows past a row's end).  idv_mix_write: noisy = float(g_clean c + g_noise v), clean_out = float(g_clean c), noise_out =
+ * float(g_noise v), each ONE fp32 rounding of a double expression of the input samples, zeros from n to L - 1; the three outputs are
+ * [B][ldy].  The place of a sample in every sum depends on its index in its window alone, nothing at or past lens[b] is read, no atomics:
+ * a row's result does not depend on B, the other rows, the padding, the pitch or the alignment.
+ * IDV_EINVAL (before any GPU work) for a NULL pointer (clean_off, noise_off, lens, noise_lens, phase may be NULL), B <= 0 or B > 65535,
+ * L or Ln <= 0 or > 2^27, ldc < L / ldn < Ln where the offsets are NULL, win < 4, win > 2^27 or win % 4 != 0, a parameter that is not
+ * finite, clip <= 2 EPS, segmental not 0 or 1, work_bytes too small, ldy < L, a misaligned pointer. */
+#define IDV_MIX_WIN_FIELDS 6
+#define IDV_MIX_ROW_FIELDS 16
+#define IDV_MIX_MAX_C 0      /* max|c|, sum c^2, max|v|, sum v^2 over the row */
+#define IDV_MIX_SUM_C2 1
+#define IDV_MIX_MAX_V 2
+#define IDV_MIX_SUM_V2 3
+#define IDV_MIX_ACT_C2 4     /* sum c^2, sum v^2 and the number of samples of the active windows (the whole row in plain mode) */
+#define IDV_MIX_ACT_V2 5
+#define IDV_MIX_ACTIVE 6
+#define IDV_MIX_A 7          /* y0 = a c + b v, the mixture before the level step */
+#define IDV_MIX_B 8
+#define IDV_MIX_SUM_Y2 9     /* sum y0^2, max|y0| */
+#define IDV_MIX_MAX_Y 10
+#define IDV_MIX_G_CLEAN 11   /* clean_out = g_clean c, noise_out = g_noise v */
+#define IDV_MIX_G_NOISE 12
+#define IDV_MIX_LEVEL_DB 13  /* 20 log10(rms(y) + EPS) of the final y */
+#define IDV_MIX_CLIPPED 14   /* 1.0 where the clip rule applied */
+#define IDV_MIX_LEN 15       /* n */
+long long idv_mix_work_bytes(int B, int L, int win);
+int idv_mix_gains(const float* clean, const long long* clean_off, long long ldc, const float* noise, const long long* noise_off,
+                  long long ldn, const int* lens, const int* noise_lens, const int* phase, int B, int L, int Ln, const double* par,
+                  int segmental, double target_db, double clip, int win, double thresh_db, void* work, long long work_bytes, double* rows,
+                  void* stream);
+int idv_mix_write(const float* clean, const long long* clean_off, long long ldc, const float* noise, const long long* noise_off,
+                  long long ldn, const int* lens, const int* noise_lens, const int* phase, int B, int L, int Ln, const double* rows,
+                  float* noisy, float* clean_out, float* noise_out, long long ldy, void* stream);
+
 /* ---- time-Winograd convs with two co tiles per workgroup (cgemm_tw.hip, cgemm_tw2.hip; additive entries: IDV_ABI_VERSION is
  * unchanged).  A layer with an even number of 32-channel co tiles runs workgroups of eight waves that stage the raw input rows once
  * for two co tiles; the outputs are bit-identical to the one-co-tile kernels (the train-mode moment sums within the rounding of a
