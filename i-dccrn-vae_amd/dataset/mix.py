@@ -3,9 +3,13 @@
 
   * :func:`snr_mix`  mixes a padded batch of clean rows with cyclically read noise rows at a given SNR and level, per row;
   * :class:`SignalPool`  holds recordings of any lengths in one device buffer;
-  * :func:`mix_draw`  mixes rows read in place from two pools;
+  * :func:`mix_draw`  mixes rows read in place from two pools; ``clean=``: a [rows, samples] device tensor stands in for the clean
+    rows (the reverberant speech of dataset/reverb.py ``reverb_draw``);
   * :func:`draw_batch`  names the rows and parameters of training batch k on the host, a function of ``(seed, k)`` alone;
-  * :class:`DynamicMixtures`  yields ``(noisy, clean, noise)`` like ``dataload.SyntheticMixtures``, mixed afresh from two pools.
+  * :class:`DynamicMixtures`  yields ``(noisy, clean, noise)`` like ``dataload.SyntheticMixtures``, mixed afresh from two pools; with
+    ``rir_pool=`` a ``RirPool`` the rows that ``draw_reverb`` picks (``p_reverb``) are convolved with a room impulse response before
+    they are mixed, and ``target="early"`` yields as ``clean`` the speech under the direct sound and ``early_ms``
+    milliseconds of reflections instead of the whole response.
 
 The definition is ``normalize`` / ``snr_mixer`` / ``segmental_snr_mixer`` of the DNS-Challenge synthesizer, restated in float64 in
 tests/mix_ref.py (parity with that package is unpinned: it is not installed where this was written), with one deliberate difference: a
@@ -222,9 +226,11 @@ def draw_batch(k: int, seed: int, clean_lengths: Sequence[int], noise_lengths: S
 
 
 def mix_draw(clean_pool: SignalPool, noise_pool: SignalPool, draw: Draw, samples: int, segmental: bool = False, target_db: float = -25.0,
-             clip: float = 0.99, win: int = 1600, thresh_db: float = -50.0, stats: bool = False):
+             clip: float = 0.99, win: int = 1600, thresh_db: float = -50.0, stats: bool = False, clean: Optional[torch.Tensor] = None):
     """The rows a :class:`Draw` names, read in place from the two pools through device tables of offsets (no gather copy) and mixed as
-    by :func:`snr_mix` -> ``(noisy, clean_out, noise_out, info)``, the signals float32 [rows, samples].  The guards run on the host."""
+    by :func:`snr_mix` -> ``(noisy, clean_out, noise_out, info)``, the signals float32 [rows, samples].  ``clean``: a float32
+    [rows, samples] tensor on the pools' device whose row b, its first ``draw.lens[b]`` samples, stands in for the clean segment the
+    draw names (the segment after reverberation, say); the noise rows are still read in place.  The guards run on the host."""
     if not isinstance(clean_pool, SignalPool) or not isinstance(noise_pool, SignalPool):
         raise ValueError("mix: clean_pool and noise_pool must be SignalPool objects")
     if clean_pool.device != noise_pool.device:
@@ -247,10 +253,19 @@ def mix_draw(clean_pool: SignalPool, noise_pool: SignalPool, draw: Draw, samples
         if not 0 <= o < noise_pool.lengths[ni]:
             raise ValueError(f"mix: row {b} of the draw: 0 <= offset {o} < noise length {noise_pool.lengths[ni]} is expected")
     dev = clean_pool.device
+    if clean is not None:
+        _signals(clean, "clean")
+        if tuple(clean.shape) != (B, samples):
+            raise ValueError(f"mix: clean is {tuple(clean.shape)}; [{B}, {samples}], a row of `samples` for every row of the draw with "
+                             "draw.lens[b] samples in it, is expected")
+        ops.check_dev_f32(clean, "clean", dev)
     off = torch.tensor([[clean_pool.offsets[c] + s for c, s in zip(draw.clean_id, draw.clean_start)],
                         [noise_pool.offsets[j] for j in draw.noise_id]], dtype=torch.int64).to(dev)
     table = torch.tensor([draw.lens, [noise_pool.lengths[j] for j in draw.noise_id], draw.noise_offset], dtype=torch.int32).to(dev)
-    rows = ops.MixRows(clean_pool.data, off[0], noise_pool.data, off[1], table, B, samples, max(noise_pool.lengths))
+    if clean is None:
+        rows = ops.MixRows(clean_pool.data, off[0], noise_pool.data, off[1], table, B, samples, max(noise_pool.lengths))
+    else:
+        rows = ops.MixRows(ops._ragged_rows(clean), None, noise_pool.data, off[1], table, B, samples, max(noise_pool.lengths))
     with torch.cuda.device(dev):                            # the kernels are queued on the current device's stream
         return _mix(rows, snr, level, segmental, target_db, clip, win, thresh_db, stats)
 
@@ -259,11 +274,29 @@ class DynamicMixtures:
     """``(noisy, clean, noise)`` float32 [batch, samples] on the device, the order and shapes of ``dataload.SyntheticMixtures`` and of
     the NSVAE loader, with a fresh pairing, segment, SNR and level for every row of every batch: batch k is what :func:`draw_batch`
     names for ``(seed, k)``, read in place from the two pools (no gather copy) and mixed by the kernels of :func:`snr_mix`.  A clean
-    recording shorter than ``samples`` comes back zero-padded.  ``length``: the number of batches of one iteration (None: endless)."""
+    recording shorter than ``samples`` comes back zero-padded.  ``length``: the number of batches of one iteration (None: endless).
+
+    ``rir_pool``: a ``dataset.reverb.RirPool``.  Row b of batch k is then convolved with the impulse response that
+    ``draw_reverb(k, seed, len(rir_pool), batch, p_reverb)`` names (-1: the row stays dry), with the samples in front of its segment,
+    and mixed as the reverberant clean signal, as the DNS-Challenge synthesizer does; ``clean`` is the scaled reverberant speech.
+    ``target="early"``: ``clean`` is float32(g_clean x the row convolved with ``rir_pool.early_taps(early_ms)`` taps only), the
+    direct sound and early reflections at the gain of the mixture.  Without a pool nothing changes."""
 
     def __init__(self, clean_pool: SignalPool, noise_pool: SignalPool, batch: int, samples: int = 64000, seed: int = 123,
                  length: Optional[int] = None, segmental: bool = False, snr_db=(-5.0, 20.0), level_db=(-35, -15),
-                 target_db: float = -25.0, clip: float = 0.99, win: int = 1600, thresh_db: float = -50.0):
+                 target_db: float = -25.0, clip: float = 0.99, win: int = 1600, thresh_db: float = -50.0, rir_pool=None,
+                 p_reverb: float = 0.5, target: str = "reverberant", early_ms: float = 50.0):
+        if isinstance(p_reverb, bool) or not isinstance(p_reverb, (int, float)) or not 0.0 <= p_reverb <= 1.0:
+            raise ValueError(f"DynamicMixtures: p_reverb = {p_reverb!r}: a probability in [0, 1] is expected")
+        if target not in ("reverberant", "early"):
+            raise ValueError(f"DynamicMixtures: target = {target!r}: 'reverberant' or 'early' is expected")
+        self.early_ms = _finite("early_ms", early_ms, "DynamicMixtures")
+        if self.early_ms < 0:
+            raise ValueError(f"DynamicMixtures: early_ms = {early_ms!r}: a finite number >= 0 is expected")
+        if rir_pool is not None:
+            from .reverb import RirPool
+            if not isinstance(rir_pool, RirPool):
+                raise ValueError("DynamicMixtures: rir_pool must be a RirPool object (or None)")
         if not isinstance(clean_pool, SignalPool) or not isinstance(noise_pool, SignalPool):
             raise ValueError("DynamicMixtures: clean_pool and noise_pool must be SignalPool objects")
         if isinstance(batch, bool) or not isinstance(batch, int) or batch < 1 or batch > 65535:
@@ -274,16 +307,32 @@ class DynamicMixtures:
         draw_batch(0, seed, clean_pool.lengths, noise_pool.lengths, 1, samples, snr_db, level_db)      # the guards on the ranges
         self.clean_pool, self.noise_pool, self.batch_size, self.samples = clean_pool, noise_pool, batch, samples
         self.seed, self.length, self.snr_db, self.level_db = seed, length, snr_db, level_db
+        if rir_pool is not None and rir_pool.device != clean_pool.device:
+            raise ValueError(f"DynamicMixtures: the pools are on {clean_pool.device} and rir_pool on {rir_pool.device}")
+        self.rir_pool, self.p_reverb, self.target = rir_pool, float(p_reverb), target
 
     def draw(self, k: int) -> Draw:
         return draw_batch(k, self.seed, self.clean_pool.lengths, self.noise_pool.lengths, self.batch_size, self.samples, self.snr_db,
                           self.level_db)
 
     def batch(self, k: int, info: bool = False, stats: bool = False):
-        """Batch k -> (noisy, clean, noise), with ``info`` also the dict of :func:`snr_mix`."""
+        """Batch k -> (noisy, clean, noise), with ``info`` also the dict of :func:`snr_mix` and, with a ``rir_pool``, ``rir_id``: the
+        python list of ``draw_reverb``."""
         target_db, clip, win, thresh_db, segmental = self.mix_args
-        out = mix_draw(self.clean_pool, self.noise_pool, self.draw(k), self.samples, segmental, target_db, clip, win, thresh_db, stats)
-        return out if info else out[:3]
+        if self.rir_pool is None:
+            out = mix_draw(self.clean_pool, self.noise_pool, self.draw(k), self.samples, segmental, target_db, clip, win, thresh_db, stats)
+            return out if info else out[:3]
+        from . import reverb as RV
+        d = self.draw(k)
+        ids = RV.draw_reverb(k, self.seed, len(self.rir_pool), self.batch_size, self.p_reverb)
+        wet = RV.reverb_draw(self.clean_pool, self.rir_pool, d, ids, self.samples)
+        noisy, clean, noise, inf = mix_draw(self.clean_pool, self.noise_pool, d, self.samples, segmental, target_db, clip, win, thresh_db, stats,
+                                            clean=wet)
+        if self.target == "early":
+            early = RV.reverb_draw(self.clean_pool, self.rir_pool, d, ids, self.samples, taps=self.rir_pool.early_taps(self.early_ms))
+            clean = (inf["g_clean"][:, None] * early.double()).float()
+        inf["rir_id"] = ids
+        return (noisy, clean, noise, inf) if info else (noisy, clean, noise)
 
     def __iter__(self):
         k = 0

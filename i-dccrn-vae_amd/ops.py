@@ -1180,6 +1180,26 @@ def mix_write(rows: MixRows, rec: torch.Tensor):
     return out[0], out[1], out[2]
 
 
+# ----------------------------------------------------------------------------- reverberation
+REVERB_MAX_TAPS = 1 << 16      # taps per impulse response
+REVERB_MAX_HIST = 65535        # samples in front of a row that its convolution may reach
+
+
+def reverb_apply(x: torch.Tensor, x_off: Optional[torch.Tensor], h: torch.Tensor, h_off: Optional[torch.Tensor], table: torch.Tensor,
+                 B: int, L: int, Kmax: int) -> torch.Tensor:
+    """idv_reverb: every row convolved with its own impulse response -> fp32 [B, L], zeros from a row's length on.  ``x`` / ``h`` are
+    fp32 device tensors, either a padded batch ([B, L] / [B, Kmax], ``*_off`` None) or a flat pool with ``*_off`` the int64 device
+    table of every row's first sample; ``table`` is the int32 device tensor [3, B] of (lens, taps, hist)."""
+    check_dev_f32(x, "x")
+    check_dev_f32(h, "rir", x.device)
+    y = torch.empty(B, L, dtype=torch.float32, device=x.device)
+    ldx = 0 if x_off is not None else x.stride(0)
+    ldh = 0 if h_off is not None else h.stride(0)
+    call("idv_reverb", p(x), p(x_off), ll(ldx), p(h), p(h_off), ll(ldh), p(table[0]), p(table[1]), p(table[2]), i(B), i(L), i(Kmax),
+         p(y), ll(L), stream_ptr())
+    return y
+
+
 def mask_apply(mask: Planar, X: Planar, x_div: int = 1):
     """-> (pred planar, pred complex64 [B, F, T])."""
     B, F, T = mask.B, mask.F, mask.T

@@ -1020,6 +1020,23 @@ int idv_mix_write(const float* clean, const long long* clean_off, long long ldc,
                   long long ldn, const int* lens, const int* noise_lens, const int* phase, int B, int L, int Ln, const double* rows,
                   float* noisy, float* clean_out, float* noise_out, long long ldy, void* stream);
 
+/* ---- reverberation (reverb.hip; dataset/reverb.py reverb / reverb_draw; an additive entry: IDV_ABI_VERSION is unchanged; DESIGN.md
+ * 3.13).  Every row convolved with its own impulse response, the scipy.signal.fftconvolve(x, h)[:n] of the DNS-Challenge synthesizer's
+ * add_pyreverb (tests/reverb_ref.py).  Row b: n = lens[b] samples (device int32[B], clamped to [0, L]; NULL: L each) at x + x_off[b]
+ * (device int64[B] sample offsets: rows in place in a packed pool) or, x_off == NULL, at x + b ldx; K = taps[b] taps (device int32[B],
+ * clamped to [1, Kmax]) at h + h_off[b] or, h_off == NULL, at h + b ldh; H = hist[b] (device int32[B], clamped to [0, 65535]; NULL: 0)
+ * real samples x[-H .. -1] in front of the row's start, read in place: a segment cut from a longer recording carries the tail of what
+ * precedes it, as if the whole recording had been convolved and then cut.
+ *     y[b][i] = float( sum_{k < K} (double)h[k] (double)x[i - k] ),  x[j] = 0 for j < -H,   0 <= i < n;      y[b][i] = 0,  n <= i < L
+ * Every product is exact in double, the sum is double, the result ONE fp32 rounding of it; y is [B][ldy].  Nothing at or past x[n],
+ * before x[-H] or at or past h[K] is read.  A block-Toeplitz product on v_mfma_f64_16x16x4_f64: the place of a term in the sum of
+ * output i follows from (i, K, H) of its row alone, not from B, the other rows, L, the pitches, the offsets or the alignment; no
+ * atomics, no work buffer.
+ * IDV_EINVAL (before any GPU work) for a NULL pointer (x_off, h_off, lens, hist may be NULL), B <= 0 or B > 65535, L <= 0 or L > 2^27,
+ * Kmax <= 0 or Kmax > 65536, ldx < L / ldh < Kmax where the offsets are NULL, ldy < L, a misaligned pointer. */
+int idv_reverb(const float* x, const long long* x_off, long long ldx, const float* h, const long long* h_off, long long ldh,
+               const int* lens, const int* taps, const int* hist, int B, int L, int Kmax, float* y, long long ldy, void* stream);
+
 /* ---- time-Winograd convs with two co tiles per workgroup (cgemm_tw.hip, cgemm_tw2.hip; additive entries: IDV_ABI_VERSION is
  * unchanged).  A layer with an even number of 32-channel co tiles runs workgroups of eight waves that stage the raw input rows once
  * for two co tiles; the outputs are bit-identical to the one-co-tile kernels (the train-mode moment sums within the rounding of a
