@@ -487,6 +487,63 @@ def lstm(mod, x: Planar) -> Planar:
     return Planar(obuf, mod.hidden_size, 1, x.B, x.T, x.Tp, x.Jp)
 
 
+# ----------------------------------------------------------------------------- distinguisher: real LSTM with hidden size 1
+class RealLstm1Fn(torch.autograd.Function):
+    """nn.LSTM(2 C F, hidden_size 1, num_layers 2) behind the distinguisher's encoder blocks (pvae_module.py:2338-2346):
+    planar activation in, [B, T, 1] out, back-propagation through time on the kernels of csrc/dis.hip."""
+
+    @staticmethod
+    def forward(ctx, geom, xbuf, *params):
+        x = _mk(xbuf, geom)
+        y, save = ops.rlstm1_fwd(x, params, want_save=True)
+        ctx.save_for_backward(xbuf, save, *params)
+        ctx.geom = geom
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        # saved tensors are released by the first backward: a second one over the same forward raises in torch itself
+        xbuf, save, *params = ctx.saved_tensors
+        x = _mk(xbuf, ctx.geom)
+        need = ctx.needs_input_grad
+        # a frozen distinguisher (the generator update of adversarial.AdversarialFineTune) skips the dW_ih0 contraction
+        dx, dw, small = ops.rlstm1_bwd(x, params, save, dy.contiguous().float(), want_dx=need[1], want_dw=need[2])
+        s = lambda k, shape: small[4 * k:4 * k + 4].reshape(shape)
+        grads = (dw, s(0, (4, 1)), s(1, (4,)), s(2, (4,)), s(3, (4, 1)), s(4, (4, 1)), s(5, (4,)), s(6, (4,)))
+        return (None, _fit(dx, xbuf) if dx is not None else None) + tuple(g if n else None for g, n in zip(grads, need[2:]))
+
+
+def rlstm1(mod, x: Planar) -> torch.Tensor:
+    params = [getattr(mod, n) for n in ops.RLSTM1_NAMES]
+    if grad_mode(x.buf, *params):
+        return RealLstm1Fn.apply(_geom(x), x.buf, *params)
+    return ops.rlstm1_fwd(x, params, want_save=False)[0]
+
+
+class LsganFn(torch.autograd.Function):
+    """mean((a - 1)^2 + b^2) (distinguisher_loss, nsvae_loss.py:957-962) or, without b, mean((a - 1)^2) (the distinguisher term of
+    generator_loss, :982)."""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        a = a.contiguous().float()
+        b = b.contiguous().float() if b is not None else None
+        ctx.save_for_backward(a, b)
+        return ops.lsgan(a, b)
+
+    @staticmethod
+    def backward(ctx, g):
+        a, b = ctx.saved_tensors
+        da, db = ops.lsgan_bwd(a, b, g, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return da, db
+
+
+def lsgan(a: torch.Tensor, b: Optional[torch.Tensor] = None) -> torch.Tensor:
+    if grad_mode(a, b):
+        return LsganFn.apply(a, b)
+    return ops.lsgan(a.contiguous().float(), b.contiguous().float() if b is not None else None)
+
+
 # ----------------------------------------------------------------------------- STFT / ISTFT / mask
 class StftFn(torch.autograd.Function):
     @staticmethod

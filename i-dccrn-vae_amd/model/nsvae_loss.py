@@ -1,5 +1,5 @@
 """NSVAE / supervised / two-phase losses (reference: model/nsvae_loss.py: standard_nsvae_loss_true_kl :243-473,
-ete_train_se_loss :755-806, two_phase_loss :809-948) on the HIP reduction kernels."""
+ete_train_se_loss :755-806, two_phase_loss :809-948, adversarial_second_phase_loss :953-986) on the HIP reduction kernels."""
 import torch
 
 from .. import autograd as AG
@@ -155,3 +155,24 @@ class two_phase_loss(_KLMixin):
                              (miu_noisy_speech, log_sigma_noisy_speech, delta_noisy_speech),
                              (miu_noisy_noise, log_sigma_noisy_noise, delta_noisy_noise),
                              1.0 if self.latent_num == 2 else self.alpha, -1.0)
+
+
+class adversarial_second_phase_loss():
+    """LSGAN losses of the adversarial decoder fine-tune, reference :953-986.  The arguments the reference accepts and ignores
+    (the noise distinguisher's outputs, the noise signals) are accepted and ignored here too."""
+
+    def __init__(self, latent_num):
+        self.latent_num = latent_num
+
+    def distinguisher_loss(self, dis_true_clean, dis_est_clean, dis_true_noise=None, dis_est_noise=None):
+        """mean((D(clean) - 1)^2 + D(estimate)^2) over [B, T, 1]"""
+        return AG.lsgan(dis_true_clean, dis_est_clean)
+
+    def si_snr(self, source, estimate_source, eps=1e-8):
+        return _si_snr(source, estimate_source, eps)
+
+    def generator_loss(self, true_clean, est_clean, dis_est_clean, true_noise=None, est_noise=None, dis_est_noise=None):
+        """-> (0.5 * mean((D(estimate) - 1)^2) + si_snr, si_snr, mean((D(estimate) - 1)^2))"""
+        loss_recon = self.si_snr(true_clean, est_clean)
+        loss_dis = AG.lsgan(dis_est_clean)
+        return 0.5 * loss_dis + loss_recon, loss_recon, loss_dis

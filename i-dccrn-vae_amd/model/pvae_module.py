@@ -3,7 +3,8 @@ return tuples and state_dict keys (reference: model/pvae_module.py), running on 
 
 Classes: STFT, ISTFT, Encoder, Decoder, standard_DCCRN, DCCRN_ (supervised DCCRN-CL),
 pvae_dccrn_encoder_skip_prepare / pvae_dccrn_decoder_skip_prepare (CVAE / NVAE pre-training),
-nsvae_pvae_dccrn_encoder_twophase / nsvae_pvae_dccrn_decoder_twophase (NSVAE and decoder fine-tune).
+nsvae_pvae_dccrn_encoder_twophase / nsvae_pvae_dccrn_decoder_twophase (NSVAE and decoder fine-tune),
+dis_Encoder / distinguisher (the LSGAN distinguisher of the adversarial decoder fine-tune).
 The reference's other encoder/decoder variants are ablation copies of these.
 
 A batch stays in the planar-J device layout from STFT to ISTFT; tensors handed back to the caller
@@ -555,6 +556,69 @@ class nsvae_pvae_dccrn_encoder_twophase(_VAEEncoderBase):
             else:
                 out += [None, None, None, None]
         return (*out, skiper, C, F, stft_x)
+
+
+class dis_Encoder(Encoder):
+    """reference: model/pvae_module.py:2271-2294: an Encoder block whose ComplexBatchNormal carries dis_cbn=True (its init_flag
+    never drops: every train-mode call overwrites the running buffers with the batch moments)."""
+
+    def __init__(self, in_channel, out_channel, kernel_size, stride, chw, padding=None, causal=False):
+        super().__init__(in_channel, out_channel, kernel_size, stride, chw, padding, causal)
+        self.bn = ComplexBatchNormal(chw[0], chw[1], chw[2], dis_cbn=True)
+
+
+class _RealLSTM1(nn.LSTM):
+    """The distinguisher's real nn.LSTM(input_size, hidden_size=1, num_layers=2): owns weight_ih_l0 ... bias_hh_l1 under torch's own
+    names (state_dict parity) and runs on the hidden-size-1 kernels of csrc/dis.hip, reading the planar activation in place."""
+
+    def forward_planar(self, x: Planar) -> torch.Tensor:
+        if self.hidden_size != 1 or self.num_layers != 2 or not self.bias or self.bidirectional or self.dropout or self.proj_size:
+            raise NotImplementedError("distinguisher LSTM HIP path: hidden_size 1, 2 unidirectional layers with bias (the reference's)")
+        if 2 * x.C * x.F != self.input_size:
+            raise RuntimeError(f"distinguisher LSTM expects {self.input_size} features, got 2*{x.C}*{x.F}")
+        return AG.rlstm1(self, x)
+
+    def forward(self, x, hx=None):
+        """[T, B, K] (K = (c F + f) 2 + d, as the reference builds it) -> ([T, B, 1], None): the planar form of the same call."""
+        if hx is not None:
+            raise NotImplementedError("distinguisher LSTM: zero initial state only")
+        _need_cuda(x)
+        T, B, K = x.shape
+        pl = Planar.from_tensor5(x.reshape(T, B, K // 2, 2).permute(1, 2, 0, 3).unsqueeze(2).float())
+        return self.forward_planar(pl).permute(1, 0, 2), None
+
+
+class distinguisher(nn.Module):
+    """LSGAN distinguisher of the adversarial decoder fine-tune.  reference: model/pvae_module.py:2295-2351.
+    forward(x [B, L], train=True) -> [B, T, 1] (no sigmoid): STFT -> six dis_Encoder blocks -> nn.LSTM(2 C F, 1, num_layers)."""
+
+    def __init__(self, net_params, causal, device, zdim, n_fft, hop_len, win_length):
+        super().__init__()
+        self.device = device
+        self.causal = causal
+        self.stft = STFT(n_fft, hop_len, win_length=win_length, device=device)
+        ch = net_params["encoder_channels"]
+        self.encoders = nn.ModuleList([
+            dis_Encoder(in_channel=ch[i], out_channel=ch[i + 1], kernel_size=net_params["encoder_kernel_sizes"][i],
+                        stride=net_params["encoder_strides"][i], padding=net_params["encoder_paddings"][i],
+                        chw=net_params["encoder_chw"][i], causal=causal)
+            for i in range(len(ch) - 1)])
+        dims = net_params["lstm_dim"]
+        self.lstms = nn.ModuleList([
+            _RealLSTM1(input_size=dims[i] * 2, hidden_size=1, num_layers=net_params["lstm_layer_num"])
+            for i in range(len(dims) - 1)])
+        self.epsilon = 1e-6
+
+    def forward(self, x, train=True):
+        if not train and torch.is_grad_enabled():
+            _eval_builds_no_graph(type(self).__name__, x)
+            with torch.no_grad():                                    # eval mode builds no graph
+                return self.forward(x, False)
+        if len(self.lstms) != 1:
+            raise NotImplementedError("distinguisher: one LSTM stack (lstm_dim of two entries), as every shipped configuration has")
+        X = self.stft.planar(x)
+        top = _run_encoders(self.encoders, X, train)[-1]
+        return self.lstms[0].forward_planar(top)
 
 
 class _VAEDecoderBase(nn.Module):

@@ -1641,3 +1641,84 @@ def stft_bwd(dX: Planar, plan: "DftPlan", Lx: int) -> torch.Tensor:
 def reparam_bwd(lat: Planar, off, zdim: int, eps_r, eps_i, ns: int, dz: Planar, dlat: Planar):
     call("idv_reparam_bwd", lat.ptr(), i(lat.C), i(off[0]), i(off[1]), i(off[2]), i(zdim), p(eps_r), p(eps_i), i(ns), i(lat.B),
          i(lat.T), i(lat.Tp), i(lat.Jp), dz.ptr(), i(dz.Jp), dlat.ptr(), stream_ptr())
+
+
+# ----------------------------------------------------------------------------- distinguisher (csrc/dis.hip)
+RLSTM1_NAMES = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0", "weight_ih_l1", "weight_hh_l1", "bias_ih_l1", "bias_hh_l1")
+
+
+def _rlstm1_check(x: Planar, params):
+    """Shape checks of the hidden-size-1 nn.LSTM on a planar activation -> the eight tensors, contiguous fp32 on x's device."""
+    K = 2 * x.C * x.F
+    if len(params) != 8:
+        raise L.IdvError("rlstm1: the eight nn.LSTM(K, 1, 2) tensors are expected")
+    want = [(4, K), (4, 1), (4,), (4,), (4, 1), (4, 1), (4,), (4,)]
+    out = []
+    for n, t, s in zip(RLSTM1_NAMES, params, want):
+        check_dev_f32(t, n, x.buf.device)
+        if t.dtype != torch.float32 or tuple(t.shape) != s:
+            raise L.IdvError(f"rlstm1: {n} is {t.dtype} {tuple(t.shape)}, expected float32 {s} (input features 2*C*F = {K})")
+        out.append(t.detach().contiguous())
+    if x.Tp < x.T + 1 or x.Jp < x.B * x.Tp or x.Jp % 4:
+        raise L.IdvError("rlstm1: not a planar activation")
+    return out
+
+
+def rlstm1_fwd(x: Planar, params, want_save: bool):
+    """nn.LSTM(2*C*F, 1, 2) over the frames of x -> (y [B, T, 1], save or None)."""
+    w = _rlstm1_check(x, params)
+    dev = x.buf.device
+    K = 2 * x.C * x.F
+    save = torch.empty(int(_ll_fn("idv_rlstm1_save_doubles")(i(x.B), i(x.T))), dtype=torch.float64, device=dev) if want_save else None
+    scratch = torch.empty(int(_ll_fn("idv_rlstm1_fwd_scratch_doubles")(i(K), i(x.Jp))), dtype=torch.float64, device=dev)
+    y = torch.empty(x.B, x.T, 1, dtype=torch.float32, device=dev)
+    call("idv_rlstm1_fwd", x.ptr(), i(x.C), i(x.F), i(x.B), i(x.T), i(x.Tp), i(x.Jp), *[p(t) for t in w], p(save), p(scratch), p(y),
+         stream_ptr())
+    return y, save
+
+
+def rlstm1_bwd(x: Planar, params, save: torch.Tensor, dy: torch.Tensor, want_dx: bool, want_dw: bool):
+    """-> (dx Planar or None, dW_ih0 [4, K] or None, dsmall[28]: dW_hh0, db_ih0, db_hh0, dW_ih1, dW_hh1, db_ih1, db_hh1)."""
+    w = _rlstm1_check(x, params)
+    dev = x.buf.device
+    K = 2 * x.C * x.F
+    check_dev_f32(dy, "dy", dev)
+    if dy.dtype != torch.float32 or dy.numel() != x.B * x.T or not dy.is_contiguous():
+        raise L.IdvError(f"rlstm1_bwd: dy must be contiguous float32 [B, T, 1] = [{x.B}, {x.T}, 1]")
+    if save is None or save.dtype != torch.float64 or save.numel() != 12 * x.B * x.T:
+        raise L.IdvError("rlstm1_bwd: save is not what rlstm1_fwd(..., want_save=True) returned for this shape")
+    scratch = torch.empty(int(_ll_fn("idv_rlstm1_bwd_scratch_doubles")(i(K), i(x.B), i(x.Jp))), dtype=torch.float64, device=dev)
+    dx = like(x) if want_dx else None
+    dw = torch.empty(4, K, dtype=torch.float32, device=dev) if want_dw else None
+    small = torch.empty(28, dtype=torch.float32, device=dev)
+    call("idv_rlstm1_bwd", x.ptr(), i(x.C), i(x.F), i(x.B), i(x.T), i(x.Tp), i(x.Jp), p(dy), p(w[0]), p(w[1]), p(w[4]), p(w[5]),
+         p(save), p(scratch), dx.ptr() if dx is not None else p(None), p(dw), p(small), stream_ptr())
+    return dx, dw, small
+
+
+def _lsgan_pair(a, b):
+    check_dev_f32(a, "a")
+    if a.dtype != torch.float32 or not a.is_contiguous() or a.numel() == 0:
+        raise L.IdvError("lsgan: contiguous non-empty float32 distinguisher outputs expected")
+    if b is not None:
+        check_dev_f32(b, "b", a.device)
+        if b.dtype != torch.float32 or not b.is_contiguous() or b.shape != a.shape:
+            raise L.IdvError(f"lsgan: the two distinguisher outputs differ: {tuple(a.shape)} vs {tuple(b.shape)}")
+
+
+def lsgan(a: torch.Tensor, b: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mean((a - 1)^2 + b^2), or mean((a - 1)^2) without b."""
+    _lsgan_pair(a, b)
+    out = torch.empty(1, dtype=torch.float32, device=a.device)
+    call("idv_lsgan", p(a), p(b), ll(a.numel()), p(out), stream_ptr())
+    return out[0]
+
+
+def lsgan_bwd(a: torch.Tensor, b: Optional[torch.Tensor], gout: torch.Tensor, want_a: bool = True, want_b: bool = True):
+    _lsgan_pair(a, b)
+    da = torch.empty_like(a) if want_a else None
+    db = torch.empty_like(b) if (b is not None and want_b) else None
+    if da is None and db is None:
+        return None, None
+    call("idv_lsgan_bwd", p(a), p(b), ll(a.numel()), p(gout.reshape(1).contiguous().float()), p(da), p(db), stream_ptr())
+    return da, db

@@ -1051,6 +1051,40 @@ int idv_tw_pair(int mask);
 /* Number of paired kernel launches of this process so far; reset != 0 also sets the count back to 0. */
 long long idv_tw_pair_launches(int reset);
 
+/* ---- distinguisher of the adversarial decoder fine-tune (dis.hip; model/pvae_module.py distinguisher, model/nsvae_loss.py
+ * adversarial_second_phase_loss, adversarial.py; additive entries: IDV_ABI_VERSION is unchanged).
+ *
+ * The real two-layer nn.LSTM(2 C F, hidden_size 1) of model/pvae_module.py:2319-2346 with h0 = c0 = 0, gate order i, f, g, o.  x is
+ * the last dis_Encoder block's planar activation act[2][C][F][Jp], read in place: feature k = (c F + f) 2 + d of the reference's
+ * [T, B, 2 C F] input is plane (d, c, f), frame t of row b is column b Tp + 1 + t; no other column is read.  wih0 [4][2 C F],
+ * whh0 / wih1 / whh1 / b* [4]: the eight nn.LSTM tensors as they are.  y [B][T] fp32 = the layer-1 hidden state (the reference's
+ * [B, T, 1] output).  Every sum is double in an order fixed by (k, t): y of a row does not depend on the other rows; no atomics.
+ * save: idv_rlstm1_save_doubles(B, T) doubles that idv_rlstm1_bwd reads (activated gates, cell states, tanh(c) of both layers), or
+ * NULL when no backward follows; scratch: idv_rlstm1_fwd_scratch_doubles(2 C F, Jp) doubles, free again when the call has run.
+ * IDV_EINVAL (before any GPU work) for a NULL pointer (save may be NULL), C, F <= 0 or C F > 32768, B <= 0 or B > 65535, T <= 0 or
+ * T > 2^20, Tp < T + 1, Jp < B Tp or not a multiple of 4, x not 16-byte aligned, another pointer not aligned to its element. */
+long long idv_rlstm1_save_doubles(int B, int T);
+long long idv_rlstm1_fwd_scratch_doubles(int K, int Jp);
+long long idv_rlstm1_bwd_scratch_doubles(int K, int B, int Jp);
+int idv_rlstm1_fwd(const float* x, int C, int F, int B, int T, int Tp, int Jp, const float* wih0, const float* whh0,
+                   const float* bih0, const float* bhh0, const float* wih1, const float* whh1, const float* bih1,
+                   const float* bhh1, double* save, double* scratch, float* y, void* stream);
+/* Back-propagation through time of idv_rlstm1_fwd.  dy [B][T]; save: what the forward left; scratch:
+ * idv_rlstm1_bwd_scratch_doubles(2 C F, B, Jp) doubles.  dx (may be NULL): act[2][C][F][Jp] gradient, every column of [0, Jp) written,
+ * zeros wherever the column is not a frame (the planar invariant); dwih0 (may be NULL: a frozen distinguisher) [4][2 C F];
+ * dsmall[28] = dW_hh0[4], db_ih0[4], db_hh0[4], dW_ih1[4], dW_hh1[4], db_ih1[4], db_hh1[4].  Per-row partial sums in double, added
+ * over the rows b = 0, 1, ...; dW_ih0 summed along j in double, 1024-column tiles in ascending order.  Refusals as idv_rlstm1_fwd
+ * (dx 16-byte aligned). */
+int idv_rlstm1_bwd(const float* x, int C, int F, int B, int T, int Tp, int Jp, const float* dy, const float* wih0,
+                   const float* whh0, const float* wih1, const float* whh1, const double* save, double* scratch,
+                   float* dx, float* dwih0, float* dsmall, void* stream);
+/* LSGAN terms of model/nsvae_loss.py:957-962, :982: out[0] = (sum_i (a[i] - 1)^2 + sum_i b[i]^2) / n, b == NULL: the first sum
+ * alone.  Double sums in a fixed order, one fp32 rounding.  idv_lsgan_bwd: da[i] = gout[0] 2 (a[i] - 1) / n, db[i] = gout[0] 2 b[i] / n
+ * (gout: device scalar; da or db may be NULL, not both).  IDV_EINVAL for a NULL a / out / gout, n <= 0 or n > 2^28, a misaligned
+ * pointer. */
+int idv_lsgan(const float* a, const float* b, long long n, float* out, void* stream);
+int idv_lsgan_bwd(const float* a, const float* b, long long n, const float* gout, float* da, float* db, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
