@@ -172,6 +172,24 @@ class SignalPool:
     def member(self, k: int) -> torch.Tensor:
         return self.data[self.offsets[k]:self.offsets[k] + self.lengths[k]]
 
+    def stats(self) -> dict:
+        """Per member, device tensors: ``peak`` = max|x|, ``rms`` and ``activity`` (float64), from one pass of the window kernel of
+        csrc/assemble.hip over the pool (dataset/assemble.py ``pool_stats``); computed once and kept."""
+        if getattr(self, "_stats", None) is None:
+            from .assemble import pool_stats
+            self._stats = pool_stats(self)
+        return self._stats
+
+    def usable(self, clip: float = 0.99) -> list:
+        """The python list of the members with ``peak <= clip``: the recordings no sample of which clips.  One synchronisation per
+        pool and threshold, not per batch; ValueError where no member is left."""
+        clip = _finite("clip", clip, "usable")
+        kept = self.__dict__.setdefault("_usable", {})
+        if clip not in kept:
+            from .assemble import usable_members
+            kept[clip] = usable_members(self, clip)
+        return list(kept[clip])
+
 
 class Draw(NamedTuple):
     """Batch k as :func:`draw_batch` names it, one entry per row."""
@@ -226,11 +244,14 @@ def draw_batch(k: int, seed: int, clean_lengths: Sequence[int], noise_lengths: S
 
 
 def mix_draw(clean_pool: SignalPool, noise_pool: SignalPool, draw: Draw, samples: int, segmental: bool = False, target_db: float = -25.0,
-             clip: float = 0.99, win: int = 1600, thresh_db: float = -50.0, stats: bool = False, clean: Optional[torch.Tensor] = None):
+             clip: float = 0.99, win: int = 1600, thresh_db: float = -50.0, stats: bool = False, clean: Optional[torch.Tensor] = None,
+             noise: Optional[torch.Tensor] = None):
     """The rows a :class:`Draw` names, read in place from the two pools through device tables of offsets (no gather copy) and mixed as
     by :func:`snr_mix` -> ``(noisy, clean_out, noise_out, info)``, the signals float32 [rows, samples].  ``clean``: a float32
     [rows, samples] tensor on the pools' device whose row b, its first ``draw.lens[b]`` samples, stands in for the clean segment the
-    draw names (the segment after reverberation, say); the noise rows are still read in place.  The guards run on the host."""
+    draw names (the segment after reverberation, say); the noise rows are still read in place.  ``noise``: a float32 [rows, samples]
+    tensor whose row b, read from offset 0 with length ``samples``, stands in for the noise recording and offset the draw names (an
+    assembled noise clip, say).  The guards run on the host."""
     if not isinstance(clean_pool, SignalPool) or not isinstance(noise_pool, SignalPool):
         raise ValueError("mix: clean_pool and noise_pool must be SignalPool objects")
     if clean_pool.device != noise_pool.device:
@@ -259,6 +280,18 @@ def mix_draw(clean_pool: SignalPool, noise_pool: SignalPool, draw: Draw, samples
             raise ValueError(f"mix: clean is {tuple(clean.shape)}; [{B}, {samples}], a row of `samples` for every row of the draw with "
                              "draw.lens[b] samples in it, is expected")
         ops.check_dev_f32(clean, "clean", dev)
+    if noise is not None:
+        _signals(noise, "noise")
+        if tuple(noise.shape) != (B, samples):
+            raise ValueError(f"mix: noise is {tuple(noise.shape)}; [{B}, {samples}], a row of `samples` for every row of the draw, is expected")
+        ops.check_dev_f32(noise, "noise", dev)
+        clean_off = None if clean is not None else torch.tensor([clean_pool.offsets[c] + s for c, s in zip(draw.clean_id, draw.clean_start)],
+                                                                dtype=torch.int64).to(dev)
+        table = torch.tensor([draw.lens, [samples] * B, [0] * B], dtype=torch.int32).to(dev)
+        rows = ops.MixRows(clean_pool.data if clean is None else ops._ragged_rows(clean), clean_off, ops._ragged_rows(noise), None, table, B,
+                           samples, samples)
+        with torch.cuda.device(dev):
+            return _mix(rows, snr, level, segmental, target_db, clip, win, thresh_db, stats)
     off = torch.tensor([[clean_pool.offsets[c] + s for c, s in zip(draw.clean_id, draw.clean_start)],
                         [noise_pool.offsets[j] for j in draw.noise_id]], dtype=torch.int64).to(dev)
     table = torch.tensor([draw.lens, [noise_pool.lengths[j] for j in draw.noise_id], draw.noise_offset], dtype=torch.int32).to(dev)
@@ -280,12 +313,21 @@ class DynamicMixtures:
     ``draw_reverb(k, seed, len(rir_pool), batch, p_reverb)`` names (-1: the row stays dry), with the samples in front of its segment,
     and mixed as the reverberant clean signal, as the DNS-Challenge synthesizer does; ``clean`` is the scaled reverberant speech.
     ``target="early"``: ``clean`` is float32(g_clean x the row convolved with ``rir_pool.early_taps(early_ms)`` taps only), the
-    direct sound and early reflections at the gain of the mixture.  Without a pool nothing changes."""
+    direct sound and early reflections at the gain of the mixture.  Without a pool nothing changes.
+
+    ``clips=True`` (dataset/assemble.py): the clean and the noise row of every mixture are CLIPS, several recordings of
+    the pool's usable members (``SignalPool.usable(clip)``: no sample above ``clip``) laid end to end with ``gap`` samples of pause
+    until the row is full, as ``draw_clips(k, seed, ..., stream="clean" / "noise")`` names them; of the ``tries`` candidates of a row
+    the device takes the first whose share of active 50 ms windows (at ``fs``) exceeds ``clean_activity`` / ``noise_activity``, or
+    the most active one.  A short recording then no longer leaves a zero tail and a mixture holds several noise sources in a row.
+    With a ``rir_pool`` the rows ``draw_reverb`` names are convolved whole (the history in front of a clip is zero); SNR and level
+    are those of ``draw_batch(k)``.  With ``clips=False`` none of this runs."""
 
     def __init__(self, clean_pool: SignalPool, noise_pool: SignalPool, batch: int, samples: int = 64000, seed: int = 123,
                  length: Optional[int] = None, segmental: bool = False, snr_db=(-5.0, 20.0), level_db=(-35, -15),
                  target_db: float = -25.0, clip: float = 0.99, win: int = 1600, thresh_db: float = -50.0, rir_pool=None,
-                 p_reverb: float = 0.5, target: str = "reverberant", early_ms: float = 50.0):
+                 p_reverb: float = 0.5, target: str = "reverberant", early_ms: float = 50.0, clips: bool = False, tries: int = 4,
+                 gap: int = 3200, clean_activity: float = 0.6, noise_activity: float = 0.0, fs: int = 16000):
         if isinstance(p_reverb, bool) or not isinstance(p_reverb, (int, float)) or not 0.0 <= p_reverb <= 1.0:
             raise ValueError(f"DynamicMixtures: p_reverb = {p_reverb!r}: a probability in [0, 1] is expected")
         if target not in ("reverberant", "early"):
@@ -310,6 +352,18 @@ class DynamicMixtures:
         if rir_pool is not None and rir_pool.device != clean_pool.device:
             raise ValueError(f"DynamicMixtures: the pools are on {clean_pool.device} and rir_pool on {rir_pool.device}")
         self.rir_pool, self.p_reverb, self.target = rir_pool, float(p_reverb), target
+        if not isinstance(clips, bool):
+            raise ValueError(f"DynamicMixtures: clips = {clips!r}: True or False is expected")
+        self.clips = clips
+        if clips:
+            from . import assemble as AS
+            AS.window_of(fs, "DynamicMixtures")
+            self.gate = (_finite("clean_activity", clean_activity, "DynamicMixtures"), _finite("noise_activity", noise_activity, "DynamicMixtures"))
+            self.tries, self.gap, self.fs = tries, gap, fs
+            AS.draw_clips(0, seed, clean_pool.lengths, 1, samples, tries, gap)              # the guards on tries and gap
+            if batch * tries > AS.MAX_ROWS:
+                raise ValueError(f"DynamicMixtures: batch x tries = {batch * tries}; at most {AS.MAX_ROWS} candidate rows are supported")
+            self.usable = (clean_pool.usable(self.mix_args[1]), noise_pool.usable(self.mix_args[1]))      # one synchronisation per pool
 
     def draw(self, k: int) -> Draw:
         return draw_batch(k, self.seed, self.clean_pool.lengths, self.noise_pool.lengths, self.batch_size, self.samples, self.snr_db,
@@ -317,8 +371,12 @@ class DynamicMixtures:
 
     def batch(self, k: int, info: bool = False, stats: bool = False):
         """Batch k -> (noisy, clean, noise), with ``info`` also the dict of :func:`snr_mix` and, with a ``rir_pool``, ``rir_id``: the
-        python list of ``draw_reverb``."""
+        python list of ``draw_reverb``; with ``clips=True`` also ``clean_clips`` / ``noise_clips`` (the :class:`~.assemble.Clips`),
+        ``clean_chosen`` / ``noise_chosen`` and ``clean_accepted`` / ``noise_accepted`` (int32 on the device)."""
         target_db, clip, win, thresh_db, segmental = self.mix_args
+        if self.clips:
+            out = self._clip_batch(k, stats)
+            return out if info else out[:3]
         if self.rir_pool is None:
             out = mix_draw(self.clean_pool, self.noise_pool, self.draw(k), self.samples, segmental, target_db, clip, win, thresh_db, stats)
             return out if info else out[:3]
@@ -333,6 +391,30 @@ class DynamicMixtures:
             clean = (inf["g_clean"][:, None] * early.double()).float()
         inf["rir_id"] = ids
         return (noisy, clean, noise, inf) if info else (noisy, clean, noise)
+
+    def _clip_batch(self, k: int, stats: bool):
+        from . import assemble as AS
+        target_db, clip, win, thresh_db, segmental = self.mix_args
+        d = self.draw(k)                                       # the SNR and the level of every row
+        extra, rows = {}, []
+        for name, pool, ids, gate in zip(("clean", "noise"), (self.clean_pool, self.noise_pool), self.usable, self.gate):
+            c = AS.draw_clips(k, self.seed, pool.lengths, self.batch_size, self.samples, self.tries, self.gap, ids, name)
+            r, a = AS.assemble(pool, c, self.samples, gate, self.fs)
+            rows.append(r)
+            extra.update({f"{name}_clips": c, f"{name}_chosen": a["chosen"], f"{name}_accepted": a["accepted"]})
+        speech, early = rows[0], None
+        if self.rir_pool is not None:
+            from . import reverb as RV
+            extra["rir_id"] = RV.draw_reverb(k, self.seed, len(self.rir_pool), self.batch_size, self.p_reverb)
+            speech = RV.reverb_rows(rows[0], self.rir_pool, extra["rir_id"])
+            if self.target == "early":
+                early = RV.reverb_rows(rows[0], self.rir_pool, extra["rir_id"], taps=self.rir_pool.early_taps(self.early_ms))
+        noisy, clean, noise, inf = snr_mix(speech, rows[1], d.snr_db, d.level_db, segmental=segmental, target_db=target_db, clip=clip,
+                                           win=win, thresh_db=thresh_db, stats=stats)
+        if early is not None:
+            clean = (inf["g_clean"][:, None] * early.double()).float()
+        inf.update(extra)
+        return noisy, clean, noise, inf
 
     def __iter__(self):
         k = 0

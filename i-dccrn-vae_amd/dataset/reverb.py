@@ -147,6 +147,32 @@ def draw_reverb(k: int, seed: int, n_rirs: int, batch: int, p: float = 0.5) -> l
     return out
 
 
+def reverb_rows(x: torch.Tensor, rir_pool: RirPool, rir_ids: Sequence[int], taps=None) -> torch.Tensor:
+    """``x`` [B, L] float32 on the pool's device, every row whole (an assembled clip: the history in front of it is zero), each
+    convolved as by :func:`reverb` with member ``rir_ids[b]`` of ``rir_pool`` read in place (-1: dry, the unit impulse) -> float32
+    [B, L].  ``taps``: one tap count per MEMBER, as in :func:`reverb_draw`.  The guards run on the host."""
+    if not isinstance(rir_pool, RirPool):
+        raise ValueError("reverb_rows: rir_pool must be a RirPool")
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype != torch.float32:
+        raise ValueError("reverb_rows: x must be a float32 [B, L] tensor")
+    B, L = x.shape
+    if B < 1 or B > 65535 or L < 1 or L > MAX_LEN:
+        raise ValueError(f"reverb_rows: a batch of {B} rows of {L} samples; 1 .. 65535 rows of 1 .. 2^27 samples are supported")
+    if isinstance(rir_ids, (str, bytes)) or not isinstance(rir_ids, Sequence) or len(rir_ids) != B:
+        raise ValueError(f"reverb_rows: rir_ids must name one impulse response (or -1) for each of the {B} rows")
+    if any(isinstance(r, bool) or not isinstance(r, int) or not -1 <= r < len(rir_pool) for r in rir_ids):
+        raise ValueError(f"reverb_rows: rir_ids must be integers in -1 .. {len(rir_pool) - 1} (-1: dry)")
+    member_taps = rir_pool.lengths if taps is None else _counts("taps", taps, len(rir_pool), rir_pool.lengths, "reverb_rows")
+    if not x.is_cuda or x.device != rir_pool.device:
+        raise ValueError(f"reverb_rows: x is on {x.device}, rir_pool on {rir_pool.device}")
+    x = ops._ragged_rows(x)
+    tp = [1 if r < 0 else member_taps[r] for r in rir_ids]
+    h_off = torch.tensor([rir_pool.unit_offset if r < 0 else rir_pool.offsets[r] for r in rir_ids], dtype=torch.int64).to(x.device)
+    table = torch.tensor([[L] * B, tp, [0] * B], dtype=torch.int32).to(x.device)
+    with torch.cuda.device(x.device):
+        return ops.reverb_apply(x, None, rir_pool.data, h_off, table, B, L, max(tp))
+
+
 def reverb_draw(clean_pool: SignalPool, rir_pool: RirPool, draw: Draw, rir_ids: Sequence[int], samples: int, taps=None) -> torch.Tensor:
     """The clean rows a :class:`~.mix.Draw` names, each convolved with member ``rir_ids[b]`` of ``rir_pool`` (-1: dry, the unit
     impulse) -> float32 [rows, samples], zeros from a row's length on.  Rows and responses are read in place through device tables of

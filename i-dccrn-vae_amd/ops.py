@@ -6,6 +6,7 @@ from __future__ import annotations
 import os
 from typing import NamedTuple, Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -1198,6 +1199,71 @@ def reverb_apply(x: torch.Tensor, x_off: Optional[torch.Tensor], h: torch.Tensor
     call("idv_reverb", p(x), p(x_off), ll(ldx), p(h), p(h_off), ll(ldh), p(table[0]), p(table[1]), p(table[2]), i(B), i(L), i(Kmax),
          p(y), ll(L), stream_ptr())
     return y
+
+
+# ----------------------------------------------------------------------------- clip assembly
+ASM_MAX_PIECES = 64            # IDV_ASM_MAX_PIECES: pieces per candidate row
+ASM_MAX_TRIES = 16             # IDV_ASM_MAX_TRIES: candidates per row
+ASM_MAX_ROWS = 65535           # candidate rows (B tries) of one call
+ASM_WIN_FIELDS = 2             # IDV_ASM_WIN_FIELDS: max|x|, sum x^2 per window
+
+
+class AsmTables(NamedTuple):
+    """Where the kernels of csrc/assemble.hip find their candidate rows: ``pool`` is the flat fp32 device buffer the pieces point
+    into, ``src`` (int64) / ``len`` / ``dst`` (int32) the device piece arrays, ``first`` / ``count`` (int32) index them per candidate
+    row r = b tries + t."""
+    pool: torch.Tensor
+    src: torch.Tensor
+    len: torch.Tensor
+    dst: torch.Tensor
+    first: torch.Tensor
+    count: torch.Tensor
+    B: int
+    tries: int
+    samples: int
+
+    def args(self):
+        return (p(self.pool), ll(self.pool.numel()), p(self.src), p(self.len), p(self.dst), p(self.first), p(self.count),
+                i(self.src.numel()))
+
+
+def asm_tables(pool: torch.Tensor, src, lens, dst, first, count, B: int, tries: int, samples: int) -> AsmTables:
+    """The python lists of a candidate table -> :class:`AsmTables`, uploaded in ONE copy: the int64 offsets in front, the four int32
+    arrays behind them in the same buffer."""
+    P, R = len(src), len(first)
+    small = np.zeros(2 * ((2 * P + 2 * R + 1) // 2), dtype=np.int32)
+    small[:P], small[P:2 * P], small[2 * P:2 * P + R], small[2 * P + R:2 * P + 2 * R] = lens, dst, first, count
+    host = np.concatenate([np.asarray(src, dtype=np.int64), small.view(np.int64)])
+    dev = torch.from_numpy(host).to(pool.device, non_blocking=False)
+    s32 = dev[P:].view(torch.int32)
+    return AsmTables(pool, dev[:P], s32[:P], s32[P:2 * P], s32[2 * P:2 * P + R], s32[2 * P + R:2 * P + 2 * R], B, tries, samples)
+
+
+def asm_activity(tab: AsmTables, rowlen: Optional[torch.Tensor], win: int, target_db: float, energy_thresh: float, min_activity: float):
+    """idv_asm_activity -> dict of device tensors: ``rowstat`` float64 [R, 2] (max|x|, sum x^2), ``active`` / ``windows`` int32 [R],
+    ``activity`` float64 [R], ``chosen`` / ``accepted`` int32 [B], ``window_stats`` float64 [R, ceil(samples / win), 2]: a view of the
+    work buffer of this device and stream, which the next call overwrites."""
+    check_dev_f32(tab.pool, "pool")
+    R, dev = tab.B * tab.tries, tab.pool.device
+    nbytes = int(_ll_fn("idv_asm_work_bytes")(i(R), i(tab.samples), i(win)))
+    if nbytes < 0:
+        raise ValueError(f"assemble: {R} candidate rows of {tab.samples} samples in windows of {win} are not supported")
+    work = _mix_work(nbytes, dev)
+    rowstat = torch.empty(R, 2, dtype=torch.float64, device=dev)
+    act = torch.empty(R, dtype=torch.float64, device=dev)
+    ints = torch.empty(2 * R + 2 * tab.B, dtype=torch.int32, device=dev)
+    active, windows, chosen, accepted = ints[:R], ints[R:2 * R], ints[2 * R:2 * R + tab.B], ints[2 * R + tab.B:]
+    call("idv_asm_activity", *tab.args(), p(rowlen), i(tab.B), i(tab.tries), i(tab.samples), i(win), d(target_db), d(energy_thresh),
+         d(min_activity), p(work), ll(work.numel()), p(rowstat), p(active), p(windows), p(act), p(chosen), p(accepted), stream_ptr())
+    return {"rowstat": rowstat, "active": active, "windows": windows, "activity": act, "chosen": chosen, "accepted": accepted,
+            "window_stats": work[:nbytes].view(torch.float64).view(R, -1, ASM_WIN_FIELDS)}
+
+
+def asm_write(tab: AsmTables, chosen: torch.Tensor) -> torch.Tensor:
+    """idv_asm_write: -> fp32 [B, samples], row b the candidate ``chosen[b]`` (int32 on the device) of its ``tries``."""
+    out = torch.empty(tab.B, tab.samples, dtype=torch.float32, device=tab.pool.device)
+    call("idv_asm_write", *tab.args(), p(chosen), i(tab.B), i(tab.tries), i(tab.samples), p(out), ll(tab.samples), stream_ptr())
+    return out
 
 
 def mask_apply(mask: Planar, X: Planar, x_div: int = 1):

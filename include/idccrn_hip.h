@@ -1085,6 +1085,41 @@ int idv_rlstm1_bwd(const float* x, int C, int F, int B, int T, int Tp, int Jp, c
 int idv_lsgan(const float* a, const float* b, long long n, float* out, void* stream);
 int idv_lsgan_bwd(const float* a, const float* b, long long n, const float* gout, float* da, float* db, void* stream);
 
+/* ---- clip assembly (assemble.hip; dataset/assemble.py assemble / activity / SignalPool.stats; additive entries: IDV_ABI_VERSION is
+ * unchanged).  The definition is build_audio / activitydetector of the DNS-Challenge synthesizer restated
+ * (tests/assemble_ref.py; parity with the package itself is unpinned).
+ *
+ * A candidate row r = b tries + t is count[r] <= IDV_ASM_MAX_PIECES pieces first[r] .. first[r] + count[r] - 1 of the piece arrays
+ * (device, npieces entries each): piece i copies len[i] samples from pool + src[i] (int64 sample offsets) to positions dst[i] ..
+ * dst[i] + len[i] - 1 of the row.  The pieces of a row are sorted by dst and do not overlap; positions no piece covers are +0.  A row
+ * holds n = rowlen[r] positions (device int32, clamped to [0, samples]; NULL: samples each).  A piece that does not lie inside
+ * [0, pool_n) or inside [0, n) is dropped whole: nothing outside a named piece, and nothing outside the pool, is ever read.
+ *
+ * idv_asm_activity, three launches: (a) one wave per win-sample window of every candidate: max|x| and sum x^2 in double into work
+ * (idv_asm_work_bytes(B tries, samples, win) = 16 B tries ceil(samples / win) bytes, 8-byte aligned); (b) one workgroup per row b, for
+ * each candidate in double: k = 10^(target_db / 20) / (sqrt(sum x^2 / n) + EPS), per window db = 20 log10(k^2 sum x^2 + EPS),
+ * p = 1 / (1 + exp(1 - 0.2 db)), s_j = 0.8 p_j + 0.2 p_(j-1) where p_j > p_(j-1), else 0.05 p_j + 0.95 p_(j-1), p_(-1) = 0; the window is
+ * active when s_j > energy_thresh.  rowstat[r][2] = max|x|, sum x^2; active[r], windows[r] = ceil(n / win) (int32);
+ * activity[r] = active / windows (double, 0 for n = 0); chosen[b] = the first t with activity > min_activity and accepted[b] = 1, or,
+ * when there is none, the t with the most active windows (the lowest on a tie) and accepted[b] = 0.
+ * idv_asm_write: out[b][0 .. samples) = candidate chosen[b] (read on the device, clamped to [0, tries)) of row b, its pieces copied
+ * bit for bit, +0 elsewhere; out is [B][ldo].
+ * The order of every sum follows from a sample's index in its window and a window's index in its row alone; no atomics.
+ * IDV_EINVAL (before any GPU work) for a NULL pointer (rowlen may be NULL), B <= 0, tries outside 1 .. IDV_ASM_MAX_TRIES, B tries >
+ * 65535, samples <= 0 or > 2^27, win < 4, > 2^27 or no multiple of 4 (a window starts on a quad of its row), npieces <= 0 or > 2^30,
+ * pool_n <= 0, work_bytes too small, ldo < samples, a non-finite parameter, a pointer not aligned to its element. */
+#define IDV_ASM_MAX_PIECES 64
+#define IDV_ASM_MAX_TRIES 16
+#define IDV_ASM_WIN_FIELDS 2
+long long idv_asm_work_bytes(int R, int samples, int win);
+int idv_asm_activity(const float* pool, long long pool_n, const long long* src, const int* len, const int* dst, const int* first,
+                     const int* count, int npieces, const int* rowlen, int B, int tries, int samples, int win, double target_db,
+                     double energy_thresh, double min_activity, void* work, long long work_bytes, double* rowstat, int* active,
+                     int* windows, double* activity, int* chosen, int* accepted, void* stream);
+int idv_asm_write(const float* pool, long long pool_n, const long long* src, const int* len, const int* dst, const int* first,
+                  const int* count, int npieces, const int* chosen, int B, int tries, int samples, float* out, long long ldo,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif
