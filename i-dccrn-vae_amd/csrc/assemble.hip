@@ -15,29 +15,21 @@
 //
 // The 64 pieces of a row sit in LDS; a lane finds the piece under the first sample of ITS quad by a 7-step search and loads the 16
 // bytes wherever they lie (4-byte aligned vector loads); a quad that straddles a piece's end, a pause or the row's end is read sample
-// by sample.  The order of every sum is fixed by the sample's index IN ITS WINDOW alone, as in mix.hip: sample i belongs to quad i / 4,
-// quad q to lane q % 64; a lane adds its quads in increasing q, the four terms of a quad in increasing i, the 64 lanes meet in an xor
-// butterfly; a row adds its windows k = t, t + 256, ... in thread t and the threads in an LDS tree.  So a candidate's numbers do not
-// depend on B, on tries, on the other rows or on where its pieces lie in the pool.  A piece that is not inside the pool and inside its
-// row is dropped whole, so no table can make a kernel read outside the pool.  No atomics, no spin, every loop bounded.
-#include "common.hpp"
+// by sample.  Every sum is taken in the fixed order of rows.hpp, so a candidate's numbers do not depend on B, on tries, on the other
+// rows or on where its pieces lie in the pool.  A piece that is not inside the pool and inside its row is dropped whole, so no table
+// can make a kernel read outside the pool.  No atomics, no spin, every loop bounded.
+#include "rows.hpp"
 #include "../../include/idccrn_hip.h"
 
 #include <cmath>
 
 namespace {
 
-constexpr int AS_MAX_LEN = 1 << 27;           // samples per row
 constexpr int AS_MAXP = IDV_ASM_MAX_PIECES;
 constexpr int AS_WF = IDV_ASM_WIN_FIELDS;     // doubles per window: max|x|, sum x^2
 constexpr double AS_EPS = 2.220446049250313e-16;
 constexpr double AS_A = -1.0, AS_B = 0.2;     // the logistic of activitydetector
 constexpr double AS_ATT = 0.8, AS_REL = 0.05; // its attack and release
-
-// four floats at any 4-byte aligned address, one 16-byte load or store
-struct __attribute__((packed, aligned(4))) quad_t {
-    float x, y, z, w;
-};
 
 struct Piece {
     long long src;
@@ -111,69 +103,28 @@ __device__ __forceinline__ float4 load_row4(const float* __restrict__ pool, cons
     return make_float4(t[0], t[1], t[2], t[3]);
 }
 
-__device__ __forceinline__ double wave_max_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
-__device__ __forceinline__ void acc_sq(double& s, double& mx, float a) {
-    const double d = (double)a;
-    s += d * d;
-    mx = fmax(mx, fabs(d));
-}
-
-__device__ __forceinline__ int row_len(const int* __restrict__ rowlen, int r, int samples) {
-    return rowlen ? max(0, min(rowlen[r], samples)) : samples;
-}
-
 __global__ __launch_bounds__(256) void asm_window_kernel(Tables T, const int* __restrict__ rowlen, int samples, int win, int nwin,
                                                          double* __restrict__ W) {
     __shared__ Piece sh[AS_MAXP];
-    const int r = blockIdx.y, lane = threadIdx.x & 63;
-    const int k = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int r = blockIdx.y;
+    Window w = wave_window();
     const int n = row_len(rowlen, r, samples);
     const int c = load_pieces(T, r, n, sh, threadIdx.x);
     __syncthreads();
-    if (k >= nwin) return;
-    const long long s0 = (long long)k * win;
+    if (w.k >= nwin) return;
     double s = 0, m = 0;
-    if (s0 < n) {                                          // wave-uniform
-        const int w0 = (int)s0, cnt = min(win, n - w0);
-        const int nquad = (cnt + 3) >> 2;
-        for (int q = lane; q < nquad; q += 64) {
-            const float4 a = load_row4(T.pool, sh, c, w0 + 4 * q);
+    if (w.cut(win, n)) {                                   // wave-uniform
+        for (int q = w.lane; q < w.nquad; q += 64) {
+            const float4 a = load_row4(T.pool, sh, c, w.w0 + 4 * q);
             acc_sq(s, m, a.x), acc_sq(s, m, a.y), acc_sq(s, m, a.z), acc_sq(s, m, a.w);
         }
         s = wave_sum_d(s);
         m = wave_max_d(m);
     }
-    if (lane == 0) {
-        double* w = W + ((size_t)r * nwin + k) * AS_WF;
-        w[0] = m, w[1] = s;
+    if (w.lane == 0) {
+        double* o = W + ((size_t)r * nwin + w.k) * AS_WF;
+        o[0] = m, o[1] = s;
     }
-}
-
-// the 256 threads' values -> their sum (an LDS tree, the same order whatever the values) / their maximum, in every thread
-__device__ __forceinline__ double block_sum(double v, double* sh, int tid) {
-    __syncthreads();
-    sh[tid] = v;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) sh[tid] += sh[tid + o];
-        __syncthreads();
-    }
-    return sh[0];
-}
-__device__ __forceinline__ double block_max(double v, double* sh, int tid) {
-    __syncthreads();
-    sh[tid] = v;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) sh[tid] = fmax(sh[tid], sh[tid + o]);
-        __syncthreads();
-    }
-    return sh[0];
 }
 
 __device__ __forceinline__ double energy_prob(double k2, double sum) {
@@ -239,35 +190,20 @@ __global__ __launch_bounds__(256) void asm_write_kernel(Tables T, const int* __r
     const long long i0 = 4LL * ((long long)blockIdx.x * 256 + threadIdx.x);
     if (i0 >= samples) return;
     const int p = (int)i0;
-    const float4 a = load_row4(T.pool, sh, c, p);
-    const size_t at = (size_t)b * ldo + p;
-    if (p + 3 < samples) {
-        *reinterpret_cast<quad_t*>(out + at) = quad_t{a.x, a.y, a.z, a.w};
-        return;
-    }
-    const float y[4] = {a.x, a.y, a.z, a.w};
-    for (int e = 0; p + e < samples; ++e) out[at + e] = y[e];
+    store4(out + (size_t)b * ldo, p, samples, load_row4(T.pool, sh, c, p));
 }
 
 bool tables_ok(const float* pool, long long pool_n, const long long* src, const int* len, const int* dst, const int* first,
                const int* count, int npieces, int B, int tries, int samples) {
     if (!pool || !src || !len || !dst || !first || !count) return false;
     if (pool_n <= 0 || npieces <= 0 || npieces > (1 << 30)) return false;
-    if (B <= 0 || tries < 1 || tries > IDV_ASM_MAX_TRIES || (long long)B * tries > 65535) return false;
-    if (samples <= 0 || samples > AS_MAX_LEN) return false;
-    if (((uintptr_t)pool & 3) || ((uintptr_t)src & 7) || ((uintptr_t)len & 3) || ((uintptr_t)dst & 3) || ((uintptr_t)first & 3) ||
-        ((uintptr_t)count & 3))
-        return false;
-    return true;
+    if (B <= 0 || tries < 1 || tries > IDV_ASM_MAX_TRIES || !row_limits_ok((long long)B * tries, samples)) return false;
+    return aligned_to(4, {pool, len, dst, first, count}) && aligned_to(8, {src});
 }
 
 }  // namespace
 
-extern "C" long long idv_asm_work_bytes(int R, int samples, int win) {
-    if (R <= 0 || R > 65535 || samples <= 0 || samples > AS_MAX_LEN || win < 4 || win > AS_MAX_LEN || win % 4 != 0) return -1;
-    const long long nwin = ((long long)samples + win - 1) / win;
-    return (long long)R * nwin * AS_WF * (long long)sizeof(double);
-}
+extern "C" long long idv_asm_work_bytes(int R, int samples, int win) { return window_work_bytes(R, samples, win, AS_WF); }
 
 extern "C" int idv_asm_activity(const float* pool, long long pool_n, const long long* src, const int* len, const int* dst, const int* first,
                                 const int* count, int npieces, const int* rowlen, int B, int tries, int samples, int win, double target_db,
@@ -275,11 +211,9 @@ extern "C" int idv_asm_activity(const float* pool, long long pool_n, const long 
                                 int* windows, double* activity, int* chosen, int* accepted, void* stream) {
     if (!tables_ok(pool, pool_n, src, len, dst, first, count, npieces, B, tries, samples)) return IDV_EINVAL;
     const long long need = idv_asm_work_bytes(B * tries, samples, win);
-    if (need < 0 || !work || work_bytes < need || ((uintptr_t)work & 7)) return IDV_EINVAL;
+    if (need < 0 || !work || work_bytes < need) return IDV_EINVAL;
     if (!rowstat || !active || !windows || !activity || !chosen || !accepted) return IDV_EINVAL;
-    if (((uintptr_t)rowstat & 7) || ((uintptr_t)activity & 7) || ((uintptr_t)active & 3) || ((uintptr_t)windows & 3) ||
-        ((uintptr_t)chosen & 3) || ((uintptr_t)accepted & 3) || ((uintptr_t)rowlen & 3))
-        return IDV_EINVAL;
+    if (!aligned_to(8, {work, rowstat, activity}) || !aligned_to(4, {active, windows, chosen, accepted, rowlen})) return IDV_EINVAL;
     if (!std::isfinite(target_db) || !std::isfinite(energy_thresh) || !std::isfinite(min_activity)) return IDV_EINVAL;
     const int nwin = (int)(((long long)samples + win - 1) / win);
     const Tables T{pool, pool_n, src, len, dst, first, count, npieces};
@@ -295,7 +229,7 @@ extern "C" int idv_asm_write(const float* pool, long long pool_n, const long lon
                              const int* count, int npieces, const int* chosen, int B, int tries, int samples, float* out, long long ldo,
                              void* stream) {
     if (!tables_ok(pool, pool_n, src, len, dst, first, count, npieces, B, tries, samples)) return IDV_EINVAL;
-    if (!chosen || !out || ldo < samples || ((uintptr_t)chosen & 3) || ((uintptr_t)out & 3)) return IDV_EINVAL;
+    if (!chosen || !out || ldo < samples || !aligned_to(4, {chosen, out})) return IDV_EINVAL;
     const Tables T{pool, pool_n, src, len, dst, first, count, npieces};
     const unsigned gx = (unsigned)(((long long)samples + 1023) / 1024);
     hipLaunchKernelGGL(asm_write_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, T, chosen, tries, samples, out, ldo);

@@ -18,7 +18,7 @@
 //   (c) set_moments_kernel / sil_kernel / sil_final_kernel: column means and variances of a set of sampled latent vectors, the score
 //       of every vector, and their mean.
 // No atomics anywhere: the same sequence of calls gives the same bits.
-#include "common.hpp"
+#include "rows.hpp"
 #include "../../include/idccrn_hip.h"
 
 namespace {
@@ -33,25 +33,6 @@ struct Lat {
 };
 
 __device__ __forceinline__ int row_frames(const int* frames, int b, int T) { return frames ? min(max(frames[b], 1), T) : T; }
-
-// ((w0 + w1) + w2) + w3 of the four waves' values (lane 0 of each holds it); sh: 4 doubles, free again after the call
-__device__ double waves_sum(double v, double* sh) {
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((sh[0] + sh[1]) + sh[2]) + sh[3];
-}
-
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
 
 // test_prevae.py:25-43 and :45-69 for one (t, h), fp32 step by step
 struct Elem {
@@ -405,7 +386,7 @@ __global__ __launch_bounds__(256) void sil_final_kernel(const double* __restrict
     __shared__ double sh[4];
     double s = 0;
     for (int n = threadIdx.x; n < N; n += 256) s += score[n];
-    s = waves_sum(wave_sum_d(s), sh);
+    s = waves_sum<4>(s, sh);
     if (threadIdx.x != 0) return;
     out[0] = s / (double)N;
     double md = 0, var[4] = {0, 0, 0, 0};

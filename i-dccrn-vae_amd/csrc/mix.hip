@@ -19,27 +19,19 @@
 //
 // A row is base + off[b] (device int64 sample offsets: rows read in place in a packed pool) or base + b ld (off == NULL: a padded
 // batch), at any alignment: a lane loads the 16 bytes of ITS quad wherever they lie (4-byte aligned vector loads); a quad that
-// straddles the row's end or the noise's wrap is read sample by sample.  The order of every sum is fixed by the sample's index IN ITS
-// WINDOW alone: sample i belongs to quad i / 4, quad q to lane q % 64; a lane adds its quads in increasing q, the four terms of a quad in
-// increasing i, the 64 lanes meet in an xor butterfly; a row adds its windows k = t, t + 256, ... in thread t and the threads in an LDS
-// tree.  So a row's result does not depend on B, on the other rows, on what lies at or past n (it is never read), on the row pitch or on
-// the base alignment.  No atomics; pow, log10 and sqrt run in double on the device, nothing returns to the host.
-#include "common.hpp"
+// straddles the row's end or the noise's wrap is read sample by sample.  Every sum is taken in the fixed order of rows.hpp, so a row's
+// result does not depend on B, on the other rows, on what lies at or past n (it is never read), on the row pitch or on the base
+// alignment.  No atomics; pow, log10 and sqrt run in double on the device, nothing returns to the host.
+#include "rows.hpp"
 #include "../../include/idccrn_hip.h"
 
 #include <cmath>
 
 namespace {
 
-constexpr int MX_MAX_LEN = 1 << 27;           // samples per row
 constexpr int MX_WF = IDV_MIX_WIN_FIELDS;     // doubles per window: max|c|, sum c^2, max|v|, sum v^2, max|y0|, sum y0^2
 constexpr int MX_RF = IDV_MIX_ROW_FIELDS;     // doubles per row, the IDV_MIX_* indices of the header
 constexpr double MX_EPS = 2.220446049250313e-16;
-
-// four floats at any 4-byte aligned address, one 16-byte load
-struct __attribute__((packed, aligned(4))) quad_t {
-    float x, y, z, w;
-};
 
 struct Row {
     const float* c;       // n samples
@@ -52,26 +44,12 @@ __device__ __forceinline__ Row row_of(const float* __restrict__ clean, const lon
                                       const int* __restrict__ lens, const int* __restrict__ noise_lens, const int* __restrict__ phase, int L,
                                       int Ln, int b) {
     Row r;
-    r.c = clean + (clean_off ? clean_off[b] : (long long)b * ldc);
-    r.v = noise + (noise_off ? noise_off[b] : (long long)b * ldn);
-    r.n = max(0, min(lens ? lens[b] : L, L));
+    r.c = row_base(clean, clean_off, ldc, b);
+    r.v = row_base(noise, noise_off, ldn, b);
+    r.n = row_len(lens, b, L);
     r.m = max(1, min(noise_lens ? noise_lens[b] : Ln, Ln));
     const int o = phase ? phase[b] : 0;
     r.o = o > 0 ? o % r.m : 0;
-    return r;
-}
-
-// samples p .. p + 3 of a row's cnt samples; those that do not exist are +0
-__device__ __forceinline__ float4 load_clean(const float* __restrict__ x, int p, int cnt) {
-    float4 r;
-    if (p + 3 < cnt) {
-        const quad_t q = *reinterpret_cast<const quad_t*>(x + p);
-        return make_float4(q.x, q.y, q.z, q.w);
-    }
-    r.x = p < cnt ? x[p] : 0.f;
-    r.y = p + 1 < cnt ? x[p + 1] : 0.f;
-    r.z = p + 2 < cnt ? x[p + 2] : 0.f;
-    r.w = 0.f;
     return r;
 }
 
@@ -102,18 +80,6 @@ __device__ __forceinline__ int wrap(int j0, int d, int m) {
     return (int)j;
 }
 
-__device__ __forceinline__ double wave_max_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
-__device__ __forceinline__ void acc_sq(double& s, double& mx, float a) {
-    const double d = (double)a;
-    s += d * d;
-    mx = fmax(mx, fabs(d));
-}
-
 #define MIX_ROW_PARAMS                                                                                                                   \
     const float *__restrict__ clean, const long long *__restrict__ clean_off, long long ldc, const float *__restrict__ noise,           \
         const long long *__restrict__ noise_off, long long ldn, const int *__restrict__ lens, const int *__restrict__ noise_lens,       \
@@ -121,47 +87,41 @@ __device__ __forceinline__ void acc_sq(double& s, double& mx, float a) {
 #define MIX_ROW_ARGS clean, clean_off, ldc, noise, noise_off, ldn, lens, noise_lens, phase, L, Ln
 
 __global__ __launch_bounds__(256) void window_stats_kernel(MIX_ROW_PARAMS, int win, int nwin, double* __restrict__ W) {
-    const int b = blockIdx.y, lane = threadIdx.x & 63;
-    const int k = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (k >= nwin) return;
+    const int b = blockIdx.y;
+    Window w = wave_window();
+    if (w.k >= nwin) return;
     const Row r = row_of(MIX_ROW_ARGS, b);
-    const long long s0 = (long long)k * win;
     double sc = 0, mc = 0, sv = 0, mv = 0;
-    if (s0 < r.n) {                                        // wave-uniform
-        const int w0 = (int)s0, cnt = min(win, r.n - w0);
-        const int jw = wrap(r.o, w0, r.m);
-        const int nquad = (cnt + 3) >> 2;
-        for (int q = lane; q < nquad; q += 64) {
-            const float4 a = load_clean(r.c + w0, 4 * q, cnt);
-            const float4 u = load_noise(r.v, wrap(jw, 4 * q, r.m), r.m, 4 * q, cnt);
+    if (w.cut(win, r.n)) {                                 // wave-uniform
+        const int jw = wrap(r.o, w.w0, r.m);
+        for (int q = w.lane; q < w.nquad; q += 64) {
+            const float4 a = load4(r.c + w.w0, 4 * q, w.cnt);
+            const float4 u = load_noise(r.v, wrap(jw, 4 * q, r.m), r.m, 4 * q, w.cnt);
             acc_sq(sc, mc, a.x), acc_sq(sc, mc, a.y), acc_sq(sc, mc, a.z), acc_sq(sc, mc, a.w);
             acc_sq(sv, mv, u.x), acc_sq(sv, mv, u.y), acc_sq(sv, mv, u.z), acc_sq(sv, mv, u.w);
         }
         sc = wave_sum_d(sc), sv = wave_sum_d(sv);
         mc = wave_max_d(mc), mv = wave_max_d(mv);
     }
-    if (lane == 0) {
-        double* w = W + ((size_t)b * nwin + k) * MX_WF;
-        w[0] = mc, w[1] = sc, w[2] = mv, w[3] = sv;
+    if (w.lane == 0) {
+        double* o = W + ((size_t)b * nwin + w.k) * MX_WF;
+        o[0] = mc, o[1] = sc, o[2] = mv, o[3] = sv;
     }
 }
 
 __global__ __launch_bounds__(256) void window_level_kernel(MIX_ROW_PARAMS, int win, int nwin, const double* __restrict__ R,
                                                            double* __restrict__ W) {
-    const int b = blockIdx.y, lane = threadIdx.x & 63;
-    const int k = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (k >= nwin) return;
+    const int b = blockIdx.y;
+    Window w = wave_window();
+    if (w.k >= nwin) return;
     const Row r = row_of(MIX_ROW_ARGS, b);
     const double ga = R[(size_t)b * MX_RF + IDV_MIX_A], gb = R[(size_t)b * MX_RF + IDV_MIX_B];
-    const long long s0 = (long long)k * win;
     double sy = 0, my = 0;
-    if (s0 < r.n) {
-        const int w0 = (int)s0, cnt = min(win, r.n - w0);
-        const int jw = wrap(r.o, w0, r.m);
-        const int nquad = (cnt + 3) >> 2;
-        for (int q = lane; q < nquad; q += 64) {
-            const float4 a = load_clean(r.c + w0, 4 * q, cnt);
-            const float4 u = load_noise(r.v, wrap(jw, 4 * q, r.m), r.m, 4 * q, cnt);
+    if (w.cut(win, r.n)) {
+        const int jw = wrap(r.o, w.w0, r.m);
+        for (int q = w.lane; q < w.nquad; q += 64) {
+            const float4 a = load4(r.c + w.w0, 4 * q, w.cnt);
+            const float4 u = load_noise(r.v, wrap(jw, 4 * q, r.m), r.m, 4 * q, w.cnt);
             const double y0 = fma(ga, (double)a.x, gb * (double)u.x), y1 = fma(ga, (double)a.y, gb * (double)u.y);
             const double y2 = fma(ga, (double)a.z, gb * (double)u.z), y3 = fma(ga, (double)a.w, gb * (double)u.w);
             sy += y0 * y0, sy += y1 * y1, sy += y2 * y2, sy += y3 * y3;
@@ -170,32 +130,10 @@ __global__ __launch_bounds__(256) void window_level_kernel(MIX_ROW_PARAMS, int w
         sy = wave_sum_d(sy);
         my = wave_max_d(my);
     }
-    if (lane == 0) {
-        double* w = W + ((size_t)b * nwin + k) * MX_WF;
-        w[4] = my, w[5] = sy;
+    if (w.lane == 0) {
+        double* o = W + ((size_t)b * nwin + w.k) * MX_WF;
+        o[4] = my, o[5] = sy;
     }
-}
-
-// the 256 threads' values -> their sum (an LDS tree, the same order whatever the values) / their maximum, in every thread
-__device__ __forceinline__ double block_sum(double v, double* sh, int tid) {
-    __syncthreads();
-    sh[tid] = v;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) sh[tid] += sh[tid + o];
-        __syncthreads();
-    }
-    return sh[0];
-}
-__device__ __forceinline__ double block_max(double v, double* sh, int tid) {
-    __syncthreads();
-    sh[tid] = v;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) sh[tid] = fmax(sh[tid], sh[tid + o]);
-        __syncthreads();
-    }
-    return sh[0];
 }
 
 __global__ __launch_bounds__(256) void row_gains_kernel(const int* __restrict__ lens, int L, int win, int nwin, const double* __restrict__ W,
@@ -203,7 +141,7 @@ __global__ __launch_bounds__(256) void row_gains_kernel(const int* __restrict__ 
                                                         double* __restrict__ R) {
     __shared__ double sh[256];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int n = max(0, min(lens ? lens[b] : L, L));
+    const int n = row_len(lens, b, L);
     const int nw = (int)(((long long)n + win - 1) / win);
     const double* Wr = W + (size_t)b * nwin * MX_WF;
     double mc = 0, sc = 0, mv = 0, sv = 0;
@@ -242,7 +180,7 @@ __global__ __launch_bounds__(256) void row_final_kernel(const int* __restrict__ 
                                                         const double* __restrict__ par, double clip, double* __restrict__ R) {
     __shared__ double sh[256];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int n = max(0, min(lens ? lens[b] : L, L));
+    const int n = row_len(lens, b, L);
     const int nw = (int)(((long long)n + win - 1) / win);
     const double* Wr = W + (size_t)b * nwin * MX_WF;
     double my = 0, sy = 0;
@@ -275,7 +213,7 @@ __global__ __launch_bounds__(256) void write_kernel(MIX_ROW_PARAMS, const double
     const int p = (int)i0;
     float y[4] = {0.f, 0.f, 0.f, 0.f}, c[4] = {0.f, 0.f, 0.f, 0.f}, v[4] = {0.f, 0.f, 0.f, 0.f};
     if (p < r.n) {
-        const float4 a = load_clean(r.c, p, r.n);
+        const float4 a = load4(r.c, p, r.n);
         const float4 u = load_noise(r.v, (int)(((unsigned)r.o + (unsigned)p) % (unsigned)r.m), r.m, p, r.n);
         const float ca[4] = {a.x, a.y, a.z, a.w}, ua[4] = {u.x, u.y, u.z, u.w};
 #pragma unroll
@@ -288,32 +226,23 @@ __global__ __launch_bounds__(256) void write_kernel(MIX_ROW_PARAMS, const double
             }
         }
     }
-    const size_t at = (size_t)b * ldy + p;
-    if (p + 3 < L) {
-        *reinterpret_cast<quad_t*>(noisy + at) = quad_t{y[0], y[1], y[2], y[3]};
-        *reinterpret_cast<quad_t*>(clean_out + at) = quad_t{c[0], c[1], c[2], c[3]};
-        *reinterpret_cast<quad_t*>(noise_out + at) = quad_t{v[0], v[1], v[2], v[3]};
-        return;
-    }
-    for (int e = 0; p + e < L; ++e) noisy[at + e] = y[e], clean_out[at + e] = c[e], noise_out[at + e] = v[e];
+    const size_t at = (size_t)b * ldy;
+    store4(noisy + at, p, L, make_float4(y[0], y[1], y[2], y[3]));
+    store4(clean_out + at, p, L, make_float4(c[0], c[1], c[2], c[3]));
+    store4(noise_out + at, p, L, make_float4(v[0], v[1], v[2], v[3]));
 }
 
 bool rows_ok(const float* clean, const long long* clean_off, long long ldc, const float* noise, const long long* noise_off, long long ldn,
              int B, int L, int Ln) {
-    if (!clean || !noise || B <= 0 || B > 65535 || L <= 0 || L > MX_MAX_LEN || Ln <= 0 || Ln > MX_MAX_LEN) return false;
+    if (!clean || !noise || !row_limits_ok(B, L) || !row_limits_ok(B, Ln)) return false;
     if (!clean_off && ldc < L) return false;
     if (!noise_off && ldn < Ln) return false;
-    if (((uintptr_t)clean & 3) || ((uintptr_t)noise & 3) || ((uintptr_t)clean_off & 7) || ((uintptr_t)noise_off & 7)) return false;
-    return true;
+    return aligned_to(4, {clean, noise}) && aligned_to(8, {clean_off, noise_off});
 }
 
 }  // namespace
 
-extern "C" long long idv_mix_work_bytes(int B, int L, int win) {
-    if (B <= 0 || B > 65535 || L <= 0 || L > MX_MAX_LEN || win < 4 || win > MX_MAX_LEN || win % 4 != 0) return -1;
-    const long long nwin = ((long long)L + win - 1) / win;
-    return (long long)B * nwin * MX_WF * (long long)sizeof(double);
-}
+extern "C" long long idv_mix_work_bytes(int B, int L, int win) { return window_work_bytes(B, L, win, MX_WF); }
 
 extern "C" int idv_mix_gains(const float* clean, const long long* clean_off, long long ldc, const float* noise, const long long* noise_off,
                              long long ldn, const int* lens, const int* noise_lens, const int* phase, int B, int L, int Ln,
@@ -321,7 +250,7 @@ extern "C" int idv_mix_gains(const float* clean, const long long* clean_off, lon
                              long long work_bytes, double* rows, void* stream) {
     const long long need = idv_mix_work_bytes(B, L, win);
     if (need < 0 || !rows_ok(clean, clean_off, ldc, noise, noise_off, ldn, B, L, Ln)) return IDV_EINVAL;
-    if (!par || !work || !rows || work_bytes < need || ((uintptr_t)work & 7) || ((uintptr_t)rows & 7) || ((uintptr_t)par & 7)) return IDV_EINVAL;
+    if (!par || !work || !rows || work_bytes < need || !aligned_to(8, {work, rows, par})) return IDV_EINVAL;
     if (!std::isfinite(target_db) || !std::isfinite(thresh_db) || !std::isfinite(clip) || !(clip > 2 * MX_EPS)) return IDV_EINVAL;
     if (segmental != 0 && segmental != 1) return IDV_EINVAL;
     const int nwin = (int)(((long long)L + win - 1) / win);
@@ -339,8 +268,8 @@ extern "C" int idv_mix_write(const float* clean, const long long* clean_off, lon
                              long long ldn, const int* lens, const int* noise_lens, const int* phase, int B, int L, int Ln,
                              const double* rows, float* noisy, float* clean_out, float* noise_out, long long ldy, void* stream) {
     if (!rows_ok(clean, clean_off, ldc, noise, noise_off, ldn, B, L, Ln)) return IDV_EINVAL;
-    if (!rows || !noisy || !clean_out || !noise_out || ldy < L || ((uintptr_t)rows & 7)) return IDV_EINVAL;
-    if (((uintptr_t)noisy & 3) || ((uintptr_t)clean_out & 3) || ((uintptr_t)noise_out & 3)) return IDV_EINVAL;
+    if (!rows || !noisy || !clean_out || !noise_out || ldy < L) return IDV_EINVAL;
+    if (!aligned_to(8, {rows}) || !aligned_to(4, {noisy, clean_out, noise_out})) return IDV_EINVAL;
     const unsigned gx = (unsigned)(((long long)L + 1023) / 1024);
     hipLaunchKernelGGL(write_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, MIX_ROW_ARGS, rows, noisy, clean_out, noise_out, ldy);
     return idv_launch_status();

@@ -13,21 +13,12 @@
 //                      persistent state[1 + 2*rows] = (n, mean[rows], M2[rows]), all double.
 // Every sum has a fixed order (xor butterfly within a wave, waves and chunks in increasing order) and there is no atomic: the same
 // sequence of calls gives the same bits.
-#include "common.hpp"
+#include "rows.hpp"
 #include "../../include/idccrn_hip.h"
 
 namespace {
 
 constexpr int MO_CH = 2048, MO_PER = MO_CH / 256;          // columns per tile, per thread
-
-// sum over the 256 threads in a fixed order; every thread gets the result.  sh: 4 doubles, free again after the call.
-__device__ double block_sum4_d(double v, double* sh) {
-    v = wave_sum_d(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((sh[0] + sh[1]) + sh[2]) + sh[3];
-}
 
 __global__ __launch_bounds__(256) void tile_kernel(const float* __restrict__ spec, const int* __restrict__ lens, int B, int hop, int Tmax,
                                                    int Tp, int Jp, int rows, int nch, double* __restrict__ part) {
@@ -58,8 +49,8 @@ __global__ __launch_bounds__(256) void tile_kernel(const float* __restrict__ spe
             }
         }
     }
-    cnt = block_sum4_d(cnt, sh);
-    s = block_sum4_d(s, sh);
+    cnt = waves_sum<4>(cnt, sh);
+    s = waves_sum<4>(s, sh);
     const double mean = cnt > 0 ? s / cnt : 0.0;
     double m2 = 0;
 #pragma unroll
@@ -68,7 +59,7 @@ __global__ __launch_bounds__(256) void tile_kernel(const float* __restrict__ spe
             const double d = (double)v[q] - mean;
             m2 += d * d;
         }
-    m2 = block_sum4_d(m2, sh);
+    m2 = waves_sum<4>(m2, sh);
     if (threadIdx.x == 0) {
         double* o = part + ((size_t)ch * rows + r) * 3;
         o[0] = cnt;

@@ -11,7 +11,7 @@
 // is staged in LDS too where it fits XCAP samples (every ratio between the common rates and 16 kHz); a longer span (decimation by more
 // than 9 with up = 1) is read from memory with the same indices in the same order, so both forms give the same bits.  Row b reads
 // nothing at or past lens[b] and nothing of another row; columns n_out(lens[b]) .. ncols - 1 are written as zeros.
-#include "common.hpp"
+#include "rows.hpp"
 #include "../../include/idccrn_hip.h"
 
 namespace {
@@ -33,8 +33,7 @@ __global__ __launch_bounds__(256) void resample_poly_kernel(const float* __restr
     float* hs = sh;                                        // skew(ntap - 1) + 1 floats
     float* xs = sh + skew(ntap - 1) + 1;                   // XCAP floats (STAGED)
     const int b = blockIdx.y;
-    int L = lens ? lens[b] : Lmax;
-    L = max(0, min(L, Lmax));
+    const int L = row_len(lens, b, Lmax);
     const long long nout = n_out_of(L, up, down);
     const long long n0 = (long long)blockIdx.x * RS_NO, n = n0 + threadIdx.x;
     float* yr = y + (size_t)b * ldy;
@@ -91,14 +90,14 @@ extern "C" int idv_resample_ntaps(int up, int down) {
 }
 
 extern "C" long long idv_resample_len(long long L, int up, int down) {
-    if (L < 0 || L > (1LL << 27) || idv_resample_ntaps(up, down) < 0) return IDV_EINVAL;
+    if (L < 0 || L > ROWS_MAX_LEN || idv_resample_ntaps(up, down) < 0) return IDV_EINVAL;
     const int g = gcd_of(up, down);
     return n_out_of(L, up / g, down / g);
 }
 
 extern "C" int idv_resample(const float* x, long long ldx, const int* lens, int B, int L, int up, int down, const float* taps, float* y,
                             long long ldy, void* stream) {
-    if (!x || !taps || !y || B <= 0 || B > 65535 || L <= 0 || L > (1 << 27) || ldx < L) return IDV_EINVAL;
+    if (!x || !taps || !y || !row_limits_ok(B, L) || ldx < L) return IDV_EINVAL;
     if (idv_resample_ntaps(up, down) < 0) return IDV_EINVAL;
     const int g = gcd_of(up, down);
     up /= g;

@@ -29,14 +29,13 @@
 // Order: output i adds its terms in increasing c, then increasing s, then the instruction's own order of k; c, s, k follow from
 // (i mod 4096, K, H) of the row alone.  B, the other rows, L, the pitches, the pool offsets and the alignment of the pointers have
 // no part in it.  No atomics, no work buffer.
-#include "common.hpp"
+#include "rows.hpp"
 #include "../../include/idccrn_hip.h"
 
 namespace {
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 
-constexpr int RV_MAX_LEN = 1 << 27;                      // samples per row
 constexpr int RV_MAX_TAPS = 1 << 16;
 constexpr int RV_MAX_HIST = 65535;
 constexpr int RV_T = 4096;                               // outputs of a workgroup
@@ -56,9 +55,9 @@ __global__ __launch_bounds__(256) void reverb_kernel(const float* __restrict__ x
     __shared__ float hs[RV_HS + 1];
     const int b = blockIdx.y, tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
     const int i0 = blockIdx.x * RV_T;
-    const float* xr = x + (x_off ? x_off[b] : (long long)b * ldx);
-    const float* hr = h + (h_off ? h_off[b] : (long long)b * ldh);
-    const int n = max(0, min(lens ? lens[b] : L, L));
+    const float* xr = row_base(x, x_off, ldx, b);
+    const float* hr = row_base(h, h_off, ldh, b);
+    const int n = row_len(lens, b, L);
     const int K = max(1, min(taps[b], Kmax));
     const int H = max(0, min(hist ? hist[b] : 0, RV_MAX_HIST));
     const int nC = (K + 14) / 16 + 1;                                   // tap blocks: 16 c - 15 <= K - 1
@@ -140,10 +139,9 @@ __global__ __launch_bounds__(256) void reverb_kernel(const float* __restrict__ x
 
 extern "C" int idv_reverb(const float* x, const long long* x_off, long long ldx, const float* h, const long long* h_off, long long ldh,
                           const int* lens, const int* taps, const int* hist, int B, int L, int Kmax, float* y, long long ldy, void* stream) {
-    if (!x || !h || !taps || !y || B <= 0 || B > 65535 || L <= 0 || L > RV_MAX_LEN || Kmax <= 0 || Kmax > RV_MAX_TAPS) return IDV_EINVAL;
+    if (!x || !h || !taps || !y || !row_limits_ok(B, L) || Kmax <= 0 || Kmax > RV_MAX_TAPS) return IDV_EINVAL;
     if ((!x_off && ldx < L) || (!h_off && ldh < Kmax) || ldy < L) return IDV_EINVAL;
-    if (((uintptr_t)x & 3) || ((uintptr_t)h & 3) || ((uintptr_t)y & 3) || ((uintptr_t)x_off & 7) || ((uintptr_t)h_off & 7)) return IDV_EINVAL;
-    if (((uintptr_t)lens & 3) || ((uintptr_t)taps & 3) || ((uintptr_t)hist & 3)) return IDV_EINVAL;
+    if (!aligned_to(4, {x, h, y, lens, taps, hist}) || !aligned_to(8, {x_off, h_off})) return IDV_EINVAL;
     const unsigned gx = (unsigned)(((long long)L + RV_T - 1) / RV_T);
     hipLaunchKernelGGL(reverb_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, x, x_off, ldx, h, h_off, ldh, lens, taps, hist, L, Kmax,
                        y, ldy);

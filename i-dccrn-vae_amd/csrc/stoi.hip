@@ -17,7 +17,7 @@
 // double by table_kernel once per device, on the stream of the first call; later calls wait for that launch's event until it has
 // been seen complete.  No allocation, no host synchronisation.
 #include <mutex>
-#include "common.hpp"
+#include "rows.hpp"
 #include "../../include/idccrn_hip.h"
 
 namespace {
@@ -91,10 +91,6 @@ __global__ __launch_bounds__(256) void table_kernel() {
 }
 
 // ---- row geometry
-__device__ __forceinline__ int row_len(const int* lens, int b, int Lmax) {
-    const int L = lens ? lens[b] : Lmax;
-    return max(0, min(L, Lmax));
-}
 __host__ __device__ __forceinline__ int n10_of(int L, int fs16) { return fs16 ? (int)((5LL * L + 7) / 8) : L; }
 __host__ __device__ __forceinline__ int frames_of(int n) { return n > NW ? (n - NW + HOP - 1) / HOP : 0; }   // len(range(0, n - 256, 128))
 __device__ __forceinline__ int floor_div(int a, int d) { return a >= 0 ? a / d : -((-a + d - 1) / d); }
@@ -369,17 +365,6 @@ __global__ void final_kernel(const double* __restrict__ part, const int* __restr
     out[b] = (float)(extended ? sum / M : sum / ((double)NBAND * M));
 }
 
-// sum over the 1024 threads of a workgroup in a fixed order; every thread gets the result
-__device__ double block_sum_d(double v, double* sh) {
-    v = wave_sum_d(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = 0;
-    for (int q = 0; q < 16; ++q) s += sh[q];
-    return s;
-}
-
 // grid B: alpha = <e, r> / <e, e>; sqrt(mean((alpha e - r)^2)) over the first lens[b] samples, both passes in double
 __global__ __launch_bounds__(1024) void rmse_kernel(const float* __restrict__ ref, long long ref_ld, const float* __restrict__ est,
                                                     long long est_ld, const int* __restrict__ lens, int Lmax, double* __restrict__ work,
@@ -395,15 +380,15 @@ __global__ __launch_bounds__(1024) void rmse_kernel(const float* __restrict__ re
         D += ev * (double)r[n];
         Q += ev * ev;
     }
-    D = block_sum_d(D, sh);
-    Q = block_sum_d(Q, sh);
+    D = waves_sum<16, true>(D, sh);
+    Q = waves_sum<16, true>(Q, sh);
     const double alpha = D / Q;
     double S = 0;
     for (int n = threadIdx.x; n < L; n += 1024) {
         const double d = alpha * (double)e[n] - (double)r[n];
         S += d * d;
     }
-    S = block_sum_d(S, sh);
+    S = waves_sum<16, true>(S, sh);
     if (threadIdx.x == 0) {
         work[b * 3] = D;
         work[b * 3 + 1] = Q;
@@ -469,14 +454,14 @@ int ensure_tables(hipStream_t st) {
 }  // namespace
 
 extern "C" long long idv_stoi_work_bytes(int B, int Lmax, int fs) {
-    if (B <= 0 || Lmax <= 0 || Lmax > (1 << 27) || (fs != 10000 && fs != 16000)) return -1;
+    if (B <= 0 || Lmax <= 0 || Lmax > ROWS_MAX_LEN || (fs != 10000 && fs != 16000)) return -1;
     return layout(B, Lmax, fs).bytes;
 }
 
 extern "C" int idv_stoi(const float* ref, long long ref_ld, const float* est, long long est_ld, const int* lens, int B, int Lmax, int fs,
                         int extended, void* work, long long work_bytes, float* out, int* counts, void* stream) {
-    if (!ref || !est || !work || !out || B <= 0 || B > 65535 || Lmax <= 0 || (fs != 10000 && fs != 16000)) return IDV_EINVAL;
-    if (Lmax > (1 << 27) || ref_ld < Lmax || est_ld < Lmax || ((uintptr_t)work & 15)) return IDV_EINVAL;   // 8 n stays an int
+    if (!ref || !est || !work || !out || !row_limits_ok(B, Lmax) || (fs != 10000 && fs != 16000)) return IDV_EINVAL;   // 8 n stays an int
+    if (ref_ld < Lmax || est_ld < Lmax || !aligned_to(16, {work})) return IDV_EINVAL;
     const Layout l = layout(B, Lmax, fs);
     if (work_bytes < l.bytes) return IDV_EINVAL;
     hipStream_t st = (hipStream_t)stream;

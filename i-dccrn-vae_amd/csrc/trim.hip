@@ -11,20 +11,18 @@
 //                            outside the row counting as zero; the row maximum, the comparison above in double, first and last frame.
 //   (c) gather_kernel        y[b][i] = x[b][start_b + i] for i < end_b - start_b, zeros behind, bounds read on the device.
 //
-// The order of every sum is fixed by the sample's index IN ITS BLOCK alone: sample i belongs to quad i / 4, quad q to lane q % 64; a
-// lane adds its quads in increasing q, the four squares of a quad in increasing i, and the 64 lanes meet in an xor butterfly.  Where a
-// row's base is not 16-byte aligned (ldx is arbitrary) the lanes still load ALIGNED 16-byte quads, and a lane takes the first 1 .. 3
-// samples of its quad from the lane below (the block's first samples and its ragged end are scalar loads; a sample that does not
-// exist enters as +0, which changes no sum).  So E, P and the bounds of a row do not depend on B, on the other rows, on what lies at or
-// past n_b (it is never read) or on the row pitch.  No atomics.
-#include "common.hpp"
+// A block's sum is taken in the fixed order of rows.hpp (the block is the window).  Where a row's base is not 16-byte aligned (ldx is
+// arbitrary) the lanes still load ALIGNED 16-byte quads, and a lane takes the first 1 .. 3 samples of its quad from the lane below
+// (the block's first samples and its ragged end are scalar loads; a sample that does not exist enters as +0, which changes no sum).
+// So E, P and the bounds of a row do not depend on B, on the other rows, on what lies at or past n_b (it is never read) or on the row
+// pitch.  No atomics.
+#include "rows.hpp"
 #include "../../include/idccrn_hip.h"
 
 #include <cmath>
 
 namespace {
 
-constexpr int TR_MAX_LEN = 1 << 27;           // samples per row
 constexpr int TR_MAX_BLOCKS = 64;             // frame / hop
 
 // the aligned quad j of a block: samples h + 4 j .. h + 4 j + 3 of the block's cnt samples (j = -1: the h samples before the first
@@ -78,23 +76,19 @@ __device__ __forceinline__ double block_energy(const float* __restrict__ blk, in
 
 __global__ __launch_bounds__(256) void block_energy_kernel(const float* __restrict__ x, long long ldx, const int* __restrict__ lens, int Lmax,
                                                            int hop, int nblk, double* __restrict__ E) {
-    const int b = blockIdx.y, lane = threadIdx.x & 63;
-    const int k = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (k >= nblk) return;
-    int n = lens ? lens[b] : Lmax;
-    n = max(0, min(n, Lmax));
-    const long long s0 = (long long)k * hop;
+    const int b = blockIdx.y;
+    Window w = wave_window();
+    if (w.k >= nblk) return;
     double e = 0;
-    if (s0 < n) {                                          // wave-uniform
-        const int cnt = (int)min((long long)hop, n - s0);
-        const float* blk = x + (size_t)b * ldx + s0;
+    if (w.cut(hop, row_len(lens, b, Lmax))) {              // wave-uniform
+        const float* blk = x + (size_t)b * ldx + w.w0;
         const int h = (int)((4 - (((uintptr_t)blk >> 2) & 3)) & 3);
-        e = h == 0 ? block_energy<0>(blk, cnt, lane)
-          : h == 1 ? block_energy<1>(blk, cnt, lane)
-          : h == 2 ? block_energy<2>(blk, cnt, lane)
-                   : block_energy<3>(blk, cnt, lane);
+        e = h == 0 ? block_energy<0>(blk, w.cnt, w.lane)
+          : h == 1 ? block_energy<1>(blk, w.cnt, w.lane)
+          : h == 2 ? block_energy<2>(blk, w.cnt, w.lane)
+                   : block_energy<3>(blk, w.cnt, w.lane);
     }
-    if (lane == 0) E[(size_t)b * nblk + k] = e;
+    if (w.lane == 0) E[(size_t)b * nblk + w.k] = e;
 }
 
 // P[t]: the r blocks around frame t in increasing order (those outside the row are zeros and left out), over the frame length
@@ -109,21 +103,14 @@ __global__ __launch_bounds__(256) void row_scan_kernel(const double* __restrict_
                                                        int nblk, double top_db, int* __restrict__ bounds, double* __restrict__ power,
                                                        long long ldp) {
     __shared__ double shd[256];
-    __shared__ int sh0[256], sh1[256];
+    __shared__ int2 shb[256];
     const int b = blockIdx.x, tid = threadIdx.x;
-    int n = lens ? lens[b] : Lmax;
-    n = max(0, min(n, Lmax));
+    const int n = row_len(lens, b, Lmax);
     const int T = 1 + n / hop, nb = (n + hop - 1) / hop, r = frame / hop;
     const double* Er = E + (size_t)b * nblk;
     double pmax = 0;
     for (int t = tid; t < T; t += 256) pmax = fmax(pmax, frame_power(Er, nb, t, r, frame));
-    shd[tid] = pmax;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) shd[tid] = fmax(shd[tid], shd[tid + o]);
-        __syncthreads();
-    }
-    pmax = shd[0];
+    pmax = tree256(pmax, shd, tid, [](double a, double c) { return fmax(a, c); });
     const double ref_db = 10.0 * log10(fmax(1e-10, pmax));
     int t0 = 0x7fffffff, t1 = -1;
     const int Tall = 1 + Lmax / hop;
@@ -141,19 +128,11 @@ __global__ __launch_bounds__(256) void row_scan_kernel(const double* __restrict_
         }
         if (power) power[(size_t)b * ldp + t] = P;
     }
-    sh0[tid] = t0;
-    sh1[tid] = t1;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) {
-            sh0[tid] = min(sh0[tid], sh0[tid + o]);
-            sh1[tid] = max(sh1[tid], sh1[tid + o]);
-        }
-        __syncthreads();
-    }
+    // (first, last): the min and the max in one tree
+    const int2 span = tree256(make_int2(t0, t1), shb, tid, [](int2 a, int2 c) { return make_int2(min(a.x, c.x), max(a.y, c.y)); });
     if (tid == 0) {
-        t0 = sh0[0];
-        t1 = sh1[0];
+        t0 = span.x;
+        t1 = span.y;
         const bool any = t1 >= 0;
         bounds[2 * b] = any ? t0 * hop : 0;
         bounds[2 * b + 1] = any ? (int)min((long long)n, (long long)(t1 + 1) * hop) : 0;
@@ -187,19 +166,16 @@ __global__ __launch_bounds__(256) void gather_kernel(const float* __restrict__ x
 
 }  // namespace
 
-extern "C" long long idv_trim_work_bytes(int B, int L, int hop) {
-    if (B <= 0 || B > 65535 || L <= 0 || L > TR_MAX_LEN || hop <= 0 || hop > TR_MAX_LEN || hop % 4 != 0) return -1;
-    const long long nblk = ((long long)L + hop - 1) / hop;
-    return (long long)B * nblk * (long long)sizeof(double);
-}
+// hop > 0 and hop % 4 == 0 is the window_work_bytes condition win >= 4
+extern "C" long long idv_trim_work_bytes(int B, int L, int hop) { return window_work_bytes(B, L, hop, 1); }
 
 extern "C" int idv_trim_bounds(const float* x, long long ldx, const int* lens, int B, int L, int frame, int hop, double top_db, void* work,
                                long long work_bytes, int* bounds, double* power, long long ldp, void* stream) {
     const long long need = idv_trim_work_bytes(B, L, hop);
-    if (!x || !work || !bounds || need < 0 || work_bytes < need || ldx < L || ((uintptr_t)work & 7)) return IDV_EINVAL;
+    if (!x || !work || !bounds || need < 0 || work_bytes < need || ldx < L || !aligned_to(8, {work})) return IDV_EINVAL;
     if (frame <= 0 || frame % (2LL * hop) != 0 || frame / hop > TR_MAX_BLOCKS) return IDV_EINVAL;
     if (!(top_db > 0) || !std::isfinite(top_db)) return IDV_EINVAL;
-    if (power && (ldp < 1 + L / hop || ((uintptr_t)power & 7))) return IDV_EINVAL;
+    if (power && (ldp < 1 + L / hop || !aligned_to(8, {power}))) return IDV_EINVAL;
     const int nblk = (int)(((long long)L + hop - 1) / hop);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(block_energy_kernel, dim3((nblk + 3) / 4, B), dim3(256), 0, st, x, ldx, lens, L, hop, nblk, (double*)work);
@@ -208,7 +184,7 @@ extern "C" int idv_trim_bounds(const float* x, long long ldx, const int* lens, i
 }
 
 extern "C" int idv_trim_gather(const float* x, long long ldx, const int* bounds, int B, int Lout, float* y, long long ldy, void* stream) {
-    if (!x || !bounds || !y || B <= 0 || B > 65535 || Lout <= 0 || Lout > TR_MAX_LEN || ldy < Lout) return IDV_EINVAL;
+    if (!x || !bounds || !y || !row_limits_ok(B, Lout) || ldy < Lout) return IDV_EINVAL;
     const unsigned gx = (unsigned)(((long long)Lout + 1023) / 1024);
     hipLaunchKernelGGL(gather_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, x, ldx, bounds, Lout, y, ldy);
     return idv_launch_status();

@@ -37,6 +37,25 @@ def bucket(n: int) -> int:
     return (n + step - 1) // step * step
 
 
+ROWS_MAX_LEN = 1 << 27         # samples per row of the row-signal kernels (csrc/rows.hpp)
+ROWS_MAX_ROWS = 65535          # rows of one call
+_WORK = {}                     # (device, stream, tag, dtype) -> work buffer, grow-only
+
+
+def _scratch(n: int, device, tag="w", dtype=torch.float32) -> torch.Tensor:
+    """The grow-only work buffer of (device, its current stream, tag, dtype), at least ``n`` elements: weight-gradient partials
+    reused across layers and steps, the window sums of trimming and mixing (a corpus of many batch sizes keeps the largest only)."""
+    device = torch.device(device)
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (device, torch.cuda.current_stream(device).cuda_stream, tag, dtype)
+    t = _WORK.get(key)
+    if t is None or t.numel() < n:
+        t = torch.empty(bucket(n), dtype=dtype, device=device)
+        _WORK[key] = t
+    return t
+
+
 class Planar:
     """A planar-J activation  act[2][C][F][Jp]  (see include/idccrn_hip.h).
 
@@ -977,7 +996,7 @@ def istft(spec: Planar, plan: DftPlan, lengths=None) -> torch.Tensor:
 
 # ----------------------------------------------------------------------------- corpus preparation
 RESAMPLE_MAX_M = 640           # max(up, down) after reduction: 8 / 11.025 / 22.05 / 24 / 32 / 44.1 / 48 / 96 kHz <-> 16 kHz all fit
-RESAMPLE_MAX_LEN = 1 << 27     # samples per row
+RESAMPLE_MAX_LEN = ROWS_MAX_LEN
 PAD_MODES = {"reflect": 0, "constant": 1}      # IDV_PAD_REFLECT / IDV_PAD_CONSTANT
 _RESAMPLE_TAPS = {}            # (up, down, device) -> fp32 taps on the device
 
@@ -1028,8 +1047,8 @@ def resample(x: torch.Tensor, up: int, down: int, lengths: Optional[Lengths] = N
     B, Lx = x.shape
     if Lx < 1 or Lx > RESAMPLE_MAX_LEN:
         raise ValueError(f"resample: rows of {Lx} samples; 1 .. 2^27 are supported")
-    if B < 1 or B > 65535:
-        raise ValueError(f"resample: a batch of {B} rows; 1 .. 65535 are supported")
+    if B < 1 or B > ROWS_MAX_ROWS:
+        raise ValueError(f"resample: a batch of {B} rows; 1 .. {ROWS_MAX_ROWS} are supported")
     n = resample_len(Lx, up, down)
     if n > 2 ** 31 - 1 - 256:
         raise ValueError(f"resample: {n} output samples per row are not supported")
@@ -1051,9 +1070,8 @@ def stft_frames_pad(x: torch.Tensor, lengths: Lengths, n_fft: int, win: int, hop
 
 
 # ----------------------------------------------------------------------------- silence trimming
-TRIM_MAX_LEN = 1 << 27         # samples per row
+TRIM_MAX_LEN = ROWS_MAX_LEN
 TRIM_MAX_BLOCKS = 64           # frame_length / hop_length
-_TRIM_WORK = {}                # (device, stream) -> uint8 work buffer, grow-only
 
 
 def check_trim_args(top_db, frame_length, hop_length) -> float:
@@ -1070,33 +1088,20 @@ def check_trim_args(top_db, frame_length, hop_length) -> float:
     return float(top_db)
 
 
-def _trim_work(nbytes: int, device) -> torch.Tensor:
-    """Grow-only work buffer per (device, stream), as :func:`_scratch`: a corpus of many batch sizes keeps the largest one only."""
-    device = torch.device(device)
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    key = (device, torch.cuda.current_stream(device).cuda_stream)
-    t = _TRIM_WORK.get(key)
-    if t is None or t.numel() < nbytes:
-        t = torch.empty(bucket(nbytes), dtype=torch.uint8, device=device)
-        _TRIM_WORK[key] = t
-    return t
-
-
 def trim_bounds(x: torch.Tensor, top_db: float, frame_length: int, hop_length: int, lengths: Optional[Lengths] = None, power: bool = False):
     """idv_trim_bounds: x [B, L] -> int32 bounds [B, 2] on the device (start, end of the non-silent span of every row); with ``power``
     also the float64 frame powers [B, 1 + L // hop_length].  Nothing at or past lengths[b] is read."""
     B, Lx = x.shape
     if Lx < 1 or Lx > TRIM_MAX_LEN:
         raise ValueError(f"trim: rows of {Lx} samples; 1 .. 2^27 are supported")
-    if B < 1 or B > 65535:
-        raise ValueError(f"trim: a batch of {B} rows; 1 .. 65535 are supported")
+    if B < 1 or B > ROWS_MAX_ROWS:
+        raise ValueError(f"trim: a batch of {B} rows; 1 .. {ROWS_MAX_ROWS} are supported")
     check_dev_f32(x, "x")
     x = _ragged_rows(x)
     nbytes = int(_ll_fn("idv_trim_work_bytes")(i(B), i(Lx), i(hop_length)))
     if nbytes < 0:
         raise ValueError(f"trim: a batch of {B} rows of {Lx} samples at hop {hop_length} is not supported")
-    work = _trim_work(nbytes, x.device)
+    work = _scratch(nbytes, x.device, "trim", torch.uint8)
     bounds = torch.empty(B, 2, dtype=torch.int32, device=x.device)
     P = torch.empty(B, 1 + Lx // hop_length, dtype=torch.float64, device=x.device) if power else None
     call("idv_trim_bounds", p(x), ll(x.stride(0)), p(None if lengths is None else lengths.dev), i(B), i(Lx), i(frame_length),
@@ -1117,12 +1122,11 @@ def trim_gather(x: torch.Tensor, bounds: torch.Tensor, Lout: int) -> torch.Tenso
 
 
 # ----------------------------------------------------------------------------- mixture synthesis
-MIX_MAX_LEN = 1 << 27          # samples per row
+MIX_MAX_LEN = ROWS_MAX_LEN
 MIX_WIN_FIELDS = 6             # IDV_MIX_WIN_FIELDS: max|c|, sum c^2, max|v|, sum v^2, max|y0|, sum y0^2 per window
 MIX_ROW_FIELDS = 16            # IDV_MIX_ROW_FIELDS, the IDV_MIX_* indices of include/idccrn_hip.h:
 MIX_FIELD = {"max_c": 0, "sum_c2": 1, "max_v": 2, "sum_v2": 3, "act_c2": 4, "act_v2": 5, "active": 6, "a": 7, "b": 8, "sum_y2": 9,
              "max_y": 10, "g_clean": 11, "g_noise": 12, "level_db": 13, "clipped": 14, "len": 15}
-_MIX_WORK = {}                 # (device, stream) -> uint8 work buffer, grow-only
 
 
 class MixRows(NamedTuple):
@@ -1145,29 +1149,16 @@ class MixRows(NamedTuple):
                 p(self.table[2]), i(self.B), i(self.L), i(self.Ln))
 
 
-def _mix_work(nbytes: int, device) -> torch.Tensor:
-    """Grow-only work buffer per (device, stream), as :func:`_trim_work`."""
-    device = torch.device(device)
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    key = (device, torch.cuda.current_stream(device).cuda_stream)
-    t = _MIX_WORK.get(key)
-    if t is None or t.numel() < nbytes:
-        t = torch.empty(bucket(nbytes), dtype=torch.uint8, device=device)
-        _MIX_WORK[key] = t
-    return t
-
-
 def mix_gains(rows: MixRows, par: torch.Tensor, segmental: bool, target_db: float, clip: float, win: int, thresh_db: float):
     """idv_mix_gains: ``par`` float64 [B, 2] = (snr_db, level_db) on the device -> (the float64 row records [B, MIX_ROW_FIELDS],
     the float64 window sums [B, ceil(L / win), MIX_WIN_FIELDS]).  The window sums are a view of the work buffer of this device and
-    stream: the next call overwrites them."""
+    stream, which :func:`asm_activity` shares: the next call of either overwrites them."""
     check_dev_f32(rows.clean, "clean")
     check_dev_f32(rows.noise, "noise", rows.clean.device)
     nbytes = int(_ll_fn("idv_mix_work_bytes")(i(rows.B), i(rows.L), i(win)))
     if nbytes < 0:
         raise ValueError(f"mix: a batch of {rows.B} rows of {rows.L} samples in windows of {win} is not supported")
-    work = _mix_work(nbytes, rows.clean.device)
+    work = _scratch(nbytes, rows.clean.device, "mix", torch.uint8)
     rec = torch.empty(rows.B, MIX_ROW_FIELDS, dtype=torch.float64, device=rows.clean.device)
     call("idv_mix_gains", *rows.args(), p(par), i(1 if segmental else 0), d(target_db), d(clip), i(win), d(thresh_db), p(work),
          ll(work.numel()), p(rec), stream_ptr())
@@ -1204,7 +1195,7 @@ def reverb_apply(x: torch.Tensor, x_off: Optional[torch.Tensor], h: torch.Tensor
 # ----------------------------------------------------------------------------- clip assembly
 ASM_MAX_PIECES = 64            # IDV_ASM_MAX_PIECES: pieces per candidate row
 ASM_MAX_TRIES = 16             # IDV_ASM_MAX_TRIES: candidates per row
-ASM_MAX_ROWS = 65535           # candidate rows (B tries) of one call
+ASM_MAX_ROWS = ROWS_MAX_ROWS   # candidate rows (B tries) of one call
 ASM_WIN_FIELDS = 2             # IDV_ASM_WIN_FIELDS: max|x|, sum x^2 per window
 
 
@@ -1242,13 +1233,13 @@ def asm_tables(pool: torch.Tensor, src, lens, dst, first, count, B: int, tries: 
 def asm_activity(tab: AsmTables, rowlen: Optional[torch.Tensor], win: int, target_db: float, energy_thresh: float, min_activity: float):
     """idv_asm_activity -> dict of device tensors: ``rowstat`` float64 [R, 2] (max|x|, sum x^2), ``active`` / ``windows`` int32 [R],
     ``activity`` float64 [R], ``chosen`` / ``accepted`` int32 [B], ``window_stats`` float64 [R, ceil(samples / win), 2]: a view of the
-    work buffer of this device and stream, which the next call overwrites."""
+    work buffer of this device and stream, which :func:`mix_gains` shares: the next call of either overwrites it."""
     check_dev_f32(tab.pool, "pool")
     R, dev = tab.B * tab.tries, tab.pool.device
     nbytes = int(_ll_fn("idv_asm_work_bytes")(i(R), i(tab.samples), i(win)))
     if nbytes < 0:
         raise ValueError(f"assemble: {R} candidate rows of {tab.samples} samples in windows of {win} are not supported")
-    work = _mix_work(nbytes, dev)
+    work = _scratch(nbytes, dev, "mix", torch.uint8)
     rowstat = torch.empty(R, 2, dtype=torch.float64, device=dev)
     act = torch.empty(R, dtype=torch.float64, device=dev)
     ints = torch.empty(2 * R + 2 * tab.B, dtype=torch.int32, device=dev)
@@ -1536,21 +1527,10 @@ def cconv_dgrad(dy: Planar, wfrag, bias, cout_adj: int, fwd_transposed: bool, ca
     return out
 
 
-_WORK = {}
 WGRAD_BF16_CFG = -96     # ... of wgrad_bf16_kernel + its unpack (bf16x3 training mode)
 WGRAD_BF16 = os.environ.get("IDV_WGRAD_BF16", "1") != "0"
 WGRAD_GAUSS_CFG = -95    # ... of the three-product fp32 weight gradient (wgrad_combine + wgrad_kernel x 3 products + unpack)
 WGRAD_CFG = -97          # LAUNCH_LOG id of the conv weight-gradient kernel (wgrad_kernel<5, 2, 1, 1, 4, 1, 16, 2> + its unpack)
-
-
-def _scratch(n: int, device, tag="w") -> torch.Tensor:
-    """Grow-only fp32 scratch per (device, stream, tag): weight-gradient partials, reused across layers and steps."""
-    key = (str(device), torch.cuda.current_stream().cuda_stream, tag)
-    t = _WORK.get(key)
-    if t is None or t.numel() < n:
-        t = torch.empty(bucket(n), dtype=torch.float32, device=device)
-        _WORK[key] = t
-    return t
 
 
 def cconv_wgrad(x: Planar, ci_off: int, dy: Planar, cout: int, cin_total: int, transposed: bool, causal: bool, dw_re, dw_im):

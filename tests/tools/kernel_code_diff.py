@@ -10,7 +10,7 @@ llvm-readelf, and the bytes [st_value, st_value + st_size) of every function are
 new symbol or a surviving symbol with different bytes.
 
 Symbols are matched by mangled name.  A kernel whose template parameter list changed is matched by its template arguments with the
-removed positions struck out: RENAMED below is that map.
+removed positions struck out: RENAMED below is that map (empty unless the pull request at hand removes template parameters).
 """
 import hashlib
 import os
@@ -24,18 +24,17 @@ TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
 
 # kernel name -> {position of a template argument the BEFORE build had and the AFTER build has not: the value the AFTER build fixes it
 # to, as a function of the BEFORE argument list}.  A BEFORE kernel with another value there has no successor and counts as removed.
+# An entry describes ONE pull request and goes away once that is merged: applied to a BEFORE build that already has the short list it
+# would strike out live arguments.  How the removal of DBG, RDW and WVEC from the time-Winograd kernel was written:
 #   cconv_tw_kernel<PH, CIK, LEFT, DBG, RDW, WVEC, STATS, NCT> -> <PH, CIK, LEFT, STATS, NCT>   with DBG = 0, RDW = 2, WVEC = (PH == 0)
-#   cconv_tw2_kernel<LEFT, STATS, DBG, NCT>                   -> <LEFT, STATS, NCT>            with DBG = 0
-RENAMED = {
-    "cconv_tw_kernel": {3: lambda a: 0, 4: lambda a: 2, 5: lambda a: int(a[0] == 0)},
-    "cconv_tw2_kernel": {2: lambda a: 0},
-}
-_TMPL = re.compile(r"^(_ZN12_GLOBAL__N_1\d+(%s))I((?:L[ib]\d+E)+)E(.*)$" % "|".join(RENAMED))
+#   "cconv_tw_kernel": {3: lambda a: 0, 4: lambda a: 2, 5: lambda a: int(a[0] == 0)}
+RENAMED = {}
+_TMPL = re.compile(r"^(_ZN12_GLOBAL__N_1\d+(%s))I((?:L[ib]\d+E)+)E(.*)$" % "|".join(RENAMED)) if RENAMED else None
 
 
 def match_key(sym: str, before: bool) -> str:
     """The name two builds share: the mangled name, or for RENAMED kernels `name<args>` without the removed arguments."""
-    m = _TMPL.match(sym)
+    m = _TMPL.match(sym) if _TMPL else None
     if not m:
         return sym
     args = [int(a) for a in re.findall(r"L[ib](\d+)E", m.group(3))]
