@@ -1061,6 +1061,67 @@ def resample(x: torch.Tensor, up: int, down: int, lengths: Optional[Lengths] = N
     return y
 
 
+# ---- the stateful form of the resampler (csrc/stream_resample.hip)
+SR_ROW_FIELDS = ("P0", "count", "n0", "m", "parity", "end", "idle")      # IDV_SR_ROW_* of include/idccrn_hip.h
+SR_TAPS_MODES = {"auto": 0, "mem": 1, "lds": 2}                          # IDV_SR_TAPS_*
+
+
+def stream_resample_hist(up: int, down: int) -> int:
+    """H = floor(2 * half / up) + 1: the input samples a stream keeps from call to call (idv_stream_resample_hist)."""
+    return 20 * max(up, down) // up + 1
+
+
+def stream_resample_final(P: int, up: int, down: int) -> int:
+    """n_final(P) = max(0, ceil((P * up - half) / down)): the outputs that are final after P input samples."""
+    return max(0, -((10 * max(up, down) - P * up) // down))
+
+
+def _stream_resample_hist(hist) -> tuple:
+    """The guards on a resampler's history [2 parities, B, H] -> (B, H)."""
+    check_dev_f32(hist, "hist")
+    if hist.dtype != torch.float32 or hist.dim() != 3 or hist.shape[0] != 2 or not hist.is_contiguous():
+        raise ValueError("stream_resample: hist must be a contiguous float32 tensor [2, B, H]")
+    return int(hist.shape[1]), int(hist.shape[2])
+
+
+def _stream_resample_x(x, B: int, n: int):
+    """The new samples as the kernels read them: fp32 rows of n samples at any pitch -> (tensor or None, pitch)."""
+    if n == 0:
+        return None, 0
+    check_dev_f32(x, "x")
+    if x.dim() != 2 or x.shape[0] != B or x.shape[1] != n:
+        raise ValueError(f"stream_resample: x must be [{B}, {n}], got {tuple(x.shape)}")
+    x = _ragged_rows(x)
+    return x, x.stride(0)
+
+
+def stream_resample(hist: torch.Tensor, parity: int, x: Optional[torch.Tensor], n_new: int, P0: int, flush: bool, n0: int, m: int,
+                    up: int, down: int, taps_mode: str = "auto") -> torch.Tensor:
+    """idv_stream_resample: the B streams of ``hist`` [2, B, H] at position P0 take x [B, n_new] (None for n_new = 0) -> y [B, m], the
+    outputs n0 .. n0 + m - 1; ``flush``: the signals end at P0 + n_new.  Half ``parity`` of hist is read and, unless the call
+    flushes or brings nothing, half 1 - parity written."""
+    B, H = _stream_resample_hist(hist)
+    x, ldx = _stream_resample_x(x, B, n_new)
+    taps = resample_taps(up, down, hist.device)
+    y = torch.empty(B, m, dtype=torch.float32, device=hist.device)
+    call("idv_stream_resample", p(hist), i(H), i(parity), p(x), ll(ldx), i(n_new), ll(P0), i(1 if flush else 0), ll(n0), i(m), i(B),
+         i(up), i(down), p(taps), i(SR_TAPS_MODES[taps_mode]), p(y) if m else p(None), ll(m), stream_ptr())
+    return y
+
+
+def stream_resample_rows(hist: torch.Tensor, x: Optional[torch.Tensor], n_x: int, rows, ldy: int, up: int, down: int,
+                         taps_mode: str = "auto") -> torch.Tensor:
+    """idv_stream_resample_rows: ``rows`` is the device pointer of a table [B][SR_ROW_FIELDS] that idv_stream_resample_rows_check
+    has passed -> y [B, ldy], row b's outputs followed by zeros."""
+    B, H = _stream_resample_hist(hist)
+    x, ldx = _stream_resample_x(x, B, n_x)
+    taps = resample_taps(up, down, hist.device)
+    y = torch.empty(B, ldy, dtype=torch.float32, device=hist.device)
+    call("idv_stream_resample_rows", p(hist), i(H), p(x), ll(ldx), i(n_x), rows, i(B), i(up), i(down), p(taps),
+         i(SR_TAPS_MODES[taps_mode]), p(y) if ldy else p(None), ll(ldy), stream_ptr())
+    return y
+
+
 def stft_frames_pad(x: torch.Tensor, lengths: Lengths, n_fft: int, win: int, hop: int, T: int, pad_mode: str) -> Planar:
     """idv_stft_frames_ragged_pad: the frames [win][Jp] (a Planar of win // 2 "channels") of a padded batch, T columns per row."""
     fr = Planar.empty(1, win // 2, x.shape[0], T, T + 1, x.device)

@@ -12,13 +12,16 @@ emission bookkeeping from which every kernel launch takes its ranges.
 :class:`StreamingSessions` runs one such stream per slot, each starting and ending on its own; :class:`StreamingVAE` streams
 the I-DCCRN-VAE pair (noisy encoder, latent draw, fine-tuned decoder with the noisy skips) under the same contract,
 :class:`StreamingVAESessions` runs that pair one stream per slot, and :class:`StreamingVAETwoLatents` streams the two-latent
-evaluation: speech and noise decoder on one encoder pass, then a mask estimator.
+evaluation: speech and noise decoder on one encoder pass, then a mask estimator.  :class:`StreamingResampler` /
+:class:`StreamingResamplerSessions` resample a stream under the same contract, bit-identical to ``inference.resample``, and
+:class:`AtRate` / :class:`SessionsAtRate` put one in front of and one behind any of the streamers for signals at 48 or 44.1 kHz.
 """
 from __future__ import annotations
 
 from collections.abc import Iterable, Sequence
 from typing import List, NamedTuple, Optional
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -1687,3 +1690,437 @@ class StreamingVAETwoLatentsSessions(_TwoLatents, StreamingVAESessions):
                             (self.lstm_state, 16, self.H)]
         self._zero_views += [(h, h.numel() // slots, 1) for h in [self.h_in] + self.h_enc]
         self._zero_views += [(h, h.numel() // (slots * ns), ns) for ch in self.chains for h in [ch.h_dense] + ch.h_dec]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Streaming at any sample rate: a stateful rational resampler under the push / flush contract (csrc/stream_resample.hip, DESIGN
+# 3.6.5), its sessions form, and wrappers that put one in front of and one behind a streamer of the 16 kHz network.
+class ResampleStep(NamedTuple):
+    """What one push or flush of a resampled stream does: outputs n0 .. n1-1 from position P0, reading history half ``parity``."""
+    n0: int
+    n1: int
+    P0: int
+    parity: int
+
+
+class ResampleCall(NamedTuple):
+    """What one ``push(counts, end)`` of resampler sessions does: ``rows[b]`` is slot b's row of the int64 table (ops.SR_ROW_FIELDS),
+    ``m[b]`` its number of output samples, ``zero`` the slots whose history is zeroed at the end."""
+    rows: "np.ndarray"
+    m: List[int]
+    zero: List[int]
+
+
+class ResamplePlan:
+    """Sample bookkeeping of one resampled stream for a reduced ratio up / down (host side only; no tensors).
+
+    With half = 10 * max(up, down), output n reads inputs ceil((n*down - half)/up) .. floor((n*down + half)/up): after P inputs the
+    outputs below ``n_final(P) = max(0, ceil((P*up - half)/down))`` are final, and a signal of L inputs has ``n_out(L) = ceil(L *
+    up / down)`` outputs.  No pending output reads further back than ``H = floor(2*half/up) + 1`` inputs."""
+
+    def __init__(self, up: int, down: int):
+        import math
+        for v in (up, down):
+            if isinstance(v, bool) or not isinstance(v, int) or v <= 0:
+                raise ValueError("ResamplePlan: up and down must be positive ints")
+        if math.gcd(up, down) != 1 or max(up, down) > ops.RESAMPLE_MAX_M:
+            raise ValueError(f"ResamplePlan: up / down must be reduced, with max(up, down) <= {ops.RESAMPLE_MAX_M}")
+        self.up, self.down = up, down
+        self.half = 10 * max(up, down)
+        self.H = ops.stream_resample_hist(up, down)
+        self.reset()
+
+    def reset(self):
+        self.n = 0            # samples received
+        self.parity = 0       # history half the next call reads
+
+    def n_final(self, P: int) -> int:
+        return ops.stream_resample_final(P, self.up, self.down)
+
+    def n_out(self, L: int) -> int:
+        return ops.resample_len(L, self.up, self.down)
+
+    @property
+    def emitted(self) -> int:
+        """Output samples returned so far."""
+        return self.n_final(self.n)
+
+    def snapshot(self):
+        return (self.n, self.parity)
+
+    def restore(self, snap):
+        self.n, self.parity = snap
+
+    def push(self, n_new: int) -> ResampleStep:
+        if isinstance(n_new, bool) or not isinstance(n_new, int) or n_new < 0:
+            raise ValueError("push: the sample count must be an int >= 0")
+        step = ResampleStep(self.emitted, self.n_final(self.n + n_new), self.n, self.parity)
+        self.n += n_new
+        if n_new:
+            self.parity ^= 1          # the call writes the other history half
+        return step
+
+    def flush(self) -> ResampleStep:
+        """The rest of a signal of ``n`` samples; the state stays (the caller resets, as with :class:`StreamPlan`)."""
+        return ResampleStep(self.emitted, self.n_out(self.n), self.n, self.parity)
+
+    def advance(self, periods: int):
+        """Move the stream on by ``periods * down`` inputs and ``periods * up`` outputs.  The taps an output uses depend on
+        n*down - j*up alone, so the history serves the new position as it stands."""
+        if isinstance(periods, bool) or not isinstance(periods, int) or periods < 0:
+            raise ValueError("advance: periods must be an int >= 0")
+        if self.n * self.up < self.half:
+            raise ValueError("advance: the stream must be past its first half filter length (n * up >= half)")
+        self.n += periods * self.down
+
+
+class ResampleSessionPlan:
+    """Host-side bookkeeping of ``slots`` independent resampled streams in one batch: :class:`ResamplePlan`'s arithmetic on int64
+    arrays, one entry per slot, so that the cost of planning a call does not grow with a python loop over the slots."""
+
+    def __init__(self, slots: int, up: int, down: int):
+        if isinstance(slots, bool) or not isinstance(slots, int) or slots <= 0:
+            raise ValueError("ResampleSessionPlan: slots must be a positive int")
+        one = ResamplePlan(up, down)                  # the guards on the ratio
+        self.slots, self.up, self.down, self.half, self.H = slots, up, down, one.half, one.H
+        self._n = np.zeros(slots, dtype=np.int64)     # samples received per slot
+        self._parity = np.zeros(slots, dtype=np.int64)
+
+    @property
+    def positions(self) -> List[int]:
+        return self._n.tolist()
+
+    def snapshot(self):
+        return (self._n.copy(), self._parity.copy())
+
+    def restore(self, snap):
+        self._n, self._parity = snap[0].copy(), snap[1].copy()
+
+    def n_final(self, P):
+        return np.maximum(0, -((self.half - P * self.up) // self.down))
+
+    def n_out(self, L):
+        return -((-L * self.up) // self.down)
+
+    def check(self, counts, end):
+        """Every guard of a push, before anything changes -> the counts as an int64 array."""
+        c = np.asarray(counts)
+        if c.shape != (self.slots,):
+            raise ValueError(f"{len(counts)} counts for {self.slots} slots")
+        if c.dtype.kind not in "iu" or (c < 0).any():
+            raise ValueError("counts must be ints >= 0")
+        if any(isinstance(b, bool) or not isinstance(b, int) or not 0 <= b < self.slots for b in end):
+            raise ValueError(f"slot numbers lie in 0 .. {self.slots - 1}")
+        return c.astype(np.int64)
+
+    def push(self, counts, end) -> ResampleCall:
+        c = self.check(counts, end)
+        P0 = self._n
+        P1 = P0 + c
+        ends = np.zeros(self.slots, dtype=bool)
+        ends[list(end)] = True
+        ends &= P1 > 0                                # ending a slot that has received nothing is a no-op
+        n0 = self.n_final(P0)
+        m = np.where(ends, self.n_out(P1), self.n_final(P1)) - n0
+        idle = (c == 0) & ~ends
+        rows = np.stack([P0, c, n0, m, self._parity, ends.astype(np.int64), idle.astype(np.int64)], axis=1)
+        self._parity = np.where(ends, 0, self._parity ^ (c > 0))      # a call with samples writes the other history half
+        self._n = np.where(ends, 0, P1)
+        return ResampleCall(rows, m.tolist(), np.flatnonzero(ends).tolist())
+
+    def drop(self, slots):
+        slots = list(slots)
+        self._n[slots] = 0
+        self._parity[slots] = 0
+
+
+def _check_rates(name: str, fs_in, fs_out):
+    up, down = ops.resample_ratio(fs_in, fs_out)
+    if up == down:
+        raise ValueError(f"{name}: fs_in == fs_out = {fs_in} Hz leaves nothing to resample (AtRate / SessionsAtRate pass such a "
+                         "stream straight through)")
+    return up, down
+
+
+def _check_device(name: str, device) -> torch.device:
+    if not torch.cuda.is_available():
+        raise RuntimeError(f"{name} runs on the MI355X only: there is no CPU path")
+    device = torch.device("cuda" if device is None else device)
+    if device.type != "cuda":
+        raise RuntimeError(f"{name} runs on the MI355X only: there is no CPU path")
+    return torch.device("cuda", torch.cuda.current_device()) if device.index is None else device
+
+
+class StreamingResampler:
+    """Lock-step streaming resampler for ``batch`` signals from ``fs_in`` to ``fs_out`` Hz.
+
+        rs = StreamingResampler(48000, 16000, batch=B)
+        y = rs.push(x)          # x [B, n >= 0] float32 on the GPU -> [B, m]: the output samples that became final
+        y = rs.flush()          # end of all B signals -> the rest; the resampler is then reset ([B, 0] for empty signals)
+
+    All pushes and the flush together are ``inference.resample(x_full, fs_in, fs_out)[0]`` bit for bit, however the signal is
+    cut: the same fp32 taps (``scipy.signal.resample_poly``'s default filter, not soxr), the same terms in the same order in one
+    double accumulator per output.  Output n is returned by the push that delivers input ``floor((n*down + half)/up)``, half = 10
+    max(up, down): a delay of half/up input samples.  State per stream: the last ``plan.H`` input samples and the position; a
+    stream may run past 2^31 samples, and the cost of a push does not depend on the position.  ``x`` may be a column slice of a
+    longer buffer (any row pitch); anything else is made contiguous.  ``taps_mode`` ("auto", "mem", "lds") forces where the kernel
+    reads the taps; every mode gives the same bits.
+    """
+
+    def __init__(self, fs_in: int, fs_out: int, batch: int, device=None, taps_mode: str = "auto"):
+        up, down = _check_rates("StreamingResampler", fs_in, fs_out)
+        if isinstance(batch, bool) or not isinstance(batch, int) or not 0 < batch <= ops.ROWS_MAX_ROWS:
+            raise ValueError(f"StreamingResampler: batch must be an int in 1 .. {ops.ROWS_MAX_ROWS}")
+        if taps_mode not in ops.SR_TAPS_MODES:
+            raise ValueError(f"taps_mode must be one of {tuple(ops.SR_TAPS_MODES)}")
+        self.fs_in, self.fs_out, self.B, self.taps_mode = fs_in, fs_out, batch, taps_mode
+        self.device = _check_device("StreamingResampler", device)
+        self.plan = ResamplePlan(up, down)
+        self.hist = torch.zeros(2, batch, self.plan.H, dtype=torch.float32, device=self.device)
+        ops.resample_taps(up, down, self.device)
+
+    def reset(self):
+        """Zero the history and the bookkeeping (done by flush)."""
+        self.hist.zero_()
+        self.plan.reset()
+
+    def push(self, x: torch.Tensor) -> torch.Tensor:
+        check_input(x, self.B, self.device)
+        n_new = int(x.shape[1])
+        if n_new > ops.RESAMPLE_MAX_LEN:
+            raise ValueError(f"push: {n_new} samples in one call; at most 2^27 are supported")
+        pl = self.plan
+        with torch.cuda.device(self.device):
+            st = pl.push(n_new)
+            return ops.stream_resample(self.hist, st.parity, x, n_new, st.P0, False, st.n0, st.n1 - st.n0, pl.up, pl.down,
+                                       self.taps_mode)
+
+    def flush(self) -> torch.Tensor:
+        pl = self.plan
+        with torch.cuda.device(self.device):
+            st = pl.flush()
+            y = ops.stream_resample(self.hist, st.parity, None, 0, st.P0, True, st.n0, st.n1 - st.n0, pl.up, pl.down, self.taps_mode)
+            self.reset()
+        return y
+
+    def _advance(self, periods: int):
+        """Test hook: ``periods * down`` input samples and ``periods * up`` outputs further on, the history untouched."""
+        self.plan.advance(periods)
+
+
+class StreamingResamplerSessions:
+    """Streaming resampler for ``slots`` independent signals in one batch, with the contract of :class:`StreamingSessions`.
+
+        rs = StreamingResamplerSessions(44100, 16000, slots)
+        y, m = rs.push(x, counts=None, end=())   # x [slots, n] float32 on the GPU -> y [slots, max(m)], m[b] samples of slot b, zeros behind
+        rs.drop(slots); rs.positions; rs.reset()
+
+    ``counts[b]`` leading samples of row b are new for slot b (nothing at or past ``x[b, counts[b]]`` is read); ``end`` names
+    the slots whose signal ends after this call's samples: the call returns the rest of their outputs, their history is zeroed
+    and their next samples begin a new signal.  Ending a slot that has received nothing is a no-op.  Slot b's samples are the
+    bits :class:`StreamingResampler` returns for the same signal in the same slot, whatever the other slots do.  Every guard runs
+    on the host before any GPU work and before any bookkeeping changes; the table of a call is held to
+    ``idv_stream_resample_rows_check`` before it goes to the device.
+    """
+
+    def __init__(self, fs_in: int, fs_out: int, slots: int, device=None, taps_mode: str = "auto"):
+        up, down = _check_rates("StreamingResamplerSessions", fs_in, fs_out)
+        if isinstance(slots, bool) or not isinstance(slots, int) or not 0 < slots <= ops.ROWS_MAX_ROWS:
+            raise ValueError(f"StreamingResamplerSessions: slots must be an int in 1 .. {ops.ROWS_MAX_ROWS}")
+        if taps_mode not in ops.SR_TAPS_MODES:
+            raise ValueError(f"taps_mode must be one of {tuple(ops.SR_TAPS_MODES)}")
+        self.fs_in, self.fs_out, self.B, self.taps_mode = fs_in, fs_out, slots, taps_mode
+        self.up, self.down = up, down
+        self.device = _check_device("StreamingResamplerSessions", device)
+        if int(L.lib().idv_stream_resample_row_fields()) != len(ops.SR_ROW_FIELDS):
+            raise L.IdvError("libidccrn_hip.so and ops.SR_ROW_FIELDS disagree about the row table")
+        self.sessions = ResampleSessionPlan(slots, up, down)
+        self.H = self.sessions.H
+        self.hist = torch.zeros(2, slots, self.H, dtype=torch.float32, device=self.device)
+        ops.resample_taps(up, down, self.device)
+        self._table = None          # device int64 buffer of a call's table and zero list
+        self._staging = []          # [(pinned int64 buffer, event of the copy that last read it)] * 2, as _Slots._upload
+        self._turn = 0
+
+    @property
+    def positions(self) -> List[int]:
+        return self.sessions.positions
+
+    def reset(self):
+        """Zero every slot's history and bookkeeping."""
+        self.hist.zero_()
+        self.sessions.drop(range(self.B))
+
+    def _upload(self, host: torch.Tensor) -> torch.Tensor:
+        n = host.numel()
+        if self._table is None or self._table.numel() < n:
+            size = 1 << (n - 1).bit_length()
+            self._table = torch.empty(size, dtype=torch.int64, device=self.device)
+            self._staging = [(torch.empty(size, dtype=torch.int64).pin_memory(), torch.cuda.Event()) for _ in range(2)]
+        stage, ev = self._staging[self._turn]
+        self._turn ^= 1
+        ev.synchronize()            # the copy that read this buffer two calls ago
+        stage[:n].copy_(host)
+        self._table[:n].copy_(stage[:n], non_blocking=True)
+        ev.record()
+        return self._table
+
+    def _zero(self, slots_ptr, n: int):
+        if n:
+            call("idv_stream_zero_rows", p(self.hist), ll(2), i(self.B), ll(self.H), slots_ptr, i(n), stream_ptr())
+
+    def drop(self, slots):
+        """Abandon the signals of these slots: nothing is returned for them and their history is zeroed."""
+        slots = check_slots(slots, self.B)
+        if not slots:
+            return
+        self.sessions.drop(slots)
+        with torch.cuda.device(self.device):
+            table = self._upload(torch.tensor(slots, dtype=torch.int64))
+            self._zero(L._P(table.data_ptr()), len(slots))
+
+    def check(self, x, counts, end):
+        """Every guard of a push (host only; nothing changes) -> (counts, end) as lists."""
+        check_input(x, self.B, self.device)
+        n = int(x.shape[1])
+        if n > ops.RESAMPLE_MAX_LEN:
+            raise ValueError(f"push: {n} samples in one call; at most 2^27 are supported")
+        return check_counts(counts, self.B, n), check_slots(end, self.B)
+
+    def push(self, x: torch.Tensor, counts=None, end=()):
+        counts, end = self.check(x, counts, end)
+        n = int(x.shape[1])
+        snap = self.sessions.snapshot()
+        plan = self.sessions.push(counts, end)
+        ldy = max(plan.m)
+        NR = len(ops.SR_ROW_FIELDS)
+        host = torch.from_numpy(np.concatenate([plan.rows.ravel(), np.asarray(plan.zero, dtype=np.int64)]))
+        rc = L.lib().idv_stream_resample_rows_check(L._P(host.data_ptr()), self.B, n, self.up, self.down, self.H, ldy)
+        if rc != 0:                                  # a bad table never reaches a kernel
+            self.sessions.restore(snap)
+            raise L.IdvError(f"idv_stream_resample_rows_check refused the table (status {rc})")
+        with torch.cuda.device(self.device):
+            if not any(counts) and not plan.zero:    # every slot idle
+                return torch.zeros(self.B, 0, dtype=torch.float32, device=self.device), plan.m
+            table = self._upload(host)
+            y = ops.stream_resample_rows(self.hist, x if n else None, n, L._P(table.data_ptr()), ldy, self.up, self.down,
+                                         self.taps_mode)
+            self._zero(L._P(table.data_ptr() + 8 * self.B * NR), len(plan.zero))
+        return y, plan.m
+
+
+def _check_wrapped(name: str, streamer, kinds, fs, model_fs):
+    if not isinstance(streamer, kinds):
+        raise ValueError(f"{name} wraps one of {', '.join(k.__name__ for k in kinds)}")
+    if not getattr(streamer, "average", True):
+        raise ValueError(f"{name}: a streamer with average=False returns num_samples rows per stream; resample those with a "
+                         "StreamingResampler of that many rows")
+    ops.resample_ratio(fs, model_fs)                 # the guards on the rates
+
+
+class AtRate:
+    """A lock-step streamer of the ``model_fs`` network (:class:`StreamingDCCRN`, :class:`StreamingVAE`,
+    :class:`StreamingVAETwoLatents`) for signals at ``fs`` Hz: a :class:`StreamingResampler` in front of it and one behind it.
+
+        st = AtRate(StreamingDCCRN(model, batch=B), 48000)
+        y = st.push(x)          # x [B, n] at fs on the GPU -> the enhanced samples at fs that became final
+        y = st.flush()          # the three stages flush in order, each stage's flush output being the next one's last push
+
+    Pushes plus flush return, bit for bit and however the signal is cut, ``inference.resample(E(inference.resample(x, fs,
+    model_fs)[0]), model_fs, fs)[0]`` with E the wrapped streamer's whole-signal push + flush; equality with the offline model
+    follows within the streamer's own tolerance.  ``fs == model_fs`` passes straight through to the wrapped streamer.  Every guard
+    runs on the host before any GPU work and before any bookkeeping changes, the wrapped streamer's refusal to end a signal of
+    0 < L16 <= n_fft/2 samples (L16 = ceil(L * up / down)) included: a refused call leaves all three stages as they were.  Added
+    latency: half/up input samples per resampler, 30 samples (0.625 ms) at 48 kHz down and the same again on the way back.
+    """
+
+    def __init__(self, streamer, fs: int, model_fs: int = 16000):
+        _check_wrapped("AtRate", streamer, (StreamingDCCRN, StreamingVAE), fs, model_fs)
+        self.streamer, self.fs, self.model_fs = streamer, fs, model_fs
+        self.B, self.device = streamer.B, streamer.device
+        self.down = self.up = None
+        if fs != model_fs:
+            self.down = StreamingResampler(fs, model_fs, self.B, self.device)
+            self.up = StreamingResampler(model_fs, fs, self.B, self.device)
+
+    def reset(self):
+        self.streamer.reset()
+        if self.down is not None:
+            self.down.reset()
+            self.up.reset()
+
+    def push(self, x: torch.Tensor) -> torch.Tensor:
+        if self.down is None:
+            return self.streamer.push(x)
+        check_input(x, self.B, self.device)
+        if int(x.shape[1]) > ops.RESAMPLE_MAX_LEN:
+            raise ValueError(f"push: {int(x.shape[1])} samples in one call; at most 2^27 are supported")
+        return self.up.push(self.streamer.push(self.down.push(x)))
+
+    def flush(self) -> torch.Tensor:
+        if self.down is None:
+            return self.streamer.flush()
+        self.streamer.plan.check_flush(self.down.plan.n_out(self.down.plan.n))      # before anything changes
+        mid = self.streamer.push(self.down.flush())
+        mid = torch.cat([mid, self.streamer.flush()], dim=1)
+        return torch.cat([self.up.push(mid), self.up.flush()], dim=1)
+
+
+class SessionsAtRate:
+    """A sessions streamer of the ``model_fs`` network (:class:`StreamingSessions`, :class:`StreamingVAESessions`,
+    :class:`StreamingVAETwoLatentsSessions`) for signals at ``fs`` Hz, with the same ``push`` / ``drop`` / ``positions`` contract.
+
+        st = SessionsAtRate(StreamingSessions(model, slots), 44100)
+        y, m = st.push(x, counts=None, end=())   # x [slots, n] at fs -> y [slots, max(m)] at fs, m[b] samples of slot b, zeros behind
+        st.drop(slots); st.positions; st.set_seed(slots, seed)
+
+    The down-resampler's ``m`` is the streamer's ``counts`` and the streamer's ``m`` the up-resampler's ``counts``: at 44.1 kHz
+    slots at different phases get 159, 160 or 161 samples from the same push.  ``end`` passes through all three stages within
+    the call.  Slot b returns the bits :class:`AtRate` returns for the same signal in the same slot.  ``positions`` counts samples
+    at ``fs``.  Every guard runs on the host before any GPU work and before any bookkeeping changes, as in :class:`AtRate`.
+    """
+
+    def __init__(self, sessions, fs: int, model_fs: int = 16000):
+        _check_wrapped("SessionsAtRate", sessions, (StreamingSessions, StreamingVAESessions), fs, model_fs)
+        self.sessions, self.fs, self.model_fs = sessions, fs, model_fs
+        self.B, self.device = sessions.B, sessions.device
+        self.down = self.up = None
+        if fs != model_fs:
+            self.down = StreamingResamplerSessions(fs, model_fs, self.B, self.device)
+            self.up = StreamingResamplerSessions(model_fs, fs, self.B, self.device)
+
+    @property
+    def positions(self) -> List[int]:
+        return self.sessions.positions if self.down is None else self.down.positions
+
+    def reset(self):
+        self.sessions.reset()
+        if self.down is not None:
+            self.down.reset()
+            self.up.reset()
+
+    def drop(self, slots):
+        slots = check_slots(slots, self.B)
+        self.sessions.drop(slots)
+        if self.down is not None:
+            self.down.drop(slots)
+            self.up.drop(slots)
+
+    def set_seed(self, slots, seed):
+        """Forwarded to the wrapped VAE sessions (a slot's seed can be set only between signals)."""
+        if not hasattr(self.sessions, "set_seed"):
+            raise ValueError(f"{type(self.sessions).__name__} draws nothing: it has no seeds")
+        self.sessions.set_seed(slots, seed)
+
+    def push(self, x: torch.Tensor, counts=None, end=()):
+        if self.down is None:
+            return self.sessions.push(x, counts, end)
+        counts, end = self.down.check(x, counts, end)
+        pos = self.down.positions
+        for b in end:                                # the wrapped streamer's refusal, before anything changes
+            L16 = self.down.sessions.n_out(pos[b] + counts[b])
+            if L16 > 0:
+                self.sessions.plan.check_flush(L16)
+        y, m = self.down.push(x, counts, end)
+        y, m = self.sessions.push(y, m, end)
+        return self.up.push(y, m, end)

@@ -833,6 +833,58 @@ int idv_stream_estimate(const float* speech, const float* noise, const float* X,
 int idv_stream_eps_pair_rows(const long long* seeds, const long long* rows, int B, int ns, int zdim, int k_launch, float* eps_sr,
                              float* eps_si, float* eps_nr, float* eps_ni, void* stream);
 
+/* ---- streaming at any sample rate: stateful polyphase resampler (stream_resample.hip; streaming.StreamingResampler,
+ * StreamingResamplerSessions, AtRate, SessionsAtRate; additive entries: IDV_ABI_VERSION is unchanged).
+ *
+ * The definition is idv_resample's (scipy.signal.resample_poly with its default filter, not soxr) for a ratio ALREADY reduced by its
+ * gcd, m = max(up, down) <= 640, half = 10 m, taps: device fp32[2 half + 1] as idv_resample takes them:
+ *     y[n] = float(up * sum_j x[j] taps[half + n down - j up]),  max(0, ceil((n down - half) / up)) <= j <= min(L - 1, (n down + half) / up),
+ * one double accumulator per output, j increasing, no atomics: the bits of idv_resample for the whole signal, however it is cut.
+ * After P samples the outputs n < n_final(P) = max(0, ceil((P up - half) / down)) are final; a call that takes a stream from P0 to
+ * P1 = P0 + count writes outputs n_final(P0) .. n_final(P1) - 1, the end of a signal of L = P1 samples writes n_final(P0) ..
+ * ceil(L up / down) - 1.  State: hist[2 parities][B][H], H = 2 half / up + 1 = idv_stream_resample_hist(up, down) samples per
+ * stream; a call reads half parity and, unless it ends the signal or brings no samples, writes the last H samples to half 1 -
+ * parity (samples before the start of the signal as zeros), so that no workgroup reads what another one of the launch writes.
+ * Positions are 64-bit (up to 2^50) and the cost of a call does not depend on them.  Row b reads nothing at or past x[b][count_b]
+ * and nothing of another row; its bits do not depend on B, on the other rows, on the cut or on taps_mode.
+ *
+ * taps_mode: where the kernel reads the taps.  IDV_SR_TAPS_AUTO: from memory for up > 1 (an output touches the 2 half / up + 1
+ * taps of its phase only), from LDS for up = 1 (every output reads every tap); the other two force one form (tests, measurements).
+ *
+ * idv_stream_resample_hist / idv_stream_resample_final: host only; H and n_final(P), -1 for refused arguments. */
+#define IDV_SR_TAPS_AUTO 0
+#define IDV_SR_TAPS_MEM 1
+#define IDV_SR_TAPS_LDS 2
+int idv_stream_resample_hist(int up, int down);
+long long idv_stream_resample_final(long long P, int up, int down);
+/* Lock-step: B streams at position P0 receive x[b][0 .. n_new-1] (row stride ldx; NULL for n_new = 0); y[b][0 .. m-1] (row stride
+ * ldy) <- outputs n0 .. n0 + m - 1.  flush = 1: the signals end at L = P0 + n_new and no history is written.  n0 and m are the
+ * caller's to know (they size y) and are held to the definition: IDV_EINVAL unless n0 = n_final(P0) and n0 + m = n_final(P1), at
+ * flush ceil(L up / down).  IDV_EINVAL (before any GPU work) also for a ratio that is not reduced or has m > 640, H other than
+ * idv_stream_resample_hist(up, down), parity outside {0, 1}, n_new outside 0 .. 2^27, ldx < n_new, ldy < m, B outside 1 .. 65535,
+ * an unknown taps_mode and more than 2^31 - 257 positions B (m + H).  Nothing is launched for n_new = 0 and m = 0. */
+int idv_stream_resample(float* hist, int H, int parity, const float* x, long long ldx, int n_new, long long P0, int flush, long long n0,
+                        int m, int B, int up, int down, const float* taps, int taps_mode, float* y, long long ldy, void* stream);
+/* Per slot: rows is a device table [B][IDV_SR_ROW_FIELDS] of long long, row b what slot b does in this call. */
+#define IDV_SR_ROW_FIELDS 7
+#define IDV_SR_ROW_P0 0      /* samples of the slot's signal before this call */
+#define IDV_SR_ROW_COUNT 1   /* new samples x[b][0 .. count-1]; nothing at or past x[b][count] is read */
+#define IDV_SR_ROW_N0 2      /* first output of this call, n_final(P0) */
+#define IDV_SR_ROW_M 3       /* outputs of this call; columns m .. ldy-1 of y[b] are written as zeros */
+#define IDV_SR_ROW_PARITY 4  /* history half read; 1 - parity is written unless the slot ends or is idle */
+#define IDV_SR_ROW_END 5     /* 1: the signal ends at P0 + count */
+#define IDV_SR_ROW_IDLE 6    /* 1: no samples and no end; nothing of the slot's state is read or written */
+int idv_stream_resample_row_fields(void);   /* IDV_SR_ROW_FIELDS of the library */
+/* Host only, launches nothing: validates a HOST copy of the table against what idv_stream_resample checks for scalars: count in
+ * 0 .. n_x, parity / end / idle in {0, 1}, idle exactly when count = 0 and end = 0, n0 = n_final(P0), n0 + m = n_final(P0 + count)
+ * or, for a slot that ends, ceil((P0 + count) up / down), m <= ldy.  IDV_EINVAL otherwise.  Call it before the table is uploaded:
+ * idv_stream_resample_rows cannot look. */
+int idv_stream_resample_rows_check(const long long* host_rows, int B, int n_x, int up, int down, int H, long long ldy);
+/* x: [B][n_x] (row stride ldx; NULL for n_x = 0), y: [B][ldy], every column written.  The history of a slot that ends is left to
+ * idv_stream_zero_rows (hist as [2][B][H]: outer 2, inner H). */
+int idv_stream_resample_rows(float* hist, int H, const float* x, long long ldx, int n_x, const long long* rows, int B, int up, int down,
+                             const float* taps, int taps_mode, float* y, long long ldy, void* stream);
+
 /* ---- batches of utterances of different lengths (ragged.hip, reduce.hip; inference.enhance_* / compute_sisdr with `lengths`) ---
  * lens: device int32[], samples per utterance.  Utterance b has T_b = 1 + lens[b] / hop frames and hop * (T_b - 1) output samples;
  * the batch is laid out for Tmax = max_b T_b frames, Tp >= Tmax + 1.  A causal network computes frame t from frames <= t, so only
