@@ -517,3 +517,47 @@ def enhance_list(enhance: Callable, signals: Sequence[torch.Tensor], hop: int, c
         for row, k in enumerate(batch):
             out[k] = y[row, :hop * (lens[k] // hop)].clone()
     return out
+
+
+def compute_dnsmos(x: torch.Tensor, model, lengths=None, fs: int = 16000) -> dict:
+    """DNSMOS P.835 of a padded batch x [B, L] (or one recording [L]) without a clean reference: ``model`` is a
+    :class:`dnsmos.DNSMOS`; -> ``{"OVRL_raw", "SIG_raw", "BAK_raw", "OVRL", "SIG", "BAK"}`` float64 device tensors [B] (scalars for
+    [L]) and ``"num_hops"`` (int64, host), as :meth:`dnsmos.DNSMOS.score`.  The definition is the reference's
+    ``DNSMOS/dnsmos_local.py`` restated (tests/dnsmos_ref.py): parity with onnxruntime itself is unpinned, ``fs !=
+    16000`` goes through :func:`resample` (not ``librosa.resample``: unpinned), and the script's ``P808_MOS`` column is not
+    provided."""
+    if not isinstance(x, torch.Tensor) or x.dim() not in (1, 2):
+        raise ValueError("compute_dnsmos: x must be a tensor [L] or [B, L]")
+    single = x.dim() == 1
+    out = model.score(x.reshape(1, -1) if single else x, lengths, fs)
+    return {k: v[0] for k, v in out.items()} if single else out
+
+
+def dnsmos_list(signals: Sequence[torch.Tensor], model, fs: int = 16000, max_batch: int = 64) -> dict:
+    """DNSMOS P.835 of a folder of recordings of any lengths at batch throughput.  ``signals``: 1-D float32 GPU tensors.  They are
+    sorted by length and padded into batches of at most ``max_batch``, the way :func:`score_list` batches; every value equals the
+    per-recording :func:`compute_dnsmos` call's bit for bit.  Returns ``{name: CPU tensor [N]}`` in the caller's order (float64, and
+    ``"num_hops"`` int64), with one copy to the host per batch at the end."""
+    if isinstance(max_batch, bool) or not isinstance(max_batch, int) or max_batch < 1:
+        raise ValueError("dnsmos_list: max_batch must be a positive integer")
+    for k, sgn in enumerate(signals):
+        if not isinstance(sgn, torch.Tensor) or sgn.dim() != 1 or sgn.shape[0] < 1:
+            raise ValueError(f"signals[{k}] must be a non-empty 1-D tensor")
+        ops.check_dev_f32(sgn, f"signals[{k}]")
+    N = len(signals)
+    lens = [int(s.shape[0]) for s in signals]
+    order = sorted(range(N), key=lambda k: (-lens[k], k))
+    parts = []
+    for b0 in range(0, N, max_batch):
+        batch = order[b0:b0 + max_batch]
+        blens = [lens[k] for k in batch]
+        padded = _trim_pad([signals[k] for k in batch], signals[batch[0]].device)
+        parts.append(model.score(padded, blens, fs))
+    inv = torch.empty(N, dtype=torch.long)
+    inv[torch.tensor(order, dtype=torch.long)] = torch.arange(N)
+    out = {}
+    for name in ("OVRL_raw", "SIG_raw", "BAK_raw", "OVRL", "SIG", "BAK", "num_hops"):
+        dt = torch.int64 if name == "num_hops" else torch.float64
+        vals = torch.cat([part[name].cpu() for part in parts]) if parts else torch.empty(0, dtype=dt)
+        out[name] = vals[inv]
+    return out

@@ -1172,6 +1172,49 @@ int idv_asm_write(const float* pool, long long pool_n, const long long* src, con
                   const int* count, int npieces, const int* chosen, int B, int tries, int samples, float* out, long long ldo,
                   void* stream);
 
+/* ---- real 3x3 convolution on the fp32 matrix cores and DNSMOS P.835 (dnsmos.hip; dnsmos.py, inference.compute_dnsmos / dnsmos_list;
+ * additive entries: IDV_ABI_VERSION is unchanged).
+ *
+ * idv_conv3x3_fwd: y = ReLU(conv3x3(x, w) + bias), stride 1, zero padding 1, on v_mfma_f32_32x32x2_f32.  x is [N][H][W][Cin], y is
+ * [N][H][W][Cout], or with pool != 0 the 2x2 / stride-2 maximum of that map, [N][H / 2][W / 2][Cout] (floor: an odd last row / column is
+ * dropped); the un-pooled map is never written.  wp: idv_conv3x3_wfloats(Cin, Cout) floats that idv_conv3x3_pack made of w
+ * [Cout][Cin][3][3].  One accumulator per output sums k = (chunk of 32 channels, tap ky 3 + kx, channel) in ascending order, starting
+ * from 0; the bias is added last.  An output depends on its own image alone.  idv_conv3x3_tile(0 / 1): the rows / columns of output
+ * pixels one workgroup owns.
+ * idv_conv3x3_c1_fwd: the 1 -> C first layer on the vector ALU: f [N][H][W] -> y [N][H][W][C], w1 [C][9], one fmaf chain over the taps.
+ * idv_conv3x3_c1_fused_fwd: idv_conv3x3_fwd applied to idv_conv3x3_c1_fwd(f) (C1 = its Cin) without the C1-channel map in memory: the
+ * first layer is evaluated while a chunk is staged; the same bits as the two calls.
+ * idv_conv3x3_gmax: x [N][P][C] -> out [N][C], the maximum over the P pixels.
+ * IDV_EINVAL (before any GPU work) for a NULL pointer, N, H, W <= 0, H or W > 32768, Cin not in {32, 64, 128}, Cout not in {32, 64},
+ * pool with H < 2 or W < 2, C outside 1 .. 1024 (c1) or no divisor of 256 (gmax), x not 16-byte aligned (idv_conv3x3_fwd), another pointer
+ * not aligned to its element. */
+int idv_conv3x3_tile(int which);
+long long idv_conv3x3_wfloats(int Cin, int Cout);
+int idv_conv3x3_pack(const float* w, int Cin, int Cout, float* packed, void* stream);
+int idv_conv3x3_fwd(const float* x, const float* wp, const float* bias, int N, int H, int W, int Cin, int Cout, int pool, float* y,
+                    void* stream);
+int idv_conv3x3_c1_fwd(const float* f, const float* w1, const float* b1, int N, int H, int W, int C, float* y, void* stream);
+int idv_conv3x3_c1_fused_fwd(const float* f, const float* w1, const float* b1, int C1, const float* wp, const float* bias, int N, int H,
+                             int W, int Cout, int pool, float* y, void* stream);
+int idv_conv3x3_gmax(const float* x, int N, long long P, int C, float* out, void* stream);
+/* idv_dnsmos_frontend: segment s = (row, start) = seg[2 s], seg[2 s + 1] (device int32) of the padded batch x [B][ldx]; its sample j is
+ * x[row][(start + j) mod lengths[row]], so nothing at or past a row's length is read and the tiled clip is never built.  Frame t (900
+ * of them) is samples 160 t .. 160 t + 319; re / im = frame x the two [161][320] matrices (mats: idv_dnsmos_frontend_wfloats() floats
+ * made by idv_dnsmos_frontend_pack) on the fp32 matrix cores, k ascending; p = (sqrt(re re + im im))^2 with one fp32 rounding per
+ * operation; feat [nseg][900][161] = float(ln(max(floor_p, p)) / ln_div), the logarithm and the quotient in double.  A segment whose row
+ * is outside [0, B) or whose length is < 1 is all floor.
+ * idv_dnsmos_head: g [N][64] -> raw [N][3]: dense 64 -> 128 ReLU, 128 -> 64 ReLU, 64 -> 3 (weights [in][out]), k-ascending fmaf chains.
+ * idv_dnsmos_clip: out [B][6] (double) = the means over the segments first[b] .. first[b] + count[b] - 1 of raw [nseg][3] and of
+ * poly_j(raw_j) (poly [3][4] double, highest power first, Horner in double); double sums in segment order.
+ * IDV_EINVAL for a NULL pointer, B, nseg, N <= 0, nseg > 2^20, ldx <= 0, floor_p or ln_div not > 0, a pointer not aligned to its element. */
+long long idv_dnsmos_frontend_wfloats(void);
+int idv_dnsmos_frontend_pack(const float* re, const float* im, float* packed, void* stream);
+int idv_dnsmos_frontend(const float* x, long long ldx, const int* lengths, int B, const int* seg, int nseg, const float* mats,
+                        float floor_p, float ln_div, float* feat, void* stream);
+int idv_dnsmos_head(const float* g, int N, const float* w0, const float* b0, const float* w1, const float* b1, const float* w2,
+                    const float* b2, float* raw, void* stream);
+int idv_dnsmos_clip(const float* raw, int nseg, const int* first, const int* count, int B, const double* poly, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
