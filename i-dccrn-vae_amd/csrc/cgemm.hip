@@ -34,12 +34,15 @@ int launch_vec(const CgemmArgs& a, hipStream_t st) {
     return idv_launch_status();
 }
 
+// float4 staging of one source: whole float4s per row and 16-byte aligned rows
+inline bool stage_vec_ok(int Jp, const float* x) { return (Jp % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0); }
+
 // vector staging needs 16-byte aligned rows and the same column mapping for both sources
 template <int MODE, int WM, int WN, int MT_W, int FO_T, int JC_W, int CCK, bool SWAP, bool STATS>
 int launch_cfg(const CgemmArgs& a, hipStream_t st) {
-    const bool vec = (a.Jp % 4 == 0) && ((reinterpret_cast<uintptr_t>(a.x0) & 15) == 0) &&
-                     (a.C1 == 0 || (a.x1_div == 1 && a.Jp1 == a.Jp && (reinterpret_cast<uintptr_t>(a.x1) & 15) == 0)) &&
-                     (MODE == IDV_PW || (2 * a.C0) % CCK == 0);
+    static_assert(MODE != IDV_PW, "the point-wise mode chooses its form in pw_gemm_form");
+    const bool vec = stage_vec_ok(a.Jp, a.x0) && (a.C1 == 0 || (a.x1_div == 1 && a.Jp1 == a.Jp && stage_vec_ok(a.Jp1, a.x1))) &&
+                     (2 * a.C0) % CCK == 0;
     if (vec) return launch_vec<MODE, WM, WN, MT_W, FO_T, JC_W, CCK, SWAP, STATS, true>(a, st);
     return launch_vec<MODE, WM, WN, MT_W, FO_T, JC_W, CCK, SWAP, STATS, false>(a, st);
 }
@@ -72,6 +75,14 @@ int launch_conv(const CgemmArgs& a, int mode, hipStream_t st) {
         case 1221324: return launch_cfg<IDV_TCONV, 2, 2, 1, 3, 2, 4, false, STATS>(a, st);
         default: return IDV_EINVAL;
     }
+}
+
+// The kernel form of idv_pw_gemm as the decimal digits <WM><WN><swap><vec>: WM x WN waves (2 x 2 with 128-column tiles, or
+// 4 x 1 with 64-column tiles where the rows come in whole 256-row blocks), the store (0 planar, 1 row-major) and the staging
+// (1 float4, 0 scalar).  The point-wise mode has one source and no K-chunk condition: float4 staging needs stage_vec_ok alone.
+int pw_gemm_form(int M, int swap, int Jp, const float* x) {
+    const int wm = ((M + 31) / 32) % 8 == 0 ? 4 : 2;
+    return wm * 1000 + (wm == 4 ? 1 : 2) * 100 + (swap ? 10 : 0) + (stage_vec_ok(Jp, x) ? 1 : 0);
 }
 
 }  // namespace
@@ -134,9 +145,15 @@ extern "C" int idv_cconv2d_fwd_img(const float* x0, int C0, const float* x1, int
     return launch_conv<false>(a, transposed ? IDV_TCONV : IDV_CONV, (hipStream_t)stream);
 }
 
+extern "C" int idv_pw_gemm_form(int M, int swap, int Jp, const float* x) {
+    if (M <= 0 || Jp <= 0) return IDV_EINVAL;
+    return pw_gemm_form(M, swap, Jp, x);
+}
+
 extern "C" int idv_pw_gemm(const float* x, int K, const float* wfrag, const float* bias, const float* prelu_slope,
                            float* out, int M, int B, int Tp, int Jp, int t_valid, int swap, int ldo, void* stream) {
-    if (!x || !wfrag || !bias || !out || K <= 0 || (K & 1) || M <= 0 || B <= 0 || Tp <= 1) return IDV_EINVAL;
+    if (!x || !wfrag || !bias || !out || K <= 0 || (K & 1) || M <= 0 || B <= 0 || Tp <= 1 || t_valid < 1) return IDV_EINVAL;
+    if (swap && ldo < M) return IDV_EINVAL;                  // rows of the row-major store would overlap
     CgemmArgs a{};
     a.x0 = x; a.x1 = nullptr; a.C0 = K / 2; a.C1 = 0;
     a.Fin = 1; a.Fout = 1;
@@ -151,10 +168,15 @@ extern "C" int idv_pw_gemm(const float* x, int K, const float* wfrag, const floa
     // M = 1024 / 3072 / 6144, K = 1280, B = 64: 1.20 / 3.08 / 5.88 -> 1.16 / 2.97 / 5.60 ms against the 2 x 2 form, which the
     // other row counts keep.  Measured and removed: four column tiles per wave, four row tiles per wave, and 16 / 32
     // planes per K chunk (a quarter of the barriers per MFMA).
-    if (a.Mtiles % 8 == 0) {
-        if (swap) return launch_cfg<IDV_PW, 4, 1, 2, 1, 2, 8, true, false>(a, st);
-        return launch_cfg<IDV_PW, 4, 1, 2, 1, 2, 8, false, false>(a, st);
+    switch (pw_gemm_form(M, swap, Jp, x)) {
+        case 4100: return launch_vec<IDV_PW, 4, 1, 2, 1, 2, 8, false, false, false>(a, st);
+        case 4101: return launch_vec<IDV_PW, 4, 1, 2, 1, 2, 8, false, false, true>(a, st);
+        case 4110: return launch_vec<IDV_PW, 4, 1, 2, 1, 2, 8, true, false, false>(a, st);
+        case 4111: return launch_vec<IDV_PW, 4, 1, 2, 1, 2, 8, true, false, true>(a, st);
+        case 2200: return launch_vec<IDV_PW, 2, 2, 2, 1, 2, 8, false, false, false>(a, st);
+        case 2201: return launch_vec<IDV_PW, 2, 2, 2, 1, 2, 8, false, false, true>(a, st);
+        case 2210: return launch_vec<IDV_PW, 2, 2, 2, 1, 2, 8, true, false, false>(a, st);
+        case 2211: return launch_vec<IDV_PW, 2, 2, 2, 1, 2, 8, true, false, true>(a, st);
+        default: return IDV_EINVAL;
     }
-    if (swap) return launch_cfg<IDV_PW, 2, 2, 2, 1, 2, 8, true, false>(a, st);
-    return launch_cfg<IDV_PW, 2, 2, 2, 1, 2, 8, false, false>(a, st);
 }

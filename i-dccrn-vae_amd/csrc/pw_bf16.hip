@@ -215,6 +215,14 @@ int launch_pw(const PwBf16Args& a0, hipStream_t st) {
     return idv_launch_status();
 }
 
+// Column tile of a launch over M rows and J columns: the one with the fewest idle workgroup slots in the last round of 256
+// (64 only where it fills that round better by more than 0.02)
+int pw_bf16_coltile(int M, int J) {
+    const long long mb = (M + 255) / 256;
+    auto eff = [&](int jt) { const long long n = ((J + jt - 1) / jt) * mb; return (double)n / (double)(((n + 255) / 256) * 256); };
+    return eff(64) > eff(128) + 0.02 ? 64 : 128;
+}
+
 // one thread: one (octet, j) slot = 8 consecutive planes
 __global__ void planar_to_kimage_kernel(const float* __restrict__ x, int nvalid, int nplanes, int J, int Jp,
                                         unsigned short* __restrict__ img, long long lo_off) {
@@ -274,6 +282,11 @@ __global__ void pack_lstm_ih_bf16_kernel(const float* __restrict__ w_re, const f
 
 }  // namespace
 
+extern "C" int idv_pw_bf16_coltile(int M, int B, int Tp) {
+    if (M <= 0 || B <= 0 || Tp <= 1 || (long long)B * Tp > 0x7fffffffLL) return IDV_EINVAL;
+    return pw_bf16_coltile(M, B * Tp);
+}
+
 extern "C" long long idv_lstm_ih_bf16_bytes(int H, int K) { return (long long)(8 * H / 32) * (K / 16) * 2 * 64 * 16; }
 
 extern "C" int idv_lstm_proj_bf16_supported(int H, int K) { return (H > 0 && K > 0 && (8 * H) % 256 == 0 && K % 64 == 0) ? 1 : 0; }
@@ -312,11 +325,8 @@ extern "C" int idv_lstm_proj_bf16x3(const void* ximg, long long lo_off_slots, in
     a.J = B * Tp; a.Jp = Jp; a.Tp = Tp; a.t_valid = T; a.nB = B;
     a.wfrag = (const uint4*)wfrag_bf16; a.bias = bias; a.out = G;
     a.out_part_stride = (long long)T * B * 8 * H; a.ldo = 8 * H; a.M = 8 * H;
-    // fewest idle workgroup slots in the last round of 256
-    const long long mb = (a.M + 255) / 256;
-    auto eff = [&](int jt) { const long long n = ((a.J + jt - 1) / jt) * mb; return (double)n / (double)(((n + 255) / 256) * 256); };
     hipStream_t st = (hipStream_t)stream;
-    return eff(64) > eff(128) + 0.02 ? launch_pw<2, 2, true>(a, st) : launch_pw<4, 2, true>(a, st);
+    return pw_bf16_coltile(a.M, a.J) == 64 ? launch_pw<2, 2, true>(a, st) : launch_pw<4, 2, true>(a, st);
 }
 
 // Layer-1 input projection of the complex LSTM from the K-major split image of h0 that idv_lstm_rec_pers wrote (4 runs x
@@ -338,9 +348,7 @@ extern "C" int idv_lstm_proj1_bf16x3(const void* himg, long long lo_off_slots, c
         a.wfrag = (const uint4*)wfrag_bf16 + (long long)s * (4 * H / 32) * (H / 16) * 2 * 64;
         a.bias = bias + s * 4 * H; a.out = G1 + (long long)s * T * B * 4 * H;
         a.out_part_stride = 2LL * T * B * 4 * H; a.ldo = 4 * H; a.M = 4 * H;
-        const long long mb = (a.M + 255) / 256;
-        auto eff = [&](int jt) { const long long n = ((a.J + jt - 1) / jt) * mb; return (double)n / (double)(((n + 255) / 256) * 256); };
-        const int rc = eff(64) > eff(128) + 0.02 ? launch_pw<2, 2, true>(a, st) : launch_pw<4, 2, true>(a, st);
+        const int rc = pw_bf16_coltile(a.M, a.J) == 64 ? launch_pw<2, 2, true>(a, st) : launch_pw<4, 2, true>(a, st);
         if (rc) return rc;
     }
     return IDV_OK;
@@ -434,17 +442,15 @@ extern "C" int idv_pack_pw_bf16(const float* w, int M, int K, void* wfrag, void*
 // (Kp = K rounded up to 64, the padding octets hold zeros or anything finite -- their weights are zero)
 extern "C" int idv_pw_bf16x3(const void* ximg, long long lo_off_slots, int K, const void* wfrag_bf16, const float* bias, float* out,
                              int M, int B, int Tp, int Jp, int t_valid, void* stream) {
-    if (!ximg || !wfrag_bf16 || !out || K <= 0 || M <= 0 || B <= 0 || Tp <= 1 || Jp < B * Tp || (reinterpret_cast<uintptr_t>(ximg) & 15))
+    if (!ximg || !wfrag_bf16 || !out || K <= 0 || M <= 0 || B <= 0 || Tp <= 1 || t_valid < 1 || Jp < B * Tp || (reinterpret_cast<uintptr_t>(ximg) & 15))
         return IDV_EINVAL;
     PwBf16Args a{};
     const int Kp = (K + 63) / 64 * 64;
     a.ximg = (const u32x4*)ximg; a.lo_off = lo_off_slots; a.KO = Kp / 8; a.part_stride = 0;
     a.J = B * Tp; a.Jp = Jp; a.Tp = Tp; a.t_valid = t_valid; a.nB = B;
     a.wfrag = (const uint4*)wfrag_bf16; a.bias = bias; a.out = out; a.out_part_stride = 0; a.ldo = 0; a.M = M;
-    const long long mb = (M + 255) / 256;
-    auto eff = [&](int jt) { const long long n = ((a.J + jt - 1) / jt) * mb; return (double)n / (double)(((n + 255) / 256) * 256); };
     hipStream_t st = (hipStream_t)stream;
-    return eff(64) > eff(128) + 0.02 ? launch_pw<2, 1, false>(a, st) : launch_pw<4, 1, false>(a, st);
+    return pw_bf16_coltile(a.M, a.J) == 64 ? launch_pw<2, 1, false>(a, st) : launch_pw<4, 1, false>(a, st);
 }
 
 // idv_pw_bf16x3 with the transposed store of the LSTM gate layout: out[(t * B + b) * ldo + m] for the valid (t, b) -- the
@@ -459,10 +465,8 @@ extern "C" int idv_pw_bf16x3_rows(const void* ximg, long long lo_off_slots, int 
     a.ximg = (const u32x4*)ximg; a.lo_off = lo_off_slots; a.KO = Kp / 8; a.part_stride = 0;
     a.J = B * Tp; a.Jp = Jp; a.Tp = Tp; a.t_valid = T; a.nB = B;
     a.wfrag = (const uint4*)wfrag_bf16; a.bias = bias; a.out = out_rows; a.out_part_stride = 0; a.ldo = ldo; a.M = M;
-    const long long mb = (M + 255) / 256;
-    auto eff = [&](int jt) { const long long n = ((a.J + jt - 1) / jt) * mb; return (double)n / (double)(((n + 255) / 256) * 256); };
     hipStream_t st = (hipStream_t)stream;
-    return eff(64) > eff(128) + 0.02 ? launch_pw<2, 1, true>(a, st) : launch_pw<4, 1, true>(a, st);
+    return pw_bf16_coltile(a.M, a.J) == 64 ? launch_pw<2, 1, true>(a, st) : launch_pw<4, 1, true>(a, st);
 }
 
 extern "C" int idv_stft_frames_kimage(const float* x, int B, int L, int n_fft, int win, int hop, int T, void* img, long long lo_off,

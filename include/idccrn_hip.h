@@ -192,9 +192,17 @@ int idv_ctconv_c1_img_fwd(const void* x0_img, long long lo_off0_slots, int C0, c
 
 /* out[m][j] = bias[m] + sum_k w[m][k] x[k][j] over K planes of stride Jp: ComplexDense.forward
  * (complex_progress.py:83-89, one call per real/imag linear), the LSTM input projections, and the
- * DFT / inverse DFT.  swap=1 writes out[((tp-1)*B + b)*ldo + m] instead of planar rows. */
+ * DFT / inverse DFT.  swap=1 writes out[((tp-1)*B + b)*ldo + m] instead of planar rows.
+ * Refused (-1) before any GPU work: K odd, Tp <= 1, t_valid < 1, Jp < B*Tp, and swap != 0 with ldo < M (rows of the
+ * row-major store would overlap). */
 int idv_pw_gemm(const float* x, int K, const float* wfrag, const float* bias, const float* prelu_slope, float* out,
                 int M, int B, int Tp, int Jp, int t_valid, int swap, int ldo, void* stream);
+/* Which kernel form idv_pw_gemm launches for (M, swap, Jp, x), decided on the host by the function the launch itself
+ * calls: the decimal digits <WM><WN><swap><vec> -- WM x WN waves per workgroup (22: 2 x 2 waves, 128-column tiles; 41:
+ * 4 x 1 waves, 64-column tiles, taken where ((M+31)/32) % 8 == 0), the store (0 planar, 1 row-major) and the staging
+ * (1: float4, needs Jp % 4 == 0 and x 16-byte aligned; 0: scalar).  E.g. 2201, 4110.  x is only looked at as an
+ * address.  -1 for M <= 0 or Jp <= 0. */
+int idv_pw_gemm_form(int M, int swap, int Jp, const float* x);
 
 /* Train-mode ComplexBatchNormal (complex_progress.py:131-160): sums -> moments[5][C] (mean_r, mean_i,
  * Vrr+eps, Vri, Vii+eps), running buffers updated in place (first call copies, later 0.9/0.1 blend),
@@ -355,7 +363,11 @@ int idv_planar_to_kimage(const float* x, int nvalid, int nplanes, int J, int Jp,
  * windowed DFT / inverse DFT of STFT.forward / ISTFT.forward (pvae_module.py:21-27, :38-42) and the two linears of
  * ComplexDense (complex_progress.py:83-89).  ximg: K-major split image with K rounded up to 64 planes
  * (idv_planar_to_kimage with nplanes = that, or idv_stft_frames_kimage = idv_stft_frames writing the image directly);
- * wfrag: idv_pack_pw_bf16 of the row-major [M][K] matrix (idv_pw_bf16_wfrag_bytes). */
+ * wfrag: idv_pack_pw_bf16 of the row-major [M][K] matrix (idv_pw_bf16_wfrag_bytes).  t_valid < 1 is refused (-1). */
+/* Column tile (64 or 128) the bf16x3 point-wise entries launch with for M rows per launch and B*Tp columns, by the function
+ * the launches themselves call (idv_lstm_proj_bf16x3: M = 8H; idv_lstm_proj1_bf16x3: M = 4H per launch).  -1 for M <= 0,
+ * B <= 0 or Tp <= 1. */
+int idv_pw_bf16_coltile(int M, int B, int Tp);
 /* the same contraction with the row-major transposed store out[(t*B + b)*ldo + m] over the valid (t, b): dh = W^T dG in the
  * form idv_lstm_bptt reads (bf16x3 training mode) */
 int idv_pw_bf16x3_rows(const void* ximg, long long lo_off_slots, int K, const void* wfrag_bf16, const float* bias, float* out_rows,

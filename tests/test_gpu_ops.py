@@ -743,7 +743,8 @@ def test_image_writing_variants_are_bit_identical(ops):
 
 def test_pw_bf16x3_rows_matches_the_fp32_swap_store(ops):
     """idv_pw_bf16x3_rows (dh = W^T dG in BPTT's row-major form, bf16x3 training) against idv_pw_gemm with the transposed
-    store, same operands: 2e-5."""
+    store, same operands: 2e-5.  The reference here, idv_pw_gemm's swap store at this shape, is itself pinned against float64
+    by tests/test_gpu_pw.py (case rows96)."""
     g = torch.Generator().manual_seed(4)
     K, M, B, T = 256, 96, 3, 37
     w = (torch.randn(M, K, generator=g) * 0.1).cuda()
