@@ -498,12 +498,13 @@ __global__ void sisnr_bwd_kernel(const float* __restrict__ src, int src_ld, int 
     const double dR = -(10.0 / 2.302585092994046) / ((double)B * (R + eps)) * (double)gout[0];
     const double p = 2.0 * a * E / (E + eps);
     const double r2 = st / ((en + eps) * (en + eps));
-    const float cs = (float)(dR * (p / (en + eps) + r2 * (2.0 * a + 2.0 * (D - a * E) / (E + eps))));
-    const float ce = (float)(dR * (-2.0 * r2));
+    // cs s and ce e nearly cancel where the estimate is close to parallel to the source (all of it at L = 1): summed in double
+    const double cs = dR * (p / (en + eps) + r2 * (2.0 * a + 2.0 * (D - a * E) / (E + eps)));
+    const double ce = dR * (-2.0 * r2);
     const float* s = src + (size_t)(b / src_div) * src_ld;
     const float* e = est + (size_t)b * est_ld;
     for (int n = blockIdx.x * blockDim.x + threadIdx.x; n < L; n += gridDim.x * blockDim.x)
-        dest[(size_t)b * L + n] = cs * s[n] + ce * e[n];
+        dest[(size_t)b * L + n] = (float)(cs * (double)s[n] + ce * (double)e[n]);
 }
 
 // multiple_recon_loss backward (model/nsvae_loss.py:775-797): loss_cpx and loss_mag terms
@@ -570,6 +571,17 @@ __global__ void ckl_bwd_kernel(LatRef q1, LatRef q2, int zdim, float eps, int B,
         float o_dr0, o_di0, o_dsg;
         guard_bwd(g1, d1r0, d1i0, eps, dd1r, dd1i, o_dr0, o_di0, o_dsg);
         ds1 += o_dsg;
+        if (g1.on) {
+            // dd1 = alpha + beta d0 with alpha = -coeff d2 and beta = 0.5 scale / ld1.  The guard's Jacobian takes beta d0 to
+            // beta scale d0 (1 - |d0|^2 / ((a0 + e) a0)), and a0^2 = |d0|^2 + e makes the bracket e (1 + a0) / ((a0 + e) a0):
+            // formed directly.  As the difference of its two terms it is rounding noise, and with q2 == NULL (alpha = 0) it is
+            // all there is of d KL / d delta.
+            float ar, ai, unused;
+            guard_bwd(g1, d1r0, d1i0, eps, -coeff * d2r, -coeff * d2i, ar, ai, unused);
+            const float k = 0.5f * g1.scale / ld1 * g1.scale * (eps * (1.f + g1.a0) / ((g1.a0 + eps) * g1.a0));
+            o_dr0 = ar + k * d1r0;
+            o_di0 = ai + k * d1i0;
+        }
         float* dr1 = dq1; float* di1 = dq1 + (size_t)q1.H * q1.Jp;
         dr1[(size_t)(q1.o_miu + h) * q1.Jp + j] += gs * dm1r;
         di1[(size_t)(q1.o_miu + h) * q1.Jp + j] += gs * dm1i;
@@ -631,6 +643,11 @@ __global__ __launch_bounds__(256) void rowsum_kernel(const float* __restrict__ x
 }
 
 }  // namespace
+
+void idv_launch_zero_guard_cols(float* act, int planes, int B, int T, int Tp, int Jp, hipStream_t st) {
+    hipLaunchKernelGGL(zero_guard_cols_kernel, dim3(grid_for((long long)planes * B * (Tp - T))), dim3(256), 0, st, act, planes, B,
+                       T, Tp, Jp);
+}
 
 extern "C" int idv_cbn_apply_prelu_to(const float* y, const float* fold, const float* prelu_slope, int C, int F, int B, int Tp,
                                       int Jp, int t_valid, float* out, void* stream) {
@@ -713,9 +730,8 @@ extern "C" int idv_mask_apply_bwd(const float* mask, const float* X, int x_div, 
     if (!mask || !X || !dmask || (!dpred && !dpred_c) || x_div < 1 || F <= 0 || B <= 0 || T <= 0) return IDV_EINVAL;
     if (dX && x_div != 1) return IDV_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(zero_guard_cols_kernel, dim3(grid_for(2LL * F * B * (Tp - T))), dim3(256), 0, st, dmask, 2 * F, B, T, Tp, Jp);
-    if (dX)
-        hipLaunchKernelGGL(zero_guard_cols_kernel, dim3(grid_for(2LL * F * B * (Tp - T))), dim3(256), 0, st, dX, 2 * F, B, T, Tp, JpX);
+    idv_launch_zero_guard_cols(dmask, 2 * F, B, T, Tp, Jp, st);
+    if (dX) idv_launch_zero_guard_cols(dX, 2 * F, B, T, Tp, JpX, st);
     hipLaunchKernelGGL(mask_bwd_kernel, dim3(grid_for((long long)B * F * T)), dim3(256), 0, st, mask, X, x_div, JpX, dpred,
                        dpred_c, F, B, T, Tp, Jp, dmask, dX);
     return idv_launch_status();
@@ -724,7 +740,7 @@ extern "C" int idv_mask_apply_bwd(const float* mask, const float* X, int x_div, 
 extern "C" int idv_complex_to_planar(const float* in_c, float* act, int F, int B, int T, int Tp, int Jp, void* stream) {
     if (!in_c || !act || F <= 0 || B <= 0 || T <= 0 || Tp < T + 1) return IDV_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(zero_guard_cols_kernel, dim3(grid_for(2LL * F * B * (Tp - T))), dim3(256), 0, st, act, 2 * F, B, T, Tp, Jp);
+    idv_launch_zero_guard_cols(act, 2 * F, B, T, Tp, Jp, st);
     hipLaunchKernelGGL(complex_to_planar_kernel, dim3(grid_for((long long)B * F * T)), dim3(256), 0, st, in_c, act, F, B, T, Tp, Jp);
     return idv_launch_status();
 }
@@ -760,7 +776,8 @@ extern "C" int idv_reparam_bwd(const float* lat, int Hl, int off_miu, int off_ls
 
 extern "C" int idv_sisnr_bwd(const float* source, int src_ld, int src_div, const float* est, int est_ld, int B, int L,
                              const double* work, const float* grad_out, float* dest, void* stream) {
-    if (!source || !est || !work || !grad_out || !dest || B <= 0 || L <= 0 || src_div < 1) return IDV_EINVAL;
+    if (!source || !est || !work || !grad_out || !dest || B <= 0 || B > 65535 || L <= 0 || src_div < 1 || src_ld < L || est_ld < L)
+        return IDV_EINVAL;
     int gx = (L + 255) / 256;
     if (gx > 64) gx = 64;
     hipLaunchKernelGGL(sisnr_bwd_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, source, src_ld, src_div, est, est_ld, B,
@@ -781,6 +798,12 @@ extern "C" int idv_ckl_bwd(const float* q1, int H1, int Jp1, int o1_miu, int o1_
                            int Jp2, int o2_miu, int o2_ls, int o2_dl, int zdim, float eps, int B, int T, int Tp,
                            const float* grad_out, float* dq1, void* stream) {
     if (!q1 || !grad_out || !dq1 || zdim <= 0 || B <= 0 || T <= 0) return IDV_EINVAL;
+    if (!idv_group_ok(o1_miu, zdim, H1) || !idv_group_ok(o1_ls, zdim, H1) || !idv_group_ok(o1_dl, zdim, H1) ||
+        !idv_planar_ok(B, T, Tp, Jp1))
+        return IDV_EINVAL;
+    if (q2 && (!idv_group_ok(o2_miu, zdim, H2) || !idv_group_ok(o2_ls, zdim, H2) || !idv_group_ok(o2_dl, zdim, H2) ||
+               !idv_planar_ok(B, T, Tp, Jp2)))
+        return IDV_EINVAL;
     LatRef a{q1, H1, Jp1, o1_miu, o1_ls, o1_dl}, b{q2, H2, Jp2, o2_miu, o2_ls, o2_dl};
     hipLaunchKernelGGL(ckl_bwd_kernel, dim3(grid_for((long long)B * zdim * T)), dim3(256), 0, (hipStream_t)stream, a, b, zdim,
                        eps, B, T, Tp, grad_out, dq1);
@@ -791,6 +814,9 @@ extern "C" int idv_miu_dist_bwd(const float* q1, int H1, int Jp1, int off1, cons
                                 int zdim, int B, int T, int Tp, const float* grad_out, const float* loss_value, float* dq1,
                                 float* dq2, void* stream) {
     if (!q1 || !q2 || !grad_out || !loss_value || (!dq1 && !dq2) || zdim <= 0 || B <= 0 || T <= 0) return IDV_EINVAL;
+    if (!idv_group_ok(off1, zdim, H1) || !idv_group_ok(off2, zdim, H2) || !idv_planar_ok(B, T, Tp, Jp1) ||
+        !idv_planar_ok(B, T, Tp, Jp2))
+        return IDV_EINVAL;
     LatRef a{q1, H1, Jp1, off1, 0, 0}, b{q2, H2, Jp2, off2, 0, 0};
     hipLaunchKernelGGL(miu_dist_bwd_kernel, dim3(grid_for(2LL * zdim * B * T)), dim3(256), 0, (hipStream_t)stream, a, b, zdim, B,
                        T, Tp, grad_out, loss_value, dq1, dq2);

@@ -24,6 +24,11 @@ static inline int idv_launch_status() {
     return e == hipSuccess ? IDV_OK : IDV_ELAUNCH;
 }
 
+// Argument checks of the latent entries (reduce.hip, backward.hip): a channel group [off, off + zdim) lies inside the latent's H
+// channels; a guard column stands in front of the T frames and every utterance lies inside the pitch.
+static inline bool idv_group_ok(int off, int zdim, int H) { return off >= 0 && off <= H - zdim; }
+static inline bool idv_planar_ok(int B, int T, int Tp, int Jp) { return Tp >= T + 1 && (long long)Jp >= (long long)B * Tp; }
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -49,6 +54,9 @@ __device__ __forceinline__ float tanhf_(float x) {
 // ~10^4 workgroups the same-address atomics cost more than the contraction (enc1, B = 32: 4.1 ms against 1.65) -- and this
 // kernel folds the replicas into stats[C][5] (+=, fixed order).  elementwise.hip
 int idv_launch_stats_collapse(const double* work, int rep, int n, double* stats, hipStream_t st);
+// Zero the guard columns tp == 0 and tp > T of every utterance in `planes` planar rows of pitch Jp (the layout invariant above).
+// backward.hip
+void idv_launch_zero_guard_cols(float* act, int planes, int B, int T, int Tp, int Jp, hipStream_t st);
 // one more launch of a time-Winograd kernel with two co tiles per workgroup (the count behind idv_tw_pair_launches).  cgemm_tw.hip
 void idv_tw_pair_note_launch();
 

@@ -553,8 +553,7 @@ extern "C" int idv_reparam(const float* lat, int Hl, int off_miu, int off_ls, in
                            const float* eps_i, int ns, int B, int T, int Tp, int Jp, float* z, int Jpz, void* stream) {
     if (!lat || !eps_r || !eps_i || !z || zdim <= 0 || ns <= 0 || B <= 0 || T <= 0) return IDV_EINVAL;
     if (off_miu + zdim > Hl || off_ls + zdim > Hl || off_dl + zdim > Hl || Jpz < B * ns * Tp) return IDV_EINVAL;
-    hipLaunchKernelGGL(zero_guard_kernel, dim3(grid_for(2LL * zdim * B * ns)), dim3(256), 0, (hipStream_t)stream, z, 2 * zdim,
-                       B * ns, Tp, Jpz);
+    idv_launch_zero_guard_cols(z, 2 * zdim, B * ns, T, Tp, Jpz, (hipStream_t)stream);
     hipLaunchKernelGGL(reparam_kernel, dim3(grid_for((long long)B * zdim * T)), dim3(256), 0, (hipStream_t)stream, lat, Hl,
                        off_miu, off_ls, off_dl, zdim, eps_r, eps_i, ns, B, T, Tp, Jp, z, Jpz);
     return idv_launch_status();

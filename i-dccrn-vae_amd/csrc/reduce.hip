@@ -226,7 +226,8 @@ inline int grid_for(long long n, int cap = 1024) {
 
 extern "C" int idv_sisnr(const float* source, int src_ld, int src_div, const float* est, int est_ld, int B, int L,
                          double* work, float* out, void* stream) {
-    if (!source || !est || !work || !out || B <= 0 || L <= 0 || src_div < 1) return IDV_EINVAL;
+    if (!source || !est || !work || !out || B <= 0 || B > 65535 || L <= 0 || src_div < 1 || src_ld < L || est_ld < L)
+        return IDV_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(work, 0, sizeof(double) * 3 * B, st) != hipSuccess) return IDV_ELAUNCH;
     int gx = grid_for(L, 64);
@@ -237,7 +238,7 @@ extern "C" int idv_sisnr(const float* source, int src_ld, int src_div, const flo
 
 extern "C" int idv_sisdr(const float* ref, int ref_ld, const float* est, int est_ld, int B, int L, double* work, float* out,
                          void* stream) {
-    if (!ref || !est || !work || !out || B <= 0 || L <= 0) return IDV_EINVAL;
+    if (!ref || !est || !work || !out || B <= 0 || B > 65535 || L <= 0 || ref_ld < L || est_ld < L) return IDV_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(work, 0, sizeof(double) * 3 * B, st) != hipSuccess) return IDV_ELAUNCH;
     hipLaunchKernelGGL(sisnr_partial_kernel, dim3(grid_for(L, 64), B), dim3(256), 0, st, ref, ref_ld, 1, est, est_ld, L, work);
@@ -262,7 +263,7 @@ extern "C" int idv_sisdr_ragged(const float* ref, int ref_ld, const float* est, 
 extern "C" int idv_msd(const float* a, int Ca, int ca0, int JpA, const float* b, int Cb, int cb0, int JpB, int C, int F, int B,
                        int Tp, int t_valid, double* work, float* out, void* stream) {
     if (!a || !b || !work || !out || C <= 0 || F <= 0 || B <= 0 || Tp <= 1 || t_valid < 1 || t_valid >= Tp || ca0 < 0 || cb0 < 0 ||
-        ca0 + C > Ca || cb0 + C > Cb || JpA < B * Tp || JpB < B * Tp)
+        ca0 + C > Ca || cb0 + C > Cb || JpA < B * Tp || JpB < B * Tp || 2LL * C * F > 65535)
         return IDV_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(work, 0, sizeof(double) * 3, st) != hipSuccess) return IDV_ELAUNCH;
@@ -296,6 +297,12 @@ extern "C" int idv_ckl(const float* q1, int H1, int Jp1, int o1_miu, int o1_ls, 
                        int o2_miu, int o2_ls, int o2_dl, int zdim, float eps, int B, int T, int Tp, double* work, float* out,
                        void* stream) {
     if (!q1 || !work || !out || zdim <= 0 || B <= 0 || T <= 0) return IDV_EINVAL;
+    if (!idv_group_ok(o1_miu, zdim, H1) || !idv_group_ok(o1_ls, zdim, H1) || !idv_group_ok(o1_dl, zdim, H1) ||
+        !idv_planar_ok(B, T, Tp, Jp1))
+        return IDV_EINVAL;
+    if (q2 && (!idv_group_ok(o2_miu, zdim, H2) || !idv_group_ok(o2_ls, zdim, H2) || !idv_group_ok(o2_dl, zdim, H2) ||
+               !idv_planar_ok(B, T, Tp, Jp2)))
+        return IDV_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(work, 0, sizeof(double) * 3, st) != hipSuccess) return IDV_ELAUNCH;
     LatRef a{q1, H1, Jp1, o1_miu, o1_ls, o1_dl}, b{q2, H2, Jp2, o2_miu, o2_ls, o2_dl};
@@ -308,6 +315,9 @@ extern "C" int idv_ckl(const float* q1, int H1, int Jp1, int o1_miu, int o1_ls, 
 extern "C" int idv_miu_dist(const float* q1, int H1, int Jp1, int off1, const float* q2, int H2, int Jp2, int off2, int zdim,
                             int B, int T, int Tp, double* work, float* out, void* stream) {
     if (!q1 || !q2 || !work || !out || zdim <= 0 || B <= 0 || T <= 0) return IDV_EINVAL;
+    if (!idv_group_ok(off1, zdim, H1) || !idv_group_ok(off2, zdim, H2) || !idv_planar_ok(B, T, Tp, Jp1) ||
+        !idv_planar_ok(B, T, Tp, Jp2))
+        return IDV_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(work, 0, sizeof(double) * 3 * 2 * zdim, st) != hipSuccess) return IDV_ELAUNCH;
     LatRef a{q1, H1, Jp1, off1, 0, 0}, b{q2, H2, Jp2, off2, 0, 0};

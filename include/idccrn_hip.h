@@ -383,14 +383,18 @@ int idv_lstm_proj_bf16x3(const void* ximg, long long lo_off_slots, int K, const 
 
 /* reparameterization (pvae_module.py:1832-1886) with the two randn draws supplied by the caller.
  * lat: planar LSTM output [2][Hl][Jp]; miu/log_sigma/delta are channel offsets off_miu/off_ls/off_dl
- * (zdim channels each).  eps_r/eps_i: [B][ns][T][zdim].  z: planar [2][zdim][Jpz], columns (b*ns+s)*Tp+tp. */
+ * (zdim channels each).  eps_r/eps_i: [B][ns][T][zdim].  z: planar [2][zdim][Jpz], columns (b*ns+s)*Tp+tp; its guard columns
+ * tp == 0 and every tp > T (Tp may exceed T + 1) are written as +0.0, columns at or beyond B*ns*Tp are left alone.
+ * IDV_EINVAL: a channel group past Hl, Jpz < B*ns*Tp. */
 int idv_reparam(const float* lat, int Hl, int off_miu, int off_ls, int off_dl, int zdim, const float* eps_r,
                 const float* eps_i, int ns, int B, int T, int Tp, int Jp, float* z, int Jpz, void* stream);
 
 /* ---- losses ---------------------------------------------------------------------------------- */
 
 /* si_snr (model/sisnr_loss.py:7-19): three dot products per utterance; out[0] = -mean_b(snr).
- * src_div: source row = b / src_div (repeat over num_samples).  work: 3*B doubles (zeroed here). */
+ * src_div: source row = b / src_div (repeat over num_samples).  work: 3*B doubles (zeroed here); afterwards
+ * work[3b .. 3b+2] = (<s,s>, <e,s>, <e,e>) of utterance b.  IDV_EINVAL (idv_sisnr, idv_sisdr, idv_sisnr_bwd): B > 65535
+ * (one grid row per utterance), a row pitch src_ld / ref_ld / est_ld shorter than L. */
 int idv_sisnr(const float* source, int src_ld, int src_div, const float* est, int est_ld, int B, int L, double* work,
               float* out, void* stream);
 /* Enhancement inference.  idv_sisdr: compute_sisdr of utils/eval_metrics.py:49-64 on the device, one value per
@@ -406,14 +410,16 @@ int idv_recon_loss(const float* pred_c, const float* ori, long long sb, long lon
 /* Closed-form complex-Gaussian KL, mean over (b,t): cal_kl_arbi_prior
  * (model/pretrain_pvaes_loss.py:225-281, eps 1e-9) / cal_kl (model/nsvae_loss.py:275-328, eps 1e-10).
  * q1, q2: planar latents [2][Hn][Jpn] with channel offsets on_miu / on_ls / on_dl; q2 == NULL is the
- * standard prior (0, 0, 0).  work: 3 doubles.  out[0] = mean KL. */
+ * standard prior (0, 0, 0).  work: 3 doubles.  out[0] = mean KL.
+ * IDV_EINVAL (idv_ckl, idv_ckl_bwd, and with one offset per latent idv_miu_dist, idv_miu_dist_bwd): a channel offset outside
+ * [0, Hn - zdim], Tp < T + 1, Jpn < B*Tp; for q2 only where q2 is given. */
 int idv_ckl(const float* q1, int H1, int Jp1, int o1_miu, int o1_ls, int o1_dl, const float* q2, int H2, int Jp2,
             int o2_miu, int o2_ls, int o2_dl, int zdim, float eps, int B, int T, int Tp, double* work, float* out,
             void* stream);
 /* One term of residual_loss (model/nsvae_loss.py:363-446: torch.mean((connct - connct2).pow(2)) per skip connection): the mean
  * over [B, C, F, T, 2] of (a[:, ca0:ca0+C] - b[:, cb0:cb0+C])^2 for two planar activations with Ca / Cb channels.  The reference
  * computes and RETURNS the term but never adds it to the loss it back-propagates (:460-466), so there is no gradient entry.
- * work: 3 doubles. */
+ * work: 3 doubles.  IDV_EINVAL: 2*C*F > 65535 (one grid row per (part, channel, bin)). */
 int idv_msd(const float* a, int Ca, int ca0, int JpA, const float* b, int Cb, int cb0, int JpB, int C, int F, int B, int Tp,
             int t_valid, double* work, float* out, void* stream);
 /* Minibatch mutual-information estimate of the CVAE / NVAE ELBO (complex_standard_vae_loss.mutual_information,
@@ -428,7 +434,8 @@ int idv_mi_fwd(const float* lat, int H, int Jp, int o_miu, int o_ls, int o_dl, c
                int T, int Tp, float eps, float* work, double* acc, float* out, void* stream);
 int idv_mi_bwd(const float* lat, int H, int Jp, int o_miu, int o_ls, int o_dl, const float* z, int Jpz, int zdim, int ns, int B,
                int T, int Tp, float eps, const float* work, const float* gout, float* dlat, float* dz, void* stream);
-/* miu_dis_loss term (model/nsvae_loss.py:349-360): sqrt(sum_{h,ri} mean_{b,t} (miu1 - miu2)^2). */
+/* miu_dis_loss term (model/nsvae_loss.py:349-360): sqrt(sum_{h,ri} mean_{b,t} (miu1 - miu2)^2).  work: 3*2*zdim doubles;
+ * afterwards work[3*(2h + ri)] = sum_{b,t} (miu1 - miu2)^2 of channel h, part ri.  Refusals as for idv_ckl. */
 int idv_miu_dist(const float* q1, int H1, int Jp1, int off1, const float* q2, int H2, int Jp2, int off2, int zdim,
                  int B, int T, int Tp, double* work, float* out, void* stream);
 
