@@ -242,6 +242,40 @@ __global__ void conv3x3_c1_kernel(const float* __restrict__ f, const float* __re
     }
 }
 
+// the first layer with the 2x2 / 2 floor max-pool behind it: f [N][H][W] -> y [N][H / 2][W / 2][C].  One thread per output reads the
+// 4 x 4 feature patch under its pooling window once and takes the maximum of the four c1_value: the bits of the pool of
+// conv3x3_c1_kernel's map, which is never written
+__global__ void conv3x3_c1_pool_kernel(const float* __restrict__ f, const float* __restrict__ w1, const float* __restrict__ b1, int N, int H,
+                                       int W, int C, float* __restrict__ y) {
+    const int Ho = H >> 1, Wo = W >> 1;
+    const long long n = (long long)N * Ho * Wo * C;
+    for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
+        const int c = (int)(e % C);
+        const long long pix = e / C;
+        const int px = (int)(pix % Wo);
+        const int py = (int)((pix / Wo) % Ho);
+        const long long im = pix / ((long long)Wo * Ho);
+        float w[9], patch[16];
+#pragma unroll
+        for (int t = 0; t < 9; ++t) w[t] = w1[c * 9 + t];
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const int fy = 2 * py - 1 + q / 4, fx = 2 * px - 1 + q % 4;
+            patch[q] = ((unsigned)fy < (unsigned)H && (unsigned)fx < (unsigned)W) ? f[(im * H + fy) * W + fx] : 0.f;
+        }
+        const float b = b1[c];
+        float m = 0.f;                               // every c1_value is >= 0 (ReLU)
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+            float v[9];
+#pragma unroll
+            for (int t = 0; t < 9; ++t) v[t] = patch[(d / 2 + t / 3) * 4 + d % 2 + t % 3];
+            m = fmaxf(m, c1_value(w, b, v));
+        }
+        y[e] = m;
+    }
+}
+
 // x [N][P][C] -> out [N][C] = max over the P pixels (exact: a maximum has no order)
 __global__ __launch_bounds__(256) void gmax_kernel(const float* __restrict__ x, long long P, int C, float* __restrict__ out) {
     __shared__ float part[256];
@@ -428,6 +462,15 @@ extern "C" int idv_conv3x3_c1_fwd(const float* f, const float* w1, const float* 
         return IDV_EINVAL;
     hipLaunchKernelGGL(conv3x3_c1_kernel, dim3(grid_for((long long)N * H * W * C, 256)), dim3(256), 0, (hipStream_t)stream, f, w1, b1, N, H, W,
                        C, y);
+    return idv_launch_status();
+}
+
+extern "C" int idv_conv3x3_c1_pool_fwd(const float* f, const float* w1, const float* b1, int N, int H, int W, int C, float* y, void* stream) {
+    if (!f || !w1 || !b1 || !y || N <= 0 || H < 2 || W < 2 || H > 32768 || W > 32768 || C <= 0 || C > 1024 || !aligned(f, 4) ||
+        !aligned(w1, 4) || !aligned(b1, 4) || !aligned(y, 4))
+        return IDV_EINVAL;
+    hipLaunchKernelGGL(conv3x3_c1_pool_kernel, dim3(grid_for((long long)N * (H / 2) * (W / 2) * C, 256)), dim3(256), 0, (hipStream_t)stream, f,
+                       w1, b1, N, H, W, C, y);
     return idv_launch_status();
 }
 

@@ -519,25 +519,26 @@ def enhance_list(enhance: Callable, signals: Sequence[torch.Tensor], hop: int, c
     return out
 
 
-def compute_dnsmos(x: torch.Tensor, model, lengths=None, fs: int = 16000) -> dict:
+def compute_dnsmos(x: torch.Tensor, model, lengths=None, fs: int = 16000, p808=None) -> dict:
     """DNSMOS P.835 of a padded batch x [B, L] (or one recording [L]) without a clean reference: ``model`` is a
     :class:`dnsmos.DNSMOS`; -> ``{"OVRL_raw", "SIG_raw", "BAK_raw", "OVRL", "SIG", "BAK"}`` float64 device tensors [B] (scalars for
     [L]) and ``"num_hops"`` (int64, host), as :meth:`dnsmos.DNSMOS.score`.  The definition is the reference's
     ``DNSMOS/dnsmos_local.py`` restated (tests/dnsmos_ref.py): parity with onnxruntime itself is unpinned, ``fs !=
-    16000`` goes through :func:`resample` (not ``librosa.resample``: unpinned), and the script's ``P808_MOS`` column is not
-    provided."""
+    16000`` goes through :func:`resample` (not ``librosa.resample``: unpinned).  ``p808`` (a :class:`dnsmos.P808`): also the
+    script's ``"P808_MOS"`` column, float64 [B], over the same segments (tests/p808_ref.py; parity with librosa / onnxruntime
+    unpinned); without it the result is that of the call without the argument."""
     if not isinstance(x, torch.Tensor) or x.dim() not in (1, 2):
         raise ValueError("compute_dnsmos: x must be a tensor [L] or [B, L]")
     single = x.dim() == 1
-    out = model.score(x.reshape(1, -1) if single else x, lengths, fs)
+    out = model.score(x.reshape(1, -1) if single else x, lengths, fs, p808=p808)
     return {k: v[0] for k, v in out.items()} if single else out
 
 
-def dnsmos_list(signals: Sequence[torch.Tensor], model, fs: int = 16000, max_batch: int = 64) -> dict:
+def dnsmos_list(signals: Sequence[torch.Tensor], model, fs: int = 16000, max_batch: int = 64, p808=None) -> dict:
     """DNSMOS P.835 of a folder of recordings of any lengths at batch throughput.  ``signals``: 1-D float32 GPU tensors.  They are
     sorted by length and padded into batches of at most ``max_batch``, the way :func:`score_list` batches; every value equals the
     per-recording :func:`compute_dnsmos` call's bit for bit.  Returns ``{name: CPU tensor [N]}`` in the caller's order (float64, and
-    ``"num_hops"`` int64), with one copy to the host per batch at the end."""
+    ``"num_hops"`` int64), with one copy to the host per batch at the end.  ``p808`` (a :class:`dnsmos.P808`): also ``"P808_MOS"``."""
     if isinstance(max_batch, bool) or not isinstance(max_batch, int) or max_batch < 1:
         raise ValueError("dnsmos_list: max_batch must be a positive integer")
     for k, sgn in enumerate(signals):
@@ -552,11 +553,11 @@ def dnsmos_list(signals: Sequence[torch.Tensor], model, fs: int = 16000, max_bat
         batch = order[b0:b0 + max_batch]
         blens = [lens[k] for k in batch]
         padded = _trim_pad([signals[k] for k in batch], signals[batch[0]].device)
-        parts.append(model.score(padded, blens, fs))
+        parts.append(model.score(padded, blens, fs, p808=p808))
     inv = torch.empty(N, dtype=torch.long)
     inv[torch.tensor(order, dtype=torch.long)] = torch.arange(N)
     out = {}
-    for name in ("OVRL_raw", "SIG_raw", "BAK_raw", "OVRL", "SIG", "BAK", "num_hops"):
+    for name in ("OVRL_raw", "SIG_raw", "BAK_raw", "OVRL", "SIG", "BAK", "num_hops") + (("P808_MOS",) if p808 is not None else ()):
         dt = torch.int64 if name == "num_hops" else torch.float64
         vals = torch.cat([part[name].cpu() for part in parts]) if parts else torch.empty(0, dtype=dt)
         out[name] = vals[inv]

@@ -1201,6 +1201,8 @@ int idv_asm_write(const float* pool, long long pool_n, const long long* src, con
  * from 0; the bias is added last.  An output depends on its own image alone.  idv_conv3x3_tile(0 / 1): the rows / columns of output
  * pixels one workgroup owns.
  * idv_conv3x3_c1_fwd: the 1 -> C first layer on the vector ALU: f [N][H][W] -> y [N][H][W][C], w1 [C][9], one fmaf chain over the taps.
+ * idv_conv3x3_c1_pool_fwd: the same layer with the 2x2 / stride-2 floor maximum behind it, y [N][H / 2][W / 2][C]: the bits of the pool of
+ * idv_conv3x3_c1_fwd's map (the same device function), which is never written; H, W >= 2.
  * idv_conv3x3_c1_fused_fwd: idv_conv3x3_fwd applied to idv_conv3x3_c1_fwd(f) (C1 = its Cin) without the C1-channel map in memory: the
  * first layer is evaluated while a chunk is staged; the same bits as the two calls.
  * idv_conv3x3_gmax: x [N][P][C] -> out [N][C], the maximum over the P pixels.
@@ -1213,6 +1215,7 @@ int idv_conv3x3_pack(const float* w, int Cin, int Cout, float* packed, void* str
 int idv_conv3x3_fwd(const float* x, const float* wp, const float* bias, int N, int H, int W, int Cin, int Cout, int pool, float* y,
                     void* stream);
 int idv_conv3x3_c1_fwd(const float* f, const float* w1, const float* b1, int N, int H, int W, int C, float* y, void* stream);
+int idv_conv3x3_c1_pool_fwd(const float* f, const float* w1, const float* b1, int N, int H, int W, int C, float* y, void* stream);
 int idv_conv3x3_c1_fused_fwd(const float* f, const float* w1, const float* b1, int C1, const float* wp, const float* bias, int N, int H,
                              int W, int Cout, int pool, float* y, void* stream);
 int idv_conv3x3_gmax(const float* x, int N, long long P, int C, float* out, void* stream);
@@ -1233,6 +1236,30 @@ int idv_dnsmos_frontend(const float* x, long long ldx, const int* lengths, int B
 int idv_dnsmos_head(const float* g, int N, const float* w0, const float* b0, const float* w1, const float* b1, const float* w2,
                     const float* b2, float* raw, void* stream);
 int idv_dnsmos_clip(const float* raw, int nseg, const int* first, const int* count, int B, const double* poly, double* out, void* stream);
+
+/* ---- DNSMOS P.808, the P808_MOS column (p808.hip; dnsmos.py P808; additive entries: IDV_ABI_VERSION is unchanged).
+ *
+ * idv_p808_mel: segment s = (row, start) = seg[2 s], seg[2 s + 1] (device int32) of the padded batch x [B][ldx]; a[j] =
+ * x[row][(start + j) mod lengths[row]] for 0 <= j < 144000, so nothing at or past a row's length is read.  Frame t (900 of them) is
+ * a[160 t - 160 .. 160 t + 160], zero outside [0, 144000).  dft: [2][161][324] doubles, the windowed cosine table and the windowed
+ * negated sine table, element [k][n], n = 321 .. 323 zero.  mel: [120][161] doubles.  re / im = frame x table, p = re re + im im,
+ * S [nseg][900][120] = sum_k mel[m][k] p[t][k], all in double on v_mfma_f64_16x16x4_f64, k ascending in steps of 4; smax [nseg] = the
+ * maximum of the segment's S.  work: idv_p808_mel_work_doubles(nseg) doubles (per-workgroup maxima; -1 for nseg outside 1 .. 2^20).
+ * No atomics; a segment's bits do not depend on the other segments.  A segment whose row is outside [0, B) or whose length is < 1
+ * is all zero.
+ * idv_p808_db: feat [nseg][per] (float) = ((max(ls, -80) + 40) / 40), ls = 10 log10(max(1e-10, S)) - 10 log10(max(1e-10, smax[s])) in
+ * double, rounded once (librosa power_to_db with ref = max, top_db = 80: the largest ls is 0).
+ * idv_p808_head: g [N][64] -> raw [N]: dense 64 -> 64 ReLU, 64 -> 64 ReLU, 64 -> 1 (weights [in][out]), k-ascending fmaf chains.
+ * idv_p808_clip: out [B] (double) = the mean over the segments first[b] .. first[b] + count[b] - 1 of raw [nseg], a double sum in order.
+ * IDV_EINVAL (before any GPU work) for a NULL pointer, B, nseg, N <= 0, nseg > 2^20, ldx <= 0, per outside 1 .. 2^31, a pointer not
+ * aligned to its element. */
+long long idv_p808_mel_work_doubles(int nseg);
+int idv_p808_mel(const float* x, long long ldx, const int* lengths, int B, const int* seg, int nseg, const double* dft, const double* mel,
+                 double* S, double* smax, double* work, void* stream);
+int idv_p808_db(const double* S, const double* smax, int nseg, long long per, float* feat, void* stream);
+int idv_p808_head(const float* g, int N, const float* w0, const float* b0, const float* w1, const float* b1, const float* w2,
+                  const float* b2, float* raw, void* stream);
+int idv_p808_clip(const float* raw, int nseg, const int* first, const int* count, int B, double* out, void* stream);
 
 #ifdef __cplusplus
 }
