@@ -109,6 +109,12 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw_kernel(c
     constexpr int NE = CIK * RT;
     constexpr int NBUF = 2;
     constexpr int RDW = 2;                       // weight ring depth in k-steps
+    // A wave's loads return in order, so the first wait for weights fetched AFTER a staging load also waits for the staging load.
+    // Even-row phase with two co tiles: an item's loads go behind the weight loads of their k-step instead of in front of them, and
+    // the wait that retires them comes a k-step later (10 -> 18 MFMAs after issue; dec0-3 at B = 64: -0.5 .. -0.8 ms on two cards
+    // of three, nothing on the third).  Measured to gain nothing: the same in the other three forms, and a ring of KS k-steps on
+    // top of it here.
+    constexpr bool STAGE_BEHIND_W = PH == 0 && NCT == 2;
     constexpr bool WVEC = (TW_WVEC_MASK >> PH) & 1;
     constexpr int NITEM = CIK * NRAW * 16;       // staging items per chunk: (channel, raw row, 2 column pairs)
     constexpr int NTHR = 256 * NCT;
@@ -370,11 +376,15 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw_kernel(c
                         if ((k & 1) && k < 6) stage_plane2(Pn, si, k >> 1);
                         if (k == (NTW == 9 ? 7 : 6)) stage_plane2(Pn, si, 3);
                         if (k == NTW - 1) stage_plane2(Pn, si, 4);
-                        if (k == NTW - 1) stage_load(nxt2, si);
+                        if (k == NTW - 1 && !STAGE_BEHIND_W) stage_load(nxt2, si);
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 load_w(chunk * KS + ul + RDW, a_w[ul % RDW]);
+                if (STAGE_BEHIND_W && staging) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    stage_load(nxt2, si);
+                }
             }
         }
     };

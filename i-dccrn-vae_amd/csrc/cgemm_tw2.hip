@@ -32,6 +32,8 @@
 
 namespace {
 
+typedef f32x4 f32x4_a4 __attribute__((aligned(4)));     // a 16-byte global load at any float
+
 struct Tw2Args {
     const float* x0;      // planar [2][Cin][Fin][Jp]
     int Cin;
@@ -204,21 +206,27 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw2_kernel(
         const float* bi = br + (size_t)Cin * a.Fin * a.Jp;
         const bool dead = item_cl(i) >= Cin - ci0;
         const unsigned ov = dead ? 4u : off_v[i];
-        v_r[i] = *(const f32x4*)(br + ov);
-        v_i[i] = *(const f32x4*)(bi + ov);
-        e_r[i] = (br + ov)[LEFT ? -1 : 4];
-        e_i[i] = (bi + ov)[LEFT ? -1 : 4];
+        // the five-column window as ONE vector (its first four columns) and one scalar (the fifth) on both tap sides; tap left: the
+        // vector starts a float in front of the 16-byte slot.  (Loaded as the aligned slot and the column in front, the compiler
+        // merges the two into this same pair of loads, re-assembles v / e from their components right behind the loads and waits
+        // for them there: a global round trip per chunk in the slot that issues them.)
+        const float* pr = br + ov - (LEFT ? 1 : 0);
+        const float* pi = bi + ov - (LEFT ? 1 : 0);
+        using Win = std::conditional_t<LEFT, f32x4_a4, f32x4>;
+        v_r[i] = *(const Win*)pr;
+        v_i[i] = *(const Win*)pi;
+        e_r[i] = pr[4];
+        e_i[i] = pi[4];
     };
     float fr[5], fi[5];
     auto stage_window = [&](int chunk, int i) {
         if (!item_exists(i)) return;
         const int cvalid = Cin - chunk * CIK;
-        constexpr bool left = LEFT;
         if (interior[i] && cvalid >= CIK) {
 #pragma unroll
             for (int q = 0; q < 5; ++q) {
-                fr[q] = left ? (q == 0 ? e_r[i] : v_r[i][q == 0 ? 0 : q - 1]) : (q == 4 ? e_r[i] : v_r[i][q == 4 ? 3 : q]);
-                fi[q] = left ? (q == 0 ? e_i[i] : v_i[i][q == 0 ? 0 : q - 1]) : (q == 4 ? e_i[i] : v_i[i][q == 4 ? 3 : q]);
+                fr[q] = q == 4 ? e_r[i] : v_r[i][q == 4 ? 3 : q];
+                fi[q] = q == 4 ? e_i[i] : v_i[i][q == 4 ? 3 : q];
             }
             return;
         }
@@ -226,8 +234,8 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw2_kernel(
         if (item_cl(i) >= cvalid || !((m >> 5) & 1u)) m &= ~0x1fu;
 #pragma unroll
         for (int q = 0; q < 5; ++q) {
-            const float xr = left ? (q == 0 ? e_r[i] : v_r[i][q == 0 ? 0 : q - 1]) : (q == 4 ? e_r[i] : v_r[i][q == 4 ? 3 : q]);
-            const float xi = left ? (q == 0 ? e_i[i] : v_i[i][q == 0 ? 0 : q - 1]) : (q == 4 ? e_i[i] : v_i[i][q == 4 ? 3 : q]);
+            const float xr = q == 4 ? e_r[i] : v_r[i][q == 4 ? 3 : q];
+            const float xi = q == 4 ? e_i[i] : v_i[i][q == 4 ? 3 : q];
             const bool cok = (m >> q) & 1u;
             fr[q] = cok ? xr : 0.f;
             fi[q] = cok ? xi : 0.f;
@@ -370,6 +378,11 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw2_kernel(
                         cb = k < 14 ? ((k & 1) ? cby : cbx) : -1.f;
                         ai = k < 14 ? k >> 1 : 7 + (k - 14);
                     }
+                    // A role with empty slots (wave 3: slot 15; edge waves: slot 15, or every fourth) never reads those slots' weights.
+                    // Left dead, their registers are handed out again while the group's 16-byte load is still in flight, and the write
+                    // to one waits for ALL the wave's loads (vmcnt(0)) right behind the load's issue, in every k-step.  Read here, where
+                    // the group's first MFMA waits for the load anyway, they stay the load's until it has landed.
+                    if ((ROLE_B || EDGE) && s4 == 0) asm volatile("" ::"v"(a_w[k]), "v"(a_w[k + 1]), "v"(a_w[k + 2]), "v"(a_w[k + 3]));
                     if (s4 == 0) {
                         // the next group's operands (of this k-step, or group 0 of the next one: after the barrier in the last k-step)
                         const float* src = g < 3 ? P + (size_t)(2 * ul + half) * RT : bnext;
