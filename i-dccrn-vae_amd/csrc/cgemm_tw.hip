@@ -59,10 +59,6 @@ struct TwArgs {
 };
 
 constexpr int TW_PACK_CI = 8;      // pack granularity in complex input channels (cgemm_wino's WCIK)
-// weight fragments as [64 lanes][4 tiles] groups with 16-byte loads (bit PH set) or slot-major [slot][64 lanes] with 4-byte loads: measured
-// (B = 64, dec0-3) even-row phase 22.0 -> 21.1 ms with the vector form, odd-row phase 14.1 -> 17.8 ms: the even-row phase only.  Read by
-// the pack kernel and the conv kernels alike.
-constexpr int TW_WVEC_MASK = 1;
 // co tiles on different XCDs: dec0-3 at B = 64 34.7 -> 34.3 ms (dec0, eight co tiles: 9.81 -> 9.54) against one XCD per column block
 constexpr int TW_XCD_SPLIT = 1;
 // two co tiles per workgroup, odd-row phase: waves 4 .. 7 stage one k-step later than their SIMD partners (see the kernel's main loop)
@@ -112,10 +108,10 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw_kernel(c
     // A wave's loads return in order, so the first wait for weights fetched AFTER a staging load also waits for the staging load.
     // Even-row phase with two co tiles: an item's loads go behind the weight loads of their k-step instead of in front of them, and
     // the wait that retires them comes a k-step later (10 -> 18 MFMAs after issue; dec0-3 at B = 64: -0.5 .. -0.8 ms on two cards
-    // of three, nothing on the third).  Measured to gain nothing: the same in the other three forms, and a ring of KS k-steps on
-    // top of it here.
+    // of three, nothing on the third).  Measured to gain nothing: the same in the other three forms (the odd-row phase again behind
+    // its two 16-byte weight loads: 7 -> 14 / 9 MFMAs paired, 7 -> 10 .. 14 unpaired, no faster), and a ring of KS k-steps on top of
+    // it here.
     constexpr bool STAGE_BEHIND_W = PH == 0 && NCT == 2;
-    constexpr bool WVEC = (TW_WVEC_MASK >> PH) & 1;
     constexpr int NITEM = CIK * NRAW * 16;       // staging items per chunk: (channel, raw row, 2 column pairs)
     constexpr int NTHR = 256 * NCT;
     constexpr int NLD = (NITEM + NTHR - 1) / NTHR;
@@ -288,27 +284,24 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw_kernel(c
 
     // ---- weights in a ring of RDW k-steps: the wave's tiles of a channel pair are packed as groups of [64 lanes][4 tiles] (lane =
     // channel parity x 32 + co; idv_pack_cconv_tw): even-row phase two 16-byte loads + one 4-byte load ([64 lanes]) per k-step,
-    // odd-row phase two 16-byte loads
+    // odd-row phase two 16-byte loads.  The odd-row phase's eighth slot (zero taps, no tile) has a register of its own in the ring:
+    // see the main loop.
     constexpr int WS = tw_wslots<PH>();
+    constexpr int NWR = PH == 0 ? NTW : 8;                    // weight registers per ring slot
     const size_t wregion = PH == 1 ? (size_t)a.cotiles * a.UP * tw_ntp<0>() : (edge ? (size_t)a.cotiles * a.UP * (tw_ntp<0>() + tw_ntp<1>()) : 0);
     const float* wbase = a.wfrag + (wregion + (size_t)ct * a.UP * NTP) * 64 + (size_t)w4 * WS * 64;
     const int total_ks = nchunk * KS;
-    float a_w[RDW][NTW];
-    auto load_w = [&](int g, float (&dst)[NTW]) {
+    float a_w[RDW][NWR];
+    auto load_w = [&](int g, float (&dst)[NWR]) {
         g = g < total_ks ? g : total_ks - 1;                  // (past the end of K: an unused re-fetch)
         const float* ws = wbase + (size_t)g * NTP * 64;
-        if (WVEC) {
-            const f32x4 w0 = *(const f32x4*)(ws + lane * 4), w1 = *(const f32x4*)(ws + 256 + lane * 4);
+        const f32x4 w0 = *(const f32x4*)(ws + lane * 4), w1 = *(const f32x4*)(ws + 256 + lane * 4);
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                dst[k] = w0[k];
-                if (4 + k < NTW) dst[4 + k] = w1[k];
-            }
-            if (NTW == 9) dst[NTW - 1] = ws[512 + lane];
-        } else {                                              // slot-major [slot][64 lanes]: one 4-byte load per tile
-#pragma unroll
-            for (int k = 0; k < NTW; ++k) dst[k] = ws[k * 64 + lane];
+        for (int k = 0; k < 4; ++k) {
+            dst[k] = w0[k];
+            dst[4 + k] = w1[k];
         }
+        if (NTW == 9) dst[NTW - 1] = ws[512 + lane];
     };
     float xa[NTW], xb[NTW];
     // operands of tiles 2 j, 2 j + 1 (j < NPAIR: one 8-byte read per raw row) or of the single tile; base = buffer + channel of this half-wave
@@ -360,6 +353,12 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw_kernel(c
 #pragma unroll
                 for (int k = 0; k < NTW; ++k) {
                     const float b = xa[k] + cbj[UNI ? 0 : (k >> 1 < NPAIR ? k >> 1 : NPAIR)] * xb[k];
+                    // Odd-row phase: no wave reads the eighth slot's weights (seven tiles).  Left dead, that register is handed out again
+                    // while the second group's 16-byte load is still in flight, and the write to it waits for ALL the wave's loads
+                    // (vmcnt(0)) right behind the load's issue, in every k-step (that form measured 14.1 -> 17.8 ms on dec0-3 at B = 64).
+                    // Read here, where the group's first MFMA waits for the load anyway, it stays the load's until it has landed.
+                    if (PH == 1 && k == 4)
+                        asm volatile("" ::"v"(a_w[ul % RDW][4]), "v"(a_w[ul % RDW][5]), "v"(a_w[ul % RDW][6]), "v"(a_w[ul % RDW][7]));
                     acc[k] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_w[ul % RDW][k], b, acc[k], 0, 0, 0);
                     if (ul == KS - 1 && k == 0) {
                         // every wave has stored chunk + 1 (k-steps 1, 2) and issued its last reads of P: after this barrier Pn is complete
@@ -530,7 +529,7 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw_kernel(c
 // with the time-transformed taps  tau 0: W_h0,  tau 1: W_h0 + W_h1,  tau 2: W_h1.  A third region in the even-row phase's layout holds
 // the RAW frequency taps of the edge workgroups in place of the frequency products r: waves 0, 2 the tap W4 (the even-row phase's
 // slot r = 0), waves 1, 3 the tap W2 = slot r = 1 minus slot r = 2 ((W4 + W2 + W0) / 2 - (W4 - W2 + W0) / 2).
-__global__ void pack_cconv_tw_kernel(const float* __restrict__ wino, int cotiles, int UN, int UP, int vec, float* __restrict__ out) {
+__global__ void pack_cconv_tw_kernel(const float* __restrict__ wino, int cotiles, int UN, int UP, int cin, float* __restrict__ out) {
     const long long n0 = (long long)cotiles * UP * tw_ntp<0>() * 64, n1 = (long long)cotiles * UP * tw_ntp<1>() * 64;
     for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < n0 + n1 + n0; idx += (long long)gridDim.x * blockDim.x) {
         const bool raw = idx >= n0 + n1;
@@ -543,15 +542,15 @@ __global__ void pack_cconv_tw_kernel(const float* __restrict__ wino, int cotiles
         const int u = (int)(t_ % UP);
         const int ct = (int)(t_ / UP);
         float val = 0.f;
-        // per (channel pair u, wave w) WS = 9 / 8 slots: groups of [64 lanes][4 tiles] (+ one of [64 lanes] in the even-row phase)
+        // per (channel pair u, wave w) WS = 9 / 8 slots: two groups of [64 lanes][4 tiles] (+ one of [64 lanes] in the even-row phase);
+        // the odd-row phase's slot 7 (and wave 3's slot 6) hold zero taps
         const int ws_ = ph ? tw_wslots<1>() : tw_wslots<0>();
         const int pos = t * 64 + lane, w = pos / (ws_ * 64), q = pos % (ws_ * 64);
-        const bool vec_ = (vec >> ph) & 1;
-        const int k = !vec_ ? q >> 6 : (q < 512 ? (q >> 8) * 4 + (q & 3) : 8);
-        const int ln = !vec_ ? q & 63 : (q < 512 ? (q & 255) >> 2 : q - 512);
+        const int k = q < 512 ? (q >> 8) * 4 + (q & 3) : 8;
+        const int ln = q < 512 ? (q & 255) >> 2 : q - 512;
         const int tt = k < (ph ? 7 : 9) ? tw_tile(ph, w, k) : -1;
         const int ci = 2 * u + (ln >> 5), co = ln & 31;
-        if (tt >= 0 && ci * 3 < UN) {
+        if (tt >= 0 && ci < cin) {                             // (channels past cin: zero taps, whatever the source holds there)
             const int r = tt / 9, g = (tt % 9) / 3, tau = tt % 3;
             const float* src = wino + ((((size_t)ph * cotiles + ct) * UN + (size_t)ci * 3 + g) * 4 + (raw ? 0 : r)) * 64;
             float w0 = src[co], w1 = src[32 + co];
@@ -653,7 +652,7 @@ extern "C" int idv_pack_cconv_tw(const float* wino_frag, int Cout, int cin_used,
     const long long n = idv_cconv_tw_wfrag_floats(Cout, cin_used);
     const unsigned blocks = (unsigned)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256);
     hipLaunchKernelGGL(pack_cconv_tw_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, wino_frag, cotiles, cpad * 3, cpad / 2,
-                       TW_WVEC_MASK, tw_frag);
+                       cin_used, tw_frag);
     return idv_launch_status();
 }
 
