@@ -25,11 +25,8 @@ int launch_vec(const CgemmArgs& a, hipStream_t st) {
     const long long nblk = b.map_ft ? (long long)((b.jtiles + 7) / 8) * 8 * b.ftiles * b.mblocks : ((tiles + 7) / 8) * 8 * b.mblocks;
     if (nblk > 0x7fffffffLL) return IDV_EINVAL;
     dim3 grid((unsigned)nblk);
-    auto k = cgemm_kernel<MODE, WM, WN, MT_W, FO_T, JC_W, CCK, SWAP, STATS, VEC>;
-    if (smem > 64 * 1024) {
-        if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-            return IDV_ELAUNCH;
-    }
+    constexpr auto k = cgemm_kernel<MODE, WM, WN, MT_W, FO_T, JC_W, CCK, SWAP, STATS, VEC>;
+    if (int rc = idv_dyn_smem_once<k>(smem)) return rc;
     hipLaunchKernelGGL(k, grid, dim3(WM * WN * 64), smem, st, b);
     return idv_launch_status();
 }

@@ -504,10 +504,8 @@ int launch_bf16(const CgemmArgs& a, hipStream_t st) {
     b.map_ft = 1;
     const long long nblk = (long long)((b.jtiles + 7) / 8) * 8 * b.ftiles * b.mblocks;
     if (nblk > 0x7fffffffLL) return IDV_EINVAL;
-    auto k = cgemm_bf16_kernel<MODE, WM, WN, FO_T, JC_W, STATS, MT_W, IMGIN, AD>;
-    if (smem > 64 * 1024 &&
-        hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-        return IDV_ELAUNCH;
+    constexpr auto k = cgemm_bf16_kernel<MODE, WM, WN, FO_T, JC_W, STATS, MT_W, IMGIN, AD>;
+    if (int rc = idv_dyn_smem_once<k>(smem)) return rc;
     hipLaunchKernelGGL(k, dim3((unsigned)nblk), dim3(WM * WN * 64), smem, st, b);
     return idv_launch_status();
 }

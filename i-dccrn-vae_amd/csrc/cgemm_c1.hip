@@ -292,10 +292,8 @@ template <bool IMGIN>
 static int launch_c1(const CgemmArgs& a, hipStream_t st) {
     constexpr size_t smem = (size_t)2 * C1_BUF * sizeof(unsigned short);
     static_assert(smem >= (size_t)C1_ROWS * 10 * C1_JT * sizeof(float), "P exchange fits in the patch buffers");
-    auto k = ctconv_c1_bf16_kernel<IMGIN>;
-    if (smem > 64 * 1024 &&
-        hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-        return IDV_ELAUNCH;
+    constexpr auto k = ctconv_c1_bf16_kernel<IMGIN>;
+    if (int rc = idv_dyn_smem_once<k>(smem)) return rc;
     dim3 grid((a.J + C1_JT - 1) / C1_JT, (a.Fin + C1_FI - 1) / C1_FI);
     hipLaunchKernelGGL(k, grid, dim3(256), smem, st, a);
     return idv_launch_status();

@@ -21,6 +21,7 @@
 // fragment order, a chunk ahead.
 #include <cstdlib>
 #include "cgemm.hpp"
+#include "conv_epilogue.hpp"
 #include "../../include/idccrn_hip.h"
 
 namespace {
@@ -315,8 +316,7 @@ __global__ __launch_bounds__(WM* WN * 64, OCC) void cgemm_gauss_kernel(const Gau
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int co = ct * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-        const f32x4 e0 = *(const f32x4*)(a.epi + (size_t)co * 8);           // table is allocated for every row of every tile
-        const float e4 = a.epi[(size_t)co * 8 + 4], e5 = a.epi[(size_t)co * 8 + 5];
+        const EpiRow e = epi_row(a.epi, co);
         const bool cok = co < a.Cout;
         float st[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -333,34 +333,16 @@ __global__ __launch_bounds__(WM* WN * 64, OCC) void cgemm_gauss_kernel(const Gau
                 const float t1 = acc[rt][jc][0][r], t2 = acc[rt][jc][1][r], t3 = acc[rt][jc][2][r];
                 float re = t1 - t3, im = t1 + t2;
                 if (a.add && cok && inb) {
-                    re += a.add[((size_t)co * a.Fout + fo) * a.add_Jp + ja];
-                    im += a.add[((size_t)(a.Cout + co) * a.Fout + fo) * a.add_Jp + ja];
+                    re += epi_addend(a.add, co, a.Fout, fo, a.add_Jp, ja);
+                    im += epi_addend(a.add, a.Cout + co, a.Fout, fo, a.add_Jp, ja);
                 }
-                float yr, yi;
-                if (a.has_fold) {
-                    yr = e0[0] * re + e0[1] * im + e4;
-                    yi = e0[2] * re + e0[3] * im + e5;
-                } else {
-                    yr = re + e4;
-                    yi = im + e5;
-                }
-                if (has_act) {
-                    yr = yr >= 0.f ? yr : slope * yr;
-                    yi = yi >= 0.f ? yi : slope * yi;
-                }
-                yr = keep ? yr : 0.f;
-                yi = keep ? yi : 0.f;
+                const EpiPoint y = epi_point(re, im, e.z, e.sr, e.si, a.has_fold, has_act, slope);
+                const float yr = keep ? y.r : 0.f, yi = keep ? y.i : 0.f;
                 if (cok && inb) {
                     a.out[((size_t)co * a.Fout + fo) * a.Jp + j] = yr;
                     a.out[((size_t)(a.Cout + co) * a.Fout + fo) * a.Jp + j] = yi;
                 }
-                if (STATS && inb && keep) {
-                    st[0] += yr;
-                    st[1] += yi;
-                    st[2] += yr * yr;
-                    st[3] += yi * yi;
-                    st[4] += yr * yi;
-                }
+                if (STATS && inb && keep) epi_stats_add(st, yr, yi);
             }
         }
         if (STATS) {
@@ -437,10 +419,8 @@ int launch_gauss_v(const GaussArgs& a, hipStream_t st) {
     const long long tiles = (long long)b.jtiles * b.ftiles;
     const long long nblk = b.map_ft ? (long long)((b.jtiles + 7) / 8) * 8 * b.ftiles * b.mblocks : ((tiles + 7) / 8) * 8 * b.mblocks;
     if (nblk > 0x7fffffffLL) return IDV_EINVAL;
-    auto k = cgemm_gauss_kernel<MODE, WM, WN, FO_T, JC_W, CIK, STATS, VEC, NBUF, OCC>;
-    if (smem > 64 * 1024 &&
-        hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-        return IDV_ELAUNCH;
+    constexpr auto k = cgemm_gauss_kernel<MODE, WM, WN, FO_T, JC_W, CIK, STATS, VEC, NBUF, OCC>;
+    if (int rc = idv_dyn_smem_once<k>(smem)) return rc;
     hipLaunchKernelGGL(k, dim3((unsigned)nblk), dim3(WM * WN * 64), smem, st, b);
     return idv_launch_status();
 }
@@ -552,7 +532,8 @@ extern "C" int idv_cconv2d_gauss_fwd(const float* x0, int C0, const float* x1, i
                                      double* stats_work, int stats_rep, int transposed, int tshift, int Cout, int Fin, int B, int Tp,
                                      int Jp, int t_valid_out, const float* addend, int addend_div, int addend_Jp, void* stream) {
     if (!x0 || !wfrag || !epi || !out || C0 <= 0 || Cout <= 0 || Fin <= 0 || B <= 0 || Tp <= 1) return IDV_EINVAL;
-    if (stats && stats_work && (stats_rep < 2 || (stats_rep & (stats_rep - 1)))) return IDV_EINVAL;
+    const EpiStatsTarget sums{stats, stats_work, stats_rep};
+    if (!sums.ok()) return IDV_EINVAL;
     if (addend && (addend_div < 1 || B % addend_div || addend_Jp < (B / addend_div) * Tp)) return IDV_EINVAL;
     if (C1 > 0 && (!x1 || x1_div < 1)) return IDV_EINVAL;
     if (tshift != 0 && tshift != -1) return IDV_EINVAL;
@@ -564,15 +545,12 @@ extern "C" int idv_cconv2d_gauss_fwd(const float* x0, int C0, const float* x1, i
     a.J = B * Tp; a.Jp = Jp; a.Tp = Tp; a.Jp1 = C1 > 0 ? Jp1 : Jp; a.x1_div = x1_div < 1 ? 1 : x1_div;
     a.wfrag = wfrag; a.KS = (C0 + C1 + CIK - 1) / CIK * CIK * 15; a.epi = epi; a.has_fold = has_fold; a.slope = prelu_slope; a.out = out;
     a.Cout = Cout; a.cotiles = (Cout + 31) / 32;
-    a.tshift = tshift; a.t_valid = t_valid_out; a.stats = stats;
+    a.tshift = tshift; a.t_valid = t_valid_out;
     a.add = addend; a.add_div = addend ? addend_div : 1; a.add_Jp = addend_Jp;
     if (Jp < a.J) return IDV_EINVAL;
     // chunk-relative offsets are 32-bit: CIK channels of one source must stay below 2^32 floats (they do: 2 x 257 x Jp)
     if ((long long)CIK * Fin * (long long)(Jp > a.Jp1 ? Jp : a.Jp1) >= 0xffffffffLL) return IDV_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    if (!stats) return launch_cfg<false>(a, transposed, st);
-    if (!stats_work) return launch_cfg<true>(a, transposed, st);
-    a.stats = stats_work; a.stats_rep = stats_rep;       // replicated sums, folded into `stats` afterwards (common.hpp)
-    const int rc = launch_cfg<true>(a, transposed, st);
-    return rc ? rc : idv_launch_stats_collapse(stats_work, stats_rep, Cout * 5, stats, st);
+    sums.set(a);
+    return sums.finish(!stats ? launch_cfg<false>(a, transposed, st) : launch_cfg<true>(a, transposed, st), Cout, st);
 }

@@ -30,6 +30,7 @@
 #include <cstdlib>
 #include <type_traits>
 #include "cgemm.hpp"
+#include "conv_epilogue.hpp"
 #include "cgemm_tw_map.hpp"
 #include "../../include/idccrn_hip.h"
 
@@ -431,26 +432,11 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw_kernel(c
         for (int t = 0; t < NT; ++t) v[t] = E[(t * 4 + w4) * 64 + lane];
         // time, then Gauss: P[r][q][re / im]
         float pr[NR][2], pi[NR][2];
-#pragma unroll
-        for (int r = 0; r < NR; ++r) {
-            float y[3][2];
-#pragma unroll
-            for (int g = 0; g < 3; ++g) {
-                const float m1 = v[r * 9 + g * 3], m2 = v[r * 9 + g * 3 + 1], m3 = v[r * 9 + g * 3 + 2];
-                y[g][0] = m1 + m2;
-                y[g][1] = m2 - m3;
-            }
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                pr[r][q] = y[0][q] - y[2][q];
-                pi[r][q] = y[0][q] + y[1][q];
-            }
-        }
+        tw_recombine<NR>(v, pr, pi);
         const int rg = 4 * s + w4;
         const int co = ct * 32 + (rg & 3) + 8 * (rg >> 2) + 4 * half;
         const bool cok = co < a.Cout;
-        const f32x4 e0 = *(const f32x4*)(a.epi + (size_t)co * 8);
-        const float e4 = a.epi[(size_t)co * 8 + 4], e5 = a.epi[(size_t)co * 8 + 5];
+        const EpiRow e = epi_row(a.epi, co);
         float st[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int rt = 0; rt < 2; ++rt) {
@@ -473,30 +459,13 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw_kernel(c
                     im = rt == 0 ? pi[0][q] + pi[1][q] : pi[1][q] - pi[2][q];
                 }
                 if (a.add && cok && inb[rt][q]) {
-                    re += a.add[((size_t)co * a.Fout + fo) * a.add_Jp + ja[rt][q]];
-                    im += a.add[((size_t)(a.Cout + co) * a.Fout + fo) * a.add_Jp + ja[rt][q]];
+                    re += epi_addend(a.add, co, a.Fout, fo, a.add_Jp, ja[rt][q]);
+                    im += epi_addend(a.add, a.Cout + co, a.Fout, fo, a.add_Jp, ja[rt][q]);
                 }
-                float r_, i_;
-                if (a.has_fold) {
-                    r_ = e0[0] * re + e0[1] * im + e4;
-                    i_ = e0[2] * re + e0[3] * im + e5;
-                } else {
-                    r_ = re + e4;
-                    i_ = im + e5;
-                }
-                if (has_act) {
-                    r_ = r_ >= 0.f ? r_ : slope * r_;
-                    i_ = i_ >= 0.f ? i_ : slope * i_;
-                }
-                yr[q] = keep[rt][q] ? r_ : 0.f;
-                yi[q] = keep[rt][q] ? i_ : 0.f;
-                if (STATS && keep[rt][q]) {
-                    st[0] += yr[q];
-                    st[1] += yi[q];
-                    st[2] += yr[q] * yr[q];
-                    st[3] += yi[q] * yi[q];
-                    st[4] += yr[q] * yi[q];
-                }
+                const EpiPoint y = epi_point(re, im, e.z, e.sr, e.si, a.has_fold, has_act, slope);
+                yr[q] = keep[rt][q] ? y.r : 0.f;
+                yi[q] = keep[rt][q] ? y.i : 0.f;
+                if (STATS && keep[rt][q]) epi_stats_add(st, yr[q], yi[q]);
             }
             if (cok) {
                 float* o_r = a.out + ((size_t)co * a.Fout + fo) * a.Jp + jA;
@@ -576,16 +545,8 @@ int launch_tw_ph_l(const TwArgs& a, hipStream_t st) {
     const long long nblk = tw_grid_blocks(b.grid);
     if (nblk == 0) return IDV_OK;
     if (nblk > 0x7fffffffLL) return IDV_EINVAL;
-    auto k = cconv_tw_kernel<PH, CIK, LEFT, STATS, NCT>;
-    // (once per instantiation and device: setting it on every launch is host time, a lot of it under a profiler.  Two threads that
-    // both find the flag clear both set the same value.)
-    static std::atomic<bool> attr_set[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return IDV_ELAUNCH;
-    if (smem > 64 * 1024 && !attr_set[dev].load(std::memory_order_acquire)) {
-        if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return IDV_ELAUNCH;
-        attr_set[dev].store(true, std::memory_order_release);
-    }
+    constexpr auto k = cconv_tw_kernel<PH, CIK, LEFT, STATS, NCT>;
+    if (int rc = idv_dyn_smem_once<k>(smem)) return rc;
     hipLaunchKernelGGL(k, dim3((unsigned)nblk), dim3(256 * NCT), smem, st, b);
     if (NCT > 1) idv_tw_pair_note_launch();
     return idv_launch_status();
@@ -665,7 +626,8 @@ extern "C" int idv_ctconv2d_tw_fwd(const float* x0, int C0, const float* x1, int
                                    int Cout, int Fin, int B, int Tp, int Jp, int t_valid_out, const float* addend, int addend_div,
                                    int addend_Jp, void* stream) {
     if (!x0 || !wfrag || !epi || !out || C0 <= 0 || Cout <= 0 || Fin <= 0 || B <= 0 || Tp <= 1) return IDV_EINVAL;
-    if (stats && stats_work && (stats_rep < 2 || (stats_rep & (stats_rep - 1)))) return IDV_EINVAL;
+    const EpiStatsTarget sums{stats, stats_work, stats_rep};
+    if (!sums.ok()) return IDV_EINVAL;
     if (addend && (addend_div < 1 || B % addend_div || addend_Jp < (B / addend_div) * Tp)) return IDV_EINVAL;
     if (C1 > 0 && !x1) return IDV_EINVAL;
     if (tshift != 0 && tshift != -1) return IDV_EINVAL;
@@ -685,11 +647,9 @@ extern "C" int idv_ctconv2d_tw_fwd(const float* x0, int C0, const float* x1, int
     if (Jp < a.J) return IDV_EINVAL;
     if ((long long)8 * Fin * (long long)Jp >= 0xffffffffLL) return IDV_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    a.stats = stats;
-    if (stats && stats_work) { a.stats = stats_work; a.stats_rep = stats_rep; }       // replicated sums, folded afterwards (common.hpp)
+    sums.set(a);
     int rc = 0;
     rc = launch_tw_ph<0, 8>(a, st);
     if (!rc) rc = launch_tw_ph<1, 8>(a, st);
-    if (rc || !(stats && stats_work)) return rc;
-    return idv_launch_stats_collapse(stats_work, stats_rep, Cout * 5, stats, st);
+    return sums.finish(rc, Cout, st);
 }

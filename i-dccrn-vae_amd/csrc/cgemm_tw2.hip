@@ -22,11 +22,11 @@
 // per k-step), an odd wave on planes 5 .. 8 (12), the three taps of a plane into ONE accumulator (at most five per wave).  Staging,
 // barriers, weight ring and epilogue exchange are those of a full tile; the K loop is a further copy with other operand reads and a
 // second weight region (the raw taps, time-transformed).
-#include <atomic>
 #include <cstdint>
 #include <cstdlib>
 #include <type_traits>
 #include "cgemm.hpp"
+#include "conv_epilogue.hpp"
 #include "cgemm_tw_map.hpp"
 #include "../../include/idccrn_hip.h"
 
@@ -503,26 +503,11 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw2_kernel(
 #pragma unroll
         for (int t = 0; t < NT; ++t) v[t] = E[(t * 4 + w4) * 64 + lane];
         float pr[4][2], pi[4][2];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            float y[3][2];
-#pragma unroll
-            for (int g = 0; g < 3; ++g) {
-                const float m1 = v[r * 9 + g * 3], m2 = v[r * 9 + g * 3 + 1], m3 = v[r * 9 + g * 3 + 2];
-                y[g][0] = m1 + m2;
-                y[g][1] = m2 - m3;
-            }
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                pr[r][q] = y[0][q] - y[2][q];
-                pi[r][q] = y[0][q] + y[1][q];
-            }
-        }
+        tw_recombine<4>(v, pr, pi);
         const int rg = 4 * s + w4;
         const int co = ct * 32 + (rg & 3) + 8 * (rg >> 2) + 4 * half;
         const bool cok = co < a.Cout;
-        const f32x4 e0 = *(const f32x4*)(a.epi + (size_t)co * 8);
-        const float e4 = a.epi[(size_t)co * 8 + 4], e5 = a.epi[(size_t)co * 8 + 5];
+        const EpiRow e = epi_row(a.epi, co);
         float st[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int rt = 0; rt < 2; ++rt) {
@@ -538,27 +523,10 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw2_kernel(
                     re = pr[rt][q];
                     im = pi[rt][q];
                 }
-                float r_, i_;
-                if (a.has_fold) {
-                    r_ = e0[0] * re + e0[1] * im + e4;
-                    i_ = e0[2] * re + e0[3] * im + e5;
-                } else {
-                    r_ = re + e4;
-                    i_ = im + e5;
-                }
-                if (has_act) {
-                    r_ = r_ >= 0.f ? r_ : slope * r_;
-                    i_ = i_ >= 0.f ? i_ : slope * i_;
-                }
-                yr[q] = keep[rt][q] ? r_ : 0.f;
-                yi[q] = keep[rt][q] ? i_ : 0.f;
-                if (STATS && keep[rt][q]) {
-                    st[0] += yr[q];
-                    st[1] += yi[q];
-                    st[2] += yr[q] * yr[q];
-                    st[3] += yi[q] * yi[q];
-                    st[4] += yr[q] * yi[q];
-                }
+                const EpiPoint y = epi_point(re, im, e.z, e.sr, e.si, a.has_fold, has_act, slope);
+                yr[q] = keep[rt][q] ? y.r : 0.f;
+                yi[q] = keep[rt][q] ? y.i : 0.f;
+                if (STATS && keep[rt][q]) epi_stats_add(st, yr[q], yi[q]);
             }
             if (cok) {
                 float* o_r = a.out + ((size_t)co * a.Fout + fo) * a.Jp + jA;
@@ -630,16 +598,8 @@ int launch_tw2(const Tw2Args& a, hipStream_t st) {
     b.stagger = TW2_PAIR_STAGGER;
     const long long nblk = tw_grid_blocks(b.grid);
     if (nblk > 0x7fffffffLL) return IDV_EINVAL;
-    auto k = cconv_tw2_kernel<LEFT, STATS, NCT>;
-    // (once per instantiation and device: setting it on every launch is host time, a lot of it under a profiler.  Two threads that
-    // both find the flag clear both set the same value.)
-    static std::atomic<bool> attr_set[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return IDV_ELAUNCH;
-    if (smem > 64 * 1024 && !attr_set[dev].load(std::memory_order_acquire)) {
-        if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return IDV_ELAUNCH;
-        attr_set[dev].store(true, std::memory_order_release);
-    }
+    constexpr auto k = cconv_tw2_kernel<LEFT, STATS, NCT>;
+    if (int rc = idv_dyn_smem_once<k>(smem)) return rc;
     hipLaunchKernelGGL(k, dim3((unsigned)nblk), dim3(256 * NCT), smem, st, b);
     if (NCT > 1) idv_tw_pair_note_launch();
     return idv_launch_status();
@@ -681,7 +641,8 @@ extern "C" int idv_cconv2d_tw_fwd(const float* x0, int Cin, const float* wfrag, 
                                   float* out, double* stats, double* stats_work, int stats_rep, int tshift, int Cout, int Fin, int B, int Tp,
                                   int Jp, int t_valid_out, void* stream) {
     if (!x0 || !wfrag || !epi || !out || Cin <= 0 || Cout <= 0 || Fin <= 0 || B <= 0 || Tp <= 1) return IDV_EINVAL;
-    if (stats && stats_work && (stats_rep < 2 || (stats_rep & (stats_rep - 1)))) return IDV_EINVAL;
+    const EpiStatsTarget sums{stats, stats_work, stats_rep};
+    if (!sums.ok()) return IDV_EINVAL;
     if (tshift != 0 && tshift != -1) return IDV_EINVAL;
     if (!idv_cconv_tw2_supported(Cin, Cout, Fin)) return IDV_EINVAL;
     if ((Jp & 3) || (reinterpret_cast<uintptr_t>(x0) & 15) || (reinterpret_cast<uintptr_t>(out) & 7)) return IDV_EINVAL;
@@ -696,8 +657,7 @@ extern "C" int idv_cconv2d_tw_fwd(const float* x0, int Cin, const float* wfrag, 
     if (Jp < a.J) return IDV_EINVAL;
     if ((long long)4 * Fin * (long long)Jp >= 0xffffffffLL) return IDV_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    a.stats = stats;
-    if (stats && stats_work) { a.stats = stats_work; a.stats_rep = stats_rep; }
+    sums.set(a);
     int rc;
     // two co tiles per workgroup (idv_tw_pair bit IDV_TW_PAIR_CONV): an even number of co tiles
     const bool pair = a.cotiles % 2 == 0 && (idv_tw_pair(-1) & IDV_TW_PAIR_CONV);
@@ -711,6 +671,5 @@ extern "C" int idv_cconv2d_tw_fwd(const float* x0, int Cin, const float* wfrag, 
         case 6: rc = launch_tw2<false, true, 2>(a, st); break;
         default: rc = launch_tw2<true, true, 2>(a, st); break;
     }
-    if (rc || !(stats && stats_work)) return rc;
-    return idv_launch_stats_collapse(stats_work, stats_rep, Cout * 5, stats, st);
+    return sums.finish(rc, Cout, st);
 }

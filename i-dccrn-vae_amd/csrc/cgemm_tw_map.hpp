@@ -11,6 +11,8 @@
 // The conv form (cgemm_tw2.hip) has the same geometry over OUTPUT rows: a full row tile is a pair of output rows, and with an odd
 // number of output rows whose last row has three real taps (Fin = 2 Fout - 1) that row, out[Fout - 1], goes to edge workgroups
 // (tw2_grid).
+//
+// At the end, for the kernels only: the output recombination both forms' epilogues share (tw_recombine).
 #pragma once
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
@@ -94,3 +96,27 @@ TW_HD inline bool tw_block_tile(const TwGrid& g, int bid, TwTile& t) {
     t.jt = t.edge ? 2 * col : col;
     return col < cols;
 }
+
+#if defined(__HIPCC__)
+// The inverse time and Gauss transforms of both forms' epilogues: per frequency product r the nine tiles v[r * 9 + g * 3 + tau] (Gauss
+// product g, time product tau) -> the output column pair q of the Gauss products, y[g][q], -> real / imaginary part pr[r][q], pi[r][q].
+// (The attribute spelled out: a host program that includes this header alone has no __forceinline__.)
+template <int NR>
+__device__ inline __attribute__((always_inline)) void tw_recombine(const float (&v)[NR * 9], float (&pr)[NR][2], float (&pi)[NR][2]) {
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+        float y[3][2];
+#pragma unroll
+        for (int g = 0; g < 3; ++g) {
+            const float m1 = v[r * 9 + g * 3], m2 = v[r * 9 + g * 3 + 1], m3 = v[r * 9 + g * 3 + 2];
+            y[g][0] = m1 + m2;
+            y[g][1] = m2 - m3;
+        }
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            pr[r][q] = y[0][q] - y[2][q];
+            pi[r][q] = y[0][q] + y[1][q];
+        }
+    }
+}
+#endif

@@ -31,9 +31,9 @@
 // (F(2,2): 3 x 3 = 9 tiles, 3 transformed rows).  Per wave: 32 complex output channels x 2 output rows x ONE 32-column tile.
 // Weights: 4 floats per (channel, plane) and lane as ONE 16-byte load -- one vector-memory instruction per 4 / 3 MFMAs
 // (cgemm_gauss: five per ten).
-#include <atomic>
 #include <cstdlib>
 #include "cgemm.hpp"
+#include "conv_epilogue.hpp"
 #include "../../include/idccrn_hip.h"
 
 namespace {
@@ -319,8 +319,7 @@ __global__ __launch_bounds__(WM* WN * 64, OCC) void cconv_wino_kernel(const Wino
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int co = ct * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-        const f32x4 e0 = *(const f32x4*)(a.epi + (size_t)co * 8);
-        const float e4 = a.epi[(size_t)co * 8 + 4], e5 = a.epi[(size_t)co * 8 + 5];
+        const EpiRow e = epi_row(a.epi, co);
         const bool cok = co < a.Cout;
         float st[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
         float t[2][3];                       // this phase's two output rows x Gauss products
@@ -342,34 +341,16 @@ __global__ __launch_bounds__(WM* WN * 64, OCC) void cconv_wino_kernel(const Wino
             if (fo >= a.Fout) continue;
             float re = t[rt][0] - t[rt][2], im = t[rt][0] + t[rt][1];
             if (a.add && cok && inb) {
-                re += a.add[((size_t)co * a.Fout + fo) * a.add_Jp + ja];
-                im += a.add[((size_t)(a.Cout + co) * a.Fout + fo) * a.add_Jp + ja];
+                re += epi_addend(a.add, co, a.Fout, fo, a.add_Jp, ja);
+                im += epi_addend(a.add, a.Cout + co, a.Fout, fo, a.add_Jp, ja);
             }
-            float yr, yi;
-            if (a.has_fold) {
-                yr = e0[0] * re + e0[1] * im + e4;
-                yi = e0[2] * re + e0[3] * im + e5;
-            } else {
-                yr = re + e4;
-                yi = im + e5;
-            }
-            if (has_act) {
-                yr = yr >= 0.f ? yr : slope * yr;
-                yi = yi >= 0.f ? yi : slope * yi;
-            }
-            yr = keep ? yr : 0.f;
-            yi = keep ? yi : 0.f;
+            const EpiPoint y = epi_point(re, im, e.z, e.sr, e.si, a.has_fold, has_act, slope);
+            const float yr = keep ? y.r : 0.f, yi = keep ? y.i : 0.f;
             if (cok && inb) {
                 a.out[((size_t)co * a.Fout + fo) * a.Jp + j] = yr;
                 a.out[((size_t)(a.Cout + co) * a.Fout + fo) * a.Jp + j] = yi;
             }
-            if (STATS && inb && keep) {
-                st[0] += yr;
-                st[1] += yi;
-                st[2] += yr * yr;
-                st[3] += yi * yi;
-                st[4] += yr * yi;
-            }
+            if (STATS && inb && keep) epi_stats_add(st, yr, yi);
         }
         if (STATS) {
 #pragma unroll
@@ -463,17 +444,10 @@ int launch_wino_ph(const WinoArgs& a, hipStream_t st) {
         nblk = (long long)((b.jtiles + G - 1) / G) * b.ftiles * 8;
     }
     if (nblk > 0x7fffffffLL) return IDV_EINVAL;
-    auto k = cconv_wino_kernel<PH, WM, WN, CIK, NBUF, STATS, OCC, RD>;
+    constexpr auto k = cconv_wino_kernel<PH, WM, WN, CIK, NBUF, STATS, OCC, RD>;
     // OCC 1: more than half a CU's LDS, i.e. one workgroup per CU whatever the register count says
-    const size_t smem_req = OCC == 1 ? (smem > 84 * 1024 ? smem : 84 * 1024) : smem;
-    // (once per instantiation and device, as in cgemm_tw.hip: smem_req is a constant of the instantiation)
-    static std::atomic<bool> attr_set[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return IDV_ELAUNCH;
-    if (smem_req > 64 * 1024 && !attr_set[dev].load(std::memory_order_acquire)) {
-        if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_req) != hipSuccess) return IDV_ELAUNCH;
-        attr_set[dev].store(true, std::memory_order_release);
-    }
+    constexpr size_t smem_req = OCC == 1 ? (smem > 84 * 1024 ? smem : 84 * 1024) : smem;
+    if (int rc = idv_dyn_smem_once<k>(smem_req)) return rc;
     hipLaunchKernelGGL(k, dim3((unsigned)nblk), dim3(WM * WN * 64), smem_req, st, b);
     return idv_launch_status();
 }
@@ -566,7 +540,8 @@ extern "C" int idv_cconv2d_wino_fwd(const float* x0, int C0, const float* x1, in
                                     int transposed, int tshift, int Cout, int Fin, int B, int Tp, int Jp, int t_valid_out,
                                     const float* addend, int addend_div, int addend_Jp, void* stream) {
     if (!x0 || !wfrag || !epi || !out || C0 <= 0 || Cout <= 0 || Fin <= 0 || B <= 0 || Tp <= 1) return IDV_EINVAL;
-    if (stats && stats_work && (stats_rep < 2 || (stats_rep & (stats_rep - 1)))) return IDV_EINVAL;
+    const EpiStatsTarget sums{stats, stats_work, stats_rep};
+    if (!sums.ok()) return IDV_EINVAL;
     if (addend && (addend_div < 1 || B % addend_div || addend_Jp < (B / addend_div) * Tp)) return IDV_EINVAL;
     if (C1 > 0 && !x1) return IDV_EINVAL;
     if (tshift != 0 && tshift != -1) return IDV_EINVAL;
@@ -583,8 +558,7 @@ extern "C" int idv_cconv2d_wino_fwd(const float* x0, int C0, const float* x1, in
     if (Jp < a.J) return IDV_EINVAL;
     if ((long long)WCIK * Fin * (long long)Jp >= 0xffffffffLL) return IDV_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    a.stats = stats;
-    if (stats && stats_work) { a.stats = stats_work; a.stats_rep = stats_rep; }       // replicated sums, folded afterwards (common.hpp)
+    sums.set(a);
     int rc;
     int cfg = idv_cconv_wino_config(transposed, C0 + C1, Cout);
     // transposed conv, second source: a K chunk of the odd-row phase must not straddle the two sources: where C0 is no multiple of
@@ -599,6 +573,5 @@ extern "C" int idv_cconv2d_wino_fwd(const float* x0, int C0, const float* x1, in
         case 228: rc = launch_wino_tconv<2, 2, 8>(a, st); break;
         default: return IDV_EINVAL;       // (144, one co tile: idv_cconv_wino_supported refuses it; measured 3 % slower than cgemm_gauss)
     }
-    if (rc || !(stats && stats_work)) return rc;
-    return idv_launch_stats_collapse(stats_work, stats_rep, Cout * 5, stats, st);
+    return sums.finish(rc, Cout, st);
 }

@@ -9,6 +9,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
 
 #define IDV_SLACK 256
 
@@ -22,6 +23,22 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 static inline int idv_launch_status() {
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? IDV_OK : IDV_ELAUNCH;
+}
+
+// Allow `Kernel` more than 64 KB of dynamic LDS, once per kernel and device: setting the attribute on every launch is host time, a lot
+// of it under a profiler.  smem must be a constant of the kernel (it is: every caller derives it from the template arguments).  The
+// kernel is a template ARGUMENT, not a function argument: the instantiations of one kernel template share one pointer type, and a flag
+// per type would skip all of them but the first.  Two threads that both find the flag clear both set the same value.
+template <auto Kernel>
+int idv_dyn_smem_once(size_t smem) {
+    static std::atomic<bool> attr_set[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return IDV_ELAUNCH;
+    if (smem > 64 * 1024 && !attr_set[dev].load(std::memory_order_acquire)) {
+        if (hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return IDV_ELAUNCH;
+        attr_set[dev].store(true, std::memory_order_release);
+    }
+    return IDV_OK;
 }
 
 // Argument checks of the latent entries (reduce.hip, backward.hip): a channel group [off, off + zdim) lies inside the latent's H

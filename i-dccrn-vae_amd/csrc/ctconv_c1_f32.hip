@@ -10,6 +10,7 @@
 // row tile 0 = wfrag[(cc*5 + kf)*64 + h*32 + ro], see pack.hip), i.e. every FMA is one SGPR x one VGPR.  Epilogue as
 // cgemm_kernel: bias, PReLU, outputs outside tp in [1, t_valid] zeroed, optional train-mode moments.
 #include "cgemm.hpp"
+#include "conv_epilogue.hpp"
 #include "../../include/idccrn_hip.h"
 
 namespace {
@@ -112,9 +113,7 @@ __global__ __launch_bounds__(256) void ctconv_c1_f32_kernel(const CgemmArgs a, i
             a.out[(size_t)fo * a.Jp + jcol[n]] = yr;                            // plane ro * Cout + co with Cout = 1
             a.out[((size_t)a.Fout + fo) * a.Jp + jcol[n]] = yi;
         }
-        if (STATS && keep[n]) {
-            st[0] += yr; st[1] += yi; st[2] += yr * yr; st[3] += yi * yi; st[4] += yr * yi;
-        }
+        if (STATS && keep[n]) epi_stats_add(st, yr, yi);
     };
 
     contract(m_lo - 1, pa);
