@@ -78,6 +78,10 @@ class GradAllReduce:
     ``optim.Adam.step(grad_bucket=red.bucket())`` reads them there.  Buckets are filled from the LAST registered parameters
     to the first (the order backward produces gradients in); inside a bucket the parameters keep registration order, so
     the one-bucket case (every shipped model: <= 100 MB against the 128 MB default) has the optimiser's own layout.
+    Clipping in that step: ``optim.Adam(max_norm=..., skip_nonfinite=...)`` takes the norm of group 0 from the reduced bucket
+    (with its ``scale`` and ``present`` flags), not from the rank-local ``.grad``.  After the all-reduce the bucket holds the
+    same bits on every rank and the norm kernels sum in a fixed order, so the partials, the norm, the coefficient and the
+    decision to skip a step are identical on every rank: no further collective is needed and the replicas cannot drift.
     CPU parameters (the gloo protocol test) take a plain torch loop."""
 
     def __init__(self, params: Iterable[torch.nn.Parameter], bucket_bytes: int = 128 << 20, group=None):

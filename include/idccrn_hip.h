@@ -618,6 +618,45 @@ int idv_bucket_adam(const long long* ptable, const long long* gtable, const floa
                     int n, long long total, float lr, double beta1, double beta2, float eps, float weight_decay,
                     float bias_correction1, float bias_correction2_sqrt, float grad_scale, void* stream);
 
+/* ---- global gradient norm, clipping and the non-finite guard on the bucket (bucket.hip; optim.Adam(max_norm, skip_nonfinite),
+ * optim.clip_grad_norm_; additive entries: IDV_ABI_VERSION is unchanged).  Tables, layout and the refusals of the
+ * entries above.
+ *   idv_bucket_sqnorm: partials[first + k] = the sum, over the elements of flat range [4096 k, 4096 (k + 1)) that belong to a
+ *     present parameter (non-NULL ptable row) with a gradient, of x^2 with x = the FLOAT product g * grad_scale (the first operation
+ *     of the Adam kernel) widened to double: every square is exact, every addition is in double and in a fixed order (per thread
+ *     in increasing flat index, a fixed butterfly across the wave, the four wave sums in wave order), no atomics, so two runs
+ *     return the same bits.  Gradients through gtable or gflat as in idv_bucket_adam.  Padding and absent rows are never
+ *     added, whatever they hold.  idv_bucket_sqnorm_partials(total) = ceil(total / 4096) = the partials one table takes (-1 for a
+ *     total that idv_bucket_sqnorm refuses); the caller lays the partials of several tables one after another with `first`.
+ *   idv_bucket_clip_finalize: one workgroup adds partials[0 .. count) in a fixed order and writes the 32-byte device record
+ *     (8-byte aligned, zeroed by the caller before its first use; byte offsets IDV_CLIP_*): sumsq (double), norm = sqrt(sumsq)
+ *     (double), coef (float) = min(1, max_norm / (norm + 1e-6)) formed in double and rounded once (torch's clip_grad_norm_ rule; 1
+ *     for max_norm <= 0: "norm only"), finite (int) = isfinite(sumsq) -- a float squares to at most 1.2e77, so the sum is
+ *     non-finite exactly when a gradient is -- and skipped (int64), which is incremented when guard != 0 and finite == 0.
+ *   idv_bucket_adam_clipped: idv_bucket_adam with g = (g * grad_scale) * coef + weight_decay * p, coef read from the record.
+ *     guard != 0: a step with finite == 0 returns before any store (parameters and both moments keep their bits), and the bias
+ *     corrections are formed on the device from t = t_host - skipped and the double betas (t_host >= 1: the step count the host
+ *     would have without refused steps), so a refused step does not advance them; bias_correction1 / bias_correction2_sqrt are
+ *     then only checked.  guard == 0: the host's bias corrections are used as in idv_bucket_adam.
+ *   idv_bucket_scale: tensors of the table *= coef of the record, in place (nothing is written when coef == 1).
+ * IDV_EINVAL (before any GPU work): a NULL or misaligned buffer (partials, record: 8 bytes; gflat, the moments: 16), n <= 0,
+ * total <= 0 or total & 3, first < 0, count <= 0, a NaN max_norm, both or neither of gtable / gflat, a NULL record. */
+#define IDV_CLIP_RECORD_BYTES 32
+#define IDV_CLIP_SUMSQ 0
+#define IDV_CLIP_NORM 8
+#define IDV_CLIP_COEF 16
+#define IDV_CLIP_FINITE 20
+#define IDV_CLIP_SKIPPED 24
+int idv_bucket_sqnorm_partials(long long total);
+int idv_bucket_sqnorm(const long long* ptable, const long long* gtable, const float* gflat, int n, long long total, float grad_scale,
+                      double* partials, long long first, void* stream);
+int idv_bucket_clip_finalize(const double* partials, int count, double max_norm, int guard, void* record, void* stream);
+int idv_bucket_adam_clipped(const long long* ptable, const long long* gtable, const float* gflat, float* exp_avg, float* exp_avg_sq,
+                            int n, long long total, float lr, double beta1, double beta2, float eps, float weight_decay,
+                            float bias_correction1, float bias_correction2_sqrt, float grad_scale, const void* record, int guard,
+                            long long t_host, void* stream);
+int idv_bucket_scale(const long long* table, int n, long long total, const void* record, void* stream);
+
 /* ---- complex conv / transposed conv with Winograd-transformed frequency taps (cgemm_wino.hip) -------------------------------
  * The encoder / decoder blocks' contractions (model/complex_progress.py:8-36, :222-279) with 7 instead of 10 real products per
  * input channel and pair of rows (F(2,3) on the even, F(2,2) on the odd frequency taps) on top of the three-product complex form
