@@ -1,11 +1,14 @@
-// Signal ends of streaming.StreamingDCCRN: framing from the carried input ring, the ring update, and the overlap-add with the
-// carried overlap, the istft envelope and emission of the samples that became final.
+// Signal ends of the streamers (streaming.py): framing from the carried input ring, the ring update, and the overlap-add with
+// the carried overlap, the istft envelope and emission of the samples that became final; then the draws and the repeated skips
+// of the VAE streamers.  Each signal-end step is one kernel body, template <bool ROWS>: the lock-step streamers hand it their
+// ranges by value (SigRow), the sessions streamers one row per slot in a table.  "Slot b's samples are the lock-step streamer's
+// bits" holds for these steps because both forms are the same statements; the host checks of the ranges are shared likewise.
 //
 // Index conventions (torch.stft / torch.istft, center=True, reflect padding; model/pvae_module.py:12-42): half = n_fft/2,
 // left = (n_fft - win)/2.  Frame t holds original samples s = hop*t + left - half + i, i in [0, win); s < 0 reads x[-s], and
 // at the end of the signal (L known) s >= L reads x[2(L-1) - s].  Output sample m sits at padded position P = m + half and
-// collects frame t at window index P - hop*t - left.  The host-side schedule (streaming.StreamPlan) computes every range
-// these kernels are given.
+// collects frame t at window index P - hop*t - left.  The host-side schedule (streaming.StreamPlan / SessionPlan) computes every
+// range these kernels are given.
 #include "common.hpp"
 #include "../../include/idccrn_hip.h"
 
@@ -16,145 +19,96 @@ inline int grid_of(long long n) {
     return (int)(g > 4096 ? 4096 : (g < 1 ? 1 : g));
 }
 
-// frames[i][b*Tp + 1 + tl] for the k frames t0 .. t0+k-1; samples below n_prev come from ring[b][s mod R], the others from
-// x[b][s - n_prev] (this push's input, row stride ldx)
-__global__ void stream_frames_kernel(const float* __restrict__ ring, int R, const float* __restrict__ x, long long ldx, long long n_prev,
-                                     long long L_end, int B, int n_fft, int win, int hop, long long t0, int k,
+// What the signal-end kernels read of a slot's row (the IDV_ROW_* fields of include/idccrn_hip.h).  A lock-step launch is handed
+// one by value, for all B rows alike; a sessions launch loads row b of its table.
+struct SigRow {
+    long long n_prev, count, L_end, t0, k, parity, e0, e1, p_end, carry_in, T_total, y_off;
+};
+
+__device__ __forceinline__ SigRow load_row(const long long* __restrict__ rows, int b) {
+    const long long* r = rows + (size_t)b * IDV_STREAM_ROW_FIELDS;
+    return {r[IDV_ROW_N_PREV], r[IDV_ROW_COUNT], r[IDV_ROW_L_END], r[IDV_ROW_T0],       r[IDV_ROW_K],       r[IDV_ROW_PARITY],
+            r[IDV_ROW_E0],     r[IDV_ROW_E1],    r[IDV_ROW_P_END], r[IDV_ROW_CARRY_IN], r[IDV_ROW_T_TOTAL], r[IDV_ROW_Y_OFF]};
+}
+
+// Each step below is one body.  ROWS = false (StreamingDCCRN): `lock` holds the ranges and the table is never read, so no lane
+// loads a row; ROWS = true (StreamingSessions): slot b takes its ranges from row b, which differs from lane to lane.  ROWS is
+// a compile-time constant for that reason, as in stream_conv.hpp and stream_lstm.hip.
+
+// frames[i][b*Tp + 1 + tl] for the frames t0 .. t0+k-1, tl < k_launch (lock-step: k = k_launch); samples below n_prev come from
+// ring[b][s mod R], the others from x[b][s - n_prev] (this push's input, row stride ldx).  ROWS: the columns tl >= k_b of a
+// slot are zeroed: the kernels downstream run over all k_launch columns and must not meet stale data.
+template <bool ROWS>
+__global__ void stream_frames_kernel(const float* __restrict__ ring, int R, const float* __restrict__ x, long long ldx, SigRow lock,
+                                     const long long* __restrict__ rows, int B, int n_fft, int win, int hop, int k_launch,
                                      float* __restrict__ frames, int Tp, int Jp) {
-    const int left = (n_fft - win) / 2, half = n_fft / 2;
-    const long long n = (long long)win * B * k;
-    for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
-        const int tl = (int)(e % k);
-        const int b = (int)((e / k) % B);
-        const int i = (int)(e / ((long long)k * B));
-        long long s = (long long)hop * (t0 + tl) + left - half + i;
-        if (s < 0) s = -s;
-        if (L_end >= 0 && s >= L_end) s = 2 * (L_end - 1) - s;
-        const float v = s >= n_prev ? x[(size_t)b * ldx + (size_t)(s - n_prev)] : ring[(size_t)b * R + (size_t)(s % R)];
-        frames[(size_t)i * Jp + (size_t)b * Tp + 1 + tl] = v;
-    }
-}
-
-__global__ void stream_ring_kernel(float* __restrict__ ring, int R, const float* __restrict__ x, long long ldx, int n_new, long long n_prev,
-                                   long long s0, int B) {
-    const long long cnt = n_prev + n_new - s0;
-    const long long n = cnt * B;
-    for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
-        const int b = (int)(e / cnt);
-        const long long s = s0 + e % cnt;
-        ring[(size_t)b * R + (size_t)(s % R)] = x[(size_t)b * ldx + (size_t)(s - n_prev)];
-    }
-}
-
-// padded positions P in [p_start, p_end): carried partial sum (positions below p_start + cin_len) plus the frames t0 ..
-// t0+k-1 in increasing t; P - half < e1 is final and goes to y (times 1 / envelope as idv_make_dft computes it), the rest
-// becomes the carry for positions from half + e1 on
-__global__ void stream_ola_kernel(const float* __restrict__ frames, int Tp, int Jp, const float* __restrict__ cin, int cin_len,
-                                  float* __restrict__ cout_, int cap, int B, int n_fft, int win, int hop, long long t0, int k,
-                                  long long T_total, long long e0, long long e1, long long p_end, float* __restrict__ y, int ldy,
-                                  long long y_off) {
-    const int left = (n_fft - win) / 2, half = n_fft / 2;
-    const long long p_start = half + e0, p_new = half + e1;
-    const long long span = p_end - p_start;
-    const long long n = span * B;
-    const double two_pi = 6.283185307179586476925286766559;
-    for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
-        const int b = (int)(e / span);
-        const long long P = p_start + e % span;
-        float v = (P - p_start < cin_len) ? cin[(size_t)b * cap + (size_t)(P - p_start)] : 0.f;
-        for (int tl = 0; tl < k; ++tl) {
-            const long long i = P - (long long)hop * (t0 + tl) - left;
-            if (i >= 0 && i < win) v += frames[(size_t)i * Jp + (size_t)b * Tp + 1 + tl];
-        }
-        if (P < p_new) {
-            // frames whose window covers P: P - win < hop*t + left <= P (at most ceil(win/hop) of them, wherever the stream is)
-            double env = 0.0;
-            long long t_hi = (P - left) / hop;
-            if (T_total >= 0 && t_hi > T_total - 1) t_hi = T_total - 1;
-            long long t_lo = P - left - win >= 0 ? (P - left - win) / hop + 1 : 0;
-            for (long long t = t_lo; t <= t_hi; ++t) {
-                const long long i = P - (long long)hop * t - left;
-                if (i >= 0 && i < win) {
-                    const double wn = 0.5 - 0.5 * cos(two_pi * i / win);
-                    env += wn * wn;
-                }
-            }
-            const float inv = env > 1e-11 ? (float)(1.0 / env) : 0.f;
-            y[(size_t)b * ldy + (size_t)(y_off + P - p_start)] = v * inv;
-        } else {
-            cout_[(size_t)b * cap + (size_t)(P - p_new)] = v;
-        }
-    }
-}
-
-// ---- per-row variants (streaming.StreamingSessions): every slot b takes its ranges from row b of a table of
-// IDV_STREAM_ROW_FIELDS long longs per slot (include/idccrn_hip.h).  The table is indexed by b, which differs from lane to lane.
-#define ROW(b, f) rows[(size_t)(b) * IDV_STREAM_ROW_FIELDS + (f)]
-
-// columns tl >= k_b of a slot are zeroed: the kernels downstream run over all k_launch columns and must not meet stale data
-__global__ void stream_frames_rows_kernel(const float* __restrict__ ring, int R, const float* __restrict__ x, long long ldx,
-                                          const long long* __restrict__ rows, int B, int n_fft, int win, int hop, int k_launch,
-                                          float* __restrict__ frames, int Tp, int Jp) {
     const int left = (n_fft - win) / 2, half = n_fft / 2;
     const long long n = (long long)win * B * k_launch;
     for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
         const int tl = (int)(e % k_launch);
         const int b = (int)((e / k_launch) % B);
         const int i = (int)(e / ((long long)k_launch * B));
+        const SigRow r = ROWS ? load_row(rows, b) : lock;
         float v = 0.f;
-        if (tl < ROW(b, IDV_ROW_K)) {
-            const long long n_prev = ROW(b, IDV_ROW_N_PREV), L_end = ROW(b, IDV_ROW_L_END);
-            long long s = (long long)hop * (ROW(b, IDV_ROW_T0) + tl) + left - half + i;
+        if (!ROWS || tl < r.k) {
+            long long s = (long long)hop * (r.t0 + tl) + left - half + i;
             if (s < 0) s = -s;
-            if (L_end >= 0 && s >= L_end) s = 2 * (L_end - 1) - s;
-            v = s >= n_prev ? x[(size_t)b * ldx + (size_t)(s - n_prev)] : ring[(size_t)b * R + (size_t)(s % R)];
+            if (r.L_end >= 0 && s >= r.L_end) s = 2 * (r.L_end - 1) - s;
+            v = s >= r.n_prev ? x[(size_t)b * ldx + (size_t)(s - r.n_prev)] : ring[(size_t)b * R + (size_t)(s % R)];
         }
         frames[(size_t)i * Jp + (size_t)b * Tp + 1 + tl] = v;
     }
 }
 
-// the last min(count_b, R) of the count_b new samples of slot b go to the ring at the slot's own position
-__global__ void stream_ring_rows_kernel(float* __restrict__ ring, int R, const float* __restrict__ x, long long ldx, int n_max,
-                                        const long long* __restrict__ rows, int B) {
+// the last min(count, R) of the count new samples of a row go to the ring at the row's position; n_max = min(widest count, R)
+// sizes the launch (lock-step: count = n_new for every row, so every j < n_max is written)
+template <bool ROWS>
+__global__ void stream_ring_kernel(float* __restrict__ ring, int R, const float* __restrict__ x, long long ldx, int n_max, SigRow lock,
+                                   const long long* __restrict__ rows, int B) {
     const long long n = (long long)n_max * B;
     for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
         const int b = (int)(e / n_max);
-        const long long j = e % n_max, count = ROW(b, IDV_ROW_COUNT);
-        const long long first = count > R ? count - R : 0;              // index into x[b] of the oldest sample kept
-        if (first + j >= count) continue;
-        const long long s = ROW(b, IDV_ROW_N_PREV) + first + j;
+        const long long j = e % n_max;
+        const SigRow r = ROWS ? load_row(rows, b) : lock;
+        const long long first = r.count > R ? r.count - R : 0;          // index into x[b] of the oldest sample kept
+        if (ROWS && first + j >= r.count) continue;
+        const long long s = r.n_prev + first + j;
         ring[(size_t)b * R + (size_t)(s % R)] = x[(size_t)b * ldx + (size_t)(first + j)];
     }
 }
 
-// stream_ola_kernel with the ranges, the carry parity and the output offset of each slot; the same sums in the same order
-__global__ void stream_ola_rows_kernel(const float* __restrict__ frames, int Tp, int Jp, float* __restrict__ carry, int cap,
-                                       const long long* __restrict__ rows, int B, int n_fft, int win, int hop, long long span_max,
-                                       float* __restrict__ y, long long ldy) {
+// padded positions P in [p_start, p_end), p_start = half + e0, at most span_max of them per row (lock-step: exactly): carried
+// partial sum (positions below p_start + carry_in) plus the frames t0 .. t0+k-1 in increasing t; P - half < e1 is final and
+// goes to y at y_off (times 1 / envelope as idv_make_dft computes it), the rest becomes the carry for positions from half + e1
+// on.  Lock-step: cin and cout_ are the carry read and the carry written.  ROWS: both are the [2][B][cap] carry, of which slot
+// b reads half parity_b and writes the other; a slot that sits the group out leaves its carry where it is.
+template <bool ROWS>
+__global__ void stream_ola_kernel(const float* __restrict__ frames, int Tp, int Jp, const float* cin, float* cout_, int cap, SigRow lock,
+                                  const long long* __restrict__ rows, int B, int n_fft, int win, int hop, long long span_max,
+                                  float* __restrict__ y, long long ldy) {
     const int left = (n_fft - win) / 2, half = n_fft / 2;
     const long long n = span_max * B;
     const double two_pi = 6.283185307179586476925286766559;
     for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
         const int b = (int)(e / span_max);
-        const long long e0 = ROW(b, IDV_ROW_E0), e1 = ROW(b, IDV_ROW_E1);
-        const int k = (int)ROW(b, IDV_ROW_K);
-        if (k == 0 && e0 == e1) continue;                               // the slot sits this group out: its carry stays where it is
-        const long long p_start = half + e0, p_new = half + e1;
+        const SigRow r = ROWS ? load_row(rows, b) : lock;
+        const int k = (int)r.k;
+        if (ROWS && k == 0 && r.e0 == r.e1) continue;
+        const long long p_start = half + r.e0, p_new = half + r.e1;
         const long long P = p_start + e % span_max;
-        if (P >= ROW(b, IDV_ROW_P_END)) continue;
-        const long long t0 = ROW(b, IDV_ROW_T0), T_total = ROW(b, IDV_ROW_T_TOTAL);
-        const int parity = (int)ROW(b, IDV_ROW_PARITY);
-        const float* cin = carry + (size_t)parity * B * cap;
-        float* cout_ = carry + (size_t)(1 - parity) * B * cap;
-        float v = (P - p_start < ROW(b, IDV_ROW_CARRY_IN)) ? cin[(size_t)b * cap + (size_t)(P - p_start)] : 0.f;
+        if (ROWS && P >= r.p_end) continue;
+        const float* ci = ROWS ? cin + (size_t)r.parity * B * cap : cin;
+        float* co = ROWS ? cout_ + (size_t)(1 - r.parity) * B * cap : cout_;
+        float v = (P - p_start < r.carry_in) ? ci[(size_t)b * cap + (size_t)(P - p_start)] : 0.f;
         for (int tl = 0; tl < k; ++tl) {
-            const long long i = P - (long long)hop * (t0 + tl) - left;
+            const long long i = P - (long long)hop * (r.t0 + tl) - left;
             if (i >= 0 && i < win) v += frames[(size_t)i * Jp + (size_t)b * Tp + 1 + tl];
         }
         if (P < p_new) {
+            // frames whose window covers P: P - win < hop*t + left <= P (at most ceil(win/hop) of them, wherever the stream is)
             double env = 0.0;
             long long t_hi = (P - left) / hop;
-            if (T_total >= 0 && t_hi > T_total - 1) t_hi = T_total - 1;
+            if (r.T_total >= 0 && t_hi > r.T_total - 1) t_hi = r.T_total - 1;
             long long t_lo = P - left - win >= 0 ? (P - left - win) / hop + 1 : 0;
             for (long long t = t_lo; t <= t_hi; ++t) {
                 const long long i = P - (long long)hop * t - left;
@@ -164,9 +118,9 @@ __global__ void stream_ola_rows_kernel(const float* __restrict__ frames, int Tp,
                 }
             }
             const float inv = env > 1e-11 ? (float)(1.0 / env) : 0.f;
-            y[(size_t)b * ldy + (size_t)(ROW(b, IDV_ROW_Y_OFF) + P - p_start)] = v * inv;
+            y[(size_t)b * ldy + (size_t)(r.y_off + P - p_start)] = v * inv;
         } else {
-            cout_[(size_t)b * cap + (size_t)(P - p_new)] = v;
+            co[(size_t)b * cap + (size_t)(P - p_new)] = v;
         }
     }
 }
@@ -180,7 +134,6 @@ __global__ void stream_zero_rows_kernel(float* __restrict__ buf, long long outer
         buf[((size_t)(r / inner) * B + (size_t)b) * inner + (size_t)(r % inner)] = 0.f;
     }
 }
-#undef ROW
 
 // ---- streaming.StreamingVAE: the Gaussian draws of the reparameterisation and the skips at batch B * ns
 
@@ -286,6 +239,7 @@ __global__ void stream_repeat_kernel(const float* __restrict__ x, const float* _
 }  // namespace
 
 static const long long* const no_rows = nullptr;      // the table argument of a lock-step instantiation, which never reads it
+static const SigRow no_row = {};                      // the by-value row of a ROWS instantiation, which loads its own from the table
 static float* const no_eps = nullptr;                 // the second pair of an instantiation without PAIR, which never writes it
 static const long long* const no_seeds = nullptr;     // the seed array of an instantiation without SEEDS, which never reads it
 
@@ -353,30 +307,50 @@ extern "C" int idv_stream_repeat_rows(const float* x, const float* hist, int C, 
     return idv_launch_status();
 }
 
+// The reach and range conditions of a row, shared by the scalar entries and idv_stream_rows_check: a table passes exactly when
+// the scalar entry would take each row's values.
+
+// every sample the frames t0 .. t0+k-1 (k > 0) read is in the ring or among the n_new samples of x; the start mirror is there
+static bool frames_in_reach(int R, long long n_prev, long long n_new, long long L_end, int n_fft, int win, int hop, long long t0,
+                            long long k) {
+    const int left = (n_fft - win) / 2, half = n_fft / 2;
+    const long long first = (long long)hop * t0 + left - half, last = (long long)hop * (t0 + k - 1) + left - half + win - 1;
+    const long long lo_read = first < 0 ? 0 : first;
+    const long long hi_read = (L_end >= 0 && last >= L_end) ? L_end - 1 : last;
+    return !(hi_read >= n_prev + n_new || (lo_read < n_prev && n_prev - lo_read > R) || (first < 0 && -first >= n_prev + n_new) ||
+             (first < 0 && n_prev > R));
+}
+
+// the overlap-add ranges: the final samples and the carried positions lie in [half + e0, p_end), the carry written fits cap, and
+// the last frame ends inside p_end
+static bool ola_in_range(int cap, int n_fft, int win, int hop, long long t0, long long k, long long e0, long long e1, long long p_end,
+                         long long carry_in) {
+    const int left = (n_fft - win) / 2, half = n_fft / 2;
+    return !(p_end < half + e1 || p_end - (half + e0) < carry_in || p_end - (half + e1) > cap ||
+             (k > 0 && (long long)hop * (t0 + k - 1) + left + win > p_end));
+}
+
 extern "C" int idv_stream_frames(const float* ring, int R, const float* x, long long ldx, int n_new, long long n_prev, long long L_end,
                                  int B, int n_fft, int win, int hop, long long t0, int k, float* frames, int Tp, int Jp, void* stream) {
     if (!ring || R <= 0 || (n_new > 0 && (!x || ldx < n_new)) || n_new < 0 || n_prev < 0 || B <= 0 || n_fft <= 0 || win <= 0 || win > n_fft ||
         hop <= 0 || t0 < 0 || k <= 0 || !frames || Tp < k + 1 || Jp < B * Tp)
         return IDV_EINVAL;
-    // every sample read must be in the ring or in x
-    const int left = (n_fft - win) / 2, half = n_fft / 2;
-    const long long first = (long long)hop * t0 + left - half, last = (long long)hop * (t0 + k - 1) + left - half + win - 1;
-    const long long lo_read = first < 0 ? 0 : first;
-    const long long hi_read = (L_end >= 0 && last >= L_end) ? L_end - 1 : last;
-    if (hi_read >= n_prev + n_new || (lo_read < n_prev && n_prev - lo_read > R) || (first < 0 && -first >= n_prev + n_new) ||
-        (first < 0 && n_prev > R))
-        return IDV_EINVAL;
-    hipLaunchKernelGGL(stream_frames_kernel, dim3(grid_of((long long)win * B * k)), dim3(256), 0, (hipStream_t)stream, ring, R, x,
-                       ldx, n_prev, L_end, B, n_fft, win, hop, t0, k, frames, Tp, Jp);
+    if (!frames_in_reach(R, n_prev, n_new, L_end, n_fft, win, hop, t0, k)) return IDV_EINVAL;
+    SigRow lock = {};
+    lock.n_prev = n_prev, lock.L_end = L_end, lock.t0 = t0, lock.k = k;
+    hipLaunchKernelGGL(stream_frames_kernel<false>, dim3(grid_of((long long)win * B * k)), dim3(256), 0, (hipStream_t)stream, ring, R, x,
+                       ldx, lock, no_rows, B, n_fft, win, hop, k, frames, Tp, Jp);
     return idv_launch_status();
 }
 
 extern "C" int idv_stream_ring(float* ring, int R, const float* x, long long ldx, int n_new, long long n_prev, int B, void* stream) {
     if (!ring || R <= 0 || n_new < 0 || (n_new > 0 && (!x || ldx < n_new)) || n_prev < 0 || B <= 0) return IDV_EINVAL;
     if (n_new == 0) return IDV_OK;
-    const long long s0 = (n_prev + n_new - R > n_prev) ? n_prev + n_new - R : n_prev;
-    hipLaunchKernelGGL(stream_ring_kernel, dim3(grid_of((n_prev + n_new - s0) * B)), dim3(256), 0, (hipStream_t)stream, ring, R, x,
-                       ldx, n_new, n_prev, s0, B);
+    const int n_max = n_new < R ? n_new : R;
+    SigRow lock = {};
+    lock.n_prev = n_prev, lock.count = n_new;
+    hipLaunchKernelGGL(stream_ring_kernel<false>, dim3(grid_of((long long)n_max * B)), dim3(256), 0, (hipStream_t)stream, ring, R, x, ldx,
+                       n_max, lock, no_rows, B);
     return idv_launch_status();
 }
 
@@ -387,14 +361,14 @@ extern "C" int idv_stream_ola(const float* frames, int Tp, int Jp, const float* 
         n_fft <= 0 || win <= 0 || win > n_fft || hop <= 0 || t0 < 0 || e1 < e0 || e0 < 0 || (e1 > e0 && !y) || y_off < 0 ||
         (k > 0 && (Tp < k + 1 || Jp < B * Tp)))
         return IDV_EINVAL;
-    const int left = (n_fft - win) / 2, half = n_fft / 2;
-    const long long p_start = half + e0;
-    if (p_end < half + e1 || p_end - p_start < carry_in_len || p_end - (half + e1) > cap || y_off + (e1 - e0) > ldy ||
-        (k > 0 && (long long)hop * (t0 + k - 1) + left + win > p_end))
-        return IDV_EINVAL;
+    if (!ola_in_range(cap, n_fft, win, hop, t0, k, e0, e1, p_end, carry_in_len) || y_off + (e1 - e0) > ldy) return IDV_EINVAL;
+    const long long p_start = n_fft / 2 + e0;
     if (p_end <= p_start) return IDV_OK;
-    hipLaunchKernelGGL(stream_ola_kernel, dim3(grid_of((p_end - p_start) * B)), dim3(256), 0, (hipStream_t)stream, frames, Tp, Jp,
-                       carry_in, carry_in_len, carry_out, cap, B, n_fft, win, hop, t0, k, T_total, e0, e1, p_end, y, ldy, y_off);
+    SigRow lock = {};
+    lock.t0 = t0, lock.k = k, lock.e0 = e0, lock.e1 = e1, lock.p_end = p_end, lock.carry_in = carry_in_len, lock.T_total = T_total,
+    lock.y_off = y_off;
+    hipLaunchKernelGGL(stream_ola_kernel<false>, dim3(grid_of((p_end - p_start) * B)), dim3(256), 0, (hipStream_t)stream, frames, Tp, Jp,
+                       carry_in, carry_out, cap, lock, no_rows, B, n_fft, win, hop, p_end - p_start, y, (long long)ldy);
     return idv_launch_status();
 }
 
@@ -405,7 +379,6 @@ extern "C" int idv_stream_rows_check(const long long* host_rows, int B, int R, i
     if (!host_rows || B <= 0 || R <= 0 || n_x < 0 || n_fft <= 0 || win <= 0 || win > n_fft || hop <= 0 || cap <= 0 || k_launch < 0 ||
         Tp < k_launch + 1 || ldy < 0 || span_max < 0)
         return IDV_EINVAL;
-    const int left = (n_fft - win) / 2, half = n_fft / 2;
     for (int b = 0; b < B; ++b) {
         const long long* r = host_rows + (size_t)b * IDV_STREAM_ROW_FIELDS;
         const long long n_prev = r[IDV_ROW_N_PREV], count = r[IDV_ROW_COUNT], L_end = r[IDV_ROW_L_END], t0 = r[IDV_ROW_T0],
@@ -414,19 +387,9 @@ extern "C" int idv_stream_rows_check(const long long* host_rows, int B, int R, i
         if (n_prev < 0 || count < 0 || count > n_x || L_end < -1 || t0 < 0 || k < 0 || k > k_launch || (parity != 0 && parity != 1) ||
             e0 < 0 || e1 < e0 || carry_in < 0 || carry_in > cap || y_off < 0 || y_off + (e1 - e0) > ldy || (L_end < 0) != (T_total < 0))
             return IDV_EINVAL;
-        if (k > 0) {   // every sample a frame reads is in the ring or in x[b, :count]; the start mirror is there (as idv_stream_frames)
-            const long long first = hop * t0 + left - half, last = hop * (t0 + k - 1) + left - half + win - 1;
-            const long long lo_read = first < 0 ? 0 : first;
-            const long long hi_read = (L_end >= 0 && last >= L_end) ? L_end - 1 : last;
-            if (hi_read >= n_prev + count || (lo_read < n_prev && n_prev - lo_read > R) || (first < 0 && -first >= n_prev + count) ||
-                (first < 0 && n_prev > R))
-                return IDV_EINVAL;
-        }
+        if (k > 0 && !frames_in_reach(R, n_prev, count, L_end, n_fft, win, hop, t0, k)) return IDV_EINVAL;    // x[b, :count]
         if (k == 0 && e0 == e1) continue;
-        const long long p_start = half + e0;                 // as idv_stream_ola
-        if (p_end < half + e1 || p_end - p_start < carry_in || p_end - (half + e1) > cap || p_end - p_start > span_max ||
-            (k > 0 && hop * (t0 + k - 1) + left + win > p_end))
-            return IDV_EINVAL;
+        if (!ola_in_range(cap, n_fft, win, hop, t0, k, e0, e1, p_end, carry_in) || p_end - (n_fft / 2 + e0) > span_max) return IDV_EINVAL;
     }
     return IDV_OK;
 }
@@ -436,8 +399,8 @@ extern "C" int idv_stream_frames_rows(const float* ring, int R, const float* x, 
     if (!ring || R <= 0 || ldx < 0 || !rows || B <= 0 || n_fft <= 0 || win <= 0 || win > n_fft || hop <= 0 || k_launch <= 0 || !frames ||
         Tp < k_launch + 1 || Jp < B * Tp)
         return IDV_EINVAL;
-    hipLaunchKernelGGL(stream_frames_rows_kernel, dim3(grid_of((long long)win * B * k_launch)), dim3(256), 0, (hipStream_t)stream, ring,
-                       R, x, ldx, rows, B, n_fft, win, hop, k_launch, frames, Tp, Jp);
+    hipLaunchKernelGGL(stream_frames_kernel<true>, dim3(grid_of((long long)win * B * k_launch)), dim3(256), 0, (hipStream_t)stream, ring,
+                       R, x, ldx, no_row, rows, B, n_fft, win, hop, k_launch, frames, Tp, Jp);
     return idv_launch_status();
 }
 
@@ -446,8 +409,8 @@ extern "C" int idv_stream_ring_rows(float* ring, int R, const float* x, long lon
     if (!ring || R <= 0 || n_x < 0 || (n_x > 0 && (!x || ldx < n_x)) || !rows || B <= 0) return IDV_EINVAL;
     if (n_x == 0) return IDV_OK;
     const int n_max = n_x < R ? n_x : R;
-    hipLaunchKernelGGL(stream_ring_rows_kernel, dim3(grid_of((long long)n_max * B)), dim3(256), 0, (hipStream_t)stream, ring, R, x, ldx,
-                       n_max, rows, B);
+    hipLaunchKernelGGL(stream_ring_kernel<true>, dim3(grid_of((long long)n_max * B)), dim3(256), 0, (hipStream_t)stream, ring, R, x, ldx,
+                       n_max, no_row, rows, B);
     return idv_launch_status();
 }
 
@@ -457,8 +420,8 @@ extern "C" int idv_stream_ola_rows(const float* frames, int Tp, int Jp, float* c
         hop <= 0 || span_max < 0 || ldy < 0 || (ldy > 0 && !y) || (k_launch > 0 && (Tp < k_launch + 1 || Jp < B * Tp)))
         return IDV_EINVAL;
     if (span_max == 0) return IDV_OK;
-    hipLaunchKernelGGL(stream_ola_rows_kernel, dim3(grid_of(span_max * B)), dim3(256), 0, (hipStream_t)stream, frames, Tp, Jp, carry, cap,
-                       rows, B, n_fft, win, hop, span_max, y, ldy);
+    hipLaunchKernelGGL(stream_ola_kernel<true>, dim3(grid_of(span_max * B)), dim3(256), 0, (hipStream_t)stream, frames, Tp, Jp, carry, carry,
+                       cap, no_row, rows, B, n_fft, win, hop, span_max, y, ldy);
     return idv_launch_status();
 }
 

@@ -395,6 +395,17 @@ class _StreamBase:
              p(cp.fold), p(cp.slope), out, p(hist_out), x0hist_out, p(self.work), i(cp.nsplit), i(1 if cp.transposed else 0),
              i(cp.Cout), i(cp.Fin), i(B), i(k), i(Tp), i(Jp), stream_ptr())
 
+    def _conv_call_rows(self, cp: _ConvPack, x0, h0, x1, h1, out, hist, x0hist, B, k, Tp, Jp, rows):
+        """The sessions form: the [2][...] histories whole (row b reads half parity_b and writes the other) and the table."""
+        if cp.engine == "mfma":                  # two literal call sites, as in _conv_call
+            call("idv_stream_cconv_mfma_rows", x0, p(h0), i(cp.C0), x1 if x1 is not None else p(None), p(h1), i(cp.C1), p(cp.w),
+                 p(cp.bias), p(cp.fold), p(cp.slope), out, p(hist), p(x0hist), p(self.work), i(cp.nsplit),
+                 i(1 if cp.transposed else 0), i(cp.Cout), i(cp.Fin), i(B), i(k), i(Tp), i(Jp), rows, stream_ptr())
+            return
+        call("idv_stream_cconv_rows", x0, p(h0), i(cp.C0), x1 if x1 is not None else p(None), p(h1), i(cp.C1), p(cp.w), p(cp.bias),
+             p(cp.fold), p(cp.slope), out, p(hist), p(x0hist), p(self.work), i(cp.nsplit), i(1 if cp.transposed else 0), i(cp.Cout),
+             i(cp.Fin), i(B), i(k), i(Tp), i(Jp), rows, stream_ptr())
+
     # ------------------------------------------------------------------ the lock-step signal ends (scalars, one StreamPlan)
     @staticmethod
     def _pitched(x: torch.Tensor, B: int):
@@ -650,15 +661,23 @@ class StreamingDCCRN(_Streamer):
 
 
 class _Slots:
-    """What both sessions classes share on top of their streamer (``self.B`` slots): the per-slot host plan, ``positions``,
-    ``drop`` / ``reset``, the one pinned copy that takes a call's tables to the device, and the zeroing of the slots that end.
-    ``self._zero_views`` lists the state buffers as (buffer, outer, inner) of a [outer][slots][inner] view."""
+    """What every sessions class shares (``self.B`` slots on ``self.device``): the per-slot host plan ``self.sessions``,
+    ``positions``, ``drop`` / ``reset``, the one pinned copy that takes a call's tables to the device, and the zeroing of the
+    slots that end; ``self._zero_views`` lists the state buffers as (buffer, outer, inner) of a [outer][slots][inner] view.
+    For the sessions classes of the network, mixed in in front of their streamer: ``push``, written once, and the framing.  Such
+    a class supplies what differs: ``_tables`` (the host layout of a call's tables), ``_launch`` (what its network needs of a
+    launch group), ``_ola_site`` (where the overlap-add runs) and ``_finish`` (what follows it)."""
 
     def _init_slots(self):
+        """The plan and the tables of a network's sessions: one row table (ROW_FIELDS) per launch group."""
         if int(L.lib().idv_stream_row_fields()) != NF:
             raise L.IdvError("libidccrn_hip.so and streaming.ROW_FIELDS disagree about the row table")
-        self.sessions = SessionPlan(self.B, self.n_fft, self.hop, self.win, self.cap)
-        self._table = None          # device int64 buffer of the call's tables
+        self._init_tables(SessionPlan(self.B, self.n_fft, self.hop, self.win, self.cap), 4 * self.B * NF)
+
+    def _init_tables(self, sessions, table_min: int = 0):
+        self.sessions = sessions    # the host plan: positions, snapshot / restore, push(counts, end), drop(slots)
+        self._table_min = table_min
+        self._table = None          # device int64 buffer of the call's tables; it only grows
         self._staging = []          # [(pinned int64 buffer, event of the copy that last read it)] * 2
         self._turn = 0
 
@@ -687,7 +706,7 @@ class _Slots:
         """One host-to-device copy of a call's tables through a pinned staging buffer."""
         n = host.numel()
         if self._table is None or self._table.numel() < n:
-            size = max(1 << (n - 1).bit_length(), 4 * self.B * NF)
+            size = max(1 << (n - 1).bit_length(), self._table_min)
             self._table = torch.empty(size, dtype=torch.int64, device=self.device)
             self._staging = [(torch.empty(size, dtype=torch.int64).pin_memory(), torch.cuda.Event()) for _ in range(2)]
         stage, ev = self._staging[self._turn]
@@ -702,6 +721,70 @@ class _Slots:
         if n:
             for buf, outer, inner in self._zero_views:
                 call("idv_stream_zero_rows", p(buf), ll(outer), i(self.B), ll(inner), slots_ptr, i(n), stream_ptr())
+
+    # ------------------------------------------------------------------ push of a network's sessions
+    def push(self, x: torch.Tensor, counts=None, end=()):
+        check_input(x, self.B, self.device)
+        n = int(x.shape[1])
+        counts = check_counts(counts, self.B, n)
+        end = check_slots(end, self.B)
+        snap = self.sessions.snapshot()
+        plan = self.sessions.push(counts, end)
+        B, R, cap = self.B, self.plan.ring, self.plan.carry_cap
+        ldy = max(plan.m)
+        x, ldx, _ = self._pitched(x, B)
+        ints, per = self._tables(plan)               # per: the ints of one launch group, its slots' table [B][NF] first
+        host = torch.tensor(ints, dtype=torch.int64)
+        for gi, g in enumerate(plan.groups):         # a bad table never reaches a kernel
+            rc = L.lib().idv_stream_rows_check(L._P(host.data_ptr() + 8 * gi * per), B, R, 0 if g.flush else n, self.n_fft, self.win,
+                                               self.hop, cap, g.k, g.k + 1, ldy, g.span)
+            if rc != 0:
+                self.sessions.restore(snap)
+                raise L.IdvError(f"idv_stream_rows_check refused the table of launch group {gi} (status {rc})")
+        with torch.cuda.device(self.device):
+            s = stream_ptr()
+            rows_y, frames, side = self._ola_site()
+            y = torch.zeros(rows_y, ldy, dtype=torch.float32, device=self.device)
+            if plan.groups or plan.zero:
+                table = self._upload(host).data_ptr()
+                zero = table + 8 * len(plan.groups) * per
+                ring_due = any(counts)
+                for gi, g in enumerate(plan.groups):
+                    if g.flush and ring_due:         # the flush phase reads this call's samples from the ring
+                        call("idv_stream_ring_rows", p(self.ring), i(R), p(x), ll(ldx), i(n), L._P(table), i(B), s)
+                        ring_due = False
+                    c = self._launch(g, table + 8 * gi * per, zero + 8 * len(plan.zero))
+                    if g.k > 0:
+                        self._network(c, (None, 0) if g.flush else (x if n else None, ldx))
+                    Tp = g.k + 1
+                    call("idv_stream_ola_rows", frames.ptr() if g.k > 0 else p(None), i(Tp), i(Planar.jp_for(rows_y, Tp)),
+                         p(self.carry), i(cap), getattr(c, side), i(rows_y), i(self.n_fft), i(self.win), i(self.hop), i(g.k),
+                         ll(g.span), p(y) if ldy else p(None), ll(ldy), s)
+                if ring_due:
+                    call("idv_stream_ring_rows", p(self.ring), i(R), p(x), ll(ldx), i(n), L._P(table), i(B), s)
+                self._zero(L._P(zero), len(plan.zero))
+            return self._finish(y, ldy), plan.m
+
+    def _tables(self, plan: SessionCall):
+        """(the ints of the one copy a call makes, the ints per launch group): the groups' tables, then the slots to zero."""
+        return [v for g in plan.groups for r in g.rows for v in r] + plan.zero, self.B * NF
+
+    def _launch(self, g: Group, tables: int, behind: int):
+        """What the network needs of launch group g, whose tables start at device address ``tables``; ``behind`` is the address
+        behind the slots to zero."""
+        return _Launch(g.k, L._P(tables))
+
+    def _ola_site(self):
+        """Where the overlap-add runs: (rows of y, the Planar of the inverse-DFT frames, the launch's table of those rows)."""
+        return self.B, self.ifr, "rows"
+
+    def _finish(self, y: torch.Tensor, ldy: int) -> torch.Tensor:
+        return y
+
+    def _frames(self, c, io, frames, Tp: int, Jp: int):
+        x, ldx = io
+        call("idv_stream_frames_rows", p(self.ring), i(self.plan.ring), p(x), ll(ldx), c.rows, i(self.B), i(self.n_fft), i(self.win),
+             i(self.hop), i(c.k), frames, i(Tp), i(Jp), stream_ptr())
 
 
 class StreamingSessions(_Slots, _Streamer):
@@ -732,66 +815,9 @@ class StreamingSessions(_Slots, _Streamer):
         self._zero_views = [(self.ring, 1, self.plan.ring), (self.carry, 2, self.plan.carry_cap), (self.lstm_state, 16, self.H)]
         self._zero_views += [(h, h.numel() // slots, 1) for h in [self.h_in, self.h_dense] + self.h_enc + self.h_dec]
 
-    # ------------------------------------------------------------------ push / drop
-    def push(self, x: torch.Tensor, counts=None, end=()):
-        check_input(x, self.B, self.device)
-        n = int(x.shape[1])
-        counts = check_counts(counts, self.B, n)
-        end = check_slots(end, self.B)
-        snap = self.sessions.snapshot()
-        plan = self.sessions.push(counts, end)
-        ldy = max(plan.m)
-        x = x.float()
-        if (n > 1 and x.stride(1) != 1) or (self.B > 1 and x.stride(0) < n):       # the pitch rules of StreamingDCCRN.push
-            x = x.contiguous()
-        ldx = x.stride(0) if self.B > 1 else n
-        cap = self.plan.carry_cap
-        host = torch.tensor([v for g in plan.groups for r in g.rows for v in r] + plan.zero, dtype=torch.int64)
-        for gi, g in enumerate(plan.groups):         # a bad table never reaches a kernel
-            rc = L.lib().idv_stream_rows_check(L._P(host.data_ptr() + 8 * gi * self.B * NF), self.B, self.plan.ring,
-                                               0 if g.flush else n, self.n_fft, self.win, self.hop, cap, g.k, g.k + 1, ldy, g.span)
-            if rc != 0:
-                self.sessions.restore(snap)
-                raise L.IdvError(f"idv_stream_rows_check refused the table of launch group {gi} (status {rc})")
-        with torch.cuda.device(self.device):
-            s = stream_ptr()
-            y = torch.zeros(self.B, ldy, dtype=torch.float32, device=self.device)
-            if host.numel() == 0:
-                return y, plan.m
-            table = self._upload(host)
-            rows_of = lambda gi: L._P(table.data_ptr() + 8 * gi * self.B * NF)
-            ring_due = any(counts)
-            for gi, g in enumerate(plan.groups):
-                if g.flush and ring_due:             # the flush phase reads this call's samples from the ring
-                    call("idv_stream_ring_rows", p(self.ring), i(self.plan.ring), p(x), ll(ldx), i(n), rows_of(0), i(self.B), s)
-                    ring_due = False
-                c = _Launch(g.k, rows_of(gi))
-                if g.k > 0:
-                    self._network(c, (None, 0) if g.flush else (x if n else None, ldx))
-                Tp = g.k + 1
-                call("idv_stream_ola_rows", self.ifr.ptr() if g.k > 0 else p(None), i(Tp), i(Planar.jp_for(self.B, Tp)), p(self.carry),
-                     i(cap), c.rows, i(self.B), i(self.n_fft), i(self.win), i(self.hop), i(g.k), ll(g.span), p(y) if ldy else p(None),
-                     ll(ldy), s)
-            if ring_due:
-                call("idv_stream_ring_rows", p(self.ring), i(self.plan.ring), p(x), ll(ldx), i(n), rows_of(0), i(self.B), s)
-            self._zero(L._P(table.data_ptr() + 8 * len(plan.groups) * self.B * NF), len(plan.zero))
-        return y, plan.m
-
     # ------------------------------------------------------------------ the per-row kernels of the network
-    def _frames(self, c, io, frames, Tp: int, Jp: int):
-        x, ldx = io
-        call("idv_stream_frames_rows", p(self.ring), i(self.plan.ring), p(x), ll(ldx), c.rows, i(self.B), i(self.n_fft), i(self.win),
-             i(self.hop), i(c.k), frames, i(Tp), i(Jp), stream_ptr())
-
     def _block(self, cp: _ConvPack, c, x0, h0, x1, h1, out, hist, x0hist, Tp: int, Jp: int):
-        if cp.engine == "mfma":                  # two literal call sites, as in StreamingDCCRN._conv_call
-            call("idv_stream_cconv_mfma_rows", x0, p(h0), i(cp.C0), x1 if x1 is not None else p(None), p(h1), i(cp.C1), p(cp.w),
-                 p(cp.bias), p(cp.fold), p(cp.slope), out, p(hist), p(x0hist), p(self.work), i(cp.nsplit),
-                 i(1 if cp.transposed else 0), i(cp.Cout), i(cp.Fin), i(self.B), i(c.k), i(Tp), i(Jp), c.rows, stream_ptr())
-            return
-        call("idv_stream_cconv_rows", x0, p(h0), i(cp.C0), x1 if x1 is not None else p(None), p(h1), i(cp.C1), p(cp.w), p(cp.bias),
-             p(cp.fold), p(cp.slope), out, p(hist), p(x0hist), p(self.work), i(cp.nsplit), i(1 if cp.transposed else 0), i(cp.Cout),
-             i(cp.Fin), i(self.B), i(c.k), i(Tp), i(Jp), c.rows, stream_ptr())
+        self._conv_call_rows(cp, x0, h0, x1, h1, out, hist, x0hist, self.B, c.k, Tp, Jp, c.rows)
 
     def _lstm(self, c, out, Tp: int, Jp: int):
         call("idv_stream_clstm_rows", p(self.G), p(self.lstm_wt), p(self.lstm_b1), p(self.lstm_state), p(self.hout), out, i(self.H),
@@ -1566,74 +1592,31 @@ class StreamingVAESessions(_Slots, _VAEStreamer):
 
     # ------------------------------------------------------------------ push
     def push(self, x: torch.Tensor, counts=None, end=()):
-        check_input(x, self.B, self.device)
-        n = int(x.shape[1])
-        counts = check_counts(counts, self.B, n)
-        end = check_slots(end, self.B)
-        snap = self.sessions.snapshot()
-        plan = self.sessions.push(counts, end)
-        B, Bn, ns = self.B, self.Bn, self.ns
-        ldy = max(plan.m)
-        x = x.float()
-        if (n > 1 and x.stride(1) != 1) or (B > 1 and x.stride(0) < n):            # the pitch rules of StreamingDCCRN.push
-            x = x.contiguous()
-        ldx = x.stride(0) if B > 1 else n
-        cap = self.plan.carry_cap
-        per = (B + Bn) * NF                          # a group's two tables: [B][NF], then [B * ns][NF]
-        host = torch.tensor(vae_session_tables(plan, ns, self.seeds), dtype=torch.int64)
-        for gi, g in enumerate(plan.groups):         # a bad table never reaches a kernel
-            rc = L.lib().idv_stream_rows_check(L._P(host.data_ptr() + 8 * gi * per), B, self.plan.ring, 0 if g.flush else n,
-                                               self.n_fft, self.win, self.hop, cap, g.k, g.k + 1, ldy, g.span)
-            if rc != 0:
-                self.sessions.restore(snap)
-                raise L.IdvError(f"idv_stream_rows_check refused the table of launch group {gi} (status {rc})")
-        with torch.no_grad(), torch.cuda.device(self.device):
-            s = stream_ptr()
-            # the overlap-add runs on the decoder side's rows (one per sample) or, behind an estimator, on the slots' rows
-            rows_y, frames = (Bn, self.ifr) if self._per_sample else (B, self.ifr_b)
-            y = torch.zeros(rows_y, ldy, dtype=torch.float32, device=self.device)
-            if plan.groups or plan.zero:
-                table = self._upload(host)
-                rows_of = lambda gi: L._P(table.data_ptr() + 8 * gi * per)
-                seeds = L._P(table.data_ptr() + 8 * (len(plan.groups) * per + len(plan.zero)))
-                ring_due = any(counts)
-                for gi, g in enumerate(plan.groups):
-                    if g.flush and ring_due:         # the flush phase reads this call's samples from the ring
-                        call("idv_stream_ring_rows", p(self.ring), i(self.plan.ring), p(x), ll(ldx), i(n), rows_of(0), i(B), s)
-                        ring_due = False
-                    c = _VAELaunch(g.k, rows_of(gi), L._P(table.data_ptr() + 8 * (gi * per + B * NF)), seeds)
-                    if g.k > 0:
-                        self._network(c, (None, 0) if g.flush else (x if n else None, ldx))
-                    Tp = g.k + 1
-                    call("idv_stream_ola_rows", frames.ptr() if g.k > 0 else p(None), i(Tp), i(Planar.jp_for(rows_y, Tp)),
-                         p(self.carry), i(cap), c.rows_n if self._per_sample else c.rows, i(rows_y), i(self.n_fft), i(self.win),
-                         i(self.hop), i(g.k), ll(g.span), p(y) if ldy else p(None), ll(ldy), s)
-                if ring_due:
-                    call("idv_stream_ring_rows", p(self.ring), i(self.plan.ring), p(x), ll(ldx), i(n), rows_of(0), i(B), s)
-                self._zero(L._P(table.data_ptr() + 8 * len(plan.groups) * per), len(plan.zero))
-            if not (self._per_sample and self.average):
-                return y, plan.m
-            out = torch.zeros(B, ldy, dtype=torch.float32, device=self.device)
-            if ldy:
-                call("idv_mean_over_samples", p(y), i(ns), i(B), i(ldy), p(out), s)
-        return out, plan.m
+        with torch.no_grad():
+            return super().push(x, counts, end)
+
+    def _tables(self, plan: SessionCall):
+        return vae_session_tables(plan, self.ns, self.seeds), (self.B + self.Bn) * NF
+
+    def _launch(self, g: Group, tables: int, behind: int):
+        return _VAELaunch(g.k, L._P(tables), L._P(tables + 8 * self.B * NF), L._P(behind))       # the seeds lie behind the zero list
+
+    def _ola_site(self):
+        # the overlap-add runs on the decoder side's rows (one per sample) or, behind an estimator, on the slots' rows
+        return (self.Bn, self.ifr, "rows_n") if self._per_sample else (self.B, self.ifr_b, "rows")
+
+    def _finish(self, y: torch.Tensor, ldy: int) -> torch.Tensor:
+        if not (self._per_sample and self.average):
+            return y
+        out = torch.zeros(self.B, ldy, dtype=torch.float32, device=self.device)
+        if ldy:
+            call("idv_mean_over_samples", p(y), i(self.ns), i(self.B), i(ldy), p(out), stream_ptr())
+        return out
 
     # ------------------------------------------------------------------ the per-row kernels of the network
-    def _frames(self, c, io, frames, Tp: int, Jp: int):
-        x, ldx = io
-        call("idv_stream_frames_rows", p(self.ring), i(self.plan.ring), p(x), ll(ldx), c.rows, i(self.B), i(self.n_fft), i(self.win),
-             i(self.hop), i(c.k), frames, i(Tp), i(Jp), stream_ptr())
-
     def _block(self, cp: _ConvPack, c, x0, h0, x1, h1, out, hist, x0hist, Tp: int, Jp: int, dec: bool):
         B, rows = (self.Bn, c.rows_n) if dec else (self.B, c.rows)
-        if cp.engine == "mfma":                  # two literal call sites, as in _StreamBase._conv_call
-            call("idv_stream_cconv_mfma_rows", x0, p(h0), i(cp.C0), x1 if x1 is not None else p(None), p(h1), i(cp.C1), p(cp.w),
-                 p(cp.bias), p(cp.fold), p(cp.slope), out, p(hist), p(x0hist), p(self.work), i(cp.nsplit),
-                 i(1 if cp.transposed else 0), i(cp.Cout), i(cp.Fin), i(B), i(c.k), i(Tp), i(Jp), rows, stream_ptr())
-            return
-        call("idv_stream_cconv_rows", x0, p(h0), i(cp.C0), x1 if x1 is not None else p(None), p(h1), i(cp.C1), p(cp.w), p(cp.bias),
-             p(cp.fold), p(cp.slope), out, p(hist), p(x0hist), p(self.work), i(cp.nsplit), i(1 if cp.transposed else 0), i(cp.Cout),
-             i(cp.Fin), i(B), i(c.k), i(Tp), i(Jp), rows, stream_ptr())
+        self._conv_call_rows(cp, x0, h0, x1, h1, out, hist, x0hist, B, c.k, Tp, Jp, rows)
 
     def _lstm(self, c, out, Tp: int, Jp: int):
         call("idv_stream_clstm_wide_rows", p(self.G), p(self.lstm_wt), p(self.lstm_b1), p(self.lstm_state), p(self.hstep), out,
@@ -1908,7 +1891,7 @@ class StreamingResampler:
         self.plan.advance(periods)
 
 
-class StreamingResamplerSessions:
+class StreamingResamplerSessions(_Slots):
     """Streaming resampler for ``slots`` independent signals in one batch, with the contract of :class:`StreamingSessions`.
 
         rs = StreamingResamplerSessions(44100, 16000, slots)
@@ -1934,50 +1917,16 @@ class StreamingResamplerSessions:
         self.device = _check_device("StreamingResamplerSessions", device)
         if int(L.lib().idv_stream_resample_row_fields()) != len(ops.SR_ROW_FIELDS):
             raise L.IdvError("libidccrn_hip.so and ops.SR_ROW_FIELDS disagree about the row table")
-        self.sessions = ResampleSessionPlan(slots, up, down)
+        self._init_tables(ResampleSessionPlan(slots, up, down))
         self.H = self.sessions.H
         self.hist = torch.zeros(2, slots, self.H, dtype=torch.float32, device=self.device)
+        self._zero_views = [(self.hist, 2, self.H)]
         ops.resample_taps(up, down, self.device)
-        self._table = None          # device int64 buffer of a call's table and zero list
-        self._staging = []          # [(pinned int64 buffer, event of the copy that last read it)] * 2, as _Slots._upload
-        self._turn = 0
-
-    @property
-    def positions(self) -> List[int]:
-        return self.sessions.positions
 
     def reset(self):
         """Zero every slot's history and bookkeeping."""
         self.hist.zero_()
         self.sessions.drop(range(self.B))
-
-    def _upload(self, host: torch.Tensor) -> torch.Tensor:
-        n = host.numel()
-        if self._table is None or self._table.numel() < n:
-            size = 1 << (n - 1).bit_length()
-            self._table = torch.empty(size, dtype=torch.int64, device=self.device)
-            self._staging = [(torch.empty(size, dtype=torch.int64).pin_memory(), torch.cuda.Event()) for _ in range(2)]
-        stage, ev = self._staging[self._turn]
-        self._turn ^= 1
-        ev.synchronize()            # the copy that read this buffer two calls ago
-        stage[:n].copy_(host)
-        self._table[:n].copy_(stage[:n], non_blocking=True)
-        ev.record()
-        return self._table
-
-    def _zero(self, slots_ptr, n: int):
-        if n:
-            call("idv_stream_zero_rows", p(self.hist), ll(2), i(self.B), ll(self.H), slots_ptr, i(n), stream_ptr())
-
-    def drop(self, slots):
-        """Abandon the signals of these slots: nothing is returned for them and their history is zeroed."""
-        slots = check_slots(slots, self.B)
-        if not slots:
-            return
-        self.sessions.drop(slots)
-        with torch.cuda.device(self.device):
-            table = self._upload(torch.tensor(slots, dtype=torch.int64))
-            self._zero(L._P(table.data_ptr()), len(slots))
 
     def check(self, x, counts, end):
         """Every guard of a push (host only; nothing changes) -> (counts, end) as lists."""

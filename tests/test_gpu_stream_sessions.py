@@ -337,3 +337,119 @@ def test_frames_and_ola_rows_entries_far_apart():
         assert torch.equal(carry[1 - par[b], b, :nc], cout[b, :nc]), b
         assert torch.equal(carry[par[b], b], carry_before[par[b], b]), b
     assert bool(torch.isfinite(y).all()) and not bool(y[0, :3].any())
+
+
+def _ring_case(seed=21):
+    """R = 512, four slots: nothing new; 37 samples from the last ring cell on (the write wraps); a full ring 256 million
+    samples into the signal; more samples than the ring holds.  x is NaN at and past count[b] -> (rows, ring, x)."""
+    _, S, _, _ = _mods()
+    B, R, n = 4, NFFT, 600
+    count = [0, 37, 512, 557]
+    n_prev = [300, 511, 12800 * 20000 + 300, 0]
+    g = torch.Generator().manual_seed(seed)
+    ring = torch.randn(B, R, generator=g)
+    x = torch.randn(B, n, generator=g)
+    for b in range(B):
+        x[b, count[b]:] = float("nan")
+    return _rows(S, B, n_prev=n_prev, count=count), ring, x
+
+
+def _ring_entries(rows, ring, x):
+    """idv_stream_ring_rows on the table -> the ring; idv_stream_ring with row b's n_new = count_b and n_prev_b on a clone,
+    for every b -> row b of each (the other rows of such a call take row b's ranges over their own x, NaN included)."""
+    _, S, _, L = _mods()
+    B, R = ring.shape
+    n = x.shape[1]
+    ring, x = ring.cuda(), x.cuda()
+    got = ring.clone()
+    L.call("idv_stream_ring_rows", L.p(got), L.i(R), L.p(x), L.ll(n), L.i(n), L.p(rows.cuda()), L.i(B), L.stream_ptr())
+    want = []
+    for b in range(B):
+        r = ring.clone()
+        L.call("idv_stream_ring", L.p(r), L.i(R), L.p(x), L.ll(n), L.i(int(rows[b, S.ROW_FIELDS.index("count")])),
+               L.ll(int(rows[b, S.ROW_FIELDS.index("n_prev")])), L.i(B), L.stream_ptr())
+        want.append(r[b])
+    return got, torch.stack(want)
+
+
+def test_ring_rows_entry_equals_the_lockstep_entry():
+    """Counts 0, 37, 512 and 557 at a ring of 512 in one table (a wrap inside the write, a far position, a write that starts on
+    the last ring cell, more samples than cells): row b equals the scalar entry run with that row's values."""
+    rows, ring, x = _ring_case()
+    got, want = _ring_entries(rows, ring, x)
+    assert torch.equal(got, want)
+    assert torch.equal(got[0], ring[0].cuda())                                 # count 0: untouched
+    assert not torch.equal(got[1:], ring[1:].cuda())
+    assert bool(torch.isfinite(got).all())
+
+
+def _signal_end_entries(c):
+    """The six signal-end entries on one stored case ``c``: ``rows`` [B][NF], ``ring`` [B][R], ``x`` [B][n] (n may be 0),
+    ``ifr`` [WIN][Jp], ``carry`` [2][B][cap], ``ldy``, ``span``.  The rows entries run once on the table; the scalar entries run
+    once per slot with that slot's values, and what such a run gives for row b is put where the rows entry puts it
+    (test_frames_and_ola_rows_entries_far_apart) -> frames [2][WIN][Jp], y [2][B][ldy], carry [2][2][B][cap]: index 0 from the
+    rows entries, index 1 from the scalar ones."""
+    _, S, _, L = _mods()
+    rows = torch.as_tensor(c["rows"])
+    f = lambda name: [int(v) for v in rows[:, S.ROW_FIELDS.index(name)]]
+    ring, x, ifr, carry0 = (torch.as_tensor(c[k]).cuda() for k in ("ring", "x", "ifr", "carry"))
+    ldy, span = int(c["ldy"]), int(c["span"])
+    (B, R), n, cap, half = ring.shape, x.shape[1], carry0.shape[2], NFFT // 2
+    k, t0, e0, e1, p_end, par, y_off = f("k"), f("t0"), f("e0"), f("e1"), f("p_end"), f("parity"), f("y_off")
+    KL, Tp, Jp = max(k), max(k) + 1, ifr.shape[1]
+    xp = L.p(x) if n else L.p(None)
+    rows_d = rows.cuda()
+    fr = torch.zeros(2, WIN, Jp, device="cuda")
+    y = torch.zeros(2, B, ldy, device="cuda")
+    carry = torch.stack([carry0, carry0])
+    L.call("idv_stream_frames_rows", L.p(ring), L.i(R), xp, L.ll(n), L.p(rows_d), L.i(B), L.i(NFFT), L.i(WIN), L.i(HOP), L.i(KL),
+           L.p(fr[0]), L.i(Tp), L.i(Jp), L.stream_ptr())
+    L.call("idv_stream_ola_rows", L.p(ifr), L.i(Tp), L.i(Jp), L.p(carry[0]), L.i(cap), L.p(rows_d), L.i(B), L.i(NFFT), L.i(WIN),
+           L.i(HOP), L.i(KL), L.ll(span), L.p(y[0]), L.ll(ldy), L.stream_ptr())
+    for b in range(B):
+        kb, Tb, m = k[b], k[b] + 1, e1[b] - e0[b]
+        Jb = (B * Tb + 3) // 4 * 4
+        sfr = torch.zeros(WIN, Jb, device="cuda")
+        L.call("idv_stream_frames", L.p(ring), L.i(R), xp, L.ll(n), L.i(f("count")[b]), L.ll(f("n_prev")[b]), L.ll(f("L_end")[b]),
+               L.i(B), L.i(NFFT), L.i(WIN), L.i(HOP), L.ll(t0[b]), L.i(kb), L.p(sfr), L.i(Tb), L.i(Jb), L.stream_ptr())
+        fr[1, :, b * Tp + 1:b * Tp + 1 + kb] = sfr[:, b * Tb + 1:b * Tb + 1 + kb]
+        sifr = torch.zeros(WIN, Jb, device="cuda")
+        sifr[:, b * Tb + 1:b * Tb + 1 + kb] = ifr[:, b * Tp + 1:b * Tp + 1 + kb]
+        sy = torch.zeros(B, m, device="cuda")
+        cout = torch.zeros(B, cap, device="cuda")
+        L.call("idv_stream_ola", L.p(sifr), L.i(Tb), L.i(Jb), L.p(carry0[par[b]].contiguous()), L.i(f("carry_in")[b]), L.p(cout),
+               L.i(cap), L.i(B), L.i(NFFT), L.i(WIN), L.i(HOP), L.ll(t0[b]), L.i(kb), L.ll(f("T_total")[b]), L.ll(e0[b]), L.ll(e1[b]),
+               L.ll(p_end[b]), L.p(sy), L.i(m), L.ll(0), L.stream_ptr())
+        nc = p_end[b] - (half + e1[b])
+        y[1, b, y_off[b]:y_off[b] + m] = sy[b]
+        carry[1, 1 - par[b], b, :nc] = cout[b, :nc]
+    return {"frames": fr, "y": y, "carry": carry}
+
+
+SIGNAL_END_CASES = ("far", "flush")      # test_frames_and_ola_rows_entries_far_apart's inputs; the end of a signal of 737 samples
+
+
+def _replay_signal_ends(d):
+    """Every output of the six signal-end entries for the inputs stored in ``d`` -> {"<case>.<name>": tensor}."""
+    out = {}
+    for case in SIGNAL_END_CASES:
+        c = {key[len(case) + 4:]: d[key] for key in d.files if key.startswith(case + ".in.")}
+        out.update({f"{case}.{name}": v for name, v in _signal_end_entries(c).items()})
+    out["ring.ring"] = torch.stack(_ring_entries(*(torch.as_tensor(d[f"ring.in.{k}"]) for k in ("rows", "ring", "x"))))
+    return out
+
+
+def test_signal_end_entries_give_the_recorded_bits(golden):
+    """tests/golden/stream_io_parent.npz holds inputs and the outputs of idv_stream_frames / _ring / _ola and their _rows forms
+    as the kernels gave them on the MI355X while each form had a kernel body of its own: the shared bodies give the same bits
+    (the same sums in the same order; the envelope's device cos is not reproducible on a host, so no CPU reference pins this).
+    The flush case has L_end / T_total set and an odd tail, so the end mirror and the clipped envelope are in it."""
+    d = golden("stream_io_parent")
+    out = _replay_signal_ends(d)
+    recorded = sorted(key for key in d.files if ".in." not in key)
+    assert recorded == sorted(out) and len(recorded) == 2 * 3 + 1          # per case frames, y, carry: rows and scalar forms
+    for name in recorded:
+        want = torch.as_tensor(d[name]).cuda()
+        assert bool(torch.isfinite(want).all()) and torch.equal(out[name], want), name
+    flush = d["flush.in.rows"]
+    assert (flush[:, 2] == 737).all() and (flush[:, 10] == 8).all()             # L_end, T_total

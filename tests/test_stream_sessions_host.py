@@ -270,3 +270,51 @@ def test_rows_check_accepts_the_plan_and_refuses_each_corruption():
     assert _check(g.rows, args[0], g.k, args[2], args[3], Tp=g.k) == einval, "k over Tp - 1"
     assert _check(g.rows, args[0], g.k - 1, args[2], args[3], Tp=g.k + 1) == einval, "k_b over k_launch"
     assert _check(g.rows, args[0], g.k, args[2], args[3] - 1) == einval, "span over span_max"
+
+
+def test_scalar_entries_refuse_what_rows_check_refuses():
+    """The reach conditions of idv_stream_frames and the range conditions of idv_stream_ola are the ones idv_stream_rows_check
+    holds a row to: a single-row table with one of them broken is refused, and so is the scalar entry given the same values.
+    Refusals only (they come before any launch, so any non-null pointer will do); the tables that pass go to the check alone."""
+    einval, cap, big = -1, N_FFT + WIN, 10 ** 6
+    lib = LIB.lib()
+    mem = torch.zeros(4)
+    ptr = mem.data_ptr()
+    pl = S.StreamPlan(N_FFT, HOP, WIN)
+    pl.push(700)
+    (c,) = pl.push(WIDTH)                            # mid-signal: frames 6 and 7, 300 carried positions in and out
+    assert (c.t0, c.k, c.e0, c.e1, c.p_end, c.carry_in) == (6, 2, 400, 600, 1156, 300)
+    mid = dict(n_prev=700, count=WIDTH, L_end=-1, t0=c.t0, k=c.k, parity=c.parity, e0=c.e0, e1=c.e1, p_end=c.p_end,
+               carry_in=c.carry_in, T_total=-1, y_off=0)
+    head = dict(n_prev=0, count=201, L_end=-1, t0=0, k=1, parity=0, e0=0, e1=0, p_end=LEFT + WIN, carry_in=0, T_total=-1, y_off=0)
+    no_frames = dict(mid, k=0, carry_in=0, p_end=HALF + c.e1)         # output without frames, as a flush chunk may be
+
+    def table(r):
+        return _check([[r[name] for name in S.ROW_FIELDS]], WIDTH, max(r["k"], 1), r["e1"] - r["e0"], big)
+
+    def frames(r):
+        return lib.idv_stream_frames(ptr, N_FFT, ptr, WIDTH, r["count"], r["n_prev"], r["L_end"], 1, N_FFT, WIN, HOP, r["t0"], r["k"],
+                                     ptr, r["k"] + 1, r["k"] + 1, None)
+
+    def ola(r):
+        return lib.idv_stream_ola(ptr, r["k"] + 1, r["k"] + 1, ptr, r["carry_in"], ptr, cap, 1, N_FFT, WIN, HOP, r["t0"], r["k"],
+                                  r["T_total"], r["e0"], r["e1"], r["p_end"], ptr, r["e1"] - r["e0"], r["y_off"], None)
+
+    for r in (mid, head, no_frames):
+        assert table(r) == 0
+    reach = {
+        "hi_read: a frame reads past the new samples": dict(mid, count=0),
+        "lo_read: a frame reads behind the ring's reach": dict(mid, n_prev=700 + 2 * N_FFT, count=0),
+        "the deepest start-mirror sample has not arrived": dict(head, count=200),
+        "the start mirror has gone from the ring": dict(head, n_prev=N_FFT + 1, count=0),
+    }
+    for what, r in reach.items():
+        assert table(r) == einval and frames(r) == einval, what
+    ranges = {
+        "p_end < half + e1": dict(no_frames, p_end=HALF + c.e1 - 1),
+        "carry_in > p_end - p_start": dict(mid, carry_in=c.p_end - (HALF + c.e0) + 1),
+        "carry past cap": dict(mid, p_end=HALF + c.e1 + cap + 1),
+        "last frame past p_end": dict(mid, p_end=c.p_end - 1),
+    }
+    for what, r in ranges.items():
+        assert table(r) == einval and ola(r) == einval, what
