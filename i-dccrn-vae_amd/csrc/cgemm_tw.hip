@@ -32,9 +32,15 @@
 #include "cgemm.hpp"
 #include "conv_epilogue.hpp"
 #include "cgemm_tw_map.hpp"
+#include "cgemm_tw_stage.hpp"
 #include "../../include/idccrn_hip.h"
 
 namespace {
+
+// LDS operand reads through address-space pointers: base register + compile-time offset in the read's immediate
+typedef __attribute__((address_space(3))) float LdsF;
+typedef float TwF2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(3))) TwF2 LdsF2;
 
 struct TwArgs {
     const float* x0;      // planar [2][C0][Fin][Jp]
@@ -113,6 +119,11 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw_kernel(c
     // its two 16-byte weight loads: 7 -> 14 / 9 MFMAs paired, 7 -> 10 .. 14 unpaired, no faster), and a ring of KS k-steps on top of
     // it here.
     constexpr bool STAGE_BEHIND_W = PH == 0 && NCT == 2;
+    // The K loop's address forms (operand reads on per-lane LDS bases + compile-time offsets with the transform one MFMA ahead;
+    // staging loads on a scalar base + 32-bit byte offset) in every form but the unpaired odd-row kernel, which keeps the forms it
+    // had: its loop is laid out as three copies (28, 20 and 13 MFMAs: the waves with two, one and no second staging item) whose
+    // staging-load distances tests/test_tw_odd_wvec_host.py keeps, and with either new form the compiler lays out one
+    constexpr bool KBASE = !(PH == 1 && NCT == 1);
     constexpr int NITEM = CIK * NRAW * 16;       // staging items per chunk: (channel, raw row, 2 column pairs)
     constexpr int NTHR = 256 * NCT;
     constexpr int NLD = (NITEM + NTHR - 1) / NTHR;
@@ -186,33 +197,16 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw_kernel(c
     bool interior[NLD];       // wave-uniform: every lane's item has its row and all five window columns inside the tensor
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
-        const int e = tid + i * NTHR;
-        const int c8 = e & 15;
-        const int rl = (e >> 4) % NRAW, cl = e / (16 * NRAW);
-        item_cl[i] = cl;
-        const int f = edge ? a.Fin - 2 + (rl & 1) : rbase + rl;
-        const int jc = j0 + (edge ? 64 * (rl >> 1) : 0) + 4 * c8;
-        const int je = LEFT ? jc - 1 : jc + 4;
-        const bool exists = e < NITEM;
-        const bool okr = exists && f >= 0 && f < a.Fin;
-        unsigned m = 0;
-#pragma unroll
-        for (int q = 0; q < 5; ++q) {
-            const int c = jc + q + (LEFT ? -1 : 0);
-            if (c >= 0 && c < a.J) m |= 1u << q;
-        }
-        if (okr) m |= 1u << 5;
-        if (exists) m |= 1u << 7;
-        // addresses stay inside mapped memory whatever the masks say: vector slot clamped to the row, the extra column to [0, Jp)
-        const int jcv = jc + 3 < a.Jp ? jc : 0;
-        const int jev = (je >= 0 && je < a.Jp) ? je : 0;
-        off_v[i] = okr ? (unsigned)((cl * a.Fin + f) * a.Jp + jcv) : 0u;
-        off_e[i] = okr ? (unsigned)((cl * a.Fin + f) * a.Jp + jev) : 0u;
-        if (jc + 3 >= a.Jp) m &= ~0x1fu;                      // (a column block past the row pitch: nothing valid)
-        if (!(je >= 0 && je < a.Jp)) m &= LEFT ? ~1u : ~(1u << 4);
-        okmask[i] = m;
-        interior[i] = __builtin_amdgcn_ballot_w64((m & 0xbfu) == 0xbfu) == ~0ull;
-        ldsoff[i] = (unsigned)((cl * NRAW + rl) * 288 + 4 * c8);
+        // the address function: cgemm_tw_stage.hpp.  BYTE offsets from the chunk's wave-uniform row bases: the loads take the scalar
+        // base + 32-bit lane offset form, no 64-bit address arithmetic per lane (KBASE = false, the unpaired odd-row kernel: float
+        // offsets, see the main loop)
+        const TwStageItem it = tw_stage_item(tid + i * NTHR, NRAW, NITEM, LEFT, edge, a.Fin, a.J, a.Jp, j0, rbase, KBASE ? 4u : 1u);
+        item_cl[i] = it.cl;
+        off_v[i] = it.off_v;
+        off_e[i] = it.off_e;
+        okmask[i] = it.mask;
+        interior[i] = __builtin_amdgcn_ballot_w64((it.mask & 0xbfu) == 0xbfu) == ~0ull;
+        ldsoff[i] = it.ldsoff;
     }
     auto stage_load = [&](int chunk, int i) {
         const int ci0 = chunk * CIK;
@@ -221,11 +215,18 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw_kernel(c
         const float* bi = from0 ? br + (size_t)a.C0 * a.Fin * a.Jp : br + (size_t)a.C1 * a.Fin * a.Jp;
         const int cvalid = (from0 ? a.C0 : Cin) - ci0;
         const bool dead = item_cl[i] >= cvalid;
-        const unsigned ov = dead ? 0u : off_v[i], oe = dead ? 0u : off_e[i];
-        v_r[i] = *(const f32x4*)(br + ov);
-        v_i[i] = *(const f32x4*)(bi + ov);
-        e_r[i] = br[oe];
-        e_i[i] = bi[oe];
+        const unsigned ov = dead ? 4u * TW_DUMMY : off_v[i], oe = dead ? 4u * TW_DUMMY : off_e[i];
+        if constexpr (KBASE) {
+            v_r[i] = *(const f32x4*)((const char*)br + ov);
+            v_i[i] = *(const f32x4*)((const char*)bi + ov);
+            e_r[i] = *(const float*)((const char*)br + oe);
+            e_i[i] = *(const float*)((const char*)bi + oe);
+        } else {
+            v_r[i] = *(const f32x4*)(br + ov);
+            v_i[i] = *(const f32x4*)(bi + ov);
+            e_r[i] = br[oe];
+            e_i[i] = bi[oe];
+        }
     };
     // the store of an item in ten steps that the main loop deals out between MFMAs (step 0: masks and the window of five columns;
     // steps 1 .. 9: one (Gauss, time) plane each), so that the vector ALU work hides behind the matrix pipe
@@ -305,8 +306,52 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw_kernel(c
         if (NTW == 9) dst[NTW - 1] = ws[512 + lane];
     };
     float xa[NTW], xb[NTW];
-    // operands of tiles 2 j, 2 j + 1 (j < NPAIR: one 8-byte read per raw row) or of the single tile; base = buffer + channel of this half-wave
-    auto load_raw2 = [&](const float* base, int j) {
+    // The wave's operand addresses, formed ONCE per lane: the LDS address of its first k-step's operand in the buffer the loop reads
+    // (buffer + this half-wave's channel + row / plane offset + the lane's column pair).  Even-row phase: one pair of bases for the
+    // plane pairs (8-byte reads at 2 l31) and one for plane 8 (4-byte reads at l31); odd-row phase: one pair per slot.  The k-step and
+    // the plane pair are compile-time offsets of the reads, and the bases move to the other buffer once per chunk (flip_bases).
+    constexpr int NBASE = UNI ? 2 : NPAIR + 1;
+    const LdsF* pA[NBASE];
+    const LdsF* pB[NBASE];
+    {
+        const LdsF* s0 = (const LdsF*)smem + half * RT;
+#pragma unroll
+        for (int j = 0; j < NBASE; ++j) {
+            const bool single = j == NBASE - 1;
+            const int lp = single ? (UNI ? 256 : 0) + l31 : 2 * l31;
+            pA[j] = s0 + offA[UNI ? 0 : j] + lp;
+            pB[j] = s0 + offB[UNI ? 0 : j] + lp;
+        }
+    }
+    // the largest base + compile-time offset stays inside the two patch buffers: second buffer, odd channel of the last k-step, last
+    // raw row, plane 8, last pair
+    static_assert(NE + (2 * (KS - 1) + 1) * RT + (NRAW - 1) * 288 + 256 + 31 < NBUF * NE, "operand reads stay inside the LDS allocation");
+    static_assert(((2 * (KS - 1)) * RT + (NPAIR - 1) * 64) * 4 < 65536, "k-step and plane-pair offsets fit the LDS read's immediate");
+    static_assert(NBUF == 2, "the bases alternate between two buffers");
+    int flip = NE;                                // (uniform) to the other buffer: + NE, then - NE, ...
+    auto flip_bases = [&]() {
+#pragma unroll
+        for (int j = 0; j < NBASE; ++j) {
+            pA[j] += flip;
+            pB[j] += flip;
+        }
+        flip = -flip;
+    };
+    // operands of tiles 2 j, 2 j + 1 (j < NPAIR: one 8-byte read per raw row) or of the single tile, at KOFF floats (compile time: the
+    // k-step's channel pair) from the bases
+    auto load_raw2 = [&](int koff, int j) {
+        if (j < NPAIR) {
+            const int po = koff + (UNI ? j * 64 : 0);
+            const TwF2 pa_ = *(const LdsF2*)(pA[UNI ? 0 : j] + po), pb_ = *(const LdsF2*)(pB[UNI ? 0 : j] + po);
+            xa[2 * j] = pa_.x; xa[2 * j + 1] = pa_.y;
+            xb[2 * j] = pb_.x; xb[2 * j + 1] = pb_.y;
+        } else {
+            xa[NTW - 1] = pA[NBASE - 1][koff];
+            xb[NTW - 1] = pB[NBASE - 1][koff];
+        }
+    };
+    // KBASE = false (the unpaired odd-row kernel, see the main loop): the reads at base = buffer + channel of this half-wave
+    auto load_raw2_p = [&](const float* base, int j) {
         if (j < NPAIR) {
             const int oa = UNI ? offA[0] + j * 64 : offA[UNI ? 0 : j], ob = UNI ? offB[0] + j * 64 : offB[UNI ? 0 : j];
             const float2 pa_ = *(const float2*)(base + oa + 2 * l31), pb_ = *(const float2*)(base + ob + 2 * l31);
@@ -317,10 +362,15 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw_kernel(c
             xb[NTW - 1] = base[(UNI ? offB[0] + 256 : offB[UNI ? 0 : NPAIR]) + l31];
         }
     };
-    auto load_raw_all = [&](const float* base) {
+    auto load_raw_all = [&]() {
 #pragma unroll
-        for (int j = 0; j <= NPAIR; ++j) load_raw2(base, j);
+        for (int j = 0; j <= NPAIR; ++j) {
+            if constexpr (KBASE) load_raw2(0, j);
+            else load_raw2_p(smem + (size_t)half * RT, j);
+        }
     };
+    // the frequency transform of tile k's operand
+    auto xform = [&](int k) -> float { return xa[k] + cbj[UNI ? 0 : (k >> 1 < NPAIR ? k >> 1 : NPAIR)] * xb[k]; };
 
 #pragma unroll
     for (int i = 0; i < NLD; ++i) stage_load(0, i);
@@ -332,7 +382,10 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw_kernel(c
     for (int i = 0; i < NLD; ++i) stage_load(nchunk > 1 ? 1 : 0, i);
     __syncthreads();
 
-    load_raw_all(smem + (size_t)half * RT);
+    load_raw_all();
+    // the transform runs ONE MFMA ahead of its product: a transform right in front of the MFMA that reads it costs the wait states of
+    // the vector-ALU-write -> MFMA-read hazard at every second MFMA
+    float bcur = KBASE ? xform(0) : 0.f;
     // the main loop; late_ (NCT = 2, odd-row phase only): the copy that stages one k-step later, for waves 4 .. 7, so that SIMD partners
     // do not stage at the same time.  A copy, not a branch on the wave inside the loop: the staging steps sit between the MFMAs, and
     // with a wave-uniform branch at each of them the paired kernels were SLOWER than the unpaired ones (dec0-3, B = 64: 36.4 against
@@ -345,31 +398,50 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw_kernel(c
             const int nxt = chunk + 1 < nchunk ? chunk + 1 : chunk, nxt2 = chunk + 2 < nchunk ? chunk + 2 : nchunk - 1;
 #pragma unroll
             for (int ul = 0; ul < KS; ++ul) {
-                // operands of the next k-step: of this chunk, or (last k-step, after the barrier below) of the next chunk
-                const float* bnext = ul + 1 < KS ? P + (size_t)(2 * (ul + 1) + half) * RT : Pn + (size_t)half * RT;
+                // operands of the next k-step: of this chunk, or (last k-step, after the barrier below, which moves the bases) of the
+                // next chunk
+                const int bnext = ul + 1 < KS ? 2 * (ul + 1) * RT : 0;
+                const float* bnext_p = ul + 1 < KS ? P + (size_t)(2 * (ul + 1) + half) * RT : Pn + (size_t)half * RT;
+                auto load_next = [&](int j) {
+                    if constexpr (KBASE) load_raw2(bnext, j);
+                    else load_raw2_p(bnext_p, j);
+                };
                 // staging of chunk + 1 rides on k-steps 1 (item 0) and 2 (item 1): the item's registers were loaded one chunk ago, the
                 // other buffer was last read in the previous chunk (a barrier since); the steps of the store are dealt out between MFMAs
                 const int si = ul - 1 - (LATE ? 1 : 0);
                 const bool staging = si >= 0 && si < NLD;
 #pragma unroll
                 for (int k = 0; k < NTW; ++k) {
-                    const float b = xa[k] + cbj[UNI ? 0 : (k >> 1 < NPAIR ? k >> 1 : NPAIR)] * xb[k];
+                    // (tile 0 of the next k-step: its operands were read behind MFMA 1 of this one)
+                    float bn = 0.f;
+                    if constexpr (KBASE) {
+                        bn = xform(k + 1 < NTW ? k + 1 : 0);
+                        // (odd-row phase: without this the compiler sinks the transform back in front of its product; the even-row
+                        // phase keeps it here by itself, and its unpaired kernel pays 15 more vector instructions per chunk for the
+                        // statement)
+                        if (PH == 1) asm volatile("" : "+v"(bn));
+                        __builtin_amdgcn_sched_barrier(0);    // (in FRONT of MFMA k: behind it, it would sit right in front of MFMA k + 1)
+                    } else {
+                        bcur = xform(k);
+                    }
                     // Odd-row phase: no wave reads the eighth slot's weights (seven tiles).  Left dead, that register is handed out again
                     // while the second group's 16-byte load is still in flight, and the write to it waits for ALL the wave's loads
                     // (vmcnt(0)) right behind the load's issue, in every k-step (that form measured 14.1 -> 17.8 ms on dec0-3 at B = 64).
                     // Read here, where the group's first MFMA waits for the load anyway, it stays the load's until it has landed.
                     if (PH == 1 && k == 4)
                         asm volatile("" ::"v"(a_w[ul % RDW][4]), "v"(a_w[ul % RDW][5]), "v"(a_w[ul % RDW][6]), "v"(a_w[ul % RDW][7]));
-                    acc[k] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_w[ul % RDW][k], b, acc[k], 0, 0, 0);
+                    acc[k] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_w[ul % RDW][k], bcur, acc[k], 0, 0, 0);
+                    if constexpr (KBASE) bcur = bn;
                     if (ul == KS - 1 && k == 0) {
                         // every wave has stored chunk + 1 (k-steps 1, 2) and issued its last reads of P: after this barrier Pn is complete
                         // and P may be overwritten (from k-step 1 of the next chunk on)
                         __builtin_amdgcn_sched_barrier(0);
                         __syncthreads();
+                        if constexpr (KBASE) flip_bases();    // the one address update of the chunk: every read from here on is of Pn
                     }
                     // the operand registers of the tiles done so far are free again
-                    if ((k & 1) && (k >> 1) < NPAIR) load_raw2(bnext, k >> 1);
-                    if (k == NTW - 1) load_raw2(bnext, NPAIR);
+                    if ((k & 1) && (k >> 1) < NPAIR) load_next(k >> 1);
+                    if (k == NTW - 1) load_next(NPAIR);
                     if (staging) {
                         // the store's steps between the MFMAs: window at 0, plane pairs at 1, 3, 5 and (7 or, with seven tiles, 6), plane 8 last
                         if (k == 0) stage_window(nxt, si);
@@ -645,7 +717,7 @@ extern "C" int idv_ctconv2d_tw_fwd(const float* x0, int C0, const float* x1, int
     a.tshift = tshift; a.t_valid = t_valid_out;
     a.add = addend; a.add_div = addend ? addend_div : 1; a.add_Jp = addend_Jp;
     if (Jp < a.J) return IDV_EINVAL;
-    if ((long long)8 * Fin * (long long)Jp >= 0xffffffffLL) return IDV_EINVAL;
+    if ((long long)4 * 8 * Fin * (long long)Jp >= 0xffffffffLL) return IDV_EINVAL;   // (the staging's 32-bit byte offsets)
     hipStream_t st = (hipStream_t)stream;
     sums.set(a);
     int rc = 0;

@@ -28,9 +28,15 @@
 #include "cgemm.hpp"
 #include "conv_epilogue.hpp"
 #include "cgemm_tw_map.hpp"
+#include "cgemm_tw_stage.hpp"
 #include "../../include/idccrn_hip.h"
 
 namespace {
+
+// LDS operand reads through address-space pointers: base register + compile-time offset in the read's immediate (cgemm_tw.hip)
+typedef __attribute__((address_space(3))) float LdsF;
+typedef float TwF2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(3))) TwF2 LdsF2;
 
 typedef f32x4 f32x4_a4 __attribute__((aligned(4)));     // a 16-byte global load at any float
 
@@ -171,31 +177,13 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw2_kernel(
     auto item_cl = [&](int i) -> int { return (tid + i * NTHR) / (16 * NRAW); };
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
-        const int e = tid + i * NTHR;
-        const int c8 = e & 15;
-        // (NCT = 2, no item: channel CIK is dead in every chunk, and its row 0 is the dump row behind the buffer)
-        const int cl = e / (16 * NRAW), rl = (NCT == 2 && e >= NITEM) ? 0 : (e >> 4) % NRAW;
-        const int f = edge ? (rl < 6 ? a.Fin - 3 + rl % 3 : -1) : rbase + rl;
-        const int jc = j0 + (edge && rl >= 3 ? 64 : 0) + 4 * c8;
-        const int je = LEFT ? jc - 1 : jc + 4;
-        const bool exists = e < NITEM;
-        const bool okr = exists && f >= 0 && f < a.Fin;
-        unsigned m = 0;
-#pragma unroll
-        for (int q = 0; q < 5; ++q) {
-            const int c = jc + q + (LEFT ? -1 : 0);
-            if (c >= 0 && c < a.J) m |= 1u << q;
-        }
-        if (okr) m |= 1u << 5;
-        // the extra column is loaded at the vector slot's offset - 1 / + 4: one float outside the row at the buffer's edges, inside the
-        // slack every planar buffer has in front and behind (masked)
-        const int jcv = jc + 3 < a.Jp ? jc : 0;
-        off_v[i] = okr ? (unsigned)((cl * a.Fin + f) * a.Jp + jcv) : 4u;
-        if (jc + 3 >= a.Jp) m &= ~0x1fu;
-        if (!(je >= 0 && je < a.Jp)) m &= LEFT ? ~1u : ~(1u << 4);
-        okmask[i] = m;
-        interior[i] = __builtin_amdgcn_ballot_w64((m & 0x3fu) == 0x3fu) == ~0ull;
-        ldsoff[i] = (unsigned)((cl * NRAW + rl) * 288 + 4 * c8);
+        // the address function: cgemm_tw_stage.hpp.  A BYTE offset from the chunk's wave-uniform row bases: scalar base + 32-bit lane
+        // offset.  (NCT = 2, no item: channel CIK is dead in every chunk, and its row 0 is the dump row behind the buffer)
+        const TwStageItem it = tw2_stage_item(tid + i * NTHR, NITEM, NCT == 2, LEFT, edge, a.Fin, a.J, a.Jp, j0, rbase);
+        off_v[i] = it.off_v;
+        okmask[i] = it.mask;
+        interior[i] = __builtin_amdgcn_ballot_w64((it.mask & 0x3fu) == 0x3fu) == ~0ull;
+        ldsoff[i] = it.ldsoff;
     }
     // the second item exists in waves 0 .. 2 only (448 items); NCT = 2: one item in every thread (wave 7: a dead one)
     auto item_exists = [&](int i) -> bool { return i == 0 || wave * 64 + 256 < NITEM; };
@@ -205,13 +193,13 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw2_kernel(
         const float* br = a.x0 + (size_t)ci0 * a.Fin * a.Jp;
         const float* bi = br + (size_t)Cin * a.Fin * a.Jp;
         const bool dead = item_cl(i) >= Cin - ci0;
-        const unsigned ov = dead ? 4u : off_v[i];
+        const unsigned ov = dead ? 4u * TW2_DUMMY : off_v[i];
         // the five-column window as ONE vector (its first four columns) and one scalar (the fifth) on both tap sides; tap left: the
         // vector starts a float in front of the 16-byte slot.  (Loaded as the aligned slot and the column in front, the compiler
         // merges the two into this same pair of loads, re-assembles v / e from their components right behind the loads and waits
         // for them there: a global round trip per chunk in the slot that issues them.)
-        const float* pr = br + ov - (LEFT ? 1 : 0);
-        const float* pi = bi + ov - (LEFT ? 1 : 0);
+        const float* pr = (const float*)((const char*)br + ov) - (LEFT ? 1 : 0);
+        const float* pi = (const float*)((const char*)bi + ov) - (LEFT ? 1 : 0);
         using Win = std::conditional_t<LEFT, f32x4_a4, f32x4>;
         v_r[i] = *(const Win*)pr;
         v_i[i] = *(const Win*)pi;
@@ -289,19 +277,32 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw2_kernel(
     // row each); group 3 = plane 6 of x, y (slots 0, 1) and product 2's plane pair (slots 2, 3).  Role B (wave 3): slots 4 g .. 4 g + 3 of
     // tw2_slot(3, .), one 4-byte read per row.
     float xa[2][4], xb[2][4];
-    auto load_grp_a = [&](const float* base, int g, float (&oa)[4], float (&ob)[4]) {
+    // The reads go through per-lane LDS BASES that a loop forms once (run(): the address of the wave's operand in k-step 0 of the
+    // buffer being read); the k-step (koff floats), the plane and -- where it is constant -- the row are compile-time offsets of
+    // the reads, and the bases move to the other buffer once per chunk.  Role A: five bases at 2 l31.  Row ya is the row behind xa in all
+    // three waves, and the two 8-byte reads go out as ONE two-address read, whose two offsets are 8 bits of 8 bytes: xa / ya have a
+    // base per k-step (pb[0], pb[2]), so that the pair needs no address add; rows xb, yb, 2a (2b a constant in front of it) one each.
+    static_assert(tw2_ra(tw2_qy(tw2_main_acc(0))) == tw2_ra(tw2_qx(tw2_main_acc(0))) + 1 &&
+                  tw2_ra(tw2_qy(tw2_main_acc(1))) == tw2_ra(tw2_qx(tw2_main_acc(1))) + 1 &&
+                  tw2_ra(tw2_qy(tw2_main_acc(2))) == tw2_ra(tw2_qx(tw2_main_acc(2))) + 1, "row ya = row xa + 1");
+    static_assert(KS == 2, "one xa / ya base per k-step");
+    auto load_grp_a = [&](const LdsF* const* pb, int koff, int g, float (&oa)[4], float (&ob)[4]) {
+        const LdsF* px = koff ? pb[2] + (koff - 2 * RT) : pb[0];
         if (g < 3) {
-            const float2 xa_ = *(const float2*)(base + rxa + g * 64 + 2 * l31), xb_ = *(const float2*)(base + rxb + g * 64 + 2 * l31);
-            const float2 ya_ = *(const float2*)(base + rya + g * 64 + 2 * l31), yb_ = *(const float2*)(base + ryb + g * 64 + 2 * l31);
+            const TwF2 xa_ = *(const LdsF2*)(px + g * 64), xb_ = *(const LdsF2*)(pb[1] + koff + g * 64);
+            const TwF2 ya_ = *(const LdsF2*)(px + 288 + g * 64), yb_ = *(const LdsF2*)(pb[3] + koff + g * 64);
             oa[0] = xa_.x; oa[2] = xa_.y; ob[0] = xb_.x; ob[2] = xb_.y;
             oa[1] = ya_.x; oa[3] = ya_.y; ob[1] = yb_.x; ob[3] = yb_.y;
         } else {
-            oa[0] = base[rxa + 3 * 64 + 2 * l31]; ob[0] = base[rxb + 3 * 64 + 2 * l31];
-            oa[1] = base[rya + 3 * 64 + 2 * l31]; ob[1] = base[ryb + 3 * 64 + 2 * l31];
-            const float2 pa_ = *(const float2*)(base + r2a + 2 * l31), pb_ = *(const float2*)(base + r2b + 2 * l31);
+            oa[0] = px[3 * 64]; ob[0] = pb[1][koff + 3 * 64];
+            oa[1] = px[288 + 3 * 64]; ob[1] = pb[3][koff + 3 * 64];
+            const TwF2 pa_ = *(const LdsF2*)(pb[4] + koff), pb_ = *(const LdsF2*)(pb[4] + koff + (tw2_rb(2) - tw2_ra(2)) * 288);
             oa[2] = pa_.x; oa[3] = pa_.y; ob[2] = pb_.x; ob[3] = pb_.y;
         }
     };
+    // Role B (wave 3) reads 4 bytes per row at constant rows: base = buffer + channel of this half-wave, formed per k-step.  (On
+    // per-lane bases like role A's the compiler pairs fewer of these reads into two-address reads, more LDS read instructions per
+    // chunk; wave 3 keeps this form.)
     auto load_grp_b = [&](const float* base, int g, float (&oa)[4], float (&ob)[4]) {
 #pragma unroll
         for (int s4 = 0; s4 < 4; ++s4) {
@@ -314,14 +315,38 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw2_kernel(
     };
     // Edge workgroup: the products of tw2_eslot, one 4-byte read each from raw slot 3 c + tap of the wave's column block c
     const int eoff = (w4 >> 1) * 3 * 288;
-    auto load_grp_e = [&](auto odd_, const float* base, int g, float (&oa)[4]) {
+    // (two bases, the lane parts of tw2_poff: planes 0 .. 7 at 2 l31, plane 8 at l31; two neighbouring slots on the interleaved
+    // planes (2 j, 2 j + 1) of one tap take ONE 8-byte read)
+    auto load_grp_e = [&](auto odd_, const LdsF* const* pb, int koff, int g, float (&oa)[4]) {
 #pragma unroll
         for (int s4 = 0; s4 < 4; ++s4) {
-            int t, plane;
+            int t, plane, t2 = -1, plane2 = -1;
             if (!tw2_eslot(decltype(odd_)::value, 4 * g + s4, t, plane)) continue;
-            oa[s4] = base[eoff + t * 288 + tw2_poff(plane, l31)];
+            // slot s4 opens a pair with slot s4 + 1, or closes the pair slot s4 - 1 opened
+            const bool two = s4 < 3 && tw2_eslot(decltype(odd_)::value, 4 * g + s4 + 1, t2, plane2) && t2 == t && !(plane & 1) &&
+                             plane2 == plane + 1 && plane2 < 8;
+            const bool second = s4 > 0 && tw2_eslot(decltype(odd_)::value, 4 * g + s4 - 1, t2, plane2) && t2 == t && (plane & 1) &&
+                                plane2 == plane - 1 && plane < 8;
+            if (second) continue;
+            if (two) {
+                const TwF2 v = *(const LdsF2*)(pb[0] + koff + t * 288 + (plane >> 1) * 64);
+                oa[s4] = v.x;
+                oa[s4 + 1] = v.y;
+            } else {
+                oa[s4] = pb[plane < 8 ? 0 : 1][koff + t * 288 + (plane < 8 ? (plane >> 1) * 64 + (plane & 1) : 256)];
+            }
         }
     };
+    // role A: the largest base + compile-time offset stays inside the two patch buffers (second buffer, odd channel of the last
+    // k-step, raw row 6, plane pair 3, last pair), and the offsets fit the LDS read's immediate
+    static_assert(NEB + (2 * (KS - 1) + 1) * RT + 6 * 288 + 3 * 64 + 2 * 31 + 1 < 2 * NEB, "operand reads stay inside the LDS allocation");
+    static_assert((2 * (KS - 1) * RT + 6 * 288 + 256) * 4 < 65536, "k-step, row and plane offsets fit the LDS read's immediate");
+    // edge waves: base = buffer + half-wave channel + eoff (column block 1: 3 raw slots) + lane part, immediate = k-step + tap t <= 2 +
+    // plane; the largest is plane 8 of tap 2 of column block 1.  Wave 3 (load_grp_b, addresses formed per k-step from the buffer):
+    // raw row <= 6, plane 8
+    static_assert(NEB + (2 * (KS - 1) + 1) * RT + (3 + 2) * 288 + 256 + 31 < 2 * NEB, "edge-wave reads stay inside the LDS allocation");
+    static_assert(NEB + (2 * (KS - 1) + 1) * RT + 6 * 288 + 256 + 31 < 2 * NEB, "wave 3's reads stay inside the LDS allocation");
+    static_assert(tw2_rb(6) <= 6 && tw2_rb(3) <= 6 && tw2_ra(2) <= 6, "raw rows 0 .. 6");
 
     // chunk 0 into the first buffer, chunk 1 on its way, the first k-step's weights.  Every copy of the loop below begins with its own
     // copy of this: what a loop overwrites (staging registers, weights, operands) would otherwise have to survive, in the state this
@@ -347,36 +372,70 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw2_kernel(
         constexpr bool ROLE_B = ROLE == 1, EDGE = ROLE >= 2;
         using EdgeOdd = std::integral_constant<bool, ROLE == 3>;
         prologue();
-        if constexpr (EDGE) load_grp_e(EdgeOdd{}, smem + (size_t)half * RT, 0, xa[0]);
-        else if (ROLE_B) load_grp_b(smem + (size_t)half * RT, 0, xa[0], xb[0]);
-        else load_grp_a(smem + (size_t)half * RT, 0, xa[0], xb[0]);
+        constexpr bool AHEAD = !EDGE && !ROLE_B;
+        constexpr bool BASES = !ROLE_B;
+        constexpr int NB = EDGE ? 2 : (BASES ? 5 : 1);
+        const LdsF* pb[NB];
+        if constexpr (EDGE) {
+            pb[0] = (const LdsF*)smem + half * RT + eoff + 2 * l31;
+            pb[1] = (const LdsF*)smem + half * RT + eoff + l31;
+        } else if constexpr (BASES) {
+            const int ro[5] = {rxa, rxb, rxa + 2 * RT, ryb, r2a};
+#pragma unroll
+            for (int j = 0; j < 5; ++j) pb[j] = (const LdsF*)smem + half * RT + ro[j] + 2 * l31;
+        }
+        int flip = NEB;                           // (uniform) to the other buffer: + NEB, then - NEB, ...
+        const float* Pcur = smem;                 // (wave 3: the buffer being read)
+        auto load_grp = [&](int koff, int g) {
+            if constexpr (EDGE) load_grp_e(EdgeOdd{}, pb, koff, g, xa[g & 1]);
+            else if constexpr (ROLE_B) load_grp_b(Pcur + (size_t)(koff / RT + half) * RT, g, xa[g & 1], xb[g & 1]);
+            else load_grp_a(pb, koff, g, xa[g & 1], xb[g & 1]);
+        };
+        // frequency transform of slot k's operand (full tiles; the edge waves multiply raw rows)
+        auto xform = [&](int k) -> float {
+            float cb;
+            if constexpr (ROLE_B) {
+                int q, plane;
+                tw2_slot(3, k, q, plane);
+                cb = tw2_cb(q);
+            } else {
+                cb = k < 14 ? ((k & 1) ? cby : cbx) : -1.f;
+            }
+            return xa[(k >> 2) & 1][k & 3] + cb * xb[(k >> 2) & 1][k & 3];
+        };
+        constexpr int NK = ROLE_B ? NSLOT - 1 : NSLOT;
+        load_grp(0, 0);
+        // role A: the transform runs ONE MFMA ahead of its product (cgemm_tw.hip).  Wave 3 keeps it in front of its MFMA: ahead, the
+        // compiler pairs fewer of its 4-byte reads (see load_grp_b), and its 15 slots per k-step are not the workgroup's pace.
+        float bcur = 0.f;
+        if constexpr (AHEAD) bcur = xform(0);
         for (int chunk = 0; chunk < nchunk; ++chunk) {
-            const float* P = smem + (chunk & 1) * NEB;
             float* Pn = smem + ((chunk + 1) & 1) * NEB;
+            if constexpr (ROLE_B) Pcur = smem + (chunk & 1) * NEB;
             const int nxt = chunk + 1 < nchunk ? chunk + 1 : chunk, nxt2 = chunk + 2 < nchunk ? chunk + 2 : nchunk - 1;
 #pragma unroll
             for (int ul = 0; ul < KS; ++ul) {
-                const float* bnext = ul + 1 < KS ? P + (size_t)(2 * (ul + 1) + half) * RT : Pn + (size_t)half * RT;
                 const bool staging = ul == 0;           // both items ride on k-step 0; the barrier sits in k-step 1
 #pragma unroll
-                for (int k = 0; k < (ROLE_B ? NSLOT - 1 : NSLOT); ++k) {
+                for (int k = 0; k < NK; ++k) {
                     const int g = k >> 2, s4 = k & 3;
-                    float cb;
                     int ai;
                     bool product = true;
                     if (EDGE) {
                         int t, plane;
                         product = tw2_eslot(EdgeOdd::value, k, t, plane);
-                        cb = 0.f;
                         ai = plane - (EdgeOdd::value ? 5 : 0);
                     } else if (ROLE_B) {
-                        int q, plane;
-                        tw2_slot(3, k, q, plane);
-                        cb = tw2_cb(q);
                         ai = k < 12 ? k >> 1 : 6 + (k - 12);
                     } else {
-                        cb = k < 14 ? ((k & 1) ? cby : cbx) : -1.f;
                         ai = k < 14 ? k >> 1 : 7 + (k - 14);
+                    }
+                    // (slot 0 of the next k-step: its group was read behind slot 12 of this one)
+                    float bn = 0.f;
+                    if constexpr (AHEAD) {
+                        bn = xform(k + 1 < NK ? k + 1 : 0);
+                        asm volatile("" : "+v"(bn));          // (the transform is DONE here, not sunk to its product)
+                        __builtin_amdgcn_sched_barrier(0);    // (in FRONT of MFMA k: behind it, it would sit right in front of MFMA k + 1)
                     }
                     // A role with empty slots (wave 3: slot 15; edge waves: slot 15, or every fourth) never reads those slots' weights.
                     // Left dead, their registers are handed out again while the group's 16-byte load is still in flight, and the write
@@ -385,28 +444,31 @@ __global__ __launch_bounds__(256 * NCT, NCT == 1 ? 2 : 1) void cconv_tw2_kernel(
                     if ((ROLE_B || EDGE) && s4 == 0) asm volatile("" ::"v"(a_w[k]), "v"(a_w[k + 1]), "v"(a_w[k + 2]), "v"(a_w[k + 3]));
                     if (s4 == 0) {
                         // the next group's operands (of this k-step, or group 0 of the next one: after the barrier in the last k-step)
-                        const float* src = g < 3 ? P + (size_t)(2 * ul + half) * RT : bnext;
-                        if (!(ul == KS - 1 && g == 3)) {
-                            if constexpr (EDGE) load_grp_e(EdgeOdd{}, src, (g + 1) & 3, xa[(g + 1) & 1]);
-                            else if (ROLE_B) load_grp_b(src, (g + 1) & 3, xa[(g + 1) & 1], xb[(g + 1) & 1]);
-                            else load_grp_a(src, (g + 1) & 3, xa[(g + 1) & 1], xb[(g + 1) & 1]);
-                        }
+                        if (!(ul == KS - 1 && g == 3)) load_grp(g < 3 ? 2 * ul * RT : 2 * (ul + 1) * RT, (g + 1) & 3);
                     }
                     if constexpr (EDGE) {
                         if (product) acc[ai] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_w[k], xa[g & 1][s4], acc[ai], 0, 0, 0);
+                    } else if constexpr (AHEAD) {
+                        acc[ai] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_w[k], bcur, acc[ai], 0, 0, 0);
+                        bcur = bn;
                     } else {
-                        const float b = xa[g & 1][s4] + cb * xb[g & 1][s4];
-                        acc[ai] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_w[k], b, acc[ai], 0, 0, 0);
+                        acc[ai] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_w[k], xform(k), acc[ai], 0, 0, 0);
                     }
                     if (ul == KS - 1 && k == 0) {
                         __builtin_amdgcn_sched_barrier(0);
                         __syncthreads();
                     }
                     if (ul == KS - 1 && k == 12) {
-                        // (last k-step: group 0 of the next chunk comes from the other buffer, complete since the barrier above)
-                        if constexpr (EDGE) load_grp_e(EdgeOdd{}, bnext, 0, xa[0]);
-                        else if (ROLE_B) load_grp_b(bnext, 0, xa[0], xb[0]);
-                        else load_grp_a(bnext, 0, xa[0], xb[0]);
+                        // (last k-step: group 0 of the next chunk comes from the other buffer, complete since the barrier above: the one
+                        // address update of the chunk, every read from here on is of Pn)
+                        if constexpr (BASES) {
+#pragma unroll
+                            for (int j = 0; j < NB; ++j) pb[j] += flip;
+                            flip = -flip;
+                        } else {
+                            Pcur = Pn;
+                        }
+                        load_grp(0, 0);
                     }
                     // weights of the next k-step, group by group
                     if ((k & 3) == 3 || (ROLE_B && k == NSLOT - 2)) load_wg(chunk * KS + ul + 1, k >> 2);
@@ -655,7 +717,7 @@ extern "C" int idv_cconv2d_tw_fwd(const float* x0, int Cin, const float* wfrag, 
     a.Cout = Cout; a.cotiles = (Cout + 31) / 32;
     a.tshift = tshift; a.t_valid = t_valid_out;
     if (Jp < a.J) return IDV_EINVAL;
-    if ((long long)4 * Fin * (long long)Jp >= 0xffffffffLL) return IDV_EINVAL;
+    if ((long long)4 * 4 * Fin * (long long)Jp >= 0xffffffffLL) return IDV_EINVAL;   // (the staging's 32-bit byte offsets)
     hipStream_t st = (hipStream_t)stream;
     sums.set(a);
     int rc;
