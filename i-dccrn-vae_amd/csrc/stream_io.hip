@@ -174,16 +174,22 @@ __device__ __forceinline__ void box_muller(uint32_t wa, uint32_t wb, float& re, 
 // (eps2_r, eps2_i), the noise latent's draws; words 0 and 1 are what the kernel without PAIR writes.
 // SEEDS (idv_stream_eps_pair_rows, with ROWS): the key of slot b is seeds[b] in place of seed.  seeds is the last parameter, so
 // the kernel arguments of the forms without SEEDS sit where they sat.
-template <bool ROWS, bool PAIR, bool SEEDS>
+// AS (idv_stream_eps_pair_rows_as, with SEEDS): the counter word of slot b is draw_slots[b] * ns + s in place of b * ns + s, so
+// a stream that was saved in slot draw_slots[b] and loaded into slot b keeps its draws.  draw_slots is the last parameter, for
+// the same reason.
+template <bool ROWS, bool PAIR, bool SEEDS, bool AS = false>
 __global__ void stream_eps_kernel(unsigned long long seed, long long t0, int k, int Bn, int zdim, float* __restrict__ eps_r,
                                   float* __restrict__ eps_i, float* __restrict__ eps2_r, float* __restrict__ eps2_i, int ns,
-                                  const long long* __restrict__ rows, const long long* __restrict__ seeds) {
+                                  const long long* __restrict__ rows, const long long* __restrict__ seeds,
+                                  const long long* __restrict__ draw_slots) {
     static_assert(ROWS || !SEEDS, "per-slot seeds come with the row table");
+    static_assert(SEEDS || !AS, "per-slot draw slots come with the per-slot seeds");
     const long long n = (long long)Bn * k * zdim;
     for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
         const uint32_t u = (uint32_t)(e % zdim);
         const long long tl = (e / zdim) % k;
         const uint32_t bs = (uint32_t)(e / ((long long)zdim * k));
+        uint32_t word = bs;                                                    // counter word 2: b * ns + s
         if (ROWS) {
             const uint32_t b = bs / (uint32_t)ns;
             const long long* row = rows + (size_t)b * IDV_STREAM_ROW_FIELDS;
@@ -198,10 +204,11 @@ __global__ void stream_eps_kernel(unsigned long long seed, long long t0, int k, 
             }
             t0 = row[IDV_ROW_T0];
             if (SEEDS) seed = (unsigned long long)seeds[b];
+            if (AS) word = (uint32_t)draw_slots[b] * (uint32_t)ns + (bs - b * (uint32_t)ns);
         }
         const unsigned long long t = (unsigned long long)(t0 + tl);
         uint32_t w0, w1, w2, w3;
-        philox4x32_10((uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)t, (uint32_t)(t >> 32), bs, u, w0, w1, w2, w3);
+        philox4x32_10((uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)t, (uint32_t)(t >> 32), word, u, w0, w1, w2, w3);
         box_muller(w0, w1, eps_r[e], eps_i[e]);
         if (PAIR) box_muller(w2, w3, eps2_r[e], eps2_i[e]);
     }
@@ -242,11 +249,12 @@ static const long long* const no_rows = nullptr;      // the table argument of a
 static const SigRow no_row = {};                      // the by-value row of a ROWS instantiation, which loads its own from the table
 static float* const no_eps = nullptr;                 // the second pair of an instantiation without PAIR, which never writes it
 static const long long* const no_seeds = nullptr;     // the seed array of an instantiation without SEEDS, which never reads it
+static const long long* const no_draw_slots = nullptr;      // the draw slots of an instantiation without AS, which never reads them
 
 extern "C" int idv_stream_eps(long long seed, long long t0, int k, int B, int ns, int zdim, float* eps_r, float* eps_i, void* stream) {
     if (t0 < 0 || k <= 0 || B <= 0 || ns <= 0 || zdim <= 0 || !eps_r || !eps_i || (long long)B * ns > 0x7fffffffLL) return IDV_EINVAL;
     hipLaunchKernelGGL((stream_eps_kernel<false, false, false>), dim3(grid_of((long long)B * ns * k * zdim)), dim3(256), 0, (hipStream_t)stream,
-                       (unsigned long long)seed, t0, k, B * ns, zdim, eps_r, eps_i, no_eps, no_eps, ns, no_rows, no_seeds);
+                       (unsigned long long)seed, t0, k, B * ns, zdim, eps_r, eps_i, no_eps, no_eps, ns, no_rows, no_seeds, no_draw_slots);
     return idv_launch_status();
 }
 
@@ -256,7 +264,7 @@ extern "C" int idv_stream_eps_pair(long long seed, long long t0, int k, int B, i
         (long long)B * ns > 0x7fffffffLL)
         return IDV_EINVAL;
     hipLaunchKernelGGL((stream_eps_kernel<false, true, false>), dim3(grid_of((long long)B * ns * k * zdim)), dim3(256), 0, (hipStream_t)stream,
-                       (unsigned long long)seed, t0, k, B * ns, zdim, eps_sr, eps_si, eps_nr, eps_ni, ns, no_rows, no_seeds);
+                       (unsigned long long)seed, t0, k, B * ns, zdim, eps_sr, eps_si, eps_nr, eps_ni, ns, no_rows, no_seeds, no_draw_slots);
     return idv_launch_status();
 }
 
@@ -277,7 +285,7 @@ extern "C" int idv_stream_eps_rows(long long seed, const long long* rows, int B,
         return IDV_EINVAL;
     hipLaunchKernelGGL((stream_eps_kernel<true, false, false>), dim3(grid_of((long long)B * ns * k_launch * zdim)), dim3(256), 0,
                        (hipStream_t)stream, (unsigned long long)seed, 0LL, k_launch, B * ns, zdim, eps_r, eps_i, no_eps, no_eps, ns, rows,
-                       no_seeds);
+                       no_seeds, no_draw_slots);
     return idv_launch_status();
 }
 
@@ -289,10 +297,26 @@ extern "C" int idv_stream_eps_pair_rows(const long long* seeds, const long long*
     const dim3 grid(grid_of((long long)B * ns * k_launch * zdim));
     if (eps_nr)
         hipLaunchKernelGGL((stream_eps_kernel<true, true, true>), grid, dim3(256), 0, (hipStream_t)stream, 0ULL, 0LL, k_launch,
-                           B * ns, zdim, eps_sr, eps_si, eps_nr, eps_ni, ns, rows, seeds);
+                           B * ns, zdim, eps_sr, eps_si, eps_nr, eps_ni, ns, rows, seeds, no_draw_slots);
     else      // the single-pair form: the speech draws alone
         hipLaunchKernelGGL((stream_eps_kernel<true, false, true>), grid, dim3(256), 0, (hipStream_t)stream, 0ULL, 0LL, k_launch,
-                           B * ns, zdim, eps_sr, eps_si, no_eps, no_eps, ns, rows, seeds);
+                           B * ns, zdim, eps_sr, eps_si, no_eps, no_eps, ns, rows, seeds, no_draw_slots);
+    return idv_launch_status();
+}
+
+extern "C" int idv_stream_eps_pair_rows_as(const long long* seeds, const long long* draw_slots, const long long* rows, int B, int ns,
+                                           int zdim, int k_launch, float* eps_sr, float* eps_si, float* eps_nr, float* eps_ni,
+                                           void* stream) {
+    if (!seeds || !draw_slots || !rows || k_launch <= 0 || B <= 0 || ns <= 0 || zdim <= 0 || !eps_sr || !eps_si ||
+        (eps_nr != nullptr) != (eps_ni != nullptr) || (long long)B * ns > 0x7fffffffLL)
+        return IDV_EINVAL;
+    const dim3 grid(grid_of((long long)B * ns * k_launch * zdim));
+    if (eps_nr)
+        hipLaunchKernelGGL((stream_eps_kernel<true, true, true, true>), grid, dim3(256), 0, (hipStream_t)stream, 0ULL, 0LL, k_launch,
+                           B * ns, zdim, eps_sr, eps_si, eps_nr, eps_ni, ns, rows, seeds, draw_slots);
+    else      // the single-pair form: the speech draws alone
+        hipLaunchKernelGGL((stream_eps_kernel<true, false, true, true>), grid, dim3(256), 0, (hipStream_t)stream, 0ULL, 0LL, k_launch,
+                           B * ns, zdim, eps_sr, eps_si, no_eps, no_eps, ns, rows, seeds, draw_slots);
     return idv_launch_status();
 }
 

@@ -15,9 +15,13 @@ the I-DCCRN-VAE pair (noisy encoder, latent draw, fine-tuned decoder with the no
 evaluation: speech and noise decoder on one encoder pass, then a mask estimator.  :class:`StreamingResampler` /
 :class:`StreamingResamplerSessions` resample a stream under the same contract, bit-identical to ``inference.resample``, and
 :class:`AtRate` / :class:`SessionsAtRate` put one in front of and one behind any of the streamers for signals at 48 or 44.1 kHz.
+Every sessions class takes a slot's stream out as a :class:`SlotState` (``save``) and puts it into any slot of any object of the
+same shape (``load``): moving, compacting, parking and persisting streams.
 """
 from __future__ import annotations
 
+import json
+import struct
 from collections.abc import Iterable, Sequence
 from typing import List, NamedTuple, Optional
 
@@ -172,6 +176,31 @@ class SessionPlan:
     def restore(self, snap):
         for pl, v in zip(self.plans, snap):
             pl.n, pl.k, pl.emitted, pl.carry, pl.parity = v
+
+    def slot_state(self, b: int):
+        """Slot b's host integers (n, k, emitted, carry, parity): its row of ``snapshot()``."""
+        pl = self.plans[b]
+        return (pl.n, pl.k, pl.emitted, pl.carry, pl.parity)
+
+    def set_slot_state(self, b: int, v):
+        self.check_slot_state(v)
+        pl = self.plans[b]
+        pl.n, pl.k, pl.emitted, pl.carry, pl.parity = v
+
+    def check_slot_state(self, v):
+        """The guard on a slot's host integers that come from outside (``load``): k, emitted and carry are functions of n alone
+        (the frames that are ready, the samples they make final, the overlap behind them), so a fresh :class:`StreamPlan` that is
+        pushed n samples must arrive at them; the parity counts launch groups and is only held to {0, 1}."""
+        if (not isinstance(v, (tuple, list)) or len(v) != 5 or any(isinstance(q, bool) or not isinstance(q, int) for q in v)
+                or v[0] < 0):
+            raise ValueError("a slot's plan is five ints (n, k, emitted, carry, parity) with n >= 0")
+        n, k, emitted, carry, parity = v
+        one = self.plans[0]
+        replay = StreamPlan(one.n_fft, one.hop, one.win, max(1, one.frames_ready(n)))      # one chunk, wherever the stream is
+        replay.push(n)
+        if (k, emitted, carry) != (replay.k, replay.emitted, replay.carry) or parity not in (0, 1):
+            raise ValueError(f"a slot's plan (n, k, emitted, carry, parity) = {tuple(v)} is not one a stream of {n} samples "
+                             f"reaches: k, emitted, carry must be {(replay.k, replay.emitted, replay.carry)} and parity 0 or 1")
 
     def check(self, counts: List[int], end: List[int]):
         """Every guard of a push, before anything changes."""
@@ -660,6 +689,118 @@ class StreamingDCCRN(_Streamer):
              i(self.B), i(c.k), i(Tp), i(Jp), stream_ptr())
 
 
+STATE_KINDS = ("dccrn", "vae", "two_latents", "resampler", "at_rate")
+_STATE_MAGIC = b"IDVSLOT\x00"
+_STATE_VERSION = 1
+
+
+def _as_tuple(v):
+    """JSON gives lists back where tuples went in."""
+    return tuple(_as_tuple(q) for q in v) if isinstance(v, (list, tuple)) else v
+
+
+class SlotState:
+    """The stream of one slot of a sessions object, as ``save`` returns it and ``load`` takes it.
+
+    ``kind``: the class family, one of ``STATE_KINDS``; ``layout``: a tuple that fingerprints what the floats mean (n_fft, hop,
+    win, the (outer, inner) of every state view in order, for the VAE kinds also ns, zdim, H, latent or outtype / phase, average;
+    for resamplers up, down, H); ``plan``: the slot's host integers (``SessionPlan.slot_state``: n, k, emitted, carry, parity; a
+    resampler's: n, parity); ``seed`` / ``draw_slot``: the key and the slot number a VAE stream draws with (else None); ``data``:
+    the slot's record, float32 ``[per_slot]`` on a device or on the CPU.  A state of kind ``"at_rate"`` has no floats of its own:
+    ``stages`` holds the states of its three stages (down-resampler, network, up-resampler).
+
+    ``kind`` and ``layout`` say nothing about the weights: loading a state into a streamer with other weights of the same layout
+    is not detected and gives the output of neither model.
+    """
+
+    __slots__ = ("kind", "layout", "plan", "seed", "draw_slot", "data", "stages")
+
+    def __init__(self, kind, layout, plan, data, seed=None, draw_slot=None, stages=None):
+        self.kind, self.layout, self.plan, self.data = kind, _as_tuple(layout), _as_tuple(plan), data
+        self.seed, self.draw_slot, self.stages = seed, draw_slot, (tuple(stages) if stages is not None else None)
+
+    def __repr__(self):
+        return f"SlotState(kind={self.kind!r}, plan={self.plan}, floats={self.data.numel()}, device={self.data.device})"
+
+    def to(self, device) -> "SlotState":
+        """The same state with its floats on ``device`` (a copy only where they are elsewhere)."""
+        return SlotState(self.kind, self.layout, self.plan, self.data.to(device), self.seed, self.draw_slot,
+                         [s.to(device) for s in self.stages] if self.stages is not None else None)
+
+    def cpu(self) -> "SlotState":
+        return self.to("cpu")
+
+    def tobytes(self) -> bytes:
+        """Magic, version (uint32), header length (uint32), a JSON header, then the payload: the floats as little-endian
+        float32, or for an ``at_rate`` state the bytes of its stages one after the other (their lengths in the header)."""
+        if self.stages is not None:
+            parts = [s.tobytes() for s in self.stages]
+            payload = b"".join(parts)
+        else:
+            parts = None
+            payload = self.data.detach().cpu().contiguous().numpy().astype("<f4", copy=False).tobytes()
+        head = json.dumps({"kind": self.kind, "layout": self.layout, "plan": self.plan, "seed": self.seed,
+                           "draw_slot": self.draw_slot, "floats": None if parts is not None else int(self.data.numel()),
+                           "stages": [len(q) for q in parts] if parts is not None else None}).encode()
+        return _STATE_MAGIC + struct.pack("<II", _STATE_VERSION, len(head)) + head + payload
+
+    @staticmethod
+    def frombytes(b) -> "SlotState":
+        """The state ``tobytes`` wrote (its floats on the CPU); ``ValueError`` for anything else: every length is checked."""
+        if not isinstance(b, (bytes, bytearray, memoryview)):
+            raise ValueError("SlotState.frombytes takes bytes")
+        b = bytes(b)
+        fixed = len(_STATE_MAGIC) + 8
+        if len(b) < fixed or b[:len(_STATE_MAGIC)] != _STATE_MAGIC:
+            raise ValueError("not a SlotState: the magic is missing")
+        version, hlen = struct.unpack("<II", b[len(_STATE_MAGIC):fixed])
+        if version != _STATE_VERSION:
+            raise ValueError(f"SlotState version {version}; this package reads version {_STATE_VERSION}")
+        if hlen > len(b) - fixed:
+            raise ValueError("SlotState: truncated header")
+        try:
+            head = json.loads(b[fixed:fixed + hlen].decode())
+        except (UnicodeDecodeError, ValueError):
+            raise ValueError("SlotState: the header is not JSON") from None
+        if not isinstance(head, dict) or set(head) != {"kind", "layout", "plan", "seed", "draw_slot", "floats", "stages"}:
+            raise ValueError("SlotState: the header does not have the fields of this version")
+        is_int = lambda v: isinstance(v, int) and not isinstance(v, bool)
+        if (head["kind"] not in STATE_KINDS or not isinstance(head["layout"], list) or not isinstance(head["plan"], list)
+                or not all(is_int(v) for v in head["plan"])
+                or not all(v is None or is_int(v) for v in (head["seed"], head["draw_slot"]))):
+            raise ValueError("SlotState: a header field has the wrong type")
+        payload = b[fixed + hlen:]
+        floats, lens = head["floats"], head["stages"]
+        if (floats is None) == (lens is None) or (lens is None) == (head["kind"] == "at_rate"):
+            raise ValueError("SlotState: a state holds either floats or, for kind 'at_rate', stages")
+        if lens is None:
+            if not is_int(floats) or floats < 0 or len(payload) != 4 * floats:
+                raise ValueError(f"SlotState: the header announces {floats} floats, the payload has {len(payload)} bytes")
+            data = torch.from_numpy(np.frombuffer(payload, dtype="<f4").astype(np.float32))
+            stages = None
+        else:
+            if not isinstance(lens, list) or not all(is_int(v) and v >= 0 for v in lens) or sum(lens) != len(payload):
+                raise ValueError("SlotState: the stage lengths do not add up to the payload")
+            stages, at = [], 0
+            for n in lens:
+                stages.append(SlotState.frombytes(payload[at:at + n]))
+                at += n
+            data = torch.empty(0, dtype=torch.float32)
+        return SlotState(head["kind"], head["layout"], head["plan"], data, head["seed"], head["draw_slot"], stages)
+
+
+def _slot_list(which, slots: int, what: str) -> List[int]:
+    """Slot numbers of ``save`` / ``load`` in the caller's order (state j belongs to slot j of the list); no slot twice."""
+    if isinstance(which, torch.Tensor) or isinstance(which, (str, bytes)) or not isinstance(which, Iterable):
+        raise ValueError(f"{what}: slots must be given as a python collection of ints")
+    which = list(which)
+    if any(isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < slots for v in which):
+        raise ValueError(f"{what}: slot numbers lie in 0 .. {slots - 1}")
+    if len(set(which)) != len(which):
+        raise ValueError(f"{what}: a slot appears twice")
+    return which
+
+
 class _Slots:
     """What every sessions class shares (``self.B`` slots on ``self.device``): the per-slot host plan ``self.sessions``,
     ``positions``, ``drop`` / ``reset``, the one pinned copy that takes a call's tables to the device, and the zeroing of the
@@ -680,16 +821,154 @@ class _Slots:
         self._table = None          # device int64 buffer of the call's tables; it only grows
         self._staging = []          # [(pinned int64 buffer, event of the copy that last read it)] * 2
         self._turn = 0
+        self._state_tab = None      # (host view table, its device copy, floats per slot) of save / load, built at first use
 
     @property
     def positions(self) -> List[int]:
         return self.sessions.positions
+
+    # ------------------------------------------------------------------ save / load of a slot's stream
+    def _state_views(self):
+        """The view table of idv_stream_state_gather / _scatter from ``_zero_views`` -> (host int64 [n_views][4], its device
+        copy, floats per slot).  Built once: the state buffers are allocated at construction and never move."""
+        if self._state_tab is None:
+            rows, off = [], 0
+            for buf, outer, inner in self._zero_views:
+                if buf.dtype != torch.float32 or not buf.is_contiguous() or buf.numel() != outer * self.B * inner:
+                    raise L.IdvError("a state view does not cover its buffer as [outer][slots][inner] float32")
+                rows += [buf.data_ptr(), outer, inner, off]
+                off += outer * inner
+            host = torch.tensor(rows, dtype=torch.int64)
+            self._state_tab = (host, host.to(self.device), off)
+        return self._state_tab
+
+    def _state_layout(self):
+        return self._state_head() + (tuple((int(o), int(n)) for _, o, n in self._zero_views),) + self._state_extra()
+
+    def _state_head(self):
+        return (self.n_fft, self.hop, self.win)
+
+    def _state_extra(self):
+        return ()
+
+    def _state_of(self, b: int, data: torch.Tensor) -> "SlotState":
+        return SlotState(self._state_kind, self._state_layout(), self.sessions.slot_state(b), data)
+
+    def _state_table_check(self, slots: List[int], what: str):
+        """A bad table never reaches a kernel: both host tables are held to idv_stream_state_check."""
+        host, _, per = self._state_views()
+        sl = torch.tensor(slots, dtype=torch.int64)
+        rc = L.lib().idv_stream_state_check(L._P(host.data_ptr()), host.numel() // 4, self.B, L._P(sl.data_ptr()), len(slots), per)
+        if rc != 0:
+            raise ValueError(f"{what}: idv_stream_state_check refused the tables (status {rc})")
+        return sl
+
+    def save(self, slots) -> List["SlotState"]:
+        """The streams of these slots as they stand, one :class:`SlotState` per slot in the order given: one gather launch on
+        the current stream and no host synchronisation; the ``data`` of the states are rows of one device tensor.  The slots
+        are untouched: saving is a fork, and a caller that means a move ``drop``s them afterwards.
+
+        A state may be loaded into ANY slot of any sessions object of the same kind and layout (``load``), on any device, with
+        either conv engine and any ``frames_per_launch``.  Into an object with the same number of slots the stream continues bit
+        for bit as if it had never moved; into one with another number of slots it continues within the streaming tolerance
+        (1e-4 relative), because the K split of the conv blocks depends on the batch.  The weights are the
+        caller's to match: nothing in a state identifies them."""
+        slots = _slot_list(slots, self.B, "save")
+        if not slots:
+            return []
+        sl = self._state_table_check(slots, "save")
+        _, views, per = self._state_views()
+        with torch.cuda.device(self.device):
+            out = torch.empty(len(slots), per, dtype=torch.float32, device=self.device)
+            table = self._upload(sl)
+            call("idv_stream_state_gather", p(views), i(views.numel() // 4), i(self.B), L._P(table.data_ptr()), i(len(slots)), p(out),
+                 ll(per), stream_ptr())
+        return [self._state_of(b, out[j]) for j, b in enumerate(slots)]
+
+    def load(self, slots, states, overwrite: bool = False):
+        """Put ``states[j]`` (from ``save``, possibly by way of ``.cpu()`` / ``tobytes()`` / another device) into slot
+        ``slots[j]``, which then continues that stream.  Every guard runs on the host before any GPU work and before any
+        bookkeeping changes (``ValueError``): as many states as slots, no slot twice, ``kind`` and ``layout`` equal to this
+        object's, a plan that a stream of its n samples reaches, and a target at position 0 unless ``overwrite=True`` (the
+        stream it served is then abandoned without output).  Then one upload (states on the CPU travel with the slot list in
+        the one pinned copy), one scatter launch, and the slots' plans are set."""
+        slots = self._load_check(slots, states, overwrite)
+        self._load_apply(slots, states)
+
+    def _load_check(self, slots, states, overwrite: bool) -> List[int]:
+        """Every guard of ``load``; nothing changes -> the slot list."""
+        slots = _slot_list(slots, self.B, "load")
+        if isinstance(states, SlotState) or not isinstance(states, Iterable):
+            raise ValueError("load: states must be a list of SlotState, one per slot")
+        states = list(states)
+        if len(states) != len(slots):
+            raise ValueError(f"load: {len(states)} states for {len(slots)} slots")
+        if not slots:
+            return slots
+        layout, per = self._state_layout(), self._state_views()[2]
+        pos = self.positions
+        for b, st in zip(slots, states):
+            if not isinstance(st, SlotState):
+                raise ValueError("load: states must be a list of SlotState, one per slot")
+            if st.kind != self._state_kind:
+                raise ValueError(f"load: a state of kind {st.kind!r} does not fit {type(self).__name__} (kind {self._state_kind!r})")
+            if st.layout != layout:
+                raise ValueError(f"load: the state's layout {st.layout} is not this object's {layout}: another model shape, "
+                                 "n_fft / hop / win or class options")
+            d = st.data
+            if not isinstance(d, torch.Tensor) or d.dtype != torch.float32 or d.dim() != 1 or d.numel() != per:
+                raise ValueError(f"load: a state's data must be a float32 tensor of {per} floats")
+            self.sessions.check_slot_state(st.plan)
+            self._state_check_extra(st)
+            if pos[b] and not overwrite:
+                raise ValueError(f"load: slot {b} is {pos[b]} samples into a signal; end or drop it first, or pass overwrite=True")
+        self._state_table_check(slots, "load")
+        return slots
+
+    def _state_check_extra(self, st: "SlotState"):
+        pass
+
+    def _load_apply(self, slots: List[int], states):
+        if not slots:
+            return
+        states = list(states)
+        _, views, per = self._state_views()
+        n = len(slots)
+        with torch.cuda.device(self.device):
+            if all(st.data.device.type == "cpu" for st in states):
+                # the slot list and the records in one pinned copy: the floats ride behind the slots, two to an int64
+                host = torch.zeros(n + (n * per + 1) // 2, dtype=torch.int64)
+                host[:n] = torch.tensor(slots, dtype=torch.int64)
+                host[n:].view(torch.float32)[:n * per].copy_(torch.cat([st.data for st in states]))
+                table = self._upload(host)
+                rec = L._P(table.data_ptr() + 8 * n)
+            else:
+                first = states[0].data
+                rows = all(st.data.device == self.device and st.data.is_contiguous() and
+                           st.data.untyped_storage().data_ptr() == first.untyped_storage().data_ptr() and
+                           st.data.data_ptr() == first.data_ptr() + 4 * per * j for j, st in enumerate(states))
+                # rows of one tensor on this device, in order (what save returned): read where they lie; else gathered here
+                keep = first if rows else torch.stack([st.data.to(self.device) for st in states])
+                table = self._upload(torch.tensor(slots, dtype=torch.int64))
+                rec = p(keep)
+            call("idv_stream_state_scatter", p(views), i(views.numel() // 4), i(self.B), L._P(table.data_ptr()), i(n), rec, ll(per),
+                 stream_ptr())
+        for b, st in zip(slots, states):
+            self.sessions.set_slot_state(b, st.plan)
+            self._state_set_extra(b, st)
+
+    def _state_set_extra(self, b: int, st: "SlotState"):
+        pass
+
+    def _ended(self, slots: List[int]):
+        """Hook: these slots' signals have ended or were dropped (their state is zeroed)."""
 
     def reset(self):
         """Zero every slot's state and bookkeeping."""
         super().reset()
         if hasattr(self, "sessions"):
             self.sessions.drop(range(self.B))
+            self._ended(list(range(self.B)))
 
     def drop(self, slots):
         """Abandon the signals of these slots: nothing is returned for them and their state is zeroed; their next samples begin
@@ -698,6 +977,7 @@ class _Slots:
         if not slots:
             return
         self.sessions.drop(slots)
+        self._ended(slots)
         with torch.cuda.device(self.device):
             table = self._upload(torch.tensor(slots, dtype=torch.int64))
             self._zero(L._P(table.data_ptr()), len(slots))
@@ -763,6 +1043,7 @@ class _Slots:
                 if ring_due:
                     call("idv_stream_ring_rows", p(self.ring), i(R), p(x), ll(ldx), i(n), L._P(table), i(B), s)
                 self._zero(L._P(zero), len(plan.zero))
+                self._ended(plan.zero)
             return self._finish(y, ldy), plan.m
 
     def _tables(self, plan: SessionCall):
@@ -794,6 +1075,8 @@ class StreamingSessions(_Slots, _Streamer):
         y, m = st.push(x, counts=None, end=())   # x: [slots, n] float32 on the model's GPU
         st.drop(slots)                           # abandon the signals of these slots: no output, state zeroed
         st.positions                             # samples received per slot for its current signal (host list)
+        states = st.save(slots)                  # the streams of these slots as SlotState values; the slots go on untouched
+        st.load(slots, states, overwrite=False)  # continue those streams in these slots (of this or another object)
 
     ``counts[b]`` (host ints, 0 .. n; None: n for all) says how many leading samples of row b are new for slot b; nothing at or
     past ``x[b, counts[b]]`` is read.  ``end`` names the slots whose signal ends after this call's samples ("push, then flush"):
@@ -807,6 +1090,8 @@ class StreamingSessions(_Slots, _Streamer):
     all tables of a call go to the device in one copy from a pinned staging buffer, whose reuse waits on the event of the copy
     that last read it (two buffers alternate, so that copy is two calls back).
     """
+
+    _state_kind = "dccrn"
 
     def __init__(self, model, slots: int, frames_per_launch: int = 64, max_columns: int = 4096, conv: str = "valu"):
         super().__init__(model, slots, frames_per_launch, max_columns, conv)
@@ -1489,10 +1774,12 @@ def decoder_rows(rows: List[List[int]], ns: int) -> List[List[int]]:
     return [r for r in rows for _ in range(ns)]
 
 
-def vae_session_tables(plan: SessionCall, ns: int, seeds: Sequence[int] = ()) -> List[int]:
+def vae_session_tables(plan: SessionCall, ns: int, seeds: Sequence[int] = (), draw_slots: Sequence[int] = ()) -> List[int]:
     """The host side of the one copy a VAE sessions call makes: per launch group the slots' table [B][NF] followed by its
-    decoder-side table [B * ns][NF], then the slots to zero, then ``seeds`` (one per slot, as they stand when the call is made)."""
-    return [v for g in plan.groups for r in g.rows + decoder_rows(g.rows, ns) for v in r] + list(plan.zero) + list(seeds)
+    decoder-side table [B * ns][NF], then the slots to zero, then ``seeds`` (one per slot, as they stand when the call is made),
+    then ``draw_slots`` (one per slot; empty while every slot draws as itself)."""
+    return ([v for g in plan.groups for r in g.rows + decoder_rows(g.rows, ns) for v in r] + list(plan.zero) + list(seeds) +
+            list(draw_slots))
 
 
 class _VAELaunch(NamedTuple):
@@ -1502,6 +1789,7 @@ class _VAELaunch(NamedTuple):
     rows: object
     rows_n: object
     seeds: object
+    draws: object = None        # the slots' draw slots [B], or None while every slot draws as itself
 
 
 class StreamingVAESessions(_Slots, _VAEStreamer):
@@ -1513,6 +1801,7 @@ class StreamingVAESessions(_Slots, _VAEStreamer):
         st.drop(slots); st.positions; st.reset()
         st.seed; st.seeds; st.set_seed(slots, seed)
         er, ei = st.eps(t0, k)                   # [slots, ns, k, zdim] each, the generator of StreamingVAE.eps, every slot's own seed
+        st.save(slots); st.load(slots, states); st.draw_slots
 
     Slot b's samples are bit-identical to what ``StreamingVAE(noisy_encoder, decoder, batch=slots, seed=st.seeds[b],
     latent=latent, conv=conv)`` returns for the same signal in slot b, whatever the other slots do and for every signal the slot
@@ -1523,9 +1812,17 @@ class StreamingVAESessions(_Slots, _VAEStreamer):
     the host before any GPU work and before any bookkeeping changes.  Per launch group the kernels take two tables, the slots'
     (:class:`SessionPlan`) for the encoder side and :func:`decoder_rows` of it for the decoder side; both tables of every group,
     the list of slots to zero and the slots' seeds go to the device in one copy (:func:`vae_session_tables`).
+
+    ``save`` / ``load`` (:class:`_Slots`): a state carries the slot's seed and its draw slot, the slot number in the counter
+    word of its draws.  ``load`` gives the target slot that seed (it stays afterwards, as a ``set_seed`` value does) and that
+    draw slot until the signal ends or is dropped (``draw_slots``), so the moved stream continues with the bits of
+    ``StreamingVAE(..., batch=slots, seed=<the original seed>)`` for the signal in the original slot.  A loaded slot is in
+    mid-signal: its seed cannot be changed.  Only while some slot draws as another does the object call
+    ``idv_stream_eps_pair_rows_as``; otherwise it launches what it always launched.
     """
 
     _name = "StreamingVAESessions"
+    _state_kind = "vae"
     _skip_halves = 2
     _eps_outputs = 2               # tensors ``eps`` returns: one pair, or the speech and the noise pair
     _per_sample = True             # overlap-add at batch B * ns (self.ifr, then the mean over the samples) or at batch B (self.ifr_b)
@@ -1542,7 +1839,8 @@ class StreamingVAESessions(_Slots, _VAEStreamer):
 
     def _init_slots(self):
         super()._init_slots()
-        self._own_seeds = {}        # slot -> the seed set_seed gave it
+        self._own_seeds = {}        # slot -> the seed set_seed or load gave it
+        self._moved = {}            # slot -> the slot number its loaded stream draws with, until that signal ends or is dropped
 
     # ------------------------------------------------------------------ seeds
     @property
@@ -1561,6 +1859,44 @@ class StreamingVAESessions(_Slots, _VAEStreamer):
     def seeds(self) -> List[int]:
         """The seed every slot draws with: its own where ``set_seed`` gave it one, else ``seed``."""
         return [self._own_seeds.get(b, self._seed) for b in range(self.B)]
+
+    @property
+    def draw_slots(self) -> List[int]:
+        """The slot number every slot draws with (counter word ``draw_slot * ns + s``): its own, except for a slot that
+        ``load`` gave a stream from elsewhere, which keeps that stream's until its signal ends or is dropped."""
+        return [self._moved.get(b, b) for b in range(self.B)]
+
+    def _draw_table(self) -> List[int]:
+        """What travels behind the seeds: nothing while every slot draws as itself (idv_stream_eps_pair_rows), else the draw
+        slots (idv_stream_eps_pair_rows_as)."""
+        return self.draw_slots if any(v != b for b, v in self._moved.items()) else []
+
+    def _ended(self, slots):
+        for b in slots:
+            self._moved.pop(b, None)
+
+    # ------------------------------------------------------------------ save / load
+    def _state_extra(self):
+        return (self.ns, self.zdim, self.H, self.latent, self.average)
+
+    def _state_of(self, b: int, data: torch.Tensor) -> SlotState:
+        st = super()._state_of(b, data)
+        st.seed, st.draw_slot = self.seeds[b], self.draw_slots[b]
+        return st
+
+    def _state_check_extra(self, st: SlotState):
+        if st.seed is None or st.draw_slot is None:
+            raise ValueError("load: a VAE state carries the seed and the draw slot of its stream")
+        check_seed(st.seed)
+        v = st.draw_slot
+        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v or (v + 1) * self.ns > 2 ** 31:
+            raise ValueError("load: draw_slot must be an int >= 0 with (draw_slot + 1) * num_samples <= 2^31")
+
+    def _state_set_extra(self, b: int, st: SlotState):
+        # the slot now serves a signal in mid-stream: its seed is the stream's (and stays, as a set_seed value does), and it
+        # draws as the slot the stream began in until the signal ends
+        self._own_seeds[b] = st.seed
+        self._moved[b] = st.draw_slot
 
     def set_seed(self, slots, seed):
         """Give these slots a seed of their own; each must be between signals (position 0)."""
@@ -1584,10 +1920,15 @@ class StreamingVAESessions(_Slots, _VAEStreamer):
         row[ROW_FIELDS.index("t0")], row[ROW_FIELDS.index("k")] = t0, k
         out = torch.empty(self._eps_outputs, B, self.ns, k, self.zdim, dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            table = self._upload(torch.tensor(row * B + self.seeds, dtype=torch.int64))
+            draws = self._draw_table()
+            table = self._upload(torch.tensor(row * B + self.seeds + draws, dtype=torch.int64))
             nr, ni = (p(out[2]), p(out[3])) if self._eps_outputs == 4 else (p(None), p(None))
-            call("idv_stream_eps_pair_rows", L._P(table.data_ptr() + 8 * B * NF), L._P(table.data_ptr()), i(B), i(self.ns),
-                 i(self.zdim), i(k), p(out[0]), p(out[1]), nr, ni, stream_ptr())
+            if draws:
+                call("idv_stream_eps_pair_rows_as", L._P(table.data_ptr() + 8 * B * NF), L._P(table.data_ptr() + 8 * B * (NF + 1)),
+                     L._P(table.data_ptr()), i(B), i(self.ns), i(self.zdim), i(k), p(out[0]), p(out[1]), nr, ni, stream_ptr())
+            else:
+                call("idv_stream_eps_pair_rows", L._P(table.data_ptr() + 8 * B * NF), L._P(table.data_ptr()), i(B), i(self.ns),
+                     i(self.zdim), i(k), p(out[0]), p(out[1]), nr, ni, stream_ptr())
         return tuple(out)
 
     # ------------------------------------------------------------------ push
@@ -1596,10 +1937,12 @@ class StreamingVAESessions(_Slots, _VAEStreamer):
             return super().push(x, counts, end)
 
     def _tables(self, plan: SessionCall):
-        return vae_session_tables(plan, self.ns, self.seeds), (self.B + self.Bn) * NF
+        return vae_session_tables(plan, self.ns, self.seeds, self._draw_table()), (self.B + self.Bn) * NF
 
     def _launch(self, g: Group, tables: int, behind: int):
-        return _VAELaunch(g.k, L._P(tables), L._P(tables + 8 * self.B * NF), L._P(behind))       # the seeds lie behind the zero list
+        # the seeds lie behind the zero list, and behind them the draw slots of an object that serves a loaded stream
+        draws = L._P(behind + 8 * self.B) if self._draw_table() else None
+        return _VAELaunch(g.k, L._P(tables), L._P(tables + 8 * self.B * NF), L._P(behind), draws)
 
     def _ola_site(self):
         # the overlap-add runs on the decoder side's rows (one per sample) or, behind an estimator, on the slots' rows
@@ -1627,7 +1970,12 @@ class StreamingVAESessions(_Slots, _VAEStreamer):
         the noise pair behind them where ``eps_buf`` holds one (two decoder chains)."""
         e = [p(t) for t in self.eps_buf]
         nr, ni = e[2:] if len(e) == 4 else (p(None), p(None))
-        call("idv_stream_eps_pair_rows", c.seeds, c.rows, i(self.B), i(self.ns), i(self.zdim), i(c.k), e[0], e[1], nr, ni, stream_ptr())
+        if c.draws is not None:
+            call("idv_stream_eps_pair_rows_as", c.seeds, c.draws, c.rows, i(self.B), i(self.ns), i(self.zdim), i(c.k), e[0], e[1], nr,
+                 ni, stream_ptr())
+        else:
+            call("idv_stream_eps_pair_rows", c.seeds, c.rows, i(self.B), i(self.ns), i(self.zdim), i(c.k), e[0], e[1], nr, ni,
+                 stream_ptr())
         return tuple(e)
 
     def _repeat(self, c, di: int, sk: int, x, xn, Tp: int, Jp: int, Jpn: int):
@@ -1659,7 +2007,11 @@ class StreamingVAETwoLatentsSessions(_TwoLatents, StreamingVAESessions):
     """
 
     _name = "StreamingVAETwoLatentsSessions"
+    _state_kind = "two_latents"
     _eps_outputs = 4
+
+    def _state_extra(self):
+        return (self.ns, self.zdim, self.H, self.outtype, self.phase, self.average)
 
     def __init__(self, noisy_encoder, speech_decoder, noise_decoder, slots: int, outtype: str = "phase_mask", phase: int = 2,
                  seed: int = 0, frames_per_launch: int = 64, max_columns: int = 4096, conv: str = "valu"):
@@ -1778,6 +2130,20 @@ class ResampleSessionPlan:
 
     def restore(self, snap):
         self._n, self._parity = snap[0].copy(), snap[1].copy()
+
+    def slot_state(self, b: int):
+        """Slot b's host integers (n, parity)."""
+        return (int(self._n[b]), int(self._parity[b]))
+
+    def set_slot_state(self, b: int, v):
+        self.check_slot_state(v)
+        self._n[b], self._parity[b] = v
+
+    def check_slot_state(self, v):
+        """The guard on a slot's host integers that come from outside (``load``): n >= 0 and parity in {0, 1}."""
+        if (not isinstance(v, (tuple, list)) or len(v) != 2 or any(isinstance(q, bool) or not isinstance(q, int) for q in v)
+                or not 0 <= v[0] < 2 ** 50 or v[1] not in (0, 1)):
+            raise ValueError("a resampled slot's plan is two ints (n, parity) with 0 <= n < 2^50 and parity 0 or 1")
 
     def n_final(self, P):
         return np.maximum(0, -((self.half - P * self.up) // self.down))
@@ -1905,6 +2271,11 @@ class StreamingResamplerSessions(_Slots):
     on the host before any GPU work and before any bookkeeping changes; the table of a call is held to
     ``idv_stream_resample_rows_check`` before it goes to the device.
     """
+
+    _state_kind = "resampler"
+
+    def _state_head(self):
+        return (self.up, self.down, self.H)
 
     def __init__(self, fs_in: int, fs_out: int, slots: int, device=None, taps_mode: str = "auto"):
         up, down = _check_rates("StreamingResamplerSessions", fs_in, fs_out)
@@ -2054,6 +2425,45 @@ class SessionsAtRate:
         if self.down is not None:
             self.down.drop(slots)
             self.up.drop(slots)
+
+    def save(self, slots) -> List[SlotState]:
+        """The streams of these slots through all three stages, one :class:`SlotState` of kind ``"at_rate"`` per slot whose
+        ``stages`` are the states of the down-resampler, the network and the up-resampler (``fs == model_fs``: the wrapped
+        sessions' own states).  Three gather launches, no host synchronisation; the slots are untouched."""
+        if self.down is None:
+            return self.sessions.save(slots)
+        slots = _slot_list(slots, self.B, "save")
+        layout = (self.fs, self.model_fs)
+        stages = zip(self.down.save(slots), self.sessions.save(slots), self.up.save(slots))
+        return [SlotState("at_rate", layout, (), torch.empty(0, dtype=torch.float32), stages=st) for st in stages]
+
+    def load(self, slots, states, overwrite: bool = False):
+        """``load`` of the three stages (see :meth:`_Slots.load`).  Every guard of every stage runs before anything changes:
+        if one stage refuses, none is touched.  Beyond the stages' own guards the three plans must belong together: the network
+        has received what the down-resampler has returned, and the up-resampler what the network has returned."""
+        if self.down is None:
+            return self.sessions.load(slots, states, overwrite)
+        slots = _slot_list(slots, self.B, "load")
+        if isinstance(states, SlotState) or not isinstance(states, Iterable):
+            raise ValueError("load: states must be a list of SlotState, one per slot")
+        states = list(states)
+        if len(states) != len(slots):
+            raise ValueError(f"load: {len(states)} states for {len(slots)} slots")
+        for st in states:
+            if not isinstance(st, SlotState) or st.kind != "at_rate" or st.stages is None or len(st.stages) != 3:
+                raise ValueError("load: SessionsAtRate takes states of kind 'at_rate' with three stages")
+            if st.layout != (self.fs, self.model_fs):
+                raise ValueError(f"load: the state's rates {st.layout} are not this object's {(self.fs, self.model_fs)}")
+        parts = [[st.stages[j] for st in states] for j in range(3)]
+        objs = (self.down, self.sessions, self.up)
+        for obj, part in zip(objs, parts):
+            obj._load_check(slots, part, overwrite)
+        for d, net, u in zip(*parts):
+            if net.plan[0] != int(self.down.sessions.n_final(d.plan[0])) or u.plan[0] != net.plan[2]:
+                raise ValueError("load: the three stages of a state do not belong together (the network has received what the "
+                                 "down-resampler returned, the up-resampler what the network returned)")
+        for obj, part in zip(objs, parts):
+            obj._load_apply(slots, part)
 
     def set_seed(self, slots, seed):
         """Forwarded to the wrapped VAE sessions (a slot's seed can be set only between signals)."""

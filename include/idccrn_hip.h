@@ -891,6 +891,47 @@ int idv_stream_estimate(const float* speech, const float* noise, const float* X,
 int idv_stream_eps_pair_rows(const long long* seeds, const long long* rows, int B, int ns, int zdim, int k_launch, float* eps_sr,
                              float* eps_si, float* eps_nr, float* eps_ni, void* stream);
 
+/* ---- save, load and move a slot's stream (stream_state.hip, stream_io.hip; streaming._Slots.save / load of every sessions
+ * class; additive entries: IDV_ABI_VERSION is unchanged).
+ *
+ * The per-slot state of a sessions object lies in n_views device buffers of floats, view j an [outer_j][B][inner_j] array.  A
+ * slot's RECORD is the concatenation of its [outer_j][inner_j] blocks in view order, per_slot = sum_j outer_j inner_j floats:
+ * element (o, i) of view j sits at offset_j + o inner_j + i.  views is a table [n_views][IDV_STATE_VIEW_FIELDS] of long long,
+ * slots a list of n_slots slot numbers; both are DEVICE arrays for gather / scatter and HOST arrays for the check. */
+#define IDV_STATE_MAX_VIEWS 64
+#define IDV_STATE_VIEW_FIELDS 4
+#define IDV_STATE_VIEW_ADDR 0     /* device address of the buffer (floats) */
+#define IDV_STATE_VIEW_OUTER 1
+#define IDV_STATE_VIEW_INNER 2
+#define IDV_STATE_VIEW_OFFSET 3   /* of the view inside a record, in floats */
+/* Host only, touches no GPU: IDV_EINVAL unless 1 <= n_views <= 64, every address is non-zero, every outer and inner is
+ * positive, the offsets start at 0, increase and tile [0, per_slot) exactly (offset_{j+1} = offset_j + outer_j inner_j, the last
+ * view ends at per_slot: no overlap, no gap), 1 <= n_slots <= B, every slot lies in 0 .. B-1 and no slot appears twice.  Call it
+ * on the host copies before they are uploaded: the two entries below cannot look.  That buffer j really holds outer_j B inner_j
+ * floats is the caller's to guarantee. */
+int idv_stream_state_check(const long long* views_host, int n_views, int B, const long long* slots_host, int n_slots,
+                           long long per_slot);
+/* out[n_slots][per_slot] (contiguous) <- the records of the named slots, in ONE launch whatever n_views and n_slots are.  The
+ * view table is staged in LDS and every element finds its view by a bounded binary search over the offsets.  out is written
+ * coalesced; the buffers are read contiguously for inner > 1 and at stride B for inner = 1.  Plain loads and stores, no atomics;
+ * nothing but the named slots' elements is read, and nothing of the buffers is written.  IDV_EINVAL (nothing launched) for a
+ * NULL pointer, n_views outside 1 .. 64, n_slots outside 1 .. B or per_slot <= 0. */
+int idv_stream_state_gather(const long long* views, int n_views, int B, const long long* slots, int n_slots, float* out,
+                            long long per_slot, void* stream);
+/* The records in[n_slots][per_slot] -> the named slots: the same kernel with the copy turned round.  Every element of every
+ * view of a named slot is written, nothing else; a slot named twice would be written twice in no defined order, which is why
+ * idv_stream_state_check refuses it. */
+int idv_stream_state_scatter(const long long* views, int n_views, int B, const long long* slots, int n_slots, const float* in,
+                             long long per_slot, void* stream);
+/* idv_stream_eps_pair_rows with a draw identity per slot: draw_slots is a device array [B], and slot b draws with the counter
+ * (t0_b + tl, draw_slots[b]*ns + s, u) in place of (t0_b + tl, b*ns + s, u), so that a stream saved in slot draw_slots[b] and
+ * loaded into slot b continues with the draws it would have had.  With draw_slots[b] = b for every b it writes the bits of
+ * idv_stream_eps_pair_rows; everything else (seeds, rows, the outputs, the single-pair form, the refusals) is that entry's.
+ * draw_slots[b] * ns + ns - 1 must fit in 32 bits.  The same kernel source, compiled with one more template flag whose pointer
+ * is the last kernel argument; idv_stream_eps_pair_rows itself is unchanged. */
+int idv_stream_eps_pair_rows_as(const long long* seeds, const long long* draw_slots, const long long* rows, int B, int ns, int zdim,
+                                int k_launch, float* eps_sr, float* eps_si, float* eps_nr, float* eps_ni, void* stream);
+
 /* ---- streaming at any sample rate: stateful polyphase resampler (stream_resample.hip; streaming.StreamingResampler,
  * StreamingResamplerSessions, AtRate, SessionsAtRate; additive entries: IDV_ABI_VERSION is unchanged).
  *

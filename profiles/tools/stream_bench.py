@@ -3,6 +3,7 @@
     python profiles/tools/stream_bench.py [--batches 1,16,128,512,1024] [--seconds 2] [--catchup] [--far-seconds 3600] [--sessions]
                                            [--conv valu|mfma|both] [--vae [--sessions]]
                                            [--two-latents [--sessions] [--outtype O] [--phase P]]
+                                           [--state]
 
 Per line: device time per push (HIP events around >= --seconds of pushes after warm-up), host wall time per push (synchronised),
 the real-time factor (hop / 16 kHz = 6.25 ms over the wall time) and the algorithmic GFLOP per push (4 real products per complex
@@ -26,7 +27,11 @@ streaming.StreamingVAETwoLatents (metric "two_latents_push"; --outtype, default 
 encoder and speech decoder, StreamingVAE at the same B, ns and engine (metric "vae_push").  --two-latents --sessions measures
 streaming.StreamingVAETwoLatentsSessions (metric "two_latents_sessions_push": every slot active at the staggered positions of
 --sessions, counts as a host list on every push) and, right after it in the same process with the same three models, the lock-step
-StreamingVAETwoLatents at the same B and engine (metric "two_latents_push").
+StreamingVAETwoLatents at the same B and engine (metric "two_latents_push").  --state measures save + load of streaming.StreamingSessions
+(metric "state_save_load", default batches 16,256): after the hop pushes of --sessions (reported in the same line) the states of
+1 slot and of all slots are saved and loaded back into their own slots (overwrite=True, so the streams go on as they were), with
+the states left on the device and taken through the host (.cpu() of every state, then load from the CPU states); device time from
+events around the repetitions, wall time synchronised after every save + load.
 """
 from __future__ import annotations
 
@@ -170,6 +175,39 @@ def run(B, seconds, n=HOP, far_seconds=0, sessions=False, conv="valu", vae=False
     return st, dev_ms, wall_ms, pos
 
 
+def state_round_trips(st, reps_dev=20, reps_host=5):
+    """save + load of 1 and of all slots of a sessions object back into their own slots -> one dict per (slots, via)."""
+    out = []
+    for slots in ([0], list(range(st.B))):
+        for via in ("device", "host"):
+            def once():
+                states = st.save(slots)
+                if via == "host":
+                    states = [s.cpu() for s in states]
+                st.load(slots, states, overwrite=True)
+                return states
+            states = once()
+            once()
+            torch.cuda.synchronize()
+            reps = reps_dev if via == "device" else reps_host
+            walls = []
+            for _ in range(reps):
+                t0 = time.perf_counter()
+                once()
+                torch.cuda.synchronize()
+                walls.append(time.perf_counter() - t0)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(reps):
+                once()
+            e1.record()
+            torch.cuda.synchronize()
+            out.append({"slots_moved": len(slots), "via": via, "floats_per_slot": int(states[0].data.numel()),
+                        "device_ms_per_save_load": round(e0.elapsed_time(e1) / reps, 4),
+                        "wall_ms_per_save_load": round(1e3 * sorted(walls)[len(walls) // 2], 4), "reps": reps})
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", default=None)
@@ -182,7 +220,12 @@ def main():
     ap.add_argument("--two-latents", action="store_true")
     ap.add_argument("--outtype", default="phase_mask")
     ap.add_argument("--phase", type=int, default=2)
+    ap.add_argument("--state", action="store_true")
     a = ap.parse_args()
+    if a.state and (a.vae or a.two_latents or a.catchup or a.far_seconds or a.conv == "both"):
+        ap.error("--state measures save + load of StreamingSessions next to its hop pushes only")
+    if a.state and a.batches is None:
+        a.batches = "16,256"
     if a.two_latents and (a.catchup or a.far_seconds):
         ap.error("--two-latents measures hop pushes of StreamingVAETwoLatents / StreamingVAETwoLatentsSessions and StreamingVAE only")
     a.vae = a.vae or a.two_latents
@@ -196,6 +239,14 @@ def main():
     conv1 = "mfma" if a.conv == "both" else a.conv            # the single-engine lines below
     for B in [int(v) for v in a.batches.split(",") if v]:
         for conv, rnd in turns:
+            if a.state:
+                st, dev_ms, wall_ms, _ = run(B, a.seconds, sessions=True, conv=conv)
+                for line in state_round_trips(st):
+                    print(json.dumps({"metric": "state_save_load", "B": B, **line, "push_device_ms": round(dev_ms, 4),
+                                      "push_wall_ms": round(wall_ms, 4), "conv": conv}), flush=True)
+                del st
+                torch.cuda.empty_cache()
+                continue
             if a.two_latents:
                 two_ = (a.outtype, a.phase)
                 # (estimator or None: StreamingVAE, sessions form): the sessions form first, then its lock-step form
