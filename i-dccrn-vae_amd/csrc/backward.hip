@@ -727,7 +727,9 @@ extern "C" int idv_cbn_bwd_apply(const float* dz, const float* y, const float* f
 extern "C" int idv_mask_apply_bwd(const float* mask, const float* X, int x_div, int JpX, const float* dpred,
                                   const float* dpred_c, int F, int B, int T, int Tp, int Jp, float* dmask, float* dX,
                                   void* stream) {
-    if (!mask || !X || !dmask || (!dpred && !dpred_c) || x_div < 1 || F <= 0 || B <= 0 || T <= 0) return IDV_EINVAL;
+    if (!mask || !X || !dmask || (!dpred && !dpred_c) || x_div < 1 || F <= 0 || B <= 0 || T <= 0 || Tp < T + 1 || Jp < B * Tp ||
+        JpX < ((B - 1) / x_div + 1) * Tp)
+        return IDV_EINVAL;
     if (dX && x_div != 1) return IDV_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     idv_launch_zero_guard_cols(dmask, 2 * F, B, T, Tp, Jp, st);
@@ -738,7 +740,7 @@ extern "C" int idv_mask_apply_bwd(const float* mask, const float* X, int x_div, 
 }
 
 extern "C" int idv_complex_to_planar(const float* in_c, float* act, int F, int B, int T, int Tp, int Jp, void* stream) {
-    if (!in_c || !act || F <= 0 || B <= 0 || T <= 0 || Tp < T + 1) return IDV_EINVAL;
+    if (!in_c || !act || F <= 0 || B <= 0 || T <= 0 || Tp < T + 1 || Jp < B * Tp) return IDV_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     idv_launch_zero_guard_cols(act, 2 * F, B, T, Tp, Jp, st);
     hipLaunchKernelGGL(complex_to_planar_kernel, dim3(grid_for((long long)B * F * T)), dim3(256), 0, st, in_c, act, F, B, T, Tp, Jp);

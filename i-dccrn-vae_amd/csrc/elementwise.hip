@@ -28,9 +28,13 @@ __global__ __launch_bounds__(256) void stft_frames_kernel(const float* __restric
         const size_t col = (size_t)b * Tp + t0 + tl + 1;
         for (int k = kq; k < win; k += 8) frames[(size_t)k * Jp + col] = seg[hop * tl + k];
     }
-    // guard column tp == 0 of this utterance
+    // guard columns of this utterance: tp == 0 in its first block, tp > T in its last
     if (blockIdx.x == 0)
         for (int k = threadIdx.x; k < win; k += blockDim.x) frames[(size_t)k * Jp + (size_t)b * Tp] = 0.f;
+    const int ng = Tp - T - 1;
+    if (blockIdx.x == gridDim.x - 1)
+        for (int e = threadIdx.x; e < win * ng; e += blockDim.x)
+            frames[(size_t)(e / ng) * Jp + (size_t)b * Tp + T + 1 + e % ng] = 0.f;
 }
 
 // y[b][s] = env_inv[s + half] * sum_t frames[n = s + half - hop*t - left][b*Tp + t + 1]
@@ -399,12 +403,6 @@ __global__ void datadenorm_bwd_kernel(const float* __restrict__ dout, const floa
     }
 }
 
-__global__ void zero_guard_kernel(float* __restrict__ act, int planes, int B, int Tp, int Jp) {
-    const long long n = (long long)planes * B;
-    for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < n; idx += (long long)gridDim.x * blockDim.x)
-        act[(size_t)(idx / B) * Jp + (size_t)(idx % B) * Tp] = 0.f;
-}
-
 inline int grid_for(long long n, int bs = 256) {
     long long g = (n + bs - 1) / bs;
     return (int)(g > 8192 ? 8192 : (g < 1 ? 1 : g));
@@ -423,7 +421,7 @@ extern "C" int idv_stft_frames(const float* x, int B, int L, int n_fft, int win,
 
 extern "C" int idv_istft_ola(const float* frames, const float* env_inv, int B, int n_fft, int win, int hop, int T, int Tp,
                              int Jp, float* y, void* stream) {
-    if (!frames || !env_inv || !y || B <= 0 || T < 2 || Tp < T + 1) return IDV_EINVAL;
+    if (!frames || !env_inv || !y || B <= 0 || T < 2 || Tp < T + 1 || Jp < B * Tp) return IDV_EINVAL;
     hipLaunchKernelGGL(istft_ola_kernel, dim3(grid_for((long long)B * hop * (T - 1))), dim3(256), 0, (hipStream_t)stream,
                        frames, env_inv, B, n_fft, win, hop, T, Tp, Jp, y);
     return idv_launch_status();
@@ -431,8 +429,10 @@ extern "C" int idv_istft_ola(const float* frames, const float* env_inv, int B, i
 
 extern "C" int idv_mask_apply(const float* mask, const float* X, int x_div, int JpX, float* pred, float* pred_c, int F,
                               int B, int T, int Tp, int Jp, void* stream) {
-    if (!mask || !X || !pred || x_div < 1 || F <= 0 || B <= 0 || T <= 0) return IDV_EINVAL;
-    hipLaunchKernelGGL(zero_guard_kernel, dim3(grid_for(2LL * F * B)), dim3(256), 0, (hipStream_t)stream, pred, 2 * F, B, Tp, Jp);
+    if (!mask || !X || !pred || x_div < 1 || F <= 0 || B <= 0 || T <= 0 || Tp < T + 1 || Jp < B * Tp ||
+        JpX < ((B - 1) / x_div + 1) * Tp)
+        return IDV_EINVAL;
+    idv_launch_zero_guard_cols(pred, 2 * F, B, T, Tp, Jp, (hipStream_t)stream);
     hipLaunchKernelGGL(mask_apply_kernel, dim3(grid_for((long long)B * F * T)), dim3(256), 0, (hipStream_t)stream, mask, X,
                        x_div, JpX, pred, pred_c, F, B, T, Tp, Jp);
     return idv_launch_status();
@@ -440,18 +440,18 @@ extern "C" int idv_mask_apply(const float* mask, const float* X, int x_div, int 
 
 extern "C" int idv_datanorm(const float* X, const float* mean, const float* stdv, int F, int B, int T, int Tp, int Jp, float* out,
                             void* stream) {
-    if (!X || !mean || !stdv || !out || F <= 0 || B <= 0 || T <= 0 || Tp < T + 1) return IDV_EINVAL;
+    if (!X || !mean || !stdv || !out || F <= 0 || B <= 0 || T <= 0 || Tp < T + 1 || Jp < B * Tp) return IDV_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(out, 0, sizeof(float) * 2 * (size_t)F * Jp, st) != hipSuccess) return IDV_ELAUNCH;
+    idv_launch_zero_guard_cols(out, 2 * F, B, T, Tp, Jp, st);
     hipLaunchKernelGGL(datanorm_kernel, dim3(grid_for((long long)B * F * T)), dim3(256), 0, st, X, mean, stdv, F, B, T, Tp, Jp, out);
     return idv_launch_status();
 }
 
 extern "C" int idv_datadenorm(const float* P, const float* mean, const float* stdv, int F, int B, int T, int Tp, int Jp, float* out,
                               float* out_c, void* stream) {
-    if (!P || !mean || !stdv || !out || !out_c || F <= 0 || B <= 0 || T <= 0 || Tp < T + 1) return IDV_EINVAL;
+    if (!P || !mean || !stdv || !out || !out_c || F <= 0 || B <= 0 || T <= 0 || Tp < T + 1 || Jp < B * Tp) return IDV_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(out, 0, sizeof(float) * 2 * (size_t)F * Jp, st) != hipSuccess) return IDV_ELAUNCH;
+    idv_launch_zero_guard_cols(out, 2 * F, B, T, Tp, Jp, st);
     hipLaunchKernelGGL(datadenorm_kernel, dim3(grid_for((long long)B * F * T)), dim3(256), 0, st, P, mean, stdv, F, B, T, Tp, Jp,
                        out, out_c);
     return idv_launch_status();
@@ -459,18 +459,18 @@ extern "C" int idv_datadenorm(const float* P, const float* mean, const float* st
 
 // gradients of idv_datanorm / idv_datadenorm (training with the reference's --data_norm; model/pvae_module.py:217-221, :235-238)
 extern "C" int idv_datanorm_bwd(const float* dout, const float* stdv, int F, int B, int T, int Tp, int Jp, float* dX, void* stream) {
-    if (!dout || !stdv || !dX || F <= 0 || B <= 0 || T <= 0 || Tp < T + 1) return IDV_EINVAL;
+    if (!dout || !stdv || !dX || F <= 0 || B <= 0 || T <= 0 || Tp < T + 1 || Jp < B * Tp) return IDV_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(dX, 0, sizeof(float) * 2 * (size_t)F * Jp, st) != hipSuccess) return IDV_ELAUNCH;
+    idv_launch_zero_guard_cols(dX, 2 * F, B, T, Tp, Jp, st);
     hipLaunchKernelGGL(datanorm_bwd_kernel, dim3(grid_for((long long)B * F * T)), dim3(256), 0, st, dout, stdv, F, B, T, Tp, Jp, dX);
     return idv_launch_status();
 }
 
 extern "C" int idv_datadenorm_bwd(const float* dout, const float* dout_c, const float* stdv, int F, int B, int T, int Tp, int Jp,
                                   float* dP, void* stream) {
-    if ((!dout && !dout_c) || !stdv || !dP || F <= 0 || B <= 0 || T <= 0 || Tp < T + 1) return IDV_EINVAL;
+    if ((!dout && !dout_c) || !stdv || !dP || F <= 0 || B <= 0 || T <= 0 || Tp < T + 1 || Jp < B * Tp) return IDV_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(dP, 0, sizeof(float) * 2 * (size_t)F * Jp, st) != hipSuccess) return IDV_ELAUNCH;
+    idv_launch_zero_guard_cols(dP, 2 * F, B, T, Tp, Jp, st);
     hipLaunchKernelGGL(datadenorm_bwd_kernel, dim3(grid_for((long long)B * F * T)), dim3(256), 0, st, dout, dout_c, stdv, F, B, T, Tp,
                        Jp, dP);
     return idv_launch_status();
@@ -487,7 +487,7 @@ extern "C" int idv_outtype_estimate(const float* speech_c, const float* noise_c,
         Jp < B * Tp)
         return IDV_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(out, 0, sizeof(float) * 2 * (size_t)F * Jp, st) != hipSuccess) return IDV_ELAUNCH;
+    idv_launch_zero_guard_cols(out, 2 * F, B, T, Tp, Jp, st);
     hipLaunchKernelGGL(outtype_kernel, dim3(grid_for((long long)B * F * T)), dim3(256), 0, st, speech_c, noise_c, X, sb, sf, st_, sr,
                        mode, ns, B, F, T, Tp, Jp, out, out_c);
     return idv_launch_status();
@@ -511,7 +511,7 @@ extern "C" int idv_stream_estimate(const float* speech, const float* noise, cons
 }
 
 extern "C" int idv_planar_to_complex(const float* act, float* out_c, int F, int B, int T, int Tp, int Jp, void* stream) {
-    if (!act || !out_c || F <= 0 || B <= 0 || T <= 0) return IDV_EINVAL;
+    if (!act || !out_c || F <= 0 || B <= 0 || T <= 0 || Tp < T + 1 || Jp < B * Tp) return IDV_EINVAL;
     hipLaunchKernelGGL(planar_to_complex_kernel, dim3(grid_for((long long)B * F * T)), dim3(256), 0, (hipStream_t)stream, act,
                        out_c, F, B, T, Tp, Jp);
     return idv_launch_status();

@@ -397,28 +397,32 @@ __global__ __launch_bounds__(256) void stft_frames_kimg_kernel(const float* __re
     }
     __syncthreads();
     const int tl = threadIdx.x & 31;
-    // 33 columns per block: the 32 frames and, in the first block of an utterance, its guard column
     for (int o = threadIdx.x >> 5; o < KO; o += 8) {
-        for (int pass = 0; pass < 2; ++pass) {
-            const bool guard = pass == 1;
-            if (guard && (blockIdx.x != 0 || tl != 0)) continue;
-            if (!guard && tl >= nt) continue;
-            const size_t col = (size_t)b * Tp + (guard ? 0 : t0 + tl + 1);
-            unsigned hw[4], lw[4];
+        if (tl >= nt) continue;
+        const size_t col = (size_t)b * Tp + t0 + tl + 1;
+        unsigned hw[4], lw[4];
 #pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                const int k0 = 8 * o + 2 * w;
-                const float x0 = (!guard && k0 < win) ? seg[hop * tl + k0] : 0.f;
-                const float x1 = (!guard && k0 + 1 < win) ? seg[hop * tl + k0 + 1] : 0.f;
-                const unsigned u0 = __builtin_bit_cast(unsigned, x0) & 0xffff0000u;
-                const unsigned u1 = __builtin_bit_cast(unsigned, x1) & 0xffff0000u;
-                hw[w] = (u0 >> 16) | u1;
-                lw[w] = pack_bf16(x0 - __builtin_bit_cast(float, u0), x1 - __builtin_bit_cast(float, u1));
-            }
-            unsigned short* d = img + ((size_t)o * Jp + col) * 8;
-            *(uint4*)d = make_uint4(hw[0], hw[1], hw[2], hw[3]);
-            *(uint4*)(d + lo_off) = make_uint4(lw[0], lw[1], lw[2], lw[3]);
+        for (int w = 0; w < 4; ++w) {
+            const int k0 = 8 * o + 2 * w;
+            const float x0 = k0 < win ? seg[hop * tl + k0] : 0.f;
+            const float x1 = k0 + 1 < win ? seg[hop * tl + k0 + 1] : 0.f;
+            const unsigned u0 = __builtin_bit_cast(unsigned, x0) & 0xffff0000u;
+            const unsigned u1 = __builtin_bit_cast(unsigned, x1) & 0xffff0000u;
+            hw[w] = (u0 >> 16) | u1;
+            lw[w] = pack_bf16(x0 - __builtin_bit_cast(float, u0), x1 - __builtin_bit_cast(float, u1));
         }
+        unsigned short* d = img + ((size_t)o * Jp + col) * 8;
+        *(uint4*)d = make_uint4(hw[0], hw[1], hw[2], hw[3]);
+        *(uint4*)(d + lo_off) = make_uint4(lw[0], lw[1], lw[2], lw[3]);
+    }
+    // guard columns of this utterance, zero slots: q == 0 is tp == 0 (written by its first block), q >= 1 is tp == T + q
+    // (written by its last block)
+    const int q0 = blockIdx.x == 0 ? 0 : 1, nq = (blockIdx.x == gridDim.x - 1 ? Tp - T : 1) - q0;
+    for (int e = threadIdx.x; e < KO * nq; e += blockDim.x) {
+        const int q = q0 + e % nq;
+        unsigned short* d = img + ((size_t)(e / nq) * Jp + (size_t)b * Tp + (q == 0 ? 0 : T + q)) * 8;
+        *(uint4*)d = make_uint4(0u, 0u, 0u, 0u);
+        *(uint4*)(d + lo_off) = make_uint4(0u, 0u, 0u, 0u);
     }
 }
 

@@ -218,23 +218,27 @@ int idv_cbn_stats(const float* act, int C, int F, int B, int Tp, int Jp, int t_v
 int idv_cbn_apply_prelu(float* act, const float* fold, const float* prelu_slope, int C, int F, int B, int Tp, int Jp,
                         int t_valid, void* stream);
 
-/* STFT.forward (pvae_module.py:21-27): x[B][L] -> frames[win][Jp] (reflect-padded, centred frames);
- * the DFT itself is idv_pw_gemm with the idv_make_dft matrix. */
+/* STFT.forward (pvae_module.py:21-27): x[B][L] -> frames[win][Jp] (reflect-padded, centred frames, guard columns tp == 0
+ * and tp > T zeroed); the DFT itself is idv_pw_gemm with the idv_make_dft matrix.  L > n_fft/2, T == 1 + L/hop, Tp >= T+1,
+ * Jp >= B*Tp. */
 int idv_stft_frames(const float* x, int B, int L, int n_fft, int win, int hop, int T, float* frames, int Tp, int Jp,
                     void* stream);
 /* ISTFT.forward (pvae_module.py:38-42) tail: overlap-add of windowed inverse-DFT frames
- * frames[win][Jp] / envelope, trimmed to y[B][hop*(T-1)]. */
+ * frames[win][Jp] / envelope, trimmed to y[B][hop*(T-1)].  T >= 2, Tp >= T+1, Jp >= B*Tp. */
 int idv_istft_ola(const float* frames, const float* env_inv, int B, int n_fft, int win, int hop, int T, int Tp,
                   int Jp, float* y, void* stream);
 
 /* Mask branch of DCCRN_.forward (pvae_module.py:224-234) / decoder_twophase (:2594-2608):
  * predict = |X| tanh|M| exp(j(angle X + angle M)).  mask, X: planar [2][F][Jp] (X utterance b/x_div);
- * writes planar `pred` and the interleaved complex64 API tensor pred_c[B][F][T][2]. */
+ * writes planar `pred` (guard columns tp == 0 and tp > T zeroed) and the interleaved complex64 API tensor pred_c[B][F][T][2]
+ * (may be NULL).  x_div >= 1, Tp >= T+1, Jp >= B*Tp, JpX >= ceil(B/x_div)*Tp. */
 int idv_mask_apply(const float* mask, const float* X, int x_div, int JpX, float* pred, float* pred_c, int F, int B,
                    int T, int Tp, int Jp, void* stream);
 /* Optional data normalisation of DCCRN_.forward (pvae_module.py:217-221 / :235-238; data_mean, data_std: [F][2] from
  * dataset/mean_*_spksplit.txt): out = (X - mean) / (std + 1e-6) with the imaginary part of bins 0 and F-1 zeroed, and the
- * inverse std * P + mean written planar (out) and interleaved [B][F][T][2] (out_c).  Eval path. */
+ * inverse std * P + mean written planar (out) and interleaved [B][F][T][2] (out_c).  Eval path.  These two, their gradients and
+ * idv_outtype_estimate write the valid columns of their planar output and zero its guard columns tp == 0 and tp > T; the
+ * pitch columns [B*Tp, Jp) are not touched.  Tp >= T+1, Jp >= B*Tp. */
 int idv_datanorm(const float* X, const float* mean, const float* stdv, int F, int B, int T, int Tp, int Jp, float* out, void* stream);
 int idv_datadenorm(const float* P, const float* mean, const float* stdv, int F, int B, int T, int Tp, int Jp, float* out,
                    float* out_c, void* stream);
@@ -253,7 +257,7 @@ int idv_datadenorm_bwd(const float* dout, const float* dout_c, const float* stdv
 int idv_outtype_estimate(const float* speech_c, const float* noise_c, const float* X, long long sb, long long sf, long long st,
                          long long sr, int mode, int ns, int B, int F, int T, int Tp, int Jp, float* out, float* out_c,
                          void* stream);
-/* planar [2][F][Jp] -> interleaved [B][F][T][2] (recon_type 'real_imag', pvae_module.py:245-253). */
+/* planar [2][F][Jp] -> interleaved [B][F][T][2] (recon_type 'real_imag', pvae_module.py:245-253).  Tp >= T+1, Jp >= B*Tp. */
 int idv_planar_to_complex(const float* act, float* out_c, int F, int B, int T, int Tp, int Jp, void* stream);
 
 /* ComplexLSTM.forward (complex_progress.py:50-74): four 2-layer LSTM passes, real = rr - ii,
@@ -376,6 +380,8 @@ long long idv_pw_bf16_wfrag_bytes(int M, int K);
 int idv_pack_pw_bf16(const float* w, int M, int K, void* wfrag, void* stream);
 int idv_pw_bf16x3(const void* ximg, long long lo_off_slots, int K, const void* wfrag_bf16, const float* bias, float* out, int M,
                   int B, int Tp, int Jp, int t_valid, void* stream);
+/* idv_stft_frames straight into the K-major split image idv_pw_bf16x3 reads: slot (octet o, column j) holds samples 8o .. 8o+7
+ * of frame j (zeros from sample win on), roundup(win, 64)/8 octets; the slots of the guard columns tp == 0 and tp > T are zeros. */
 int idv_stft_frames_kimage(const float* x, int B, int L, int n_fft, int win, int hop, int T, void* img, long long lo_off_elems,
                            int Tp, int Jp, void* stream);
 int idv_lstm_proj_bf16x3(const void* ximg, long long lo_off_slots, int K, const void* wfrag_bf16, const float* bias, float* G,
@@ -527,13 +533,15 @@ int idv_cbn_bwd_apply_img(const float* dz, const float* y, const float* fold, co
 
 /* idv_mask_apply backward (pvae_module.py:224-234): gradient w.r.t. the mask from the gradients of the planar prediction
  * and / or of the interleaved complex64 tensor (either may be NULL); dX (optional, x_div == 1 only): gradient w.r.t. the
- * input spectrum, needed when the waveform itself requires grad. */
+ * input spectrum, needed when the waveform itself requires grad.  Guard columns of dmask and dX zeroed; the geometry checks of
+ * idv_mask_apply. */
 int idv_mask_apply_bwd(const float* mask, const float* X, int x_div, int JpX, const float* dpred, const float* dpred_c, int F,
                        int B, int T, int Tp, int Jp, float* dmask, float* dX, void* stream);
 /* Adjoint of repeating every utterance of a planar activation n times in a row (the skip connections of the fine-tuned
  * decoder, pvae_module.py:2563-2567): dx[row][b*Tp+tp] = sum_s drep[row][(b*n+s)*Tp+tp], rows = 2*C*F planar rows. */
 int idv_repeat_batch_bwd(const float* drep, int n, int rows, int B, int Tp, int Jp_rep, int Jp, float* dx, void* stream);
-/* interleaved [B][F][T][2] -> planar [2][F][Jp] (adjoint of idv_planar_to_complex; also packs a caller's complex tensor). */
+/* interleaved [B][F][T][2] -> planar [2][F][Jp] (adjoint of idv_planar_to_complex; also packs a caller's complex tensor);
+ * guard columns zeroed.  Tp >= T+1, Jp >= B*Tp. */
 int idv_complex_to_planar(const float* in_c, float* act, int F, int B, int T, int Tp, int Jp, void* stream);
 /* idv_istft_ola backward (pvae_module.py:38-42): dy[B][hop*(T-1)] -> dframes[win][Jp]; the inverse-DFT adjoint is idv_pw_gemm
  * with the transposed matrix. */
