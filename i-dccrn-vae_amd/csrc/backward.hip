@@ -651,7 +651,7 @@ void idv_launch_zero_guard_cols(float* act, int planes, int B, int T, int Tp, in
 
 extern "C" int idv_cbn_apply_prelu_to(const float* y, const float* fold, const float* prelu_slope, int C, int F, int B, int Tp,
                                       int Jp, int t_valid, float* out, void* stream) {
-    if (!y || !fold || !out || C <= 0 || F <= 0 || B <= 0) return IDV_EINVAL;
+    if (!y || !fold || !out || C <= 0 || F <= 0 || B <= 0 || t_valid < 1 || Tp < t_valid + 1 || Jp < B * Tp) return IDV_EINVAL;
     const int J = B * Tp;
     int gx = (J + 255) / 256;
     if (gx > 64) gx = 64;
@@ -664,7 +664,8 @@ extern "C" int idv_cbn_apply_prelu_to(const float* y, const float* fold, const f
 // C % 4 == 0; layout and edge slots as idv_planar_to_image)
 extern "C" int idv_cbn_apply_prelu_to_img(const float* y, const float* fold, const float* prelu_slope, int C, int F, int B, int Tp,
                                           int Jp, int t_valid, float* out, void* img, long long lo_off_elems, void* stream) {
-    if (!y || !fold || !out || !img || C <= 0 || (C % 4) || F <= 0 || B <= 0 || Jp < B * Tp || (lo_off_elems % 8) ||
+    if (!y || !fold || !out || !img || C <= 0 || (C % 4) || F <= 0 || B <= 0 || t_valid < 1 || Tp < t_valid + 1 ||
+        Jp < B * Tp || (lo_off_elems % 8) ||
         (reinterpret_cast<uintptr_t>(img) & 15))
         return IDV_EINVAL;
     int gx = (Jp + 255) / 256;
@@ -677,7 +678,8 @@ extern "C" int idv_cbn_apply_prelu_to_img(const float* y, const float* fold, con
 extern "C" int idv_cbn_bwd_apply_img(const float* dz, const float* y, const float* fold, const float* coef, const float* prelu_slope,
                                      int C, int F, int B, int Tp, int Jp, int t_valid, float* dy, void* img, long long lo_off_elems,
                                      void* stream) {
-    if (!dz || !y || !fold || !coef || !dy || !img || C <= 0 || (C % 4) || F <= 0 || B <= 0 || Jp < B * Tp || (lo_off_elems % 8) ||
+    if (!dz || !y || !fold || !coef || !dy || !img || C <= 0 || (C % 4) || F <= 0 || B <= 0 || t_valid < 1 || Tp < t_valid + 1 ||
+        Jp < B * Tp || (lo_off_elems % 8) ||
         (reinterpret_cast<uintptr_t>(img) & 15))
         return IDV_EINVAL;
     int gx = (Jp + 255) / 256;
@@ -689,7 +691,7 @@ extern "C" int idv_cbn_bwd_apply_img(const float* dz, const float* y, const floa
 
 extern "C" int idv_cbn_bwd_reduce(const float* dz, const float* y, const float* fold, const float* prelu_slope, int C, int F,
                                   int B, int Tp, int Jp, int t_valid, double* sums, void* stream) {
-    if (!dz || !y || !fold || !sums || C <= 0 || F <= 0 || B <= 0) return IDV_EINVAL;
+    if (!dz || !y || !fold || !sums || C <= 0 || F <= 0 || B <= 0 || t_valid < 1 || Tp < t_valid + 1 || Jp < B * Tp) return IDV_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(sums, 0, sizeof(double) * NSUM * C, st) != hipSuccess) return IDV_ELAUNCH;
     const int J = B * Tp;
@@ -715,7 +717,7 @@ extern "C" int idv_cbn_bwd_finalize(const double* sums, double count, const floa
 extern "C" int idv_cbn_bwd_apply(const float* dz, const float* y, const float* fold, const float* coef,
                                  const float* prelu_slope, int C, int F, int B, int Tp, int Jp, int t_valid, float* dy,
                                  void* stream) {
-    if (!dz || !y || !fold || !coef || !dy || C <= 0 || F <= 0 || B <= 0) return IDV_EINVAL;
+    if (!dz || !y || !fold || !coef || !dy || C <= 0 || F <= 0 || B <= 0 || t_valid < 1 || Tp < t_valid + 1 || Jp < B * Tp) return IDV_EINVAL;
     const int J = B * Tp;
     int gx = (J + 255) / 256;
     if (gx > 64) gx = 64;

@@ -530,7 +530,7 @@ extern "C" int idv_cbn_finalize(const double* stats, double count, const float* 
 }
 
 extern "C" int idv_cbn_stats(const float* act, int C, int F, int B, int Tp, int Jp, int t_valid, double* stats, void* stream) {
-    if (!act || !stats || C <= 0 || F <= 0 || B <= 0) return IDV_EINVAL;
+    if (!act || !stats || C <= 0 || F <= 0 || B <= 0 || t_valid < 1 || Tp < t_valid + 1 || Jp < B * Tp) return IDV_EINVAL;
     const int J = B * Tp;
     int gx = (J + 255) / 256;
     if (gx > 16) gx = 16;
@@ -540,7 +540,7 @@ extern "C" int idv_cbn_stats(const float* act, int C, int F, int B, int Tp, int 
 
 extern "C" int idv_cbn_apply_prelu(float* act, const float* fold, const float* prelu_slope, int C, int F, int B, int Tp,
                                    int Jp, int t_valid, void* stream) {
-    if (!act || !fold || C <= 0 || F <= 0 || B <= 0) return IDV_EINVAL;
+    if (!act || !fold || C <= 0 || F <= 0 || B <= 0 || t_valid < 1 || Tp < t_valid + 1 || Jp < B * Tp) return IDV_EINVAL;
     const int J = B * Tp;
     int gx = (J + 255) / 256;
     if (gx > 64) gx = 64;

@@ -206,15 +206,20 @@ int idv_pw_gemm_form(int M, int swap, int Jp, const float* x);
 
 /* Train-mode ComplexBatchNormal (complex_progress.py:131-160): sums -> moments[5][C] (mean_r, mean_i,
  * Vrr+eps, Vri, Vii+eps), running buffers updated in place (first call copies, later 0.9/0.1 blend),
- * fold[C][6] for idv_cbn_apply_prelu. count = B*F*T. */
+ * fold[C][6] for idv_cbn_apply_prelu. count = B*F*T > 0.  momentum weighs the OLD running value (old*momentum + new*(1 -
+ * momentum)).  moments may be NULL; the five running pointers are given together or running_mean_r is NULL (then no running
+ * buffer is touched), one without the others is -1. */
 int idv_cbn_finalize(const double* stats, double count, const float* gamma_rr, const float* gamma_ri,
                      const float* gamma_ii, const float* beta_r, const float* beta_i, int C, int first_call,
                      float momentum, float* running_mean_r, float* running_mean_i, float* Vrr, float* Vri,
                      float* Vii, float* moments, float* fold, void* stream);
 /* Moment sums of a planar activation (stand-alone ComplexBatchNormal.forward, complex_progress.py:131-143);
- * stats [C][5] doubles, zeroed by the caller; same layout as the conv epilogue's. */
+ * stats [C][5] doubles, zeroed by the caller (the sums are ADDED to what stats holds); same layout as the conv epilogue's: sum r, i,
+ * r*r, i*i, r*i over the kept columns 1 <= tp <= t_valid.  Geometry: t_valid >= 1, Tp >= t_valid + 1, Jp >= B*Tp, else -1. */
 int idv_cbn_stats(const float* act, int C, int F, int B, int Tp, int Jp, int t_valid, double* stats, void* stream);
-/* y = PReLU(Z*x + s) in place on a planar activation, guard columns stay zero. */
+/* y = PReLU(Z*x + s) in place on the kept columns of a planar activation (u >= 0 is the positive branch; prelu_slope NULL: no
+ * activation); guard columns, pitch columns [B*Tp, Jp) and everything else are neither read nor written, so zero guard columns
+ * stay zero.  Geometry: t_valid >= 1, Tp >= t_valid + 1, Jp >= B*Tp, else -1 and nothing is written. */
 int idv_cbn_apply_prelu(float* act, const float* fold, const float* prelu_slope, int C, int F, int B, int Tp, int Jp,
                         int t_valid, void* stream);
 
@@ -514,7 +519,14 @@ int idv_planar_rowsum(const float* x, int M, int Jp, int J, int accumulate, floa
  * slope term; data-parallel training all-reduces these), idv_cbn_bwd_finalize (moments = the [5][C] output of
  * idv_cbn_finalize, count = B*F*T of the whole batch; -> coef[C][12], d gamma_rr/ri/ii, d beta_r/i, dslope[1], each times
  * param_grad_scale: 1 normally, 1/world when the sums were all-reduced, because the ranks then all hold the gradient of
- * the SUM of their losses and the gradient all-reduce averages), idv_cbn_bwd_apply (dy = Z^T du + A (y - mu) + c). */
+ * the SUM of their losses and the gradient all-reduce averages), idv_cbn_bwd_apply (dy = Z^T du + A (y - mu) + c).
+ * idv_cbn_bwd_reduce overwrites sums (slot 7 of a channel is 0); the gradient takes u > 0 as the positive PReLU branch (torch's
+ * convention: u == 0 gets the slope) while the forward takes u >= 0 -- the value at u == 0 is 0 either way.  dslope may be NULL
+ * (nothing is written there); coef[c][11] is 0.
+ * Geometry of the four planar entries (idv_cbn_apply_prelu_to, idv_cbn_bwd_reduce, idv_cbn_bwd_apply and their _img twins):
+ * t_valid >= 1, Tp >= t_valid + 1, Jp >= B*Tp, else -1 and nothing is written.  out / dy get every column of [0, B*Tp) of their
+ * 2*C*F rows: the result on the kept columns 1 <= tp <= t_valid, +0.0 on the guard columns; pitch columns [B*Tp, Jp) are not
+ * written.  Guard and pitch columns of the inputs are not read. */
 int idv_cbn_apply_prelu_to(const float* y, const float* fold, const float* prelu_slope, int C, int F, int B, int Tp, int Jp,
                            int t_valid, float* out, void* stream);
 int idv_cbn_bwd_reduce(const float* dz, const float* y, const float* fold, const float* prelu_slope, int C, int F, int B,
@@ -525,7 +537,9 @@ int idv_cbn_bwd_finalize(const double* sums, double count, const float* moments,
 int idv_cbn_bwd_apply(const float* dz, const float* y, const float* fold, const float* coef, const float* prelu_slope, int C,
                       int F, int B, int Tp, int Jp, int t_valid, float* dy, void* stream);
 /* the out-of-place normalise + PReLU and the batch-norm backward apply, each also writing the split image of its result (bf16x3
- * training mode: the conv kernels read images; C % 4 == 0; image layout and edge slots as idv_planar_to_image) */
+ * training mode: the conv kernels read images; C % 4 == 0, lo_off_elems % 8 == 0, img 16-byte aligned and the planar entries'
+ * geometry, else -1; image layout and edge slots as idv_planar_to_image: every slot of [0, C/4 * F * Jp) is written, zeros in the
+ * guard and pitch columns, plus the zero slot in front of each plane and the 8 behind it) */
 int idv_cbn_apply_prelu_to_img(const float* y, const float* fold, const float* prelu_slope, int C, int F, int B, int Tp, int Jp,
                                int t_valid, float* out, void* img, long long lo_off_elems, void* stream);
 int idv_cbn_bwd_apply_img(const float* dz, const float* y, const float* fold, const float* coef, const float* prelu_slope, int C,
