@@ -14,6 +14,9 @@
     and :119; csrc/stoi.hip, DESIGN 3.8 -- the package's definition restated, parity with the package itself pinned only where it
     is installed); :func:`score_list` scores a list of recordings of any lengths in padded batches.  PESQ (an ITU program) and
     DNSMOS (an ONNX model) are third-party CPU metrics and stay out of scope (SURVEY 2, rows 12 and 14);
+  * beside them ``compute_sdr``, the BSS-eval SDR with a 512-tap distortion filter (``mir_eval.separation.bss_eval_sources`` for one
+    source; csrc/sdr.hip): the waveform metric that does not count a delay or the early reflections of a reverberant
+    mixture as error when the estimate is scored against the dry recording; ``score_list`` knows it as "sdr";
   * the resampling the evaluation scripts do with librosa in front of these (test_se_cvaefinetune.py:236-239, the 48 kHz
     VoiceBank-DEMAND references): :func:`resample` / :func:`resample_list`, a rational polyphase resampler with
     ``scipy.signal.resample_poly``'s definition (csrc/resample.hip; librosa's own soxr filter is another one and is
@@ -241,8 +244,46 @@ def compute_rmse(x_est: torch.Tensor, x_ref: torch.Tensor, lengths=None) -> torc
     return out[0] if single else out
 
 
+def compute_sdr(x_est: torch.Tensor, x_ref: torch.Tensor, filt_len: int = 512, lengths=None, details: bool = False):
+    """BSS-eval SDR in dB per utterance on the device (Vincent et al. 2006; what ``mir_eval.separation.bss_eval_sources`` reports for
+    one source with ``flen = filt_len``): inputs [L] or [B, L] on the GPU, ESTIMATE FIRST as in :func:`compute_sisdr` -> float32 tensor
+    [B] (or a scalar).  The estimate is split into the part a ``filt_len``-tap filter of the reference explains and the rest:
+    ``r[k] = sum s[n] s[n + k]``, ``d[k] = sum s[n] est[n + k]``, ``G c = d`` with ``G[i][j] = r[|i - j|]``, ``p = c * s`` over its
+    ``L + filt_len - 1`` samples, ``SDR = 10 log10(sum p^2 / sum (est - p)^2)``, every sum in double (csrc/sdr.hip, DESIGN 3.18;
+    tests/sdr_ref.py is the float64 definition; parity with the package itself is pinned only where it is installed).  A delay, a gain
+    or early reflections of up to ``filt_len`` samples (32 ms at 16 kHz) therefore do not count as distortion, which they do for SI-SDR.
+
+    ``filt_len``: a multiple of 16 in 16 .. 512.  ``lengths``: row b is scored over its first lengths[b] samples only (a row shorter
+    than ``filt_len`` is valid); nothing behind them is read and a row's value does not depend on the rest of the batch.  Special rows:
+    NaN for a silent reference, -inf for a silent estimate, +inf for a zero residual, and NaN where the Levinson solve meets a
+    non-positive prediction error -- a numerically singular ``G``, e.g. a pure tone without a noise floor, for which the package
+    returns an arbitrary finite number.  ``details=True`` also returns a dict of float64 device tensors: ``"filter"`` [B, filt_len]
+    (the ``c`` above, the estimated short channel), ``"target_energy"`` and ``"error_energy"`` [B] (without the leading axis for [L]
+    input); a float32 dB value hides everything below 4e-6 of it."""
+    if isinstance(filt_len, bool) or not isinstance(filt_len, int) or filt_len < 16 or filt_len > 512 or filt_len % 16:
+        raise ValueError(f"filt_len = {filt_len!r}: a multiple of 16 in 16 .. 512 expected")
+    e, r, lens, n, single = _score_args(x_est, x_ref, lengths)
+    B = e.shape[0]
+    nbytes = int(ops._ll_fn("idv_sdr_work_bytes")(i(B), i(n), i(filt_len)))
+    if nbytes < 0:
+        raise ValueError(f"compute_sdr: a batch of {B} rows of {n} samples is not supported")
+    work = torch.empty(nbytes, dtype=torch.uint8, device=e.device)
+    out = torch.empty(B, dtype=torch.float32, device=e.device)
+    det = torch.empty(B, 2, dtype=torch.float64, device=e.device) if details else None
+    filt = torch.empty(B, filt_len, dtype=torch.float64, device=e.device) if details else None
+    call("idv_sdr", p(r), ll(r.stride(0)), p(e), ll(e.stride(0)), p(None if lens is None else lens.dev), i(B), i(n), i(filt_len),
+         p(work), ll(nbytes), p(out), p(det), p(filt), stream_ptr())
+    if not details:
+        return out[0] if single else out
+    info = {"filter": filt, "target_energy": det[:, 0], "error_energy": det[:, 1]}
+    if single:
+        return out[0], {k: v[0] for k, v in info.items()}
+    return out, info
+
+
 # metric name of score_list -> f(padded estimates, padded references, fs, lengths)
 METRICS = {"sisdr": lambda e, r, fs, lengths: compute_sisdr(e, r, lengths=lengths),
+           "sdr": lambda e, r, fs, lengths: compute_sdr(e, r, lengths=lengths),
            "rmse": lambda e, r, fs, lengths: compute_rmse(e, r, lengths=lengths),
            "stoi": lambda e, r, fs, lengths: compute_stoi(e, r, fs=fs, lengths=lengths),
            "estoi": lambda e, r, fs, lengths: compute_estoi(e, r, fs=fs, lengths=lengths)}
@@ -252,7 +293,7 @@ def score_list(estimates: Sequence[torch.Tensor], references: Sequence[torch.Ten
                fs: int = 16000, max_batch: int = 64) -> dict:
     """Score a folder of recordings at batch throughput.  ``estimates`` / ``references``: lists of 1-D float32 GPU tensors of any
     lengths; pair k is scored over the first ``min(len(estimates[k]), len(references[k]))`` samples of both, as ``EvalMetrics.eval``
-    aligns them.  ``metrics``: names out of "sisdr", "rmse", "stoi", "estoi".  The pairs are sorted by length, padded into batches
+    aligns them.  ``metrics``: names out of "sisdr", "sdr" (:func:`compute_sdr` with its 512-tap filter), "rmse", "stoi", "estoi".  The pairs are sorted by length, padded into batches
     of at most ``max_batch`` and scored with ``lengths=``; every value equals the per-utterance call's.  Returns
     ``{metric: CPU float32 tensor [N]}`` in the caller's order, with one copy to the host per metric at the end."""
     metrics = list(metrics)

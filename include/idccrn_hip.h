@@ -1363,6 +1363,25 @@ int idv_p808_head(const float* g, int N, const float* w0, const float* b0, const
                   const float* b2, float* raw, void* stream);
 int idv_p808_clip(const float* raw, int nseg, const int* first, const int* count, int B, double* out, void* stream);
 
+/* ---- BSS-eval SDR of a padded batch (sdr.hip; inference.compute_sdr / score_list; additive entries: IDV_ABI_VERSION is unchanged;
+ * DESIGN.md 3.18).  The signal-to-distortion ratio of bss_eval_sources for one source with a K-tap distortion filter: with s = ref row,
+ * e = est row, both zero outside [0, n), n = lens[b]:
+ *   r[k] = sum_i s[i] s[i + k], d[k] = sum_i s[i] e[i + k] (k < K);  G c = d, G[i][j] = r[|i - j|];
+ *   p[i] = sum_k c[k] s[i - k], err[i] = e[i] - p[i] (i < n + K - 1);  out[b] = float(10 log10(sum p^2 / sum err^2)),
+ * every sum in double.  ref, est: rows at pitch ref_ld / est_ld >= Lmax; lens: device int32[B], samples per row (clamped to Lmax), or
+ * NULL: every row has Lmax (<= 2^27) samples.  K: a multiple of 16 in 16 .. 512.  Nothing at or past lens[b] is read and row b's
+ * result does not depend on B, on the other rows, on the pitches or on the padding.  Special rows: NaN for a silent reference
+ * (r[0] == 0) and for a solve that meets a non-positive prediction error (a numerically singular G); -inf for sum p^2 == 0 (a silent
+ * estimate); +inf for sum err^2 == 0.  details (may be NULL): double [B][2] = (sum p^2, sum err^2), NaN for a NaN row; filt (may be NULL):
+ * double [B][K] = c, NaN for a NaN row.  work: idv_sdr_work_bytes(B, Lmax, K) bytes, 16-byte aligned:
+ *   8 B (2 K T1 + K + 1 + 2 T3),  T1 = ceil(((Lmax + 14) / 16 + 1) / 256),  T3 = ceil((Lmax + K - 1) / 4096)
+ * (the per-tile lag sums, c, a status word and the per-tile energies of each row); -1 for what idv_sdr refuses.  No allocation, no
+ * atomics.  IDV_EINVAL (before any GPU work) for a NULL ref / est / work / out, B outside 1 .. 65535, Lmax outside 1 .. 2^27, a K as
+ * above, a pitch below Lmax, work_bytes too small, work not 16-byte aligned, details / filt not 8-byte aligned. */
+long long idv_sdr_work_bytes(int B, int Lmax, int K);
+int idv_sdr(const float* ref, long long ref_ld, const float* est, long long est_ld, const int* lens, int B, int Lmax, int K, void* work,
+            long long work_bytes, float* out, double* details, double* filt, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
