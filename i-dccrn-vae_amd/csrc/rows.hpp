@@ -1,5 +1,5 @@
 // Shared pieces of the kernels that work on rows of samples or frames of different lengths: trim.hip, mix.hip, assemble.hip,
-// reverb.hip, resample.hip, stoi.hip, sdr.hip, moments.hip, latent.hip.
+// reverb.hip, resample.hip, stoi.hip, sdr.hip, bss.hip, moments.hip, latent.hip.
 //
 // THE FIXED ORDER of a sum over the samples of a row, which trim.hip, mix.hip and assemble.hip share and tests/rows_ref.py restates in
 // numpy (tests/test_gpu_rows_order.py holds the kernels to it bit for bit):

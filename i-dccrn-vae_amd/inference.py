@@ -17,6 +17,9 @@
   * beside them ``compute_sdr``, the BSS-eval SDR with a 512-tap distortion filter (``mir_eval.separation.bss_eval_sources`` for one
     source; csrc/sdr.hip): the waveform metric that does not count a delay or the early reflections of a reverberant
     mixture as error when the estimate is scored against the dry recording; ``score_list`` knows it as "sdr";
+  * and ``compute_bss``, the same decomposition with the noise as second source (csrc/bss.hip): SDR, SIR (the other
+    source leaking through) and SAR (distortion the system made itself); ``score_list(..., interferers=...)`` knows them as "sir"
+    and "sar";
   * the resampling the evaluation scripts do with librosa in front of these (test_se_cvaefinetune.py:236-239, the 48 kHz
     VoiceBank-DEMAND references): :func:`resample` / :func:`resample_list`, a rational polyphase resampler with
     ``scipy.signal.resample_poly``'s definition (csrc/resample.hip; librosa's own soxr filter is another one and is
@@ -281,6 +284,85 @@ def compute_sdr(x_est: torch.Tensor, x_ref: torch.Tensor, filt_len: int = 512, l
     return out, info
 
 
+def _score_args3(x_est, x_ref, x_interf, lengths):
+    """:func:`_score_args` for an estimate and two references -> (est rows, ref rows, interferer rows, Lengths or None, samples per row,
+    single); with ``lengths`` the three inputs may differ in padded width and the lengths are held against the narrowest."""
+    if not all(isinstance(x, torch.Tensor) for x in (x_est, x_ref, x_interf)):
+        raise ValueError("x_est, x_ref and x_interf must be tensors")
+    single = x_est.dim() == 1
+    e, r, v = (x.reshape(1, -1) if single else x for x in (x_est, x_ref, x_interf))
+    if e.dim() != 2 or r.dim() != 2 or v.dim() != 2:
+        raise ValueError(f"estimate {tuple(x_est.shape)} / reference {tuple(x_ref.shape)} / interferer {tuple(x_interf.shape)}: "
+                         "[L] or [B, L] expected")
+    if e.shape[0] != r.shape[0] or e.shape[0] != v.shape[0]:
+        raise ValueError(f"estimate {tuple(e.shape)}, reference {tuple(r.shape)} and interferer {tuple(v.shape)} differ in batch size")
+    if lengths is None:
+        if e.shape != r.shape or e.shape != v.shape:
+            raise ValueError(f"estimate {tuple(e.shape)}, reference {tuple(r.shape)} and interferer {tuple(v.shape)} differ")
+        if e.shape[1] < 1:
+            raise ValueError("empty signals")
+        host, n = None, e.shape[1]
+    else:
+        host = ops.check_lengths(lengths, e.shape[0], min(e.shape[1], r.shape[1], v.shape[1]), None)
+        n = max(host)
+    ops.check_dev_f32(x_est, "x_est")
+    ops.check_dev_f32(x_ref, "x_ref", x_est.device)
+    ops.check_dev_f32(x_interf, "x_interf", x_est.device)
+    lens = None if host is None else ops.Lengths(host, e.device)
+    return e.float().contiguous(), r.float().contiguous(), v.float().contiguous(), lens, n, single
+
+
+def compute_bss(x_est: torch.Tensor, x_ref: torch.Tensor, x_interf: torch.Tensor, filt_len: int = 512, lengths=None,
+                details: bool = False):
+    """BSS-eval SDR, SIR and SAR in dB per utterance on the device, with the noise as the second source (Vincent et al. 2006; what
+    ``mir_eval.separation.bss_eval_sources(np.stack([ref, interf]), ..., compute_permutation=False)`` reports for source 0 with
+    ``flen = filt_len``): inputs [L] or [B, L] on the GPU, ESTIMATE FIRST as in :func:`compute_sdr`, then the reference of the target
+    and the reference of the interferer -> ``(sdr, sir, sar)``, float32 tensors [B] (or scalars).  With ``s = x_ref``, ``v = x_interf``,
+    ``y = x_est``: ``p1 = c * s`` is the part of ``y`` a ``filt_len``-tap filter of ``s`` alone explains (:func:`compute_sdr`'s), ``pall =
+    C_s * s + C_v * v`` the part filters of both explain jointly (a ``2 filt_len``-square system of four Toeplitz blocks), and
+
+        SDR = 10 log10(sum p1^2 / sum (y - p1)^2)         the value of :func:`compute_sdr`, bit for bit
+        SIR = 10 log10(sum p1^2 / sum (pall - p1)^2)      how much of the error is the other source leaking through
+        SAR = 10 log10(sum pall^2 / sum (y - pall)^2)     how much is distortion the system made itself
+
+    every sum in double (csrc/bss.hip; tests/bss_ref.py is the float64 definition; parity with the package itself is
+    pinned only where it is installed).  To score a NOISE estimate call it with the roles swapped: ``compute_bss(noise_est, noise,
+    clean)``.
+
+    ``filt_len``: a multiple of 16 in 16 .. 512.  ``lengths``: row b is scored over its first lengths[b] samples only; nothing behind
+    them is read and a row's values do not depend on the rest of the batch.  Each ratio is -inf for a zero numerator, otherwise +inf
+    for a zero denominator.  Special rows: three NaN for a silent reference; the SDR of :func:`compute_sdr` and NaN for SIR and SAR
+    for a silent interferer, for a row of ``filt_len`` samples or fewer (the joint system is singular whatever the signals) and where
+    the block Levinson solve meets an error matrix that is not positive definite -- a numerically singular system, e.g. an interferer
+    that is a multiple of the reference.  Rows shorter than about ``2 filt_len`` samples are OVERFITTED: the joint filters explain
+    nearly everything and SAR says nothing (293 dB at ``L = filt_len + 1 = 17``).  ``details=True`` also returns a dict of float64
+    device tensors: ``"filters"`` [B, 2, filt_len] (``C_s``, ``C_v``), ``"target_energy"`` (sum p1^2), ``"error_energy"`` (sum (y -
+    p1)^2), ``"interf_energy"`` (sum (pall - p1)^2), ``"projection_energy"`` (sum pall^2) and ``"artif_energy"`` (sum (y - pall)^2)
+    [B] (without the leading axis for [L] input), NaN where the value they stand under is NaN by the special rows."""
+    if isinstance(filt_len, bool) or not isinstance(filt_len, int) or filt_len < 16 or filt_len > 512 or filt_len % 16:
+        raise ValueError(f"filt_len = {filt_len!r}: a multiple of 16 in 16 .. 512 expected")
+    e, r, v, lens, n, single = _score_args3(x_est, x_ref, x_interf, lengths)
+    B = e.shape[0]
+    nbytes = int(ops._ll_fn("idv_bss_work_bytes")(i(B), i(n), i(filt_len)))
+    if nbytes < 0:
+        raise ValueError(f"compute_bss: a batch of {B} rows of {n} samples is not supported")
+    work = torch.empty(nbytes, dtype=torch.uint8, device=e.device)
+    out = torch.empty(B, 3, dtype=torch.float32, device=e.device)
+    det = torch.empty(B, 5, dtype=torch.float64, device=e.device) if details else None
+    filt = torch.empty(B, 2, filt_len, dtype=torch.float64, device=e.device) if details else None
+    call("idv_bss", p(r), ll(r.stride(0)), p(v), ll(v.stride(0)), p(e), ll(e.stride(0)), p(None if lens is None else lens.dev), i(B),
+         i(n), i(filt_len), p(work), ll(nbytes), p(out), p(det), p(filt), stream_ptr())
+    vals = tuple(out[0, k] if single else out[:, k] for k in range(3))
+    if not details:
+        return vals
+    info = {"filters": filt}
+    for k, name in enumerate(("target_energy", "error_energy", "interf_energy", "projection_energy", "artif_energy")):
+        info[name] = det[:, k]
+    if single:
+        info = {k: t[0] for k, t in info.items()}
+    return vals + (info,)
+
+
 # metric name of score_list -> f(padded estimates, padded references, fs, lengths)
 METRICS = {"sisdr": lambda e, r, fs, lengths: compute_sisdr(e, r, lengths=lengths),
            "sdr": lambda e, r, fs, lengths: compute_sdr(e, r, lengths=lengths),
@@ -289,16 +371,28 @@ METRICS = {"sisdr": lambda e, r, fs, lengths: compute_sisdr(e, r, lengths=length
            "estoi": lambda e, r, fs, lengths: compute_estoi(e, r, fs=fs, lengths=lengths)}
 
 
+# the names score_list takes with interferers= only
+BSS_METRICS = ("sir", "sar")
+
+
 def score_list(estimates: Sequence[torch.Tensor], references: Sequence[torch.Tensor], metrics: Sequence[str] = ("sisdr", "estoi"),
-               fs: int = 16000, max_batch: int = 64) -> dict:
+               fs: int = 16000, max_batch: int = 64, interferers: Optional[Sequence[torch.Tensor]] = None) -> dict:
     """Score a folder of recordings at batch throughput.  ``estimates`` / ``references``: lists of 1-D float32 GPU tensors of any
     lengths; pair k is scored over the first ``min(len(estimates[k]), len(references[k]))`` samples of both, as ``EvalMetrics.eval``
     aligns them.  ``metrics``: names out of "sisdr", "sdr" (:func:`compute_sdr` with its 512-tap filter), "rmse", "stoi", "estoi".  The pairs are sorted by length, padded into batches
     of at most ``max_batch`` and scored with ``lengths=``; every value equals the per-utterance call's.  Returns
-    ``{metric: CPU float32 tensor [N]}`` in the caller's order, with one copy to the host per metric at the end."""
+    ``{metric: CPU float32 tensor [N]}`` in the caller's order, with one copy to the host per metric at the end.
+
+    ``interferers``: a third list, the reference of the other source of every pair (the noise of a ``(noisy, clean, noise)`` triple when
+    speech is scored).  With it ``metrics`` also takes "sir" and "sar" (:func:`compute_bss` with its 512-tap filters; one call per
+    batch serves both and "sdr"), and triple k is scored over the first samples all three of its signals have.  "sir" or "sar"
+    without ``interferers`` raises ``ValueError``."""
     metrics = list(metrics)
     for m in metrics:
-        if m not in METRICS:
+        if m in BSS_METRICS:
+            if interferers is None:
+                raise ValueError(f"metric {m!r} needs interferers=: the references of the other source")
+        elif m not in METRICS:
             raise ValueError(f"metric {m!r}: expected one of {sorted(METRICS)}")
     if isinstance(fs, bool) or fs not in (10000, 16000):
         raise ValueError(f"fs = {fs!r}: STOI is defined here for 10000 and 16000 Hz input")
@@ -306,13 +400,19 @@ def score_list(estimates: Sequence[torch.Tensor], references: Sequence[torch.Ten
         raise ValueError(f"{len(estimates)} estimates for {len(references)} references")
     if isinstance(max_batch, bool) or not isinstance(max_batch, int) or max_batch < 1:
         raise ValueError("score_list: max_batch must be a positive integer")
-    for name, seq in (("estimates", estimates), ("references", references)):
+    if interferers is not None and len(interferers) != len(estimates):
+        raise ValueError(f"{len(interferers)} interferers for {len(estimates)} estimates")
+    named = (("estimates", estimates), ("references", references)) + ((("interferers", interferers),) if interferers is not None else ())
+    for name, seq in named:
         for k, sgn in enumerate(seq):
             if not isinstance(sgn, torch.Tensor) or sgn.dim() != 1 or sgn.shape[0] < 1:
                 raise ValueError(f"{name}[{k}] must be a non-empty 1-D tensor")
             ops.check_dev_f32(sgn, f"{name}[{k}]")
     N = len(estimates)
     lens = [min(int(a.shape[0]), int(b.shape[0])) for a, b in zip(estimates, references)]
+    if interferers is not None:
+        lens = [min(n, int(c.shape[0])) for n, c in zip(lens, interferers)]
+    joint = any(m in BSS_METRICS for m in metrics)                          # then compute_bss gives "sdr" as well
     order = sorted(range(N), key=lambda k: (-lens[k], k))
     parts = {m: [] for m in metrics}
     for b0 in range(0, N, max_batch):
@@ -324,8 +424,13 @@ def score_list(estimates: Sequence[torch.Tensor], references: Sequence[torch.Ten
         for row, k in enumerate(batch):
             pe[row, :lens[k]] = estimates[k][:lens[k]]
             pr[row, :lens[k]] = references[k][:lens[k]]
+        if joint:
+            pv = torch.zeros(len(batch), blens[0], dtype=torch.float32, device=dev)
+            for row, k in enumerate(batch):
+                pv[row, :lens[k]] = interferers[k][:lens[k]]
+            three = dict(zip(("sdr",) + BSS_METRICS, compute_bss(pe, pr, pv, lengths=blens)))
         for m in metrics:
-            parts[m].append(METRICS[m](pe, pr, fs, blens))
+            parts[m].append(three[m] if joint and m in three else METRICS[m](pe, pr, fs, blens))
     inv = torch.empty(N, dtype=torch.long)
     inv[torch.tensor(order, dtype=torch.long)] = torch.arange(N)
     out = {}

@@ -1382,6 +1382,33 @@ long long idv_sdr_work_bytes(int B, int Lmax, int K);
 int idv_sdr(const float* ref, long long ref_ld, const float* est, long long est_ld, const int* lens, int B, int Lmax, int K, void* work,
             long long work_bytes, float* out, double* details, double* filt, void* stream);
 
+/* ---- BSS-eval SDR, SIR and SAR of a padded batch with two sources (bss.hip; inference.compute_bss / score_list; additive entries:
+ * IDV_ABI_VERSION is unchanged).  bss_eval_sources for the target s = ref row and ONE interferer v = interf row, read
+ * for the target, with K-tap distortion filters; y = est row, all zero outside [0, n), n = lens[b]:
+ *   x_ab[k] = sum_i a[i] b[i + k] (a, b in {s, v}, |k| < K),  d_a[k] = sum_i a[i] y[i + k] (0 <= k < K)
+ *   G_ss c = d_s;   [G_ss G_sv; G_vs G_vv] [C_s; C_v] = [d_s; d_v],   G_ab[i][j] = x_ab[i - j]
+ *   p1 = c * s,  pall = C_s * s + C_v * v  (i < n + K - 1)
+ *   out[b] = float(10 log10 of) ( sum p1^2 / sum (y - p1)^2,  sum p1^2 / sum (pall - p1)^2,  sum pall^2 / sum (y - pall)^2 ) = (SDR, SIR, SAR),
+ * every sum in double.  The SDR column, c and its two sums are idv_sdr's, bit for bit.  ref, interf, est: rows at pitch ref_ld /
+ * interf_ld / est_ld >= Lmax; lens: device int32[B], samples per row (clamped to Lmax), or NULL: every row has Lmax (<= 2^27) samples.
+ * K: a multiple of 16 in 16 .. 512.  Nothing at or past lens[b] is read and row b's result does not depend on B, on the other rows, on
+ * the pitches or on the padding.  Each ratio: -inf for a zero numerator, otherwise +inf for a zero denominator.  Special rows: all
+ * three NaN for a silent reference (and where idv_sdr gives NaN); SDR as idv_sdr gives it and SIR = SAR = NaN for a silent interferer
+ * (x_vv[0] == 0), for n <= K (2 K unknowns, n + K - 1 equations: G is singular whatever the signals) and for a solve that meets an
+ * error matrix that is not positive definite (a numerically singular G, e.g. v = 2 s).  Rows shorter than about 2 K are overfitted:
+ * the joint filter explains nearly everything.  details (may be NULL): double [B][5] = (sum p1^2, sum (y - p1)^2, sum (pall - p1)^2,
+ * sum pall^2, sum (y - pall)^2), the first two as idv_sdr gives them, the last three NaN where SIR and SAR are NaN by the special
+ * rows; filt (may be NULL): double [B][2][K] = C_s, C_v, NaN for such a row.  work: idv_bss_work_bytes(B, Lmax, K) bytes, 16-byte aligned:
+ *   8 (B (8 K T1 + 4 K + 4 + 5 T3) + (B + 1) / 2),  T1 = ceil(((Lmax + 14) / 16 + 1) / 256),  T3 = ceil((Lmax + K - 1) / 4096)
+ * (idv_sdr's own work, its values, sums and filter, the six per-tile lag sums, C, a status word and the three per-tile energies of
+ * each row); -1 for what idv_bss refuses.  No allocation, no atomics.  IDV_EINVAL (before any GPU work) for a NULL ref / interf / est /
+ * work / out, B outside 1 .. 65535, Lmax outside 1 .. 2^27, a K as above, a pitch below Lmax, work_bytes too small, work not 16-byte
+ * aligned, details / filt not 8-byte aligned, ref / interf / est / lens / out not 4-byte aligned. */
+long long idv_bss_work_bytes(int B, int Lmax, int K);
+int idv_bss(const float* ref, long long ref_ld, const float* interf, long long interf_ld, const float* est, long long est_ld,
+            const int* lens, int B, int Lmax, int K, void* work, long long work_bytes, float* out, double* details, double* filt,
+            void* stream);
+
 #ifdef __cplusplus
 }
 #endif
