@@ -321,13 +321,13 @@ def check_slots(which, slots: int) -> List[int]:
     return sorted(set(which))
 
 
-CONV_ENGINES = ("valu", "mfma")
+CONV_ENGINES = ("valu", "mfma", "bf16x3")
 
 
 def check_conv(conv) -> str:
     """The guard on the ``conv=`` argument of both streamers (host only): the engine of the conv blocks."""
     if not isinstance(conv, str) or conv not in CONV_ENGINES:
-        raise ValueError(f"conv must be one of {CONV_ENGINES} (vector-ALU or fp32-MFMA streaming conv), got {conv!r}")
+        raise ValueError(f"conv must be one of {CONV_ENGINES} (vector-ALU, fp32-MFMA or split-bf16 MFMA streaming conv), got {conv!r}")
     return conv
 
 
@@ -336,7 +336,8 @@ def _fold_and_slope(block):
 
 
 class _ConvPack:
-    # engine: "valu" (idv_stream_cconv*) or "mfma" (idv_stream_cconv_mfma*); w is the weight pack of that engine
+    # engine: "valu" (idv_stream_cconv*), "mfma" (idv_stream_cconv_mfma*) or "bf16x3" (idv_stream_cconv_bf16*); w is the weight
+    # pack of that engine
     __slots__ = ("w", "bias", "fold", "slope", "transposed", "C0", "C1", "Cout", "Fin", "Fout", "nsplit", "engine")
 
 
@@ -369,14 +370,21 @@ class _StreamBase:
         cp.C0, cp.C1, cp.Fin = C0, C1, Fin
         cp.Fout = 2 * Fin - 1 if cp.transposed else (Fin - 1) // 2 + 1
         # the engine of a block is fixed here, from the constructor's choice and the block's shape alone
-        mfma = self.conv == "mfma" and L.lib().idv_stream_cconv_mfma_supported(i(1 if cp.transposed else 0), i(cin), i(cp.Cout)) == 1
-        cp.engine = "mfma" if mfma else "valu"
+        # (conv="bf16x3": a block the split-bf16 entries do not serve gets what conv="mfma" would give it)
+        tr = i(1 if cp.transposed else 0)
+        bf16 = self.conv == "bf16x3" and L.lib().idv_stream_cconv_bf16_supported(tr, i(cin), i(cp.Cout)) == 1
+        mfma = not bf16 and self.conv != "valu" and L.lib().idv_stream_cconv_mfma_supported(tr, i(cin), i(cp.Cout)) == 1
+        cp.engine = "bf16x3" if bf16 else ("mfma" if mfma else "valu")
         cp.bias = torch.empty(2 * cp.Cout, dtype=torch.float32, device=self.device)
         # transposed-conv weights are [Cin][Cout][5][2]: the first cin input channels are a prefix
         wsrc = (p(re.weight.detach().float()[:cin if zero_skip else None].contiguous()),
                 p(im.weight.detach().float()[:cin if zero_skip else None].contiguous()),
                 p(re.bias.detach().float().contiguous()), p(im.bias.detach().float().contiguous()))
-        if mfma:
+        if bf16:
+            cp.w = torch.empty(int(L.lib().idv_stream_cconv_bf16_wfloats(i(cin), i(cp.Cout))), dtype=torch.float32, device=self.device)
+            call("idv_stream_pack_cconv_bf16", wsrc[0], wsrc[1], wsrc[2], wsrc[3], i(cin), i(cp.Cout), i(1 if cp.transposed else 0),
+                 p(cp.w), p(cp.bias), stream_ptr())
+        elif mfma:
             cp.w = torch.empty(int(L.lib().idv_stream_cconv_mfma_wfloats(i(cin), i(cp.Cout))), dtype=torch.float32, device=self.device)
             call("idv_stream_pack_cconv_mfma", wsrc[0], wsrc[1], wsrc[2], wsrc[3], i(cin), i(cp.Cout), i(1 if cp.transposed else 0),
                  p(cp.w), p(cp.bias), stream_ptr())
@@ -420,14 +428,24 @@ class _StreamBase:
                  p(cp.fold), p(cp.slope), out, p(hist_out), x0hist_out, p(self.work), i(cp.nsplit), i(1 if cp.transposed else 0),
                  i(cp.Cout), i(cp.Fin), i(B), i(k), i(Tp), i(Jp), stream_ptr())
             return
+        if cp.engine == "bf16x3":
+            call("idv_stream_cconv_bf16", x0, p(h0), i(cp.C0), x1 if x1 is not None else p(None), p(h1), i(cp.C1), p(cp.w), p(cp.bias),
+                 p(cp.fold), p(cp.slope), out, p(hist_out), x0hist_out, p(self.work), i(cp.nsplit), i(1 if cp.transposed else 0),
+                 i(cp.Cout), i(cp.Fin), i(B), i(k), i(Tp), i(Jp), stream_ptr())
+            return
         call("idv_stream_cconv", x0, p(h0), i(cp.C0), x1 if x1 is not None else p(None), p(h1), i(cp.C1), p(cp.w), p(cp.bias),
              p(cp.fold), p(cp.slope), out, p(hist_out), x0hist_out, p(self.work), i(cp.nsplit), i(1 if cp.transposed else 0),
              i(cp.Cout), i(cp.Fin), i(B), i(k), i(Tp), i(Jp), stream_ptr())
 
     def _conv_call_rows(self, cp: _ConvPack, x0, h0, x1, h1, out, hist, x0hist, B, k, Tp, Jp, rows):
         """The sessions form: the [2][...] histories whole (row b reads half parity_b and writes the other) and the table."""
-        if cp.engine == "mfma":                  # two literal call sites, as in _conv_call
+        if cp.engine == "mfma":                  # a literal call site per engine, as in _conv_call
             call("idv_stream_cconv_mfma_rows", x0, p(h0), i(cp.C0), x1 if x1 is not None else p(None), p(h1), i(cp.C1), p(cp.w),
+                 p(cp.bias), p(cp.fold), p(cp.slope), out, p(hist), p(x0hist), p(self.work), i(cp.nsplit),
+                 i(1 if cp.transposed else 0), i(cp.Cout), i(cp.Fin), i(B), i(k), i(Tp), i(Jp), rows, stream_ptr())
+            return
+        if cp.engine == "bf16x3":
+            call("idv_stream_cconv_bf16_rows", x0, p(h0), i(cp.C0), x1 if x1 is not None else p(None), p(h1), i(cp.C1), p(cp.w),
                  p(cp.bias), p(cp.fold), p(cp.slope), out, p(hist), p(x0hist), p(self.work), i(cp.nsplit),
                  i(1 if cp.transposed else 0), i(cp.Cout), i(cp.Fin), i(B), i(k), i(Tp), i(Jp), rows, stream_ptr())
             return
@@ -634,9 +652,13 @@ class StreamingDCCRN(_Streamer):
     ``conv`` names the engine of the conv blocks: ``"valu"`` (default, vector ALU) or ``"mfma"`` (fp32 matrix cores for every
     block with at least 16 output channels, the others stay on the vector ALU; ``conv_engines`` lists the engine per block,
     enc0 .. then dec0 ..).  The engine is fixed at construction and both give the same bits, so outputs of the two can be mixed.
+    ``"bf16x3"`` runs every block with at least 16 output and 4 input channels in split-bf16 arithmetic on the bf16 matrix cores
+    (three MFMAs per product, fp32 accumulation and fp32 state; the other blocks get what ``"mfma"`` would give them).  Its
+    result is the same bits however the signal is cut into pushes, but not the bits of the fp32 engines: it stands within the
+    streaming tolerance (1e-4 relative) of them.
 
-    The streamer always runs in exact fp32, whatever ``ops.PRECISION`` is.  Weights are packed once, at construction: later
-    changes of the model's parameters are not seen by an existing streamer.
+    Without ``conv="bf16x3"`` the streamer runs in exact fp32; ``ops.PRECISION`` is never read.  Weights are packed once, at
+    construction: later changes of the model's parameters are not seen by an existing streamer.
     """
 
     def reset(self):
@@ -869,9 +891,11 @@ class _Slots:
         are untouched: saving is a fork, and a caller that means a move ``drop``s them afterwards.
 
         A state may be loaded into ANY slot of any sessions object of the same kind and layout (``load``), on any device, with
-        either conv engine and any ``frames_per_launch``.  Into an object with the same number of slots the stream continues bit
-        for bit as if it had never moved; into one with another number of slots it continues within the streaming tolerance
-        (1e-4 relative), because the K split of the conv blocks depends on the batch.  The weights are the
+        any conv engine and any ``frames_per_launch``.  Into an object with the same number of slots and the same arithmetic
+        (``"valu"`` and ``"mfma"`` are one arithmetic, ``"bf16x3"`` another) the stream continues bit for bit as if it had never
+        moved; into one with another number of slots it continues within the streaming tolerance (1e-4 relative), because the K
+        split of the conv blocks depends on the batch, and so it does between ``"bf16x3"`` and an fp32 engine: the state is fp32
+        in both, the products are not.  The weights are the
         caller's to match: nothing in a state identifies them."""
         slots = _slot_list(slots, self.B, "save")
         if not slots:
@@ -891,7 +915,10 @@ class _Slots:
         bookkeeping changes (``ValueError``): as many states as slots, no slot twice, ``kind`` and ``layout`` equal to this
         object's, a plan that a stream of its n samples reaches, and a target at position 0 unless ``overwrite=True`` (the
         stream it served is then abandoned without output).  Then one upload (states on the CPU travel with the slot list in
-        the one pinned copy), one scatter launch, and the slots' plans are set."""
+        the one pinned copy), one scatter launch, and the slots' plans are set.
+
+        The conv engine is no part of a state: every engine keeps its state in fp32.  A state saved by a ``conv="bf16x3"``
+        object continues in an fp32-engine object (and the other way round) within the streaming tolerance, not bit for bit."""
         slots = self._load_check(slots, states, overwrite)
         self._load_apply(slots, states)
 
@@ -1524,8 +1551,8 @@ class StreamingVAE(_VAEStreamer):
     same bits however the signal is cut.  The draws come from a counter-based generator (``idv_stream_eps``): a draw is a
     function of (seed, b, s, t, u) alone, the same seed gives the same draws for every signal, and ``seed`` may be set between
     signals.  ``eps`` may instead be a callable ``(t0, k) -> (eps_r, eps_i)`` ([B, ns, k, zdim] each, on the GPU) that supplies
-    the chosen latent's draws.  ``conv`` as in :class:`StreamingDCCRN`.  Exact fp32 whatever ``ops.PRECISION`` is; weights are
-    packed at construction.
+    the chosen latent's draws.  ``conv`` as in :class:`StreamingDCCRN` (``"bf16x3"`` included: the conv blocks of encoder and
+    decoder, nothing else).  ``ops.PRECISION`` is never read; weights are packed at construction.
     """
 
     def reset(self):

@@ -836,6 +836,32 @@ int idv_stream_cconv_mfma_rows(const float* x0, const float* h0, int C0, const f
                                float* work, int nsplit, int transposed, int Cout, int Fin, int B, int k_launch, int Tp, int Jp,
                                const long long* rows, void* stream);
 
+/* ---- streaming conv in split-bf16 (bf16x3) arithmetic on the bf16 matrix cores (stream_conv_bf16.hip;
+ * streaming.Streaming*(conv="bf16x3"); additive entries: IDV_ABI_VERSION is unchanged).  The same function, arguments, K parts,
+ * work layout, combine and epilogue as idv_stream_cconv / idv_stream_cconv_rows; every product w x is replaced by
+ * w_lo x_hi + w_hi x_lo + w_hi x_hi (hi = the fp32 value with its low 16 bits cleared, lo = the round-to-nearest-even bf16 of the
+ * exact difference) on v_mfma_f32_32x32x16_bf16 with fp32 accumulation.  Sources, histories, outputs and work stay fp32; x is split
+ * in registers, the weights by the pack.  Not bit-identical to the fp32 entries (about 1e-5 relative); the arithmetic of an
+ * output position depends on the layer shape and nsplit alone, never on B, k or the row table. */
+/* Floats (32-bit words of two bf16) of the bf16x3 weight pack: [co tiles of 32][ceil(Cin / 4)][5][4 fragments][64 lanes][4]. */
+long long idv_stream_cconv_bf16_wfloats(int Cin, int Cout);
+/* Inputs and bias as idv_stream_pack_cconv; w in bf16 A-fragment order, split here once (fragments: real tile hi, lo, imaginary
+ * tile hi, lo; -w_im is formed before the split; channel slots past Cin and rows past Cout are zero). */
+int idv_stream_pack_cconv_bf16(const float* w_re, const float* w_im, const float* b_re, const float* b_im, int Cin, int Cout,
+                               int transposed, float* w, float* bias, void* stream);
+/* Host only, launches nothing: 1 when the bf16x3 entries serve the block (Cin >= 4 and Cout >= 16), 0 when it stays on the fp32
+ * entries, -1 for a non-positive Cin or Cout. */
+int idv_stream_cconv_bf16_supported(int transposed, int Cin, int Cout);
+/* idv_stream_cconv with w from idv_stream_pack_cconv_bf16; IDV_EINVAL for an unsupported shape. */
+int idv_stream_cconv_bf16(const float* x0, const float* h0, int C0, const float* x1, const float* h1, int C1, const float* w,
+                          const float* bias, const float* fold, const float* prelu_slope, float* out, float* hist_out, float* x0hist_out,
+                          float* work, int nsplit, int transposed, int Cout, int Fin, int B, int k, int Tp, int Jp, void* stream);
+/* idv_stream_cconv_rows with w from idv_stream_pack_cconv_bf16; IDV_EINVAL for an unsupported shape. */
+int idv_stream_cconv_bf16_rows(const float* x0, const float* h0, int C0, const float* x1, const float* h1, int C1, const float* w,
+                               const float* bias, const float* fold, const float* prelu_slope, float* out, float* hist, float* x0hist,
+                               float* work, int nsplit, int transposed, int Cout, int Fin, int B, int k_launch, int Tp, int Jp,
+                               const long long* rows, void* stream);
+
 /* ---- streaming I-DCCRN-VAE enhancement (stream_lstm.hip, stream_io.hip; streaming.StreamingVAE; additive entries:
  * IDV_ABI_VERSION is unchanged).  The noisy encoder runs at batch B, the decoder at batch B * ns with row b * ns + s, the order
  * of idv_reparam and idv_mask_apply(x_div = ns).  The three entries below are lock-step; each has a _rows twin for sessions

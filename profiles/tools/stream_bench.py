@@ -1,7 +1,7 @@
 """Streaming enhancement benchmark: one JSON line per batch of lock-step streams, one hop (100 samples) per push.
 
     python profiles/tools/stream_bench.py [--batches 1,16,128,512,1024] [--seconds 2] [--catchup] [--far-seconds 3600] [--sessions]
-                                           [--conv valu|mfma|both] [--vae [--sessions]]
+                                           [--conv valu|mfma|bf16x3|both|mfma-bf16x3] [--vae [--sessions]]
                                            [--two-latents [--sessions] [--outtype O] [--phase P]]
                                            [--state]
 
@@ -10,8 +10,9 @@ the real-time factor (hop / 16 kHz = 6.25 ms over the wall time) and the algorit
 product of every block at its kept positions, LSTM and dense, the DFTs), computed from the shapes.  --catchup adds one line of
 4000-sample pushes at B = 64 in utterances (4 s) per second.  --far-seconds S adds one line at B = 1 measured after S seconds of
 audio went through the streamer in 1 s pushes, with no flush: time per push must not depend on the stream's position.  --conv names the engine
-of the conv blocks (streaming.check_conv); "both" measures the two engines in turn, twice, in one process per batch size, so
-that they share the card and its clocks (field "round").  --sessions measures streaming.StreamingSessions
+of the conv blocks (streaming.check_conv); "both" measures the two fp32 engines in turn, twice, in one process per batch size, so
+that they share the card and its clocks (field "round"), and "mfma-bf16x3" does the same for the fp32 MFMA and the split-bf16
+engine (field "conv_engines_bf16x3": the blocks on the split-bf16 entries).  --sessions measures streaming.StreamingSessions
 instead (metric "sessions_push"): every slot active, slot b 13 * (b % 7) samples ahead of slot 0, so the slots stand at staggered
 positions and each hop push still completes one frame per slot; counts are passed as a host list on every push.  The
 streams are never flushed; pushes are column slices of a 4 s signal taken round-robin (no copy).  Full-width DCCRN-CL,
@@ -48,6 +49,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 
 NFFT, HOP, WIN, SR = 512, 100, 400, 16000
+PAIRS = {"both": ("valu", "mfma"), "mfma-bf16x3": ("mfma", "bf16x3")}      # --conv values that measure two engines in turn
 
 
 def gflop_per_frame(st) -> float:
@@ -215,14 +217,14 @@ def main():
     ap.add_argument("--catchup", action="store_true")
     ap.add_argument("--far-seconds", type=int, default=0)
     ap.add_argument("--sessions", action="store_true")
-    ap.add_argument("--conv", choices=["valu", "mfma", "both"], default="valu")
+    ap.add_argument("--conv", choices=["valu", "mfma", "bf16x3", "both", "mfma-bf16x3"], default="valu")
     ap.add_argument("--vae", action="store_true")
     ap.add_argument("--two-latents", action="store_true")
     ap.add_argument("--outtype", default="phase_mask")
     ap.add_argument("--phase", type=int, default=2)
     ap.add_argument("--state", action="store_true")
     a = ap.parse_args()
-    if a.state and (a.vae or a.two_latents or a.catchup or a.far_seconds or a.conv == "both"):
+    if a.state and (a.vae or a.two_latents or a.catchup or a.far_seconds or a.conv in PAIRS):
         ap.error("--state measures save + load of StreamingSessions next to its hop pushes only")
     if a.state and a.batches is None:
         a.batches = "16,256"
@@ -235,8 +237,8 @@ def main():
         a.batches = "1,16" if a.two_latents else "1,16,128" if a.vae else "1,16,128,512,1024"
     torch.set_grad_enabled(False)
     budget = 1e3 * HOP / SR
-    turns = [("valu", 0), ("mfma", 0), ("valu", 1), ("mfma", 1)] if a.conv == "both" else [(a.conv, 0)]
-    conv1 = "mfma" if a.conv == "both" else a.conv            # the single-engine lines below
+    turns = [(c, rnd) for rnd in (0, 1) for c in PAIRS[a.conv]] if a.conv in PAIRS else [(a.conv, 0)]
+    conv1 = PAIRS[a.conv][1] if a.conv in PAIRS else a.conv   # the single-engine lines below
     for B in [int(v) for v in a.batches.split(",") if v]:
         for conv, rnd in turns:
             if a.state:
@@ -261,7 +263,8 @@ def main():
                                  "rtf": round(budget / wall_ms, 3), "device_rtf": round(budget / dev_ms, 3),
                                  "under_hop_budget": bool(wall_ms < budget), "gflop_per_push": round(gf, 3),
                                  "tflops_device": round(gf / dev_ms, 2), "frames_per_launch": st.cap, "conv": conv,
-                                 "conv_engines": st.conv_engines.count("mfma"), "round": rnd})
+                                 "conv_engines": st.conv_engines.count("mfma"),
+                                 "conv_engines_bf16x3": st.conv_engines.count("bf16x3"), "round": rnd})
                     print(json.dumps(line), flush=True)
                     del st
                     torch.cuda.empty_cache()
@@ -278,7 +281,8 @@ def main():
                         lstm_ms = wide_lstm_ms(st)
                         line.update({"wide_lstm_device_ms": round(lstm_ms, 4), "wide_lstm_share": round(lstm_ms / dev_ms, 3)})
                     line.update({"gflop_per_push": round(gf, 3), "tflops_device": round(gf / dev_ms, 2), "frames_per_launch": st.cap,
-                                 "conv": conv, "conv_engines": st.conv_engines.count("mfma"), "round": rnd})
+                                 "conv": conv, "conv_engines": st.conv_engines.count("mfma"),
+                                 "conv_engines_bf16x3": st.conv_engines.count("bf16x3"), "round": rnd})
                     print(json.dumps(line), flush=True)
                     del st
                     torch.cuda.empty_cache()
@@ -290,7 +294,8 @@ def main():
                               "wall_ms_per_push": round(wall_ms, 4), "rtf": round(budget / wall_ms, 3),
                               "device_rtf": round(budget / dev_ms, 3), "gflop_per_push": round(gf, 3),
                               "tflops_device": round(gf / dev_ms, 2), "frames_per_launch": st.cap, "conv": conv,
-                              "conv_engines": st.conv_engines.count("mfma"), "round": rnd}), flush=True)
+                              "conv_engines": st.conv_engines.count("mfma"),
+                              "conv_engines_bf16x3": st.conv_engines.count("bf16x3"), "round": rnd}), flush=True)
             del st
             torch.cuda.empty_cache()
     if a.catchup:
