@@ -124,6 +124,33 @@ class RirPool(SignalPool):
         self.unit_offset = int(self.data.shape[0])
         self.data = torch.cat([self.data, torch.ones(1, dtype=torch.float32, device=self.device)])
 
+    @classmethod
+    def shoebox(cls, room, source, mic, beta, taps, fs: int = 16000, device="cuda", c: float = 343.0, max_order=None,
+                max_images: int = 2 ** 28) -> "RirPool":
+        """The pool of the image-source responses of B rectangular rooms (dataset/rir.py ``shoebox_rir``, whose arguments and host
+        guards these are), member b of ``taps[b]`` samples.  The samples never leave the device: the rows are packed
+        there and the peaks come from ``idv_ism_peaks``, one small download.  Every attribute is what ``RirPool([rows .cpu()])`` of
+        the same rows holds."""
+        from . import rir as R
+        _int("fs", fs, 1, "RirPool.shoebox")
+        geom, tp, mo = R.check_rooms(room, source, mic, beta, taps, fs, c, max_order, max_images, who="RirPool.shoebox")
+        device = R._device(device, "RirPool.shoebox")
+        h, dev_taps, _ = R._launch(geom, tp, mo, device)
+        with torch.cuda.device(device):
+            peaks = ops.ism_peaks(h, dev_taps)
+            keep = torch.arange(h.shape[1], device=device)[None, :] < dev_taps[:, None]
+            data = torch.cat([h[keep], torch.ones(1, dtype=torch.float32, device=device)])
+        self = cls.__new__(cls)
+        self.lengths = list(tp)
+        self.offsets = [0]
+        for n in self.lengths[:-1]:
+            self.offsets.append(self.offsets[-1] + n)
+        self.data, self.device = data, data.device
+        self.fs = fs
+        self.peaks = [int(v) for v in peaks.tolist()]
+        self.unit_offset = int(data.shape[0]) - 1
+        return self
+
     def early_taps(self, ms: float = 50.0) -> list:
         """One tap count per member: the direct sound plus ``ms`` milliseconds of early reflections."""
         return early_taps(self.lengths, self.peaks, ms, self.fs)

@@ -1253,6 +1253,39 @@ def reverb_apply(x: torch.Tensor, x_off: Optional[torch.Tensor], h: torch.Tensor
     return y
 
 
+# ----------------------------------------------------------------------------- image-source impulse responses
+ISM_FIELDS = 17                # IDV_ISM_FIELDS, the IDV_ISM_* indices of include/idccrn_hip.h:
+ISM_FIELD = {"lx": 0, "ly": 1, "lz": 2, "sx": 3, "sy": 4, "sz": 5, "rx": 6, "ry": 7, "rz": 8, "beta": 9, "fs": 15, "c": 16}
+ISM_TILE = 64                  # samples of a tile: the work buffer holds one image count per tile
+
+
+def ism_rir(geom: torch.Tensor, taps: torch.Tensor, max_order: Optional[torch.Tensor], B: int, Kmax: int,
+            out: Optional[torch.Tensor] = None):
+    """idv_ism_rir: ``geom`` float64 [B, ISM_FIELDS], ``taps`` (and ``max_order`` or None) int32 [B] on the device -> (fp32 [B, Kmax],
+    row b its taps[b] samples and zeros behind them; int64 [B, ceil(Kmax / 64), 2]: per tile the images summed into it and those it
+    owns, whose sum over a row is the row's image count).  ``out``: a
+    float32 device tensor [B, >= Kmax] of any row pitch to write into; what lies past column Kmax stays.  The counts are a view of the
+    work buffer of this device and stream: the next call overwrites them."""
+    if not isinstance(geom, torch.Tensor) or not geom.is_cuda:
+        raise L.IdvError("ism_rir: geom must be a CUDA (ROCm) tensor; the HIP hot path has no CPU fallback")
+    nbytes = int(_ll_fn("idv_ism_work_bytes")(i(B), i(Kmax)))
+    if nbytes < 0:
+        raise ValueError(f"ism_rir: {B} rooms of {Kmax} taps are not supported")
+    work = _scratch(nbytes // 8, geom.device, "ism", torch.int64)
+    h = torch.empty(B, Kmax, dtype=torch.float32, device=geom.device) if out is None else out
+    check_dev_f32(h, "out", geom.device)
+    call("idv_ism_rir", p(geom), p(taps), p(max_order), i(B), i(Kmax), p(h), ll(h.stride(0)), p(work), ll(work.numel() * 8), stream_ptr())
+    return h, work[:nbytes // 8].view(B, -1, 2)
+
+
+def ism_peaks(h: torch.Tensor, taps: torch.Tensor) -> torch.Tensor:
+    """idv_ism_peaks: the index of max|h[b]| over the first taps[b] samples of every row, the first on ties -> int32 [B] on the device."""
+    check_dev_f32(h, "h")
+    peaks = torch.empty(h.shape[0], dtype=torch.int32, device=h.device)
+    call("idv_ism_peaks", p(h), ll(h.stride(0)), p(taps), i(h.shape[0]), p(peaks), stream_ptr())
+    return peaks
+
+
 # ----------------------------------------------------------------------------- clip assembly (DESIGN 3.15)
 ASM_MAX_PIECES = 64            # IDV_ASM_MAX_PIECES: pieces per candidate row
 ASM_MAX_TRIES = 16             # IDV_ASM_MAX_TRIES: candidates per row

@@ -1435,6 +1435,43 @@ int idv_bss(const float* ref, long long ref_ld, const float* interf, long long i
             const int* lens, int B, int Lmax, int K, void* work, long long work_bytes, float* out, double* details, double* filt,
             void* stream);
 
+/* ---- image-source impulse responses of rectangular rooms (ism.hip; dataset/rir.py shoebox_rir, RirPool.shoebox; additive entries:
+ * IDV_ABI_VERSION is unchanged).  Allen & Berkley's method as tests/ism_ref.py restates it.  Room b is the record
+ * geom[b][IDV_ISM_FIELDS] (device doubles, the indices below): image (m, q) of axis a lies at p = 2 m L + (1 - 2 q) s - r, was
+ * reflected e0 = |m - q| times at the wall at 0 and e1 = |m| times at the wall at L, g = beta0^e0 beta1^e1 (x^0 = 1); d = |p|,
+ * A = gx gy gz / (4 pi d), tau = d fs / c, n_i = rint(tau), f = tau - n_i, u = n - tau:
+ *   h[b][n] = float( sum_i A sinc(u) (1 + cos(2 pi u / 81)) / 2 ),  |u| < 40.5,  0 <= n < taps[b]
+ *   sinc(0) = 1,  sinc(u) = (-1)^(n - n_i + 1) sin(pi f) / (pi u)
+ * over the images with sum_a (e0 + e1) <= max_order[b] (device int32[B]; NULL: every image) and A != 0, every sum in double in an
+ * order that follows from the room and n alone.  taps: device int32[B], clamped to 1 .. Kmax; row b gets its taps[b] samples and
+ * zeros from there to Kmax; nothing else of h is written.  Row b does not depend on B, on the other rooms, on Kmax, on taps[b] (a
+ * shorter response is the beginning of a longer one) or on ldh.  A record that cannot be walked (a value that is not finite, L, fs or
+ * c not positive, more than 8192 images along an axis within a tile's reach) gives a row of NaN.  work: idv_ism_work_bytes(B, Kmax) =
+ * 16 B ceil(Kmax / 64) bytes, 8-byte aligned: long long [B][ceil(Kmax / 64)][2], per tile of 64 samples the images summed into it and
+ * those of them it owns (rint(tau) in the tile, or past it for the row's last tile: the sum over a row's tiles is the row's image
+ * count); zeros for the tiles at or past taps[b]; -1 for what idv_ism_rir refuses.  No allocation, no atomics.
+ * IDV_EINVAL (before any GPU work) for a NULL geom / taps / h / work, B outside 1 .. 65535, Kmax outside 1 .. 65536, ldh < Kmax,
+ * work_bytes too small, geom / work not 8-byte aligned, taps / max_order / h not 4-byte aligned.
+ * idv_ism_peaks: peaks[b] (device int32) = the index of max|h[b][n]| over n < taps[b] (clamped to 1 .. min(ldh, 65536)), the first on
+ * ties.  IDV_EINVAL for a NULL h / taps / peaks, B outside 1 .. 65535, ldh < 1, a pointer not 4-byte aligned. */
+#define IDV_ISM_FIELDS 17
+#define IDV_ISM_LX 0         /* the room's size, metres */
+#define IDV_ISM_LY 1
+#define IDV_ISM_LZ 2
+#define IDV_ISM_SX 3         /* the source */
+#define IDV_ISM_SY 4
+#define IDV_ISM_SZ 5
+#define IDV_ISM_RX 6         /* the microphone */
+#define IDV_ISM_RY 7
+#define IDV_ISM_RZ 8
+#define IDV_ISM_BETA 9       /* beta[a][w] at IDV_ISM_BETA + 2 a + w: the wall at 0 (w = 0) and at L (w = 1) of axis a */
+#define IDV_ISM_FS 15        /* samples per second */
+#define IDV_ISM_C 16         /* metres per second */
+long long idv_ism_work_bytes(int B, int Kmax);
+int idv_ism_rir(const double* geom, const int* taps, const int* max_order, int B, int Kmax, float* h, long long ldh, void* work,
+                long long work_bytes, void* stream);
+int idv_ism_peaks(const float* h, long long ldh, const int* taps, int B, int* peaks, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
